@@ -28,8 +28,8 @@ Two schedules are measured and BOTH are reported in the one JSON line:
                  they are the serial numbers); `throughput_mode` gives its whole-step bound
                  (conv FLOPs per step / ms_per_step vs the f32-MFMA peak) - per-kernel times do not exist for
                  overlapped kernels.
-Every timed region (exactly K steps between barrier + synchronize on both sides, max over ranks) is repeated
---repeats times (default 5); the median repeat is reported, min / max alongside.
+Every timed region (exactly K steps between barrier + synchronize on both sides, max over ranks) is run --repeats times
+(default 1, so that --steps K times exactly K steps per schedule); with more, the median repeat is reported, min / max alongside.
 
   roofline         : per layer the autotuner picks the arithmetic (--precision auto): f32 MFMA (peak 157.3 TFLOP/s) or bf16x3
                      (three exact bf16 pieces per operand, six bf16 MFMAs per f32 product: peak 2516.8 / 6 = 419.5 TFLOP/s
@@ -47,6 +47,10 @@ Every timed region (exactly K steps between barrier + synchronize on both sides,
                      scores <= 1e-3, classes equal, no unmatched record; `bit_exact` says whether they are even identical):
                      rank 0 tunes the tile tables once and broadcasts them, so every rank sums in the same order.  A
                      mismatch fails the run.
+  --dump-outputs D : after the timed steps, what the headline schedule's LAST timed step handed its caller - roi_cls_locs,
+                     roi_scores, rois, roi_indices, detections (+ detections_gathered for N > 1), rank 0's - as D/<name>.npy in
+                     float32 (integer outputs as float64); above 60 MiB in all, a fixed seeded sample of every array's elements.
+                     Inputs and weights are seeded, so two builds run with the same arguments can be compared array by array.
   N > 1 start-up   : ONE autotune pass on rank 0 (objective = the headline schedule), broadcast as JSON together with the two
                      head-GEMM choices; no f32-MFMA leg, no second (serial-objective) pass; `tuning_seconds` is in the line.
 """
@@ -69,6 +73,8 @@ BF16_MFMA_PEAK_TFLOPS = 2516.8   # same guide: ~2.5 PF dense bf16 MFMA = 16x the
 BF16X3_PEAK_TFLOPS = BF16_MFMA_PEAK_TFLOPS / 6.0
 FP16X2_PEAK_TFLOPS = BF16_MFMA_PEAK_TFLOPS / 3.0       # fp16 dense MFMA = the bf16 rate; three piece products per f32 product
 R_POST = 300
+OUTPUT_NAMES = ("roi_cls_locs", "roi_scores", "rois", "roi_indices", "detections")    # InFlightDetector.result's tuple
+DUMP_BUDGET_BYTES = 60 << 20                                  # --dump-outputs: under 64 MB in all, .npy headers included
 
 
 def parse(argv=None):
@@ -76,7 +82,8 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the K-step timed region is repeated (median reported)")
+    ap.add_argument("--repeats", type=int, default=1, help="how many times the K-step timed region is run (median reported; "
+                    "the default 1 keeps the timed steps at exactly --steps per schedule)")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default: 1 at --gpus 1 = configs[1]; "
                     "8 at --gpus > 1 = configs[4], 64 images over 8 GPUs; 16 = configs[2])")
     ap.add_argument("--backbone", default="resnet50")
@@ -120,6 +127,9 @@ def parse(argv=None):
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-layers", default=None, help="write the serial plan's conv launches (name, FLOPs, algorithmic bytes, tile, "
                     "K-slice slab bytes, HIP-event time) as JSON: the per-layer columns of scripts/summarize_pmc.py")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the arrays the last timed step returned as "
+                    "DIR/<name>.npy (float32 / float64; a fixed seeded sample above 60 MiB in all) for output-by-output comparison "
+                    "of two builds")
     ap.add_argument("--cpu-reps", type=int, default=8)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--check", action="store_true", default=None, help="N > 1: compare the gathered records with single-GPU forwards "
@@ -132,7 +142,10 @@ def parse(argv=None):
                     "tsod_allgather_f32 on a communicator of its own (include/tsod.h; the same ncclAllGather either way)")
     ap.add_argument("--rehearse-cpu", action="store_true", help="launcher / rendezvous / gather / timing / --check control flow "
                     "with fabricated records and NO GPU work (gloo; for the CPU test of the N>1 path - never a measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------- launcher
@@ -438,6 +451,29 @@ class Timer:
         return {"ms_per_step": statistics.median(per), "min": per[0], "max": per[-1], "n": len(per), "steps": steps}
 
 
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array of ``arrays`` ({name: tensor}) as out_dir/<name>.npy, float32 (float64 stays float64;
+    integer and bool outputs become float64, exactly).  When the arrays hold more than ``budget`` bytes in all, each one is
+    cut to the same share of its flattened elements, at positions drawn with a fixed seed: the same shapes give the same
+    positions, so two builds stay comparable element by element.  Returns {name: [shape, elements written]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        arrs[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    written = {}
+    for name, a in arrs.items():
+        shape = list(a.shape)
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = [shape, int(a.size)]
+    return written
+
+
 def compare_records(got, ref, atol=1e-3):
     """[n,300,6] detection records (x1,y1,x2,y2,score,class) of the gathered result against single-GPU forwards of the same
     images on rank 0.  Every rank runs rank 0's tile table and head-GEMM choices (broadcast at start-up), i.e. the same
@@ -726,17 +762,31 @@ def main(argv=None):
                 def submit(self, after=None):
                     outs = model(x)
                     det = hip_ops.detections(outs[0], outs[1], outs[2])
+                    self._outs = tuple(outs) + (det,)
                     if after is not None:
-                        after(tuple(outs) + (det,))
+                        after(self._outs)
                     self._next += 1
+                    return self._next - 1
+
+                def result(self, ticket):
+                    return self._outs
 
                 def drain(self):
                     torch.cuda.synchronize()
             serial_server = _Eager()
         else:
             serial_server = InFlightDetector(model, x, depth=1, tiles=tiles["serial"])
+
+        def last_step_outputs(srv):
+            """--dump-outputs: what the caller of the timed path received in its last timed step, copied to the host before
+            anything else runs on the model."""
+            arrs = dict(zip(OUTPUT_NAMES, (o.cpu() for o in srv.result(srv._next - 1))))
+            if world > 1:
+                arrs["detections_gathered"] = gathered[(srv._next - 1) % n_fly].cpu()
+            return arrs
         serial = timer.measure(make_step(serial_server, 1), args.steps, args.warmup, args.repeats)
         serial_server.drain()
+        last_outs = last_step_outputs(serial_server) if args.dump_outputs and rank == 0 and n_fly == 1 else None
         timed_outs = {}                                                   # what the timed plans computed on x (checked in `parity`)
         if rank == 0 and not args.no_graph:
             timed_outs["serial"] = [o.cpu() for o in serial_server.result(serial_server.submit())[:4]]
@@ -745,6 +795,8 @@ def main(argv=None):
             server = InFlightDetector(model, x, depth=n_fly, tiles=tiles["in_flight"])
             fly = timer.measure(make_step(server, n_fly), args.steps, args.warmup, args.repeats)
             server.drain()
+            if args.dump_outputs and rank == 0:
+                last_outs = last_step_outputs(server)
             if rank == 0:                                                  # the slot the next request would use
                 timed_outs[f"in_flight_slot{server._next % n_fly}"] = [o.cpu() for o in server.result(server.submit())[:4]]
                 server.drain()
@@ -864,6 +916,9 @@ def main(argv=None):
             parity = parity_of(timed_outs, ref_outs, getattr(cpu_baseline, "exact_outs", None), getattr(cpu_baseline, "cutoff", None),
                                getattr(cpu_baseline, "exact_cutoff", None))
         line["parity"] = parity
+        if last_outs is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(last_outs, args.dump_outputs),
+                                    "note": "the headline schedule's last timed step: {name: [shape, elements written]}"}
         print(json.dumps(line), flush=True)
         if parity is not None and not parity["ok"]:
             exit_code = 4

@@ -253,7 +253,28 @@ def main():
          **{"sd." + k: v for k, v in npd(head.state_dict()).items()})
 
 
+def seeded_state_dicts():
+    """state_dict() of the reference's modules under torch.manual_seed(0): keys in their order, dtypes, shapes and the
+    sha256 of every tensor's bytes (the values themselves are too large to store: resnet50 alone holds 23.5M parameters)."""
+    import hashlib
+    arrs = {}
+    for name, ctor in (("resnet50", lambda: ref_resnet.resnet50(include_top=False)), ("resnet34", lambda: ref_resnet.resnet34()),
+                       ("hardnet39", lambda: ref_hardnet.HarDNetFeatureExtraction(True, 39)),
+                       ("hardnet68", lambda: ref_hardnet.HarDNetFeatureExtraction(True, 68))):
+        torch.manual_seed(0)
+        sd = ctor().state_dict()
+        arrs[f"{name}.keys"] = np.array(list(sd.keys()))
+        arrs[f"{name}.dtypes"] = np.array([str(v.dtype) for v in sd.values()])
+        arrs[f"{name}.shapes"] = np.array([str(tuple(v.shape)) for v in sd.values()])
+        arrs[f"{name}.sha256"] = np.array([hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest() for v in sd.values()])
+    save("state_dicts_seeded.npz", **arrs)
+
+
 if __name__ == "__main__":
+    if "--state-dicts-only" in sys.argv:
+        seeded_state_dicts()
+        sys.exit(0)
     if "--extras-only" not in sys.argv:
         main()
     extras_round2()
+    seeded_state_dicts()
