@@ -75,10 +75,12 @@ enum { TSOD_TILE_AUTO = 0, TSOD_TILE_128x128 = 1, TSOD_TILE_128x64 = 2, TSOD_TIL
        TSOD_TILE_128x64_W8_S1 = 9, TSOD_TILE_64x64_S1_K64 = 10, TSOD_TILE_128x64_W8_S1_K64 = 11,
        TSOD_TILE_64x64_W1_S1 = 12, TSOD_TILE_128x64_W2_S1 = 13, TSOD_TILE_128x64_S1 = 14, TSOD_TILE_64x128_S1 = 15,
        TSOD_TILE_128x128_S1 = 16,
-       /* bf16x3 only, fed by LDS-DMA (conv_dma_kernel): one channel segment, Cin a multiple of the K stage (16 / 32 floats),
-        * KH * KW <= 31 and K / stage + 8 <= 640 (one table entry per K-step of a workgroup's K range); anything else is
-        * TSOD_ERR_UNSUPPORTED for these tiles (TSOD_TILE_AUTO then resolves to another tile).  Filters with more than one tap
-        * run their K-steps in (32-channel block, tap) order: another f32 summation order than the other tiles, same weights */
+       /* fed by LDS-DMA (conv_dma_kernel; BF16X3 / FP16X2, see below): one channel segment, Cin (and a second source's c2) a
+        * multiple of the K stage (16 / 32 / 64 floats), KH * KW <= 31 and K / stage + 8 <= 640 (one table entry per K-step of a
+        * workgroup's K range) - or, FP16X2 only, a 1x1 stride-1 unpadded filter over several channel segments with K <= 2048;
+        * anything else is TSOD_ERR_UNSUPPORTED for these tiles (TSOD_TILE_AUTO then resolves to another tile).  Filters with
+        * more than one tap run their K-steps in (32-channel block, tap) order: another f32 summation order than the other
+        * tiles, same weights */
        TSOD_TILE_D128x128 = 17, TSOD_TILE_D64x128 = 18, TSOD_TILE_D256x128 = 19,
        TSOD_TILE_D64x128_S2 = 20 /* two ring stages: two workgroups per CU */,
        TSOD_TILE_D128x256 = 21 /* two columns of waves share the activation stage */,
@@ -94,10 +96,15 @@ enum { TSOD_TILE_AUTO = 0, TSOD_TILE_128x128 = 1, TSOD_TILE_128x64 = 2, TSOD_TIL
 /* arithmetic of the contraction.  F32: v_mfma_f32_32x32x2_f32 (a k-ordered f32 fma chain).  BF16X3: every f32 operand cut
  * exactly into three bf16 pieces (hi + mid + lo == x), six piece products per k accumulated in f32 on
  * v_mfma_f32_32x32x16_bf16: f32-level accuracy (error ~1.3e-7 of sum|a*b|) at 0.375x the matrix-pipe time; storage,
- * accumulation and epilogue are f32 either way.  Tiles available in BF16X3: 64x64, 64x64_S1, 128x64_W8_S1, 64x64_S1_K64,
- * 128x64_S1, 64x128_S1, 128x128_S1 (TSOD_ERR_UNSUPPORTED for the others). */
+ * accumulation and epilogue are f32 either way.
+ * Tiles built in each arithmetic (a named tile outside its arithmetic's list is TSOD_ERR_UNSUPPORTED):
+ *   F32:    128x128 .. 128x128_S1 (1..16), none of the TSOD_TILE_D* tiles;
+ *   BF16X3: 64x64, 64x64_S1, 128x64_W8_S1, 64x64_S1_K64, 128x64_S1, 64x128_S1, 128x128_S1,
+ *           D128x128, D64x128, D256x128, D64x128_S2, D128x256, D128x128_K32;
+ *   FP16X2: 64x64, 64x64_S1, 128x64_W8_S1, 64x64_S1_K64, 128x64_S1, 64x128_S1, 128x128_S1,
+ *           D128x128, D256x128, D128x256, D128x128_K32, D192x128, D64x128_K64. */
 enum { TSOD_PREC_F32 = 0, TSOD_PREC_BF16X3 = 1, TSOD_PREC_FP16X2 = 2 };
-/* FP16X2 (every BF16X3 tile but TSOD_TILE_D64x128 / _S2): every f32 operand as TWO fp16 pieces of s * x
+/* FP16X2: every f32 operand as TWO fp16 pieces of s * x
  * (hi = rne(s x), lo = rne(s x - hi), s a power of two per tensor), THREE piece products per f32 product on
  * v_mfma_f32_32x32x16_f16, f32 accumulation: the f32 kernel's accuracy with half the MFMAs of BF16X3 - while |s x| stays
  * below fp16's 65504 (the CALLER picks desc.a_scale_exp for its activations' range; beyond it the piece products are inf /

@@ -162,3 +162,19 @@ def test_balanced_schedule_and_dma_tile_gates_are_host_side():
     assert L.tsod_conv2d_resolve(byref(_desc(split_k=-3)), byref(t), byref(s)) == INVALID
     auto = _desc(precision=PREC_BF16X3)                                          # the cost model's pick is one of the bf16x3 tiles
     assert L.tsod_conv2d_resolve(byref(auto), byref(t), byref(s)) == OK and t.value in _ffi.BF16X3_TILE_IDS
+
+
+def test_tile_mirror_matches_the_library():
+    """_ffi.TILES, the Python mirror of the library's tile table, against the resolver.  The default problem is one every tile
+    can run, so a named tile resolves (split_k = 1) in exactly the arithmetics the mirror lists and is TSOD_ERR_UNSUPPORTED in
+    the others; the cost model's own pick lies inside the arithmetic's list."""
+    L = lib()
+    t, s = c_int32(), c_int32()
+    assert sorted(_ffi.TILES) == list(range(1, 25))
+    for prec in (_ffi.PREC_F32, _ffi.PREC_BF16X3, _ffi.PREC_FP16X2):
+        ids = _ffi.tile_ids(prec)
+        for tile in range(1, 25):
+            rc = L.tsod_conv2d_resolve(byref(_desc(tile=tile, split_k=1, precision=prec)), byref(t), byref(s))
+            assert (rc, t.value if rc == OK else tile) == ((OK if tile in ids else UNSUPPORTED), tile), (tile, prec)
+        assert L.tsod_conv2d_resolve(byref(_desc(precision=prec)), byref(t), byref(s)) == OK and t.value in ids, prec
+    assert [len(_ffi.tile_ids(p)) for p in (0, 1, 2)] == [16, 13, 13]

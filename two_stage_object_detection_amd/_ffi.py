@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import POINTER, Structure, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from typing import NamedTuple
 
 import torch
 
@@ -18,17 +19,59 @@ TSOD_MAX_SEGMENTS = 16
 AMAX_WORDS, AMAX_STRIDE = 64, 64                 # range words of one tensor (include/tsod.h): 64 uint32, 64 bytes apart
 AMAX_BYTES = AMAX_WORDS * AMAX_STRIDE
 ACT_NONE, ACT_PRELU, ACT_RELU6, ACT_RELU = 0, 1, 2, 3
-TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4
-TILE_NAMES = {0: "auto", 1: "128x128", 2: "128x64", 3: "64x64", 4: "64x128", 5: "128x128w8", 6: "128x64w8", 7: "256x128w8",
-              8: "64x64s1", 9: "128x64w8s1", 10: "64x64s1k64", 11: "128x64w8s1k64", 12: "64x64w1s1", 13: "128x64w2s1", 14: "128x64s1", 15: "64x128s1", 16: "128x128s1",
-              17: "d128x128", 18: "d64x128", 19: "d256x128", 20: "d64x128s2", 21: "d128x256", 22: "d128x128k32", 23: "d192x128", 24: "d64x128k64"}
-TILE_IDS = tuple(range(1, 17))
 PREC_F32, PREC_BF16X3, PREC_FP16X2 = 0, 1, 2
 PREC_NAMES = {0: "f32", 1: "bf16x3", 2: "fp16x2"}
-DMA_TILE_IDS = (17, 18, 19, 20, 21, 22, 23, 24)                         # through LDS-DMA (23: fp16x2 only): one channel segment, Cin % 16 / % 32 == 0, bf16x3 ONLY
-BF16X3_TILE_IDS = (3, 8, 9, 10, 14, 15, 16) + tuple(t for t in DMA_TILE_IDS if t not in (23, 24))   # tiles that exist as bf16x3 variants (include/tsod.h)
-FP16X2_TILE_IDS = tuple(t for t in BF16X3_TILE_IDS if t not in (18, 20)) + (23, 24)   # fp16x2: every bf16x3 tile but the 64-row LDS-DMA ones, + d192x128
+TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4
 
+
+class Tile(NamedTuple):
+    name: str
+    rows: int                  # output pixels (GEMM rows) per workgroup tile
+    precisions: tuple          # the PREC_* it is built in
+    dma: bool = False          # fed by LDS-DMA (conv_dma_kernel): the shape limits of include/tsod.h
+
+
+# The TSOD_TILE_* of include/tsod.h, mirroring the library's tile table (tests/test_abi_errors.py checks it against the resolver)
+_F32, _BF16X3, _FP16X2 = (PREC_F32,), (PREC_BF16X3,), (PREC_FP16X2,)
+_ALL, _SPLIT = (PREC_F32, PREC_BF16X3, PREC_FP16X2), (PREC_BF16X3, PREC_FP16X2)
+TILES = {
+     1: Tile("128x128",        128, _F32),
+     2: Tile("128x64",         128, _F32),
+     3: Tile("64x64",          64,  _ALL),
+     4: Tile("64x128",         64,  _F32),
+     5: Tile("128x128w8",      128, _F32),
+     6: Tile("128x64w8",       128, _F32),
+     7: Tile("256x128w8",      256, _F32),
+     8: Tile("64x64s1",        64,  _ALL),
+     9: Tile("128x64w8s1",     128, _ALL),
+    10: Tile("64x64s1k64",     64,  _ALL),
+    11: Tile("128x64w8s1k64",  128, _F32),
+    12: Tile("64x64w1s1",      64,  _F32),
+    13: Tile("128x64w2s1",     128, _F32),
+    14: Tile("128x64s1",       128, _ALL),
+    15: Tile("64x128s1",       64,  _ALL),
+    16: Tile("128x128s1",      128, _ALL),
+    17: Tile("d128x128",       128, _SPLIT, dma=True),
+    18: Tile("d64x128",        64,  _BF16X3, dma=True),
+    19: Tile("d256x128",       256, _SPLIT, dma=True),
+    20: Tile("d64x128s2",      64,  _BF16X3, dma=True),
+    21: Tile("d128x256",       128, _SPLIT, dma=True),
+    22: Tile("d128x128k32",    128, _SPLIT, dma=True),
+    23: Tile("d192x128",       192, _FP16X2, dma=True),
+    24: Tile("d64x128k64",     64,  _FP16X2, dma=True),
+}
+
+
+def tile_ids(precision: int) -> tuple:
+    """The tiles built in arithmetic ``precision``, in id order (the autotuners' candidate order)."""
+    return tuple(t for t, row in TILES.items() if precision in row.precisions)
+
+
+TILE_NAMES = {TILE_AUTO: "auto", **{t: row.name for t, row in TILES.items()}}
+TILE_IDS = tile_ids(PREC_F32)
+DMA_TILE_IDS = tuple(t for t, row in TILES.items() if row.dma)
+BF16X3_TILE_IDS = tile_ids(PREC_BF16X3)
+FP16X2_TILE_IDS = tile_ids(PREC_FP16X2)
 
 class TsodError(RuntimeError):
     pass

@@ -35,6 +35,7 @@
 // 8 per 16 k at 1/16 the rate: 0.375x the matrix-pipe time at f32-level accuracy (error ~1.3e-7 of sum|a*b|, the f32 fma
 // chain's is 1.4-2.5e-7).  Storage, accumulation, epilogue, scheduling and K-slice combine are unchanged.
 #include "tsod_internal.h"
+#include <array>
 #include <limits.h>
 #include <stdlib.h>
 
@@ -1924,28 +1925,94 @@ pack_weight_fp16x2_kernel(const float *__restrict__ w, int Cout, int K, float sc
     }
 }
 
-// resident = workgroups per CU (LDS / VGPR bound); dma = 1: conv_dma_kernel (bf16x3 only, nbuf = ring stages)
-struct TileInfo { int bm, bn, threads, resident; float cost; int bk, nbuf, bf16x3, dma; };
-const TileInfo kTiles[TSOD_TILE_COUNT] = {
-    {0, 0, 0, 0, 0.f, 32, 2, 0},        {128, 128, 256, 2, 1.00f, 32, 2, 0}, {128, 64, 256, 2, 1.06f, 32, 2, 0}, {64, 64, 256, 4, 1.15f, 32, 2, 1},
-    {64, 128, 256, 2, 1.06f, 32, 2, 0}, {128, 128, 512, 2, 1.00f, 32, 2, 0}, {128, 64, 512, 2, 1.06f, 32, 2, 0}, {256, 128, 512, 1, 0.98f, 32, 2, 0},
-    {64, 64, 256, 6, 1.20f, 32, 1, 1},  {128, 64, 512, 3, 1.10f, 32, 1, 1},  {64, 64, 256, 4, 1.10f, 64, 1, 1},  {128, 64, 512, 2, 1.05f, 64, 1, 0},
-    {64, 64, 64, 8, 1.40f, 32, 1, 0},   {128, 64, 128, 4, 1.35f, 32, 1, 0}, {128, 64, 256, 4, 1.12f, 32, 1, 1}, {64, 128, 256, 4, 1.12f, 32, 1, 1},
-    {128, 128, 256, 2, 1.02f, 32, 1, 1},
-    {128, 128, 256, 2, 0.80f, 16, 4, 1, 1}, {64, 128, 256, 1, 0.95f, 32, 3, 1, 1}, {256, 128, 512, 1, 0.72f, 16, 4, 1, 1},
-    {64, 128, 256, 2, 0.98f, 32, 2, 1, 1}, {128, 256, 512, 1, 0.74f, 16, 4, 1, 1}, {128, 128, 512, 1, 0.70f, 32, 3, 1, 1},
-    {192, 128, 384, 1, 0.74f, 16, 4, 1, 1}, {64, 128, 512, 1, 0.80f, 64, 3, 1, 1}};
-// bf16x3 = 1: the tile also exists as a bf16x3 variant (three bf16 planes per operand fit the 64 KB of static LDS)
-
-// workgroups per CU: the f32 figure (VGPR / LDS bound), for bf16x3 additionally capped by its larger LDS footprint
-// tiles that exist in the fp16x2 arithmetic: the register-staged bf16x3 tiles and d128x128k32
-bool fp16x2_tile(int t) {   // (the 64-row LDS-DMA tiles would need six DMA slots in a 12-MFMA phase: not built)
-    return t == TSOD_TILE_D128x128_K32 || t == TSOD_TILE_D128x128 || t == TSOD_TILE_D256x128 || t == TSOD_TILE_D128x256 || t == TSOD_TILE_D192x128 ||
-           t == TSOD_TILE_D64x128_K64 || (kTiles[t].bf16x3 && !kTiles[t].dma);
+template <int BM, int BN, int WM, int WN, int MW, int NBUF, int BK, int PREC>
+void launch_tile(const ConvParams &p, int grid, hipStream_t s) {
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, MW, NBUF, BK, PREC>), dim3(grid), dim3(64 * (BM / WM) * (BN / WN)), 0, s, p);
 }
 
+template <int BM, int BK, int WAVES_K, int S, int WAVES_N, int NPL>
+void launch_dma_tile(const ConvParams &p, int grid, hipStream_t s) {
+    if constexpr (NPL == 2) {
+        if (p.chan_tab) {                                         // 1x1 over several channel segments (never balanced: make_sched)
+            hipLaunchKernelGGL((conv_dma_kernel<BM, BK, WAVES_K, S, false, WAVES_N, NPL, true>), dim3(grid), dim3((BM / 32) * WAVES_K * WAVES_N * 64), 0, s, p);
+            return;
+        }
+    }
+    if (p.sk_q > 0)
+        hipLaunchKernelGGL((conv_dma_kernel<BM, BK, WAVES_K, S, true, WAVES_N, NPL>), dim3(grid), dim3((BM / 32) * WAVES_K * WAVES_N * 64), 0, s, p);
+    else
+        hipLaunchKernelGGL((conv_dma_kernel<BM, BK, WAVES_K, S, false, WAVES_N, NPL>), dim3(grid), dim3((BM / 32) * WAVES_K * WAVES_N * 64), 0, s, p);
+}
+
+// The tile catalogue: one row per TSOD_TILE_*.  launch[TSOD_PREC_*] is the tile's launcher in that arithmetic, nullptr where
+// the tile is not built in it - the only record of which (tile, arithmetic) pairs exist (validate, resolve, dispatch).
+// bm / bn / bk / nbuf are taken from the launchers' own template arguments (reg_tile, dma_tile), so a row cannot disagree with
+// its kernels.  resident = workgroups per CU (LDS / VGPR bound, f32 figure: residency); cost = MFMA-cycle factor (make_sched);
+// dma: conv_dma_kernel (nbuf = ring stages).
+using TileLaunch = void (*)(const ConvParams &, int grid, hipStream_t);
+struct Tile {
+    int bm, bn, bk, nbuf, resident;
+    float cost;
+    bool dma;
+    TileLaunch launch[3];
+};
+
+// register-staged (conv_igemm_kernel): MW_F32 = MIN_WAVES of the f32 kernel, MW_SPLIT = that of the bf16x3 and fp16x2 kernels
+// (0: f32 only - the three bf16 planes per operand must fit the 64 KB of static LDS)
+template <int BM, int BN, int WM, int WN, int NBUF, int BK, int MW_F32, int MW_SPLIT>
+constexpr Tile reg_tile(int resident, float cost) {
+    Tile t = {BM, BN, BK, NBUF, resident, cost, false, {&launch_tile<BM, BN, WM, WN, MW_F32, NBUF, BK, TSOD_PREC_F32>, nullptr, nullptr}};
+    if constexpr (MW_SPLIT > 0) {
+        t.launch[TSOD_PREC_BF16X3] = &launch_tile<BM, BN, WM, WN, MW_SPLIT, NBUF, BK, TSOD_PREC_BF16X3>;
+        t.launch[TSOD_PREC_FP16X2] = &launch_tile<BM, BN, WM, WN, MW_SPLIT, NBUF, BK, TSOD_PREC_FP16X2>;
+    }
+    return t;
+}
+
+// LDS-DMA (conv_dma_kernel, no f32 form): BN = 128 * WAVES_N, S ring stages; bf16x3 three planes per operand, fp16x2 two
+template <int BM, int BK, int WAVES_K, int S, int WAVES_N, bool BF16X3, bool FP16X2>
+constexpr Tile dma_tile(int resident, float cost) {
+    Tile t = {BM, 128 * WAVES_N, BK, S, resident, cost, true, {nullptr, nullptr, nullptr}};
+    if constexpr (BF16X3) t.launch[TSOD_PREC_BF16X3] = &launch_dma_tile<BM, BK, WAVES_K, S, WAVES_N, 3>;
+    if constexpr (FP16X2) t.launch[TSOD_PREC_FP16X2] = &launch_dma_tile<BM, BK, WAVES_K, S, WAVES_N, 2>;
+    return t;
+}
+
+constexpr auto kTiles = [] {
+    std::array<Tile, TSOD_TILE_COUNT> t{};                   // (TSOD_TILE_AUTO: an empty row, never read)
+    //                            reg_tile<BM, BN, WM, WN, NBUF, BK, MW_F32, MW_SPLIT>(resident, cost)
+    t[TSOD_TILE_128x128]          = reg_tile<128, 128, 64, 64, 2, 32, 2, 0>(2, 1.00f);
+    t[TSOD_TILE_128x64]           = reg_tile<128, 64, 64, 32, 2, 32, 2, 0>(2, 1.06f);
+    t[TSOD_TILE_64x64]            = reg_tile<64, 64, 32, 32, 2, 32, 4, 2>(4, 1.15f);
+    t[TSOD_TILE_64x128]           = reg_tile<64, 128, 32, 64, 2, 32, 2, 0>(2, 1.06f);
+    t[TSOD_TILE_128x128_W8]       = reg_tile<128, 128, 64, 32, 2, 32, 4, 0>(2, 1.00f);
+    t[TSOD_TILE_128x64_W8]        = reg_tile<128, 64, 32, 32, 2, 32, 4, 0>(2, 1.06f);
+    t[TSOD_TILE_256x128_W8]       = reg_tile<256, 128, 64, 64, 2, 32, 2, 0>(1, 0.98f);
+    t[TSOD_TILE_64x64_S1]         = reg_tile<64, 64, 32, 32, 1, 32, 6, 5>(6, 1.20f);
+    t[TSOD_TILE_128x64_W8_S1]     = reg_tile<128, 64, 32, 32, 1, 32, 6, 3>(3, 1.10f);
+    t[TSOD_TILE_64x64_S1_K64]     = reg_tile<64, 64, 32, 32, 1, 64, 4, 2>(4, 1.10f);
+    t[TSOD_TILE_128x64_W8_S1_K64] = reg_tile<128, 64, 32, 32, 1, 64, 4, 0>(2, 1.05f);
+    t[TSOD_TILE_64x64_W1_S1]      = reg_tile<64, 64, 64, 64, 1, 32, 2, 0>(8, 1.40f);
+    t[TSOD_TILE_128x64_W2_S1]     = reg_tile<128, 64, 64, 64, 1, 32, 2, 0>(4, 1.35f);
+    t[TSOD_TILE_128x64_S1]        = reg_tile<128, 64, 64, 32, 1, 32, 4, 4>(4, 1.12f);
+    t[TSOD_TILE_64x128_S1]        = reg_tile<64, 128, 32, 64, 1, 32, 4, 4>(4, 1.12f);
+    t[TSOD_TILE_128x128_S1]       = reg_tile<128, 128, 64, 64, 1, 32, 2, 2>(2, 1.02f);
+    //                            dma_tile<BM, BK, WAVES_K, S, WAVES_N, BF16X3, FP16X2>(resident, cost)
+    t[TSOD_TILE_D128x128]         = dma_tile<128, 16, 1, 4, 1, true, true>(2, 0.80f);
+    t[TSOD_TILE_D64x128]          = dma_tile<64, 32, 2, 3, 1, true, false>(1, 0.95f);   // (64 rows in fp16x2: six DMA slots in a
+    t[TSOD_TILE_D256x128]         = dma_tile<256, 16, 1, 4, 1, true, true>(1, 0.72f);   //  12-MFMA phase, not built)
+    t[TSOD_TILE_D64x128_S2]       = dma_tile<64, 32, 2, 2, 1, true, false>(2, 0.98f);
+    t[TSOD_TILE_D128x256]         = dma_tile<128, 16, 1, 4, 2, true, true>(1, 0.74f);
+    t[TSOD_TILE_D128x128_K32]     = dma_tile<128, 32, 2, 3, 1, true, true>(1, 0.70f);
+    t[TSOD_TILE_D192x128]         = dma_tile<192, 16, 1, 4, 1, false, true>(1, 0.74f);
+    t[TSOD_TILE_D64x128_K64]      = dma_tile<64, 64, 4, 3, 1, false, true>(1, 0.80f);
+    return t;
+}();
+
+// workgroups per CU: the f32 figure (VGPR / LDS bound), for the split arithmetics additionally capped by their larger LDS
+// footprint (sized with three planes per operand, fp16x2 included)
 int residency(int tile, int prec) {
-    const TileInfo &t = kTiles[tile];
+    const Tile &t = kTiles[tile];
     if (!prec) return t.resident;
     const int lds = t.dma ? t.nbuf * dma_stage_bytes(t.bm, t.bk, t.bn) : t.nbuf * 3 * (t.bm + t.bn) * (t.bk / 2) * 4;
     const int fit = 160 * 1024 / lds;
@@ -1970,13 +2037,9 @@ int validate(const tsod_conv2d_desc *d) {
     TSOD_REQUIRE(d->act >= TSOD_ACT_NONE && d->act <= TSOD_ACT_RELU, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(d->tile >= 0 && d->tile < TSOD_TILE_COUNT && d->split_k >= -2 && d->split_k <= 64, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(d->precision == TSOD_PREC_F32 || d->precision == TSOD_PREC_BF16X3 || d->precision == TSOD_PREC_FP16X2, TSOD_ERR_INVALID_ARG);
-    TSOD_REQUIRE(d->precision == TSOD_PREC_F32 || d->tile == TSOD_TILE_AUTO || kTiles[d->tile].bf16x3, TSOD_ERR_UNSUPPORTED);
-    TSOD_REQUIRE((d->tile != TSOD_TILE_D192x128 && d->tile != TSOD_TILE_D64x128_K64) || d->precision == TSOD_PREC_FP16X2, TSOD_ERR_UNSUPPORTED);   // (fp16x2 only)
-    TSOD_REQUIRE(d->precision != TSOD_PREC_F32 || d->tile == TSOD_TILE_AUTO || !kTiles[d->tile].dma, TSOD_ERR_UNSUPPORTED);
-    if (d->precision == TSOD_PREC_FP16X2) {                       // (the register-staged bf16x3 tiles and the 128x128 / 32-k LDS-DMA tile)
-        TSOD_REQUIRE(d->tile == TSOD_TILE_AUTO || fp16x2_tile(d->tile), TSOD_ERR_UNSUPPORTED);
+    TSOD_REQUIRE(d->tile == TSOD_TILE_AUTO || kTiles[d->tile].launch[d->precision], TSOD_ERR_UNSUPPORTED);   // (not built in it)
+    if (d->precision == TSOD_PREC_FP16X2)
         TSOD_REQUIRE(d->a_scale_exp >= -24 && d->a_scale_exp <= 24 && d->w_scale_exp >= -40 && d->w_scale_exp <= 40, TSOD_ERR_INVALID_ARG);
-    }
     const int64_t M = (int64_t)d->N * d->OH * d->OW;
     TSOD_REQUIRE(M < (int64_t)INT_MAX, TSOD_ERR_UNSUPPORTED);
     if (d->c2 != 0) {                                   // second source: a strided 1x1 tap of another tensor
@@ -2158,10 +2221,7 @@ Sched resolve(const tsod_conv2d_desc *d) {
     best.cost = 1e300;
     for (int t = 1; t < TSOD_TILE_COUNT; ++t) {
         if (d->tile != TSOD_TILE_AUTO && d->tile != t) continue;
-        if (d->precision && !kTiles[t].bf16x3) continue;
-        if (!d->precision && kTiles[t].dma) continue;
-        if ((t == TSOD_TILE_D192x128 || t == TSOD_TILE_D64x128_K64) && d->precision != TSOD_PREC_FP16X2) continue;
-        if (d->precision == TSOD_PREC_FP16X2 && !fp16x2_tile(t)) continue;
+        if (!kTiles[t].launch[d->precision]) continue;
         if (!tile_ok_for(d, t)) continue;        // (also an explicitly named tile: the caller gets TSOD_ERR_UNSUPPORTED)
         if (d->split_k != 0) {
             const Sched s = make_sched(d, t, d->split_k);
@@ -2180,23 +2240,11 @@ Sched resolve(const tsod_conv2d_desc *d) {
     return best;
 }
 
-template <int BM, int BK, int WAVES_K, int S, int WAVES_N = 1, int NPL = 3>
-void launch_dma_tile(const ConvParams &p, int grid, hipStream_t s) {
-    if constexpr (NPL == 2) {
-        if (p.chan_tab) {                                         // 1x1 over several channel segments (never balanced: make_sched)
-            hipLaunchKernelGGL((conv_dma_kernel<BM, BK, WAVES_K, S, false, WAVES_N, NPL, true>), dim3(grid), dim3((BM / 32) * WAVES_K * WAVES_N * 64), 0, s, p);
-            return;
-        }
-    }
-    if (p.sk_q > 0)
-        hipLaunchKernelGGL((conv_dma_kernel<BM, BK, WAVES_K, S, true, WAVES_N, NPL>), dim3(grid), dim3((BM / 32) * WAVES_K * WAVES_N * 64), 0, s, p);
-    else
-        hipLaunchKernelGGL((conv_dma_kernel<BM, BK, WAVES_K, S, false, WAVES_N, NPL>), dim3(grid), dim3((BM / 32) * WAVES_K * WAVES_N * 64), 0, s, p);
-}
-
-template <int BM, int BN, int WM, int WN, int MW, int NBUF = 2, int BK = 32, int PREC = 0>
-void launch_tile(const ConvParams &p, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, MW, NBUF, BK, PREC>), dim3(grid), dim3(64 * (BM / WM) * (BN / WN)), 0, s, p);
+// bytes of the weight image an arithmetic reads: f32 [Cout][K]; bf16x3 [Cout][ceil(K/8)][hi|mid|lo][8] bf16 = 48 bytes per 8 k
+// (tsod_pack_conv_weight_bf16x3); fp16x2 [Cout][ceil(K/8)][hi|lo][8] fp16 = 32 bytes per 8 k (tsod_pack_conv_weight_fp16x2)
+uint64_t weight_image_bytes(int prec, int Cout, int K) {
+    const uint64_t groups = (uint64_t)Cout * ((K + 7) / 8);
+    return prec == TSOD_PREC_BF16X3 ? groups * 48 : prec == TSOD_PREC_FP16X2 ? groups * 32 : (uint64_t)Cout * K * sizeof(float);
 }
 
 }  // namespace
@@ -2259,10 +2307,7 @@ extern "C" int tsod_conv2d_dual_f32(const tsod_conv2d_desc *d, const float *in, 
         TSOD_REQUIRE(in2_bytes < 0xFFFFFFF0ull, TSOD_ERR_UNSUPPORTED);
         p.in2_bytes = (unsigned)in2_bytes;
         const uint64_t in_bytes = (uint64_t)d->N * d->H * d->W * d->in_pitch * sizeof(float);
-        // bf16x3 weights are pre-split: [Cout][ceil(K/8)][hi|mid|lo][8] bf16 = 48 bytes per 8 k (tsod_pack_conv_weight_bf16x3)
-        const uint64_t w_bytes = d->precision == TSOD_PREC_BF16X3 ? (uint64_t)d->Cout * ((p.K + 7) / 8) * 48
-                                 : d->precision == TSOD_PREC_FP16X2 ? (uint64_t)d->Cout * ((p.K + 7) / 8) * 32
-                                                                    : (uint64_t)d->Cout * p.K * sizeof(float);
+        const uint64_t w_bytes = weight_image_bytes(d->precision, d->Cout, p.K);
         const uint64_t out_bytes = (uint64_t)p.M * d->out_pitch * sizeof(float);
         const uint64_t res_bytes = residual ? (uint64_t)p.M * d->res_pitch * sizeof(float) : 0;
         // 32-bit buffer offsets: one activation tensor must stay below 4 GiB (shard the batch otherwise)
@@ -2309,66 +2354,14 @@ extern "C" int tsod_conv2d_dual_f32(const tsod_conv2d_desc *d, const float *in, 
     TSOD_REQUIRE((reinterpret_cast<uintptr_t>(d->amax_out) & 63u) == 0 && (reinterpret_cast<uintptr_t>(d->amax_in) & 63u) == 0 &&
                      (reinterpret_cast<uintptr_t>(d->amax_in2) & 63u) == 0, TSOD_ERR_ALIGNMENT);
     if (d->precision == TSOD_PREC_FP16X2) {
-        TSOD_REQUIRE(fp16x2_tile(sc.tile), TSOD_ERR_UNSUPPORTED);
         p.range_flag = d->range_flag;
         p.amax_in = d->amax_in;                                   // (NULL: the static a_scale_exp)
         p.amax_in2 = (d->amax_in != nullptr && p.c2 > 0) ? d->amax_in2 : nullptr;
         p.w_scale_exp = d->w_scale_exp;
         p.a_scale = ldexpf(1.f, d->a_scale_exp);
         p.acc_scale = ldexpf(1.f, -(d->a_scale_exp + d->w_scale_exp));
-        switch (sc.tile) {
-            case TSOD_TILE_64x64_S1: launch_tile<64, 64, 32, 32, 5, 1, 32, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_128x64_W8_S1: launch_tile<128, 64, 32, 32, 3, 1, 32, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_64x64_S1_K64: launch_tile<64, 64, 32, 32, 2, 1, 64, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_128x64_S1: launch_tile<128, 64, 64, 32, 4, 1, 32, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_64x128_S1: launch_tile<64, 128, 32, 64, 4, 1, 32, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_128x128_S1: launch_tile<128, 128, 64, 64, 2, 1, 32, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D128x128_K32: launch_dma_tile<128, 32, 2, 3, 1, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D128x128: launch_dma_tile<128, 16, 1, 4, 1, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D256x128: launch_dma_tile<256, 16, 1, 4, 1, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D128x256: launch_dma_tile<128, 16, 1, 4, 2, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D192x128: launch_dma_tile<192, 16, 1, 4, 1, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D64x128_K64: launch_dma_tile<64, 64, 4, 3, 1, 2>(p, sc.grid, s); break;
-            default: launch_tile<64, 64, 32, 32, 2, 2, 32, 2>(p, sc.grid, s); break;      // TSOD_TILE_64x64 (two LDS stages)
-        }
-        return tsod_launch_status();
     }
-    if (d->precision == TSOD_PREC_BF16X3) {
-        switch (sc.tile) {
-            case TSOD_TILE_64x64_S1: launch_tile<64, 64, 32, 32, 5, 1, 32, 1>(p, sc.grid, s); break;
-            case TSOD_TILE_128x64_W8_S1: launch_tile<128, 64, 32, 32, 3, 1, 32, 1>(p, sc.grid, s); break;
-            case TSOD_TILE_64x64_S1_K64: launch_tile<64, 64, 32, 32, 2, 1, 64, 1>(p, sc.grid, s); break;
-            case TSOD_TILE_128x64_S1: launch_tile<128, 64, 64, 32, 4, 1, 32, 1>(p, sc.grid, s); break;
-            case TSOD_TILE_64x128_S1: launch_tile<64, 128, 32, 64, 4, 1, 32, 1>(p, sc.grid, s); break;
-            case TSOD_TILE_128x128_S1: launch_tile<128, 128, 64, 64, 2, 1, 32, 1>(p, sc.grid, s); break;
-            case TSOD_TILE_D128x128: launch_dma_tile<128, 16, 1, 4>(p, sc.grid, s); break;
-            case TSOD_TILE_D64x128: launch_dma_tile<64, 32, 2, 3>(p, sc.grid, s); break;
-            case TSOD_TILE_D256x128: launch_dma_tile<256, 16, 1, 4>(p, sc.grid, s); break;
-            case TSOD_TILE_D64x128_S2: launch_dma_tile<64, 32, 2, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D128x256: launch_dma_tile<128, 16, 1, 4, 2>(p, sc.grid, s); break;
-            case TSOD_TILE_D128x128_K32: launch_dma_tile<128, 32, 2, 3>(p, sc.grid, s); break;
-            default: launch_tile<64, 64, 32, 32, 2, 2, 32, 1>(p, sc.grid, s); break;      // TSOD_TILE_64x64 (two LDS stages)
-        }
-        return tsod_launch_status();
-    }
-    switch (sc.tile) {
-        case TSOD_TILE_128x128: launch_tile<128, 128, 64, 64, 2>(p, sc.grid, s); break;
-        case TSOD_TILE_128x64: launch_tile<128, 64, 64, 32, 2>(p, sc.grid, s); break;
-        case TSOD_TILE_64x128: launch_tile<64, 128, 32, 64, 2>(p, sc.grid, s); break;
-        case TSOD_TILE_128x128_W8: launch_tile<128, 128, 64, 32, 4>(p, sc.grid, s); break;
-        case TSOD_TILE_128x64_W8: launch_tile<128, 64, 32, 32, 4>(p, sc.grid, s); break;
-        case TSOD_TILE_256x128_W8: launch_tile<256, 128, 64, 64, 2>(p, sc.grid, s); break;
-        case TSOD_TILE_64x64_S1: launch_tile<64, 64, 32, 32, 6, 1>(p, sc.grid, s); break;
-        case TSOD_TILE_128x64_W8_S1: launch_tile<128, 64, 32, 32, 6, 1>(p, sc.grid, s); break;
-        case TSOD_TILE_64x64_S1_K64: launch_tile<64, 64, 32, 32, 4, 1, 64>(p, sc.grid, s); break;
-        case TSOD_TILE_128x64_W8_S1_K64: launch_tile<128, 64, 32, 32, 4, 1, 64>(p, sc.grid, s); break;
-        case TSOD_TILE_64x64_W1_S1: launch_tile<64, 64, 64, 64, 2, 1>(p, sc.grid, s); break;
-        case TSOD_TILE_128x64_W2_S1: launch_tile<128, 64, 64, 64, 2, 1>(p, sc.grid, s); break;
-        case TSOD_TILE_128x64_S1: launch_tile<128, 64, 64, 32, 4, 1>(p, sc.grid, s); break;
-        case TSOD_TILE_64x128_S1: launch_tile<64, 128, 32, 64, 4, 1>(p, sc.grid, s); break;
-        case TSOD_TILE_128x128_S1: launch_tile<128, 128, 64, 64, 2, 1>(p, sc.grid, s); break;
-        default: launch_tile<64, 64, 32, 32, 4>(p, sc.grid, s); break;
-    }
+    kTiles[sc.tile].launch[d->precision](p, sc.grid, s);
     return tsod_launch_status();
 }
 
@@ -2405,7 +2398,7 @@ extern "C" int tsod_pack_conv_weight_f32(const float *w_oihw, int32_t Cout, int3
 
 extern "C" size_t tsod_conv_weight_bf16x3_bytes(int32_t Cout, int32_t K) {
     if (Cout <= 0 || K <= 0) return 0;
-    return (size_t)Cout * ((K + 7) / 8) * 48;
+    return weight_image_bytes(TSOD_PREC_BF16X3, Cout, K);
 }
 
 extern "C" int tsod_pack_conv_weight_bf16x3(const float *w_packed, int32_t Cout, int32_t K, void *w_bf16x3, tsod_stream_t stream) {
@@ -2421,7 +2414,7 @@ extern "C" int tsod_pack_conv_weight_bf16x3(const float *w_packed, int32_t Cout,
 
 extern "C" size_t tsod_conv_weight_fp16x2_bytes(int32_t Cout, int32_t K) {
     if (Cout <= 0 || K <= 0) return 0;
-    return (size_t)Cout * ((K + 7) / 8) * 32;
+    return weight_image_bytes(TSOD_PREC_FP16X2, Cout, K);
 }
 
 extern "C" int tsod_pack_conv_weight_fp16x2(const float *w_packed, int32_t Cout, int32_t K, int32_t w_scale_exp, void *w_fp16x2,

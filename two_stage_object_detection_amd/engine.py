@@ -11,7 +11,6 @@ Data layout in HBM: every activation is NHWC f32, channel pitch a multiple of 4,
 from __future__ import annotations
 
 import os
-import re
 
 from collections import OrderedDict
 from ctypes import byref, c_int32
@@ -611,8 +610,7 @@ class Plan:
             self._refresh_amax_for(st)
             cands = []
             for prec in (precisions if precisions is not None else (int(d.precision),)):
-                for tile in (_ffi.BF16X3_TILE_IDS if prec == _ffi.PREC_BF16X3 else (_ffi.FP16X2_TILE_IDS if prec == _ffi.PREC_FP16X2
-                                                                                    else _ffi.TILE_IDS)):
+                for tile in _ffi.tile_ids(prec):
                     for split in (splits or (1, -1, -2, 2, 3, 4, 6, 8, 12, 16, 24, 32)):
                         if split > 1 and ksteps // split < 2:
                             continue
@@ -689,8 +687,7 @@ class Plan:
                 st.choose(tile, split, prec)
                 slabs = max(0, int(lib().tsod_conv2d_workspace_bytes(byref(d))) - (256 << 10))
                 wbytes = d.Cout * K * (6 if prec == _ffi.PREC_BF16X3 else 4)   # (fp16x2: 4)
-                m = re.search(r"(\d+)x(\d+)", TILE_NAMES[tile])
-                tiles_m = -(-M // int(m.group(1))) if m else 8
+                tiles_m = -(-M // _ffi.TILES[tile].rows)
                 return 2 * slabs + wbytes * (tiles_m if split == -2 else 8)
             close = [c for c in second_look if c[0] <= best[0] * 1.02]
             if len(close) > 1:

@@ -365,7 +365,7 @@ def tune_conv(x: torch.Tensor, w_packed: torch.Tensor, reps: int = 5, precisions
     ksteps = (K + 31) // 32
     best = None
     for prec in precisions:
-        for tile in (_ffi.BF16X3_TILE_IDS if prec == _ffi.PREC_BF16X3 else (_ffi.FP16X2_TILE_IDS if prec == _ffi.PREC_FP16X2 else _ffi.TILE_IDS)):
+        for tile in _ffi.tile_ids(prec):
             for split in (1, -1, -2, 2, 3, 4, 6, 8, 12, 16, 24, 32):
                 if split > 1 and ksteps // split < 2:
                     continue
