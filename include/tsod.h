@@ -501,6 +501,32 @@ int tsod_proposal_targets_f32(const float *roi, int32_t R, const float *bbox, in
                               float neg_iou_thresh_low, float *sample_roi, float *gt_roi_loc, int64_t *gt_roi_label,
                               int32_t *counts, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
 
+/* ---- the losses of the ground-truth-conditioned forward (FasterRCNNTrainer, nets/frcnn_training.py:179-342) ----------
+ * Both are additive restatements of the reference's loss arithmetic on the outputs of the kernels above; one workgroup per
+ * image, sums in f64 in a fixed order (deterministic, no atomics, no workspace), each loss rounded once to f32.
+ * smooth L1 (nets/frcnn_training.py:220-238, sigma = rpn_sigma / roi_sigma): over the positives (label > 0) and their 4
+ * offsets, d = |gt - pred|, d < 1/sigma^2 ? 0.5 sigma^2 d^2 : d - 0.5/sigma^2, summed and divided by 4 * n_pos - NaN without a
+ * positive (0/0, as the reference).  Cross-entropy: log-sum-exp minus the target logit, mean over the counted rows - NaN when
+ * there is none.  status[b] = number of labels of image b the reference would index out of bounds with (IndexError there);
+ * such a label is never used as an index and its row does not count.
+ *
+ * tsod_rpn_losses_f32: nets/frcnn_training.py:262-274.  rpn_out [B*n_pix][pitch] is the fused RPN conv's output (loc in
+ *   columns [0,4A), (bg, fg) logits in [4A,6A); anchor t = pixel*A + a, quirk Q9), read in place.
+ *   gt_loc [B][n_pix*A][4], gt_label [B][n_pix*A] int64 in {-1 ignore, 0, 1} (tsod_anchor_targets_f32) ->
+ *   out [B][2] = (loc loss, cls loss with ignore_index = -1), status [B].
+ * tsod_roi_losses_f32: nets/frcnn_training.py:300-331.  cls_locs [B*S] rows of 4*n_class (pitch loc_pitch), scores [B*S]
+ *   rows of n_class logits (pitch score_pitch) - column slices of the fused head GEMM's output like tsod_detections_f32's -
+ *   sample_roi / gt_roi_loc [B][S][4], gt_roi_label [B][S] int64 in [0, n_class) ->
+ *   anchors_pred [B][S][4] = loc2bbox(sample_roi, cls_loc[row, gt_label]) (the decode of tsod_loc2bbox_f32; NaN rows for an
+ *   out-of-range label), classes_pred [B][S] int64 / classes_score_pred [B][S] = arg-max / max of the raw logits (first
+ *   maximum wins, quirk Q11), out [B][2] = (loc loss, cls loss over all n_class logits), status [B]. */
+int tsod_rpn_losses_f32(const float *rpn_out, int32_t pitch, int32_t A, int32_t B, int32_t n_pix, const float *gt_loc,
+                        const int64_t *gt_label, float sigma, float *out, int32_t *status, tsod_stream_t stream);
+int tsod_roi_losses_f32(const float *cls_locs, int32_t loc_pitch, const float *scores, int32_t score_pitch,
+                        const float *sample_roi, const float *gt_roi_loc, const int64_t *gt_roi_label, int32_t B, int32_t S,
+                        int32_t n_class, float sigma, float *anchors_pred, int64_t *classes_pred, float *classes_score_pred,
+                        float *out, int32_t *status, tsod_stream_t stream);
+
 /* ---- input step (the step before the path) ----------------------------------------------
  * dataset/dataloader.py:35-44 + dataset/transform.py:14-17: a decoded RGB image becomes an f32 CHW tensor with
  * values 0..255 and is resized to the detector's fixed size by torchvision v2 Resize, i.e. ATen's antialiased

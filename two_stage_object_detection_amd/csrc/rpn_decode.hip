@@ -12,26 +12,6 @@
 
 namespace {
 
-struct Box { float x1, y1, x2, y2; };
-
-__device__ __forceinline__ Box decode_box(float ax1, float ay1, float ax2, float ay2,
-                                          float dx, float dy, float dw, float dh) {
-    const float w = ax2 - ax1;
-    const float h = ay2 - ay1;
-    const float cx = ax1 + 0.5f * w;
-    const float cy = ay1 + 0.5f * h;
-    const float ncx = dx * w + cx;
-    const float ncy = dy * h + cy;
-    const float nw = expf(dw) * w;
-    const float nh = expf(dh) * h;
-    Box o;
-    o.x1 = ncx - 0.5f * nw;
-    o.y1 = ncy - 0.5f * nh;
-    o.x2 = ncx + 0.5f * nw;
-    o.y2 = ncy + 0.5f * nh;
-    return o;
-}
-
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 __global__ void __launch_bounds__(256)
@@ -60,7 +40,7 @@ rpn_decode_kernel(const float *__restrict__ locs, int loc_pitch, const float *__
             reinterpret_cast<float4 *>(anchors_out)[r] = make_float4(ax1, ay1, ax2, ay2);
         }
         const float *l = locs + ((long)b * HW + pix) * loc_pitch + 4 * a;
-        Box o = decode_box(ax1, ay1, ax2, ay2, l[0], l[1], l[2], l[3]);
+        tsod_box o = tsod_decode_box(ax1, ay1, ax2, ay2, l[0], l[1], l[2], l[3]);
         o.x1 = clampf(o.x1, 0.f, clamp_x);
         o.x2 = clampf(o.x2, 0.f, clamp_x);
         o.y1 = clampf(o.y1, 0.f, clamp_y);
@@ -96,7 +76,7 @@ loc2bbox_kernel(const float *__restrict__ src, const float *__restrict__ loc, lo
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
         const float4 s = reinterpret_cast<const float4 *>(src)[t];
         const float4 l = reinterpret_cast<const float4 *>(loc)[t];
-        const Box o = decode_box(s.x, s.y, s.z, s.w, l.x, l.y, l.z, l.w);
+        const tsod_box o = tsod_decode_box(s.x, s.y, s.z, s.w, l.x, l.y, l.z, l.w);
         reinterpret_cast<float4 *>(out)[t] = make_float4(o.x1, o.y1, o.x2, o.y2);
     }
 }
@@ -108,7 +88,7 @@ proposal_decode_kernel(const float *__restrict__ anchor, const float *__restrict
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
         const float4 a = reinterpret_cast<const float4 *>(anchor)[t];
         const float4 l = reinterpret_cast<const float4 *>(loc)[t];
-        Box o = decode_box(a.x, a.y, a.z, a.w, l.x, l.y, l.z, l.w);
+        tsod_box o = tsod_decode_box(a.x, a.y, a.z, a.w, l.x, l.y, l.z, l.w);
         o.x1 = clampf(o.x1, 0.f, clamp_x);
         o.x2 = clampf(o.x2, 0.f, clamp_x);
         o.y1 = clampf(o.y1, 0.f, clamp_y);
@@ -142,7 +122,7 @@ detections_kernel(const float *__restrict__ cls_locs, int loc_pitch, const float
     if (lane == 0) {
         const float *l = cls_locs + (long)k * loc_pitch + bi * 4;
         const float *r = rois + (long)k * 4;
-        Box o = decode_box(r[0], r[1], r[2], r[3], l[0], l[1], l[2], l[3]);
+        tsod_box o = tsod_decode_box(r[0], r[1], r[2], r[3], l[0], l[1], l[2], l[3]);
         float *d = det + (long)k * 6;
         d[0] = o.x1; d[1] = o.y1; d[2] = o.x2; d[3] = o.y2; d[4] = best; d[5] = (float)bi;
     }

@@ -54,6 +54,26 @@ __device__ __forceinline__ unsigned tsod_amax_reduce_bits(unsigned mine) {
     return (unsigned)__builtin_amdgcn_readfirstlane((int)mine);
 }
 static_assert(TSOD_AMAX_WORDS == 64, "one word per lane of a wave");
+// utils/loc_bbox_iou.py:29-61 (loc2bbox) for one box, op for op (the library is built with -ffp-contract=off): the one decode
+// of tsod_rpn_decode_f32, tsod_proposal_decode_f32, tsod_loc2bbox_f32, tsod_detections_f32 and tsod_roi_losses_f32
+struct tsod_box { float x1, y1, x2, y2; };
+__device__ __forceinline__ tsod_box tsod_decode_box(float ax1, float ay1, float ax2, float ay2,
+                                                    float dx, float dy, float dw, float dh) {
+    const float w = ax2 - ax1;
+    const float h = ay2 - ay1;
+    const float cx = ax1 + 0.5f * w;
+    const float cy = ay1 + 0.5f * h;
+    const float ncx = dx * w + cx;
+    const float ncy = dy * h + cy;
+    const float nw = expf(dw) * w;
+    const float nh = expf(dh) * h;
+    tsod_box o;
+    o.x1 = ncx - 0.5f * nw;
+    o.y1 = ncy - 0.5f * nh;
+    o.x2 = ncx + 0.5f * nw;
+    o.y2 = ncy + 0.5f * nh;
+    return o;
+}
 // fp16x2 activation exponent for a tensor whose abs-max has these bits: 2^e * absmax < 2^15 (fp16 ends at 65504), e in [-24, 24]
 // (zero / subnormal abs-max: 24; inf: -24 - the range flag of the launch then reports the non-finite input)
 __device__ __forceinline__ int tsod_fp16x2_exp_from_bits(unsigned bits) {

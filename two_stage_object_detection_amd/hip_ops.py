@@ -711,6 +711,62 @@ def proposal_targets(roi: torch.Tensor, bbox: torch.Tensor, label: torch.Tensor,
     return sample_roi, gt_roi_loc, gt_roi_label, counts
 
 
+def rpn_losses(rpn_out: torch.Tensor, A: int, gt_loc: torch.Tensor, gt_label: torch.Tensor, sigma: float = 1.0):
+    """The RPN's two losses per image (tsod_rpn_losses_f32; nets/frcnn_training.py:220-238, 262-274).
+    rpn_out [B*h*w, >= 6A] with row stride = pitch: the fused loc + score conv output (``RegionProposalNetwork.propose``),
+    read in place; gt_loc [B, h*w*A, 4] f32, gt_label [B, h*w*A] int64 (-1 / 0 / 1) ->
+    (out [B,2] f32 = (loc loss, cls loss), status [B] int32 = labels outside {-1, 0, 1})."""
+    require_cuda(rpn_out, "rpn_losses")
+    B, n = gt_label.shape
+    if rpn_out.dim() != 2 or rpn_out.stride(1) != 1 or rpn_out.shape[1] < 6 * A or n % A or rpn_out.shape[0] != B * (n // A):
+        raise ValueError(f"rpn_losses: rpn_out {tuple(rpn_out.shape)} does not hold B={B} images of {n} anchors at A={A}")
+    if tuple(gt_loc.shape) != (B, n, 4):
+        raise ValueError(f"rpn_losses: gt_loc {tuple(gt_loc.shape)}, expected {(B, n, 4)}")
+    dev = rpn_out.device
+    gt_loc = gt_loc.to(dev, torch.float32).contiguous()
+    gt_label = gt_label.to(dev, torch.int64).contiguous()
+    out = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(lib().tsod_rpn_losses_f32(ptr(rpn_out), rpn_out.stride(0), int(A), B, n // A, ptr(gt_loc), ptr(gt_label),
+                                    float(sigma), ptr(out), ptr(status), stream_ptr()), "rpn_losses")
+    return out, status
+
+
+def roi_losses(cls_locs: torch.Tensor, scores: torch.Tensor, sample_roi: torch.Tensor, gt_roi_loc: torch.Tensor,
+               gt_roi_label: torch.Tensor, sigma: float = 1.0):
+    """The head's predictions and two losses per image (tsod_roi_losses_f32; nets/frcnn_training.py:300-331).
+    cls_locs [B,S,4*n_class], scores [B,S,n_class] (rows may be slices of the fused head GEMM's output, as for
+    ``detections``), sample_roi / gt_roi_loc [B,S,4], gt_roi_label [B,S] int64 ->
+    (anchors_pred [B,S,4], classes_pred [B,S] int64, classes_score_pred [B,S], out [B,2] = (loc loss, cls loss),
+    status [B] int32 = labels outside [0, n_class))."""
+    require_cuda(scores, "roi_losses")
+    B, S, n_class = scores.shape
+    if tuple(cls_locs.shape) != (B, S, 4 * n_class):
+        raise ValueError(f"roi_losses: cls_locs {tuple(cls_locs.shape)}, expected {(B, S, 4 * n_class)}")
+    for name, t, shp in (("sample_roi", sample_roi, (B, S, 4)), ("gt_roi_loc", gt_roi_loc, (B, S, 4)),
+                         ("gt_roi_label", gt_roi_label, (B, S))):
+        if tuple(t.shape) != shp:
+            raise ValueError(f"roi_losses: {name} {tuple(t.shape)}, expected {shp}")
+    dev = scores.device
+    lp, sp = _row_pitch(cls_locs, 4 * n_class), _row_pitch(scores, n_class)
+    if lp is None:
+        cls_locs, lp = cls_locs.contiguous(), 4 * n_class
+    if sp is None:
+        scores, sp = scores.contiguous(), n_class
+    sample_roi = sample_roi.to(dev, torch.float32).contiguous()
+    gt_roi_loc = gt_roi_loc.to(dev, torch.float32).contiguous()
+    gt_roi_label = gt_roi_label.to(dev, torch.int64).contiguous()
+    anchors_pred = torch.empty((B, S, 4), dtype=torch.float32, device=dev)
+    classes_pred = torch.empty((B, S), dtype=torch.int64, device=dev)
+    classes_score_pred = torch.empty((B, S), dtype=torch.float32, device=dev)
+    out = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(lib().tsod_roi_losses_f32(ptr(cls_locs), lp, ptr(scores), sp, ptr(sample_roi), ptr(gt_roi_loc), ptr(gt_roi_label), B, S,
+                                    n_class, float(sigma), ptr(anchors_pred), ptr(classes_pred), ptr(classes_score_pred),
+                                    ptr(out), ptr(status), stream_ptr()), "roi_losses")
+    return anchors_pred, classes_pred, classes_score_pred, out, status
+
+
 # ----------------------------------------------------------------------------- input step
 _RESIZE_TABLES: dict = {}
 
