@@ -527,6 +527,50 @@ int tsod_roi_losses_f32(const float *cls_locs, int32_t loc_pitch, const float *s
                         int32_t n_class, float sigma, float *anchors_pred, int64_t *classes_pred, float *classes_score_pred,
                         float *out, int32_t *status, tsod_stream_t stream);
 
+/* ---- the backward of those losses into the eight head parameters (FasterRCNNTrainer(head_grads=True), frozen backbone) -----
+ * What autograd computes behind the reference's losses[-1].backward() for rpn.loc / rpn.score / head.cls_loc / head.score.
+ * `up` [5] f32 on the device = d out / d (rpn_loc, rpn_cls, roi_loc, roi_cls, total loss): loss k is weighted by up[k] + up[4],
+ * times inv_B (the batch mean).  No host synchronisation, no float atomics: run to run bit-identical.  Torch's empty sets:
+ * no positive / no counted row gives zero gradients from that term (its loss is NaN); |d| == 0 gives abs's zero subgradient.
+ *
+ * tsod_proposal_targets_src_f32: tsod_proposal_targets_f32 plus sample_src [n_sample] int32 = the row of cat(roi, bbox) each
+ *   sample was taken from (the reference's keep_index, nets/frcnn_training.py:165): < R a proposal, >= R a ground-truth box.
+ * tsod_rpn_losses_grad_f32: d rpn_out [B*n_pix][d_pitch] of the two RPN losses, in the fused layout tsod_rpn_losses_f32 reads
+ *   (loc columns [0,4A), logits [4A,6A), zero columns after); n_rows [B][2] int32 out = (positives, counted rows).
+ * tsod_roi_losses_grad_f32: d both [B*S][d_pitch] of the two head losses in the fused head GEMM's layout (cls_loc columns
+ *   [0,4 n_class), score columns [4 n_class, 5 n_class), zero after) and d sample_roi [B][S][4] through the regression target
+ *   gt_roi_loc = bbox2loc(sample_roi, gt) (utils/loc_bbox_iou.py:63-88; zero rows for non-positive samples).
+ * tsod_rpn_roi_scatter_f32: adds d sample_roi into the loc columns of d rpn_out along the index chain sample_src (< R) ->
+ *   keep_idx [B][R] (tsod_nms_f32, with its padding) -> sort_idx [B][n_pre] (tsod_sort_topk_desc_f32) -> anchor t; the
+ *   unclamped decode of anchors[t] with rpn_out's offsets is recomputed, the clamp passes where 0 <= v <= clamp (x: clamp_x,
+ *   y: clamp_y, inclusive), then loc2bbox's backward.  Sample rows reaching one anchor are summed in ascending order by one
+ *   thread.  S <= 1024.
+ * tsod_wgrad_f32: dW[n][k] = sum_m dy[m][n] x[m][k], db[n] = sum_m dy[m][n] on the f32 matrix cores (v_mfma_f32_32x32x2_f32),
+ *   dy [M][dy_pitch], x [M][x_pitch] (16-byte aligned, K and x_pitch multiples of 4).  Rows [0,n0) of the result go to dw0
+ *   [n0][K] / db0 [n0], rows [n0,n0+n1) to dw1 / db1 (db may be NULL), rows past n0+n1 are dropped.  accumulate = 0 writes,
+ *   1 adds to what is there.  M is split across workgroups (about 512 of them); the M-slices' partial tiles are summed in
+ *   slice order by a second launch.  workspace: tsod_wgrad_workspace_bytes(M, N, K). */
+int tsod_proposal_targets_src_f32(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
+                                  int32_t n_sample, int32_t pos_per_image, float pos_iou_thresh, float neg_iou_thresh_high,
+                                  float neg_iou_thresh_low, float *sample_roi, float *gt_roi_loc, int64_t *gt_roi_label,
+                                  int32_t *counts, int32_t *sample_src, void *workspace, size_t workspace_bytes,
+                                  tsod_stream_t stream);
+int tsod_rpn_losses_grad_f32(const float *rpn_out, int32_t pitch, int32_t A, int32_t B, int32_t n_pix, const float *gt_loc,
+                             const int64_t *gt_label, float sigma, const float *up, float inv_B, int32_t *n_rows,
+                             float *d_rpn_out, int32_t d_pitch, tsod_stream_t stream);
+int tsod_roi_losses_grad_f32(const float *cls_locs, int32_t loc_pitch, const float *scores, int32_t score_pitch,
+                             const float *sample_roi, const float *gt_roi_loc, const int64_t *gt_roi_label, int32_t B, int32_t S,
+                             int32_t n_class, float sigma, const float *up, float inv_B, float *d_both, int32_t d_pitch,
+                             float *d_sample_roi, tsod_stream_t stream);
+int tsod_rpn_roi_scatter_f32(const float *d_sample_roi, const int32_t *sample_src, int32_t B, int32_t S, int32_t R,
+                             const int32_t *keep_idx, const int32_t *sort_idx, int32_t n_pre, const float *rpn_out, int32_t pitch,
+                             const float *anchors, int32_t A, int32_t n_pix, float clamp_x, float clamp_y, float *d_rpn_out,
+                             int32_t d_pitch, tsod_stream_t stream);
+size_t tsod_wgrad_workspace_bytes(int64_t M, int32_t N, int32_t K);
+int tsod_wgrad_f32(const float *dy, int64_t M, int32_t N, int32_t dy_pitch, const float *x, int32_t K, int32_t x_pitch,
+                   int32_t n0, float *dw0, float *db0, int32_t n1, float *dw1, float *db1, int32_t accumulate, void *workspace,
+                   size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- input step (the step before the path) ----------------------------------------------
  * dataset/dataloader.py:35-44 + dataset/transform.py:14-17: a decoded RGB image becomes an f32 CHW tensor with
  * values 0..255 and is resized to the detector's fixed size by torchvision v2 Resize, i.e. ATen's antialiased

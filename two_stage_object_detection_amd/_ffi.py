@@ -199,6 +199,18 @@ _SIGNATURES = {
                                     c_void_p, c_void_p]),
     "tsod_roi_losses_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                     c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tsod_proposal_targets_src_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_float,
+                                              c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_size_t, c_void_p]),
+    "tsod_rpn_losses_grad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p,
+                                         c_float, c_void_p, c_void_p, c_int32, c_void_p]),
+    "tsod_roi_losses_grad_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                         c_int32, c_float, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_void_p]),
+    "tsod_rpn_roi_scatter_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                         c_int32, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p]),
+    "tsod_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "tsod_wgrad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                               c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

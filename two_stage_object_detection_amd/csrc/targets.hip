@@ -172,7 +172,8 @@ proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__re
                        const long long *__restrict__ gt_label, const float *__restrict__ max_iou, const int *__restrict__ assign,
                        int n_sample, int pos_per_image, float pos_thr, float neg_hi, float neg_lo,
                        float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc, long long *__restrict__ gt_roi_label,
-                       int *__restrict__ neg_orig /* [n_sample] scratch */, int *__restrict__ counts /* [4] */) {
+                       int *__restrict__ neg_orig /* [n_sample] scratch */, int *__restrict__ counts /* [4] */,
+                       int *__restrict__ sample_src /* [n_sample] or nullptr: the candidate each slot came from */) {
     __shared__ int s_wave[17];
     const int tid = threadIdx.x;
     const int N = R + G;
@@ -201,6 +202,7 @@ proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__re
             if (slot < 0) continue;
             const float4 box = n < R ? roi[n] : gt[n - R];
             sample_roi[slot] = box;
+            if (sample_src != nullptr) sample_src[slot] = n;
             if (G > 0) {
                 const int g = assign[n];
                 gt_roi_loc[slot] = bbox2loc_dev(box, gt[g]);
@@ -269,11 +271,11 @@ extern "C" size_t tsod_proposal_targets_workspace_bytes(int32_t R, int32_t G, in
     return 2 * align16((size_t)(R + G) * 4) + align16((size_t)n_sample * 4);
 }
 
-extern "C" int tsod_proposal_targets_f32(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
-                                         int32_t n_sample, int32_t pos_per_image, float pos_iou_thresh,
-                                         float neg_iou_thresh_high, float neg_iou_thresh_low, float *sample_roi,
-                                         float *gt_roi_loc, int64_t *gt_roi_label, int32_t *counts, void *workspace,
-                                         size_t workspace_bytes, tsod_stream_t stream) {
+static int proposal_targets(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
+                            int32_t n_sample, int32_t pos_per_image, float pos_iou_thresh,
+                            float neg_iou_thresh_high, float neg_iou_thresh_low, float *sample_roi,
+                            float *gt_roi_loc, int64_t *gt_roi_label, int32_t *counts, void *workspace,
+                            size_t workspace_bytes, int32_t *sample_src, tsod_stream_t stream) {
     TSOD_REQUIRE(sample_roi && gt_roi_loc && gt_roi_label && counts, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(R >= 0 && G >= 0 && R + G > 0 && n_sample > 0 && pos_per_image >= 0, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE((roi || R == 0) && ((bbox && gt_label) || G == 0), TSOD_ERR_INVALID_ARG);
@@ -293,8 +295,32 @@ extern "C" int tsod_proposal_targets_f32(const float *roi, int32_t R, const floa
     hipLaunchKernelGGL(proposal_select_kernel, dim3(1), dim3(1024), 0, s, r4, R, g4, G,
                        reinterpret_cast<const long long *>(gt_label), max_iou, assign, n_sample, pos_per_image, pos_iou_thresh,
                        neg_iou_thresh_high, neg_iou_thresh_low, reinterpret_cast<float4 *>(sample_roi),
-                       reinterpret_cast<float4 *>(gt_roi_loc), reinterpret_cast<long long *>(gt_roi_label), neg_orig, counts);
+                       reinterpret_cast<float4 *>(gt_roi_loc), reinterpret_cast<long long *>(gt_roi_label), neg_orig, counts,
+                       sample_src);
     return tsod_launch_status();
+}
+
+extern "C" int tsod_proposal_targets_f32(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
+                                         int32_t n_sample, int32_t pos_per_image, float pos_iou_thresh,
+                                         float neg_iou_thresh_high, float neg_iou_thresh_low, float *sample_roi,
+                                         float *gt_roi_loc, int64_t *gt_roi_label, int32_t *counts, void *workspace,
+                                         size_t workspace_bytes, tsod_stream_t stream) {
+    return proposal_targets(roi, R, bbox, G, gt_label, n_sample, pos_per_image, pos_iou_thresh, neg_iou_thresh_high,
+                            neg_iou_thresh_low, sample_roi, gt_roi_loc, gt_roi_label, counts, workspace, workspace_bytes,
+                            nullptr, stream);
+}
+
+// the same, and sample_src[slot] = the row of cat(roi, bbox) the slot was taken from (keep_index, :165): < R a proposal,
+// >= R the ground-truth box n - R.  What the backward of the RoI-head regression loss maps each sample back with.
+extern "C" int tsod_proposal_targets_src_f32(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
+                                             int32_t n_sample, int32_t pos_per_image, float pos_iou_thresh,
+                                             float neg_iou_thresh_high, float neg_iou_thresh_low, float *sample_roi,
+                                             float *gt_roi_loc, int64_t *gt_roi_label, int32_t *counts, int32_t *sample_src,
+                                             void *workspace, size_t workspace_bytes, tsod_stream_t stream) {
+    TSOD_REQUIRE(sample_src, TSOD_ERR_INVALID_ARG);
+    return proposal_targets(roi, R, bbox, G, gt_label, n_sample, pos_per_image, pos_iou_thresh, neg_iou_thresh_high,
+                            neg_iou_thresh_low, sample_roi, gt_roi_loc, gt_roi_label, counts, workspace, workspace_bytes,
+                            sample_src, stream);
 }
 
 extern "C" int tsod_bbox2loc_f32(const float *src, const float *dst, int64_t n, float *out, tsod_stream_t stream) {

@@ -767,6 +767,121 @@ def roi_losses(cls_locs: torch.Tensor, scores: torch.Tensor, sample_roi: torch.T
     return anchors_pred, classes_pred, classes_score_pred, out, status
 
 
+# ----------------------------------------------------------------------------- head gradients (FasterRCNNTrainer(head_grads=True))
+def proposal_targets_src(roi: torch.Tensor, bbox: torch.Tensor, label: torch.Tensor, n_sample: int, pos_per_image: int,
+                         pos_iou_thresh: float, neg_iou_thresh_high: float, neg_iou_thresh_low: float):
+    """``proposal_targets`` plus sample_src [n_sample] int32: the row of cat(roi, bbox) each sample came from (< R: a
+    proposal; the reference's keep_index) (tsod_proposal_targets_src_f32)."""
+    require_cuda(roi, "proposal_targets_src")
+    dev = roi.device
+    roi, bbox = roi.contiguous(), bbox.to(dev, torch.float32).contiguous()
+    label = label.to(dev, torch.int64).contiguous()
+    R, G = roi.shape[0], bbox.shape[0]
+    sample_roi = torch.empty((n_sample, 4), dtype=torch.float32, device=dev)
+    gt_roi_loc = torch.empty((n_sample, 4), dtype=torch.float32, device=dev)
+    gt_roi_label = torch.empty((n_sample,), dtype=torch.int64, device=dev)
+    counts = torch.empty((4,), dtype=torch.int32, device=dev)
+    src = torch.empty((n_sample,), dtype=torch.int32, device=dev)
+    ws_bytes = lib().tsod_proposal_targets_workspace_bytes(R, G, n_sample)
+    ws = ARENA.get(dev, ws_bytes)
+    check(lib().tsod_proposal_targets_src_f32(ptr(roi) if R else None, R, ptr(bbox) if G else None, G,
+                                              ptr(label) if G else None, int(n_sample), int(pos_per_image),
+                                              float(pos_iou_thresh), float(neg_iou_thresh_high), float(neg_iou_thresh_low),
+                                              ptr(sample_roi), ptr(gt_roi_loc), ptr(gt_roi_label), ptr(counts), ptr(src),
+                                              ptr(ws), ws_bytes, stream_ptr()), "proposal_targets_src")
+    return sample_roi, gt_roi_loc, gt_roi_label, counts, src
+
+
+def _upstream(up: torch.Tensor) -> torch.Tensor:
+    up = up.to(torch.float32).contiguous()
+    if up.numel() != 5:
+        raise ValueError(f"upstream gradients: 5 values (rpn_loc, rpn_cls, roi_loc, roi_cls, total), got {up.numel()}")
+    return up
+
+
+def rpn_losses_grad(rpn_out: torch.Tensor, A: int, gt_loc: torch.Tensor, gt_label: torch.Tensor, sigma: float,
+                    up: torch.Tensor, inv_B: float):
+    """d (the two RPN losses) / d rpn_out (tsod_rpn_losses_grad_f32): rpn_out [B*h*w, pitch] as for ``rpn_losses``, ``up`` [5]
+    device upstream gradients -> (d_rpn_out [B*h*w, pitch] (zero pad columns), n_rows [B,2] int32 = (positives, counted))."""
+    require_cuda(rpn_out, "rpn_losses_grad")
+    B, n = gt_label.shape
+    if rpn_out.dim() != 2 or rpn_out.stride(1) != 1 or rpn_out.shape[1] < 6 * A or n % A or rpn_out.shape[0] != B * (n // A):
+        raise ValueError(f"rpn_losses_grad: rpn_out {tuple(rpn_out.shape)} does not hold B={B} images of {n} anchors at A={A}")
+    dev = rpn_out.device
+    gt_loc = gt_loc.to(dev, torch.float32).contiguous()
+    gt_label = gt_label.to(dev, torch.int64).contiguous()
+    pitch = rpn_out.shape[1]
+    d = torch.empty((rpn_out.shape[0], pitch), dtype=torch.float32, device=dev)
+    n_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    check(lib().tsod_rpn_losses_grad_f32(ptr(rpn_out), rpn_out.stride(0), int(A), B, n // A, ptr(gt_loc), ptr(gt_label),
+                                         float(sigma), ptr(_upstream(up)), float(inv_B), ptr(n_rows), ptr(d), pitch,
+                                         stream_ptr()), "rpn_losses_grad")
+    return d, n_rows
+
+
+def roi_losses_grad(both: torch.Tensor, n_class: int, sample_roi: torch.Tensor, gt_roi_loc: torch.Tensor,
+                    gt_roi_label: torch.Tensor, sigma: float, up: torch.Tensor, inv_B: float):
+    """d (the two head losses) / d both, d sample_roi (tsod_roi_losses_grad_f32).  ``both`` [B*S, pitch]: the fused head GEMM's
+    output (cls_loc columns [0, 4 n_class), scores [4 n_class, 5 n_class)); sample_roi / gt_roi_loc [B,S,4], gt_roi_label [B,S]
+    -> (d_both [B*S, pitch] (zero pad columns), d_sample_roi [B,S,4])."""
+    require_cuda(both, "roi_losses_grad")
+    B, S = gt_roi_label.shape
+    if both.dim() != 2 or both.stride(1) != 1 or both.shape[0] != B * S or both.shape[1] < 5 * n_class:
+        raise ValueError(f"roi_losses_grad: both {tuple(both.shape)} does not hold {B}x{S} rows of {5 * n_class} columns")
+    dev = both.device
+    sample_roi = sample_roi.to(dev, torch.float32).contiguous()
+    gt_roi_loc = gt_roi_loc.to(dev, torch.float32).contiguous()
+    gt_roi_label = gt_roi_label.to(dev, torch.int64).contiguous()
+    pitch = both.shape[1]
+    d = torch.empty((B * S, pitch), dtype=torch.float32, device=dev)
+    d_roi = torch.empty((B, S, 4), dtype=torch.float32, device=dev)
+    check(lib().tsod_roi_losses_grad_f32(ptr(both), both.stride(0), ptr(both[:, 4 * n_class:]), both.stride(0), ptr(sample_roi),
+                                         ptr(gt_roi_loc), ptr(gt_roi_label), B, S, int(n_class), float(sigma),
+                                         ptr(_upstream(up)), float(inv_B), ptr(d), pitch, ptr(d_roi), stream_ptr()),
+          "roi_losses_grad")
+    return d, d_roi
+
+
+def rpn_roi_scatter(d_rpn_out: torch.Tensor, d_sample_roi: torch.Tensor, sample_src: torch.Tensor, keep_idx: torch.Tensor,
+                    sort_idx: torch.Tensor, rpn_out: torch.Tensor, anchors: torch.Tensor, A: int, clamp_x, clamp_y):
+    """Add d sample_roi into the loc columns of ``d_rpn_out`` (in place) along sample_src [B,S] -> keep_idx [B,R] ->
+    sort_idx [B,n_pre] -> anchor, through the clamp mask and loc2bbox's backward (tsod_rpn_roi_scatter_f32)."""
+    require_cuda(d_rpn_out, "rpn_roi_scatter")
+    B, S = sample_src.shape
+    R, n_pre = keep_idx.shape[1], sort_idx.shape[1]
+    n_pix = rpn_out.shape[0] // B
+    for name, v in (("sample_src", sample_src), ("keep_idx", keep_idx), ("sort_idx", sort_idx)):
+        if v.dtype != torch.int32 or not v.is_contiguous() or v.shape[0] != B:
+            raise ValueError(f"rpn_roi_scatter: {name} must be contiguous int32 [B, ...], got {v.dtype} {tuple(v.shape)}")
+    if tuple(d_sample_roi.shape) != (B, S, 4) or anchors.shape[0] != n_pix * A or d_rpn_out.shape[0] != rpn_out.shape[0]:
+        raise ValueError("rpn_roi_scatter: inconsistent shapes")
+    check(lib().tsod_rpn_roi_scatter_f32(ptr(d_sample_roi.contiguous()), ptr(sample_src), B, S, R, ptr(keep_idx), ptr(sort_idx),
+                                         n_pre, ptr(rpn_out), rpn_out.stride(0), ptr(anchors.contiguous()), int(A), n_pix,
+                                         float(clamp_x), float(clamp_y), ptr(d_rpn_out), d_rpn_out.stride(0), stream_ptr()),
+          "rpn_roi_scatter")
+    return d_rpn_out
+
+
+def wgrad(dy: torch.Tensor, x: torch.Tensor, dw0: torch.Tensor, db0=None, dw1=None, db1=None, accumulate: bool = False):
+    """dW = dy^T x, db = dy summed over rows, on the f32 matrix cores (tsod_wgrad_f32).  dy [M, >= N] (row pitch = stride(0)),
+    x [M, K] (rows may be pitched; 16-byte aligned).  Rows [0, n0) of the [N, K] result go to ``dw0`` [n0, K] / ``db0`` [n0],
+    the next n1 rows to ``dw1`` / ``db1`` (N = dy.shape[1]; later rows are dropped).  ``accumulate``: add instead of write."""
+    require_cuda(dy, "wgrad")
+    if dy.dim() != 2 or x.dim() != 2 or dy.stride(1) != 1 or x.stride(1) != 1 or dy.shape[0] != x.shape[0]:
+        raise ValueError(f"wgrad: dy {tuple(dy.shape)} and x {tuple(x.shape)} must be row matrices with the same rows")
+    M, N = dy.shape
+    K = x.shape[1]
+    n0 = dw0.numel() // K
+    n1 = 0 if dw1 is None else dw1.numel() // K
+    for t in (dw0, db0, dw1, db1):
+        if t is not None and (not t.is_contiguous() or t.dtype != torch.float32):
+            raise ValueError("wgrad: outputs must be contiguous float32")
+    ws_bytes = lib().tsod_wgrad_workspace_bytes(M, N, K)
+    ws = ARENA.get(dy.device, ws_bytes)
+    check(lib().tsod_wgrad_f32(ptr(dy), M, N, dy.stride(0), ptr(x), K, x.stride(0), n0, ptr(dw0), ptr(db0), n1, ptr(dw1),
+                               ptr(db1), 1 if accumulate else 0, ptr(ws), ws_bytes, stream_ptr()), "wgrad")
+
+
 # ----------------------------------------------------------------------------- input step
 _RESIZE_TABLES: dict = {}
 

@@ -126,10 +126,18 @@ class HarNetRoIHead(PlanOwner, nn.Module):
     def forward_nhwc(self, feat, rois, roi_indices, img_size, feat_amax=None, range_flag=None):
         """feat NHWC [n,Hf,Wf,C]; rois [n,R,4] image coords; roi_indices [n]; img_size (H,W) (quirk Q2).  ``feat_amax``: the
         range words of ``feat`` (what an fp16x2 choice of the fused GEMM scales its input with)."""
+        n = feat.shape[0]
+        _, both, n_loc, n_sc = self.forward_fused(feat, rois, roi_indices, img_size, feat_amax, range_flag)
+        # views into the fused output (row pitch 408 for 81 classes): same values and shapes as the reference's two
+        # Linear outputs; .contiguous() them if a consumer needs dense storage
+        return both[:, :n_loc].view(n, -1, n_loc), both[:, n_loc:n_loc + n_sc].view(n, -1, n_sc)
+
+    def forward_fused(self, feat, rois, roi_indices, img_size, feat_amax=None, range_flag=None):
+        """``forward_nhwc``'s two launches, returning (fc7 [n*R, C] (the pooled means), both [n*R, pad4(5*n_class)] (the fused
+        GEMM's output: cls_loc columns, then score columns), 4*n_class, n_class) - what the trainer's backward keeps."""
         require_cuda(feat, "HarNetRoIHead")
         if not isinstance(self.classifier, HarNetClassifier):
             raise TsodError("only the reference's HarNetClassifier (mean over the 7x7 bins) has a HIP path")
-        n = feat.shape[0]
         fc7 = self.pooled(feat, rois, roi_indices, img_size)
         w, b, n_loc, n_sc = self._pack(feat.device)
         # the fused Linear as a 1x1 "conv" over M = n*R rows: same GEMM kernel as tsod_linear_f32, with the tile / K-slice /
@@ -139,9 +147,7 @@ class HarNetRoIHead(PlanOwner, nn.Module):
         both = hip_ops.conv2d_nhwc(fc7.view(1, 1, M, K), w.view(w.shape[0], 1, 1, K), shift=b, tile=tile, split_k=split,
                                    precision=prec, **self._gemm_kw(feat.device, prec, feat_amax, range_flag, fc7)
                                    ).view(M, w.shape[0])                           # [n*R, pad4(5*n_class)]
-        # views into the fused output (row pitch 408 for 81 classes): same values and shapes as the reference's two
-        # Linear outputs; .contiguous() them if a consumer needs dense storage
-        return both[:, :n_loc].view(n, -1, n_loc), both[:, n_loc:n_loc + n_sc].view(n, -1, n_sc)
+        return fc7, both, n_loc, n_sc
 
     def autotune(self, fc7: torch.Tensor, feat_amax=None, range_flag=None):
         """Pin the fastest (tile, K-slice schedule, arithmetic) of the fused cls_loc + score GEMM for M = fc7.shape[0] RoIs

@@ -66,6 +66,72 @@ class ProposalTargetCreator(object):
                              "(the reference raises IndexError at nets/frcnn_training.py:175)")
         return sample_roi[:n_keep], gt_roi_loc[:n_keep], gt_roi_label[:n_keep].to(label.dtype)
 
+    def with_sources(self, roi, bbox, label):
+        """``__call__`` plus sample_src [S] int32: the row of cat(roi, bbox) each sample came from (the reference's keep_index;
+        < len(roi): a proposal).  What FasterRCNNTrainer(head_grads=True) maps the regression target's gradient back with."""
+        require_cuda(roi, "ProposalTargetCreator")
+        sample_roi, gt_roi_loc, gt_roi_label, counts, src = hip_ops.proposal_targets_src(
+            roi, bbox, label, self.n_sample, self.pos_roi_per_image, self.pos_iou_thresh, self.neg_iou_thresh_high,
+            self.neg_iou_thresh_low)
+        n_keep, _, _, status = counts.tolist()
+        if status:
+            raise IndexError("index of a sampled negative is out of bounds for the kept labels "
+                             "(the reference raises IndexError at nets/frcnn_training.py:175)")
+        return sample_roi[:n_keep], gt_roi_loc[:n_keep], gt_roi_label[:n_keep].to(label.dtype), src[:n_keep]
+
+
+HEAD_PARAMS = ("rpn.loc.weight", "rpn.loc.bias", "rpn.score.weight", "rpn.score.bias",
+               "head.cls_loc.weight", "head.cls_loc.bias", "head.score.weight", "head.score.bias")
+
+
+class _HeadLosses(torch.autograd.Function):
+    """The five losses as one differentiable node whose backward is the HIP kernels of csrc/head_grads.hip only.
+
+    forward(per [4], saved, *the eight head parameters) -> [rpn_loc, rpn_cls, roi_loc, roi_cls, total] (total summed in the
+    order of the default path, so the values are identical).  backward: tsod_rpn_losses_grad_f32, tsod_roi_losses_grad_f32,
+    tsod_rpn_roi_scatter_f32 (the indirect term through the proposals), then tsod_wgrad_f32 for the RPN (feature map rows)
+    and for the head (fc7 rows).  It writes / adds the eight ``.grad`` tensors itself (the fused [56,C] / [408,C] results go
+    straight into the reference's parameter shapes) and returns no gradient to autograd, so ``torch.autograd.grad`` on these
+    parameters is not supported - ``.backward()`` is."""
+
+    @staticmethod
+    def forward(ctx, per, saved, *params):
+        ctx.saved = saved
+        ctx.params = params
+        return torch.cat([per, (per[0] + per[1] + per[2] + per[3]).view(1)])
+
+    @staticmethod
+    def backward(ctx, g):
+        sv, params = ctx.saved, ctx.params
+        up = g.contiguous()
+        d_rpn, _ = hip_ops.rpn_losses_grad(sv["rpn_out"], sv["A"], sv["gt_loc"], sv["gt_label"], sv["rpn_sigma"], up, sv["inv_B"])
+        d_both, d_roi = hip_ops.roi_losses_grad(sv["both"], sv["n_class"], sv["sample_roi"], sv["gt_roi_loc"], sv["gt_roi_label"],
+                                                sv["roi_sigma"], up, sv["inv_B"])
+        hip_ops.rpn_roi_scatter(d_rpn, d_roi, sv["sample_src"], sv["keep_idx"], sv["sort_idx"], sv["rpn_out"], sv["anchor"],
+                                sv["A"], sv["clamp_x"], sv["clamp_y"])
+        feat = sv["feat"]
+        _wgrad_into(d_rpn, feat.view(-1, feat.shape[-1])[:, :params[0].shape[1]], params[0:4])   # (pixel rows may be padded)
+        _wgrad_into(d_both, sv["fc7"], params[4:8])
+        return (None, None) + (None,) * len(params)
+
+
+def _wgrad_into(dy, x, params):
+    """One tsod_wgrad_f32 launch pair into (w0, b0, w1, b1).grad: written when none of them has a gradient yet, added to
+    otherwise (a missing one starts from zeros); a parameter that does not require grad gets a scratch destination."""
+    have = [p.requires_grad and p.grad is not None for p in params]
+    accumulate = any(have)
+    dst = []
+    for p, h in zip(params, have):
+        if not p.requires_grad:
+            dst.append(torch.empty_like(p))
+        elif not h:
+            p.grad = torch.zeros_like(p) if accumulate else torch.empty_like(p)
+            dst.append(p.grad)
+        else:
+            dst.append(p.grad)
+    K = x.shape[1]
+    hip_ops.wgrad(dy, x, dst[0].view(-1, K), dst[1], dst[2].view(-1, K), dst[3], accumulate=accumulate)
+
 
 class FasterRCNNTrainer(nn.Module):
     """The reference's ground-truth-conditioned forward (nets/frcnn_training.py:179-342) with its four losses.
@@ -74,6 +140,15 @@ class FasterRCNNTrainer(nn.Module):
     plus the keyword-only ``backbone`` / ``roi_op`` of ``FasterRCNN`` and ``head_img_size``.  The attribute names are the
     reference's (``feat_extra``, ``classifier``, ``rpn``, ``head``, ...), so its ``state_dict`` has the reference's key set
     and shapes and a checkpoint of train/train.py loads with ``load_state_dict(ckpt['model_state_dict'], strict=True)``.
+
+    ``head_grads=True`` (keyword-only) makes the five losses differentiable w.r.t. the eight head parameters (rpn.loc,
+    rpn.score, head.cls_loc, head.score: weight and bias) while grad mode is on: any scalar combination of them can call
+    ``.backward()`` (train/train.py's ``losses[-1] / 32``), and the backward - HIP kernels only -
+    adds into those ``.grad`` tensors what the reference's autograd puts there with the backbone frozen, including the
+    indirect term of the RoI regression loss through the (not detached) proposals.  The backbone must be frozen
+    (``feat_extra.requires_grad_(False)``): no gradient reaches it.  The autograd node keeps its own copies of what its
+    backward reads, so a backward issued after a later forward still gives its own forward's gradients.  The default
+    (``head_grads=False``) returns losses that do not require grad.
 
     ``forward(imgs, bboxes, labels, scale=1)`` -> (losses, anchors_pred [B,S,4], classes_pred [B,S] int64,
     classes_score_pred [B,S], bboxes[0][None], (labels[0] + 1)[None]) with losses = [rpn_loc, rpn_cls, roi_loc, roi_cls,
@@ -96,12 +171,15 @@ class FasterRCNNTrainer(nn.Module):
       * the module must be in eval() (BatchNorm folded), like the rest of the HIP path.
       * an IndexError of the proposal padding (quirk Q4) is recorded on the device as in ``FasterRCNN``: ``raise_if_error()``.
 
-    Not provided: backward, optimizer and training (this is the forward with its losses - validation loss, the demo
-    script's predictions); eval_fn / calculate_metrics (see the module docstring); graph capture and tuning (the forward
-    runs whatever plan the backbone holds)."""
+      * in-place updates of the eight head parameters (an optimizer step) are detected through their ``_version`` and the
+        RPN's and head's packed weight images are rebuilt before the next forward.
+
+    Not provided: backbone gradients and train-mode BatchNorm (fine-tuning the heads on a frozen backbone is what
+    ``head_grads`` covers); gradients w.r.t. the input or through RoIPool / RoIAlign; eval_fn / calculate_metrics (see the
+    module docstring); graph capture and tuning (the forward runs whatever plan the backbone holds)."""
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
-                 backbone="hardnet39", roi_op="pool", head_img_size="chw"):
+                 backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False):
         super().__init__()
         if head_img_size not in ("chw", "hw"):
             raise ValueError(f"head_img_size must be 'chw' (the reference's) or 'hw', got {head_img_size!r}")
@@ -120,11 +198,27 @@ class FasterRCNNTrainer(nn.Module):
         self.loc_normalize_std = [0.1, 0.1, 0.2, 0.2]
         self.backbone = backbone
         self.head_img_size = head_img_size
+        self.head_grads = bool(head_grads)
         self.__dict__["_uid"] = next(_UID)          # scratch ownership, as FasterRCNN's
+        self.__dict__["_head_versions"] = None
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self.__dict__["_uid"] = next(_UID)
+        self.__dict__["_head_versions"] = None
+
+    def _head_params(self):
+        named = dict(self.named_parameters())
+        return [named[k] for k in HEAD_PARAMS]
+
+    def _refresh_packs(self):
+        """Rebuild the RPN's and head's packed weights when one of the eight head parameters changed in place since they
+        were packed (``_version`` moves on every in-place update: ``optimizer.step()``, ``p.data.mul_()`` ...)."""
+        versions = tuple(p._version for p in self._head_params())
+        if self._head_versions is not None and versions != self._head_versions:
+            self.rpn.invalidate_packed()
+            self.head.invalidate_packed()
+        self.__dict__["_head_versions"] = versions
 
     def raise_if_error(self):
         """Surface the deferred IndexError of the proposal padding and a range violation of the fp16x2 conv arithmetic."""
@@ -143,34 +237,57 @@ class FasterRCNNTrainer(nn.Module):
         img_size = tuple(x.shape[1:])                                    # (C,H,W): quirk Q1 (RPN), Q2 (head)
         head_size = img_size if self.head_img_size == "chw" else tuple(x.shape[2:])
         n_sample = self.proposal_target_creator.n_sample
+        grads = self.head_grads and torch.is_grad_enabled()
+        if grads:
+            frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad]
+            if frozen:
+                raise TsodError(f"FasterRCNNTrainer(head_grads=True) computes the head parameters' gradients on a frozen "
+                                f"backbone, but feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad: call "
+                                "trainer.feat_extra.requires_grad_(False)")
+        self._refresh_packs()
         with hip_ops.ARENA.scope((self._uid, 0)):
             feat = self.feat_extra.forward_nhwc(x, 0)
             plan = self.feat_extra._plan_for(x, 0)
             feat_amax, flag = (getattr(plan, "output_amax", 0) or None), getattr(plan, "range_flag", None)
-            rpn_out, rois, anchor = self.rpn.propose(feat, img_size, scale, want_anchors=True, feat_amax=feat_amax,
-                                                     range_flag=flag)
-            gt_locs, gt_labels, s_rois, s_locs, s_labels = [], [], [], [], []
+            proposed = self.rpn.propose(feat, img_size, scale, want_anchors=True, feat_amax=feat_amax, range_flag=flag,
+                                        want_index=grads)
+            rpn_out, rois, anchor = proposed[:3]
+            gt_locs, gt_labels, s_rois, s_locs, s_labels, s_srcs = [], [], [], [], [], []
             for i in range(B):
                 bbox = bboxes[i].to(dev, torch.float32)
                 label = labels[i].to(dev)
                 gt_loc, gt_label = self.anchor_target_creator(bbox, anchor)
                 gt_locs.append(gt_loc)
                 gt_labels.append(gt_label)
-                s_roi, s_loc, s_label = self.proposal_target_creator(rois[i], bbox, label, self.loc_normalize_std)
+                if grads:
+                    s_roi, s_loc, s_label, s_src = self.proposal_target_creator.with_sources(rois[i], bbox, label)
+                    s_srcs.append(s_src)
+                else:
+                    s_roi, s_loc, s_label = self.proposal_target_creator(rois[i], bbox, label, self.loc_normalize_std)
                 if s_roi.shape[0] < n_sample:
                     raise RuntimeError(f"ProposalTargetCreator kept {s_roi.shape[0]} samples for image {i}, fewer than "
                                        f"n_sample = {n_sample}: the reference's head fails on that (quirk Q5)")
                 s_rois.append(s_roi)
                 s_locs.append(s_loc)
                 s_labels.append(s_label)
-            rpn_loss, rpn_status = hip_ops.rpn_losses(rpn_out, self.rpn.anchor_base.shape[0], torch.stack(gt_locs),
-                                                      torch.stack(gt_labels), self.rpn_sigma)
+            gt_loc_all, gt_label_all = torch.stack(gt_locs), torch.stack(gt_labels)
+            rpn_loss, rpn_status = hip_ops.rpn_losses(rpn_out, self.rpn.anchor_base.shape[0], gt_loc_all, gt_label_all,
+                                                      self.rpn_sigma)
             sample_rois = torch.stack(s_rois)
             roi_indices = torch.arange(B, dtype=torch.int32, device=dev)
-            roi_cls_locs, roi_scores = self.head.forward_nhwc(feat, sample_rois, roi_indices, head_size, feat_amax=feat_amax,
-                                                              range_flag=flag)
+            fc7, both, n_loc, n_sc = self.head.forward_fused(feat, sample_rois, roi_indices, head_size, feat_amax=feat_amax,
+                                                             range_flag=flag)
+            roi_cls_locs, roi_scores = both[:, :n_loc].view(B, -1, n_loc), both[:, n_loc:n_loc + n_sc].view(B, -1, n_sc)
+            s_locs_all, s_labels_all = torch.stack(s_locs), torch.stack(s_labels)
             anchors_pred, classes_pred, classes_score_pred, roi_loss, roi_status = hip_ops.roi_losses(
-                roi_cls_locs, roi_scores, sample_rois, torch.stack(s_locs), torch.stack(s_labels), self.roi_sigma)
+                roi_cls_locs, roi_scores, sample_rois, s_locs_all, s_labels_all, self.roi_sigma)
+            if grads:
+                saved = dict(feat=feat.clone(),           # the plan's buffer: the next forward overwrites it
+                             rpn_out=rpn_out, anchor=anchor, sort_idx=proposed[3], keep_idx=proposed[4],
+                             gt_loc=gt_loc_all, gt_label=gt_label_all, sample_roi=sample_rois, gt_roi_loc=s_locs_all,
+                             gt_roi_label=s_labels_all, sample_src=torch.stack(s_srcs), fc7=fc7, both=both,
+                             A=self.rpn.anchor_base.shape[0], n_class=n_sc, rpn_sigma=self.rpn_sigma,
+                             roi_sigma=self.roi_sigma, inv_B=1.0 / B, clamp_x=img_size[1], clamp_y=img_size[2])
             self.feat_extra.publish_range_word(plan)
         # (one read of the two status words, after the last launch: the reference raises IndexError there)
         bad = rpn_status.sum() + roi_status.sum()
@@ -178,7 +295,10 @@ class FasterRCNNTrainer(nn.Module):
             raise IndexError("a target class index is out of bounds for the logits it indexes "
                              "(the reference raises IndexError at nets/frcnn_training.py:274 / 313-331)")
         per = torch.cat([rpn_loss, roi_loss], dim=1).sum(0) / B        # [rpn_loc, rpn_cls, roi_loc, roi_cls]
-        losses = list(per.unbind(0))
-        losses = losses + [sum(losses)]
+        if grads:
+            losses = list(_HeadLosses.apply(per, saved, *self._head_params()).unbind(0))
+        else:
+            losses = list(per.unbind(0))
+            losses = losses + [sum(losses)]
         return (losses, anchors_pred, classes_pred, classes_score_pred, torch.unsqueeze(bboxes[0], dim=0),
                 torch.unsqueeze(labels[0] + 1, dim=0))

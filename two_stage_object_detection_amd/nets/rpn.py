@@ -47,22 +47,24 @@ class ProposalCreator:
             return self.n_train_pre_nms, self.n_train_post_nms
         return self.n_test_pre_nms, self.n_test_post_nms
 
-    def select(self, boxes, keys, strict=None):
-        """boxes [B,n,4] decoded+clamped, keys [B,n] (fg score, -inf = filtered) -> rois [B,n_post,4]."""
+    def select(self, boxes, keys, strict=None, want_index=False):
+        """boxes [B,n,4] decoded+clamped, keys [B,n] (fg score, -inf = filtered) -> rois [B,n_post,4].  ``want_index``: also
+        the index chain behind every roi row, (rois, sort_idx [B,n_pre] (source row of each sorted row), keep_idx [B,n_post]
+        (sorted row of each roi, with the 0,1,2,... padding of quirk Q4))."""
         n_pre, n_post = self.counts()
         if n_pre <= 0:
             n_pre = min(boxes.shape[1], 16384)
-        counts, _, bs, _ = hip_ops.sort_topk_desc(keys, boxes, n_pre)
+        counts, sort_idx, bs, _ = hip_ops.sort_topk_desc(keys, boxes, n_pre)
         # sticky device-side error word: allocated (zeroed) once per device, only ever OR-ed into by the NMS kernel,
         # cleared by raise_if_error() - no per-forward memset launch
         status = self._status.get(boxes.device)
         if status is None:
             status = self._status[boxes.device] = torch.zeros((1,), dtype=torch.int32, device=boxes.device)
-        _, rois, _, status = hip_ops.nms_sorted(bs, counts, self.nms_iou, n_post, status=status)
+        keep_idx, rois, _, status = hip_ops.nms_sorted(bs, counts, self.nms_iou, n_post, status=status)
         self.last_status = status
         if self.strict if strict is None else strict:
             self.raise_if_error()
-        return rois
+        return (rois, sort_idx, keep_idx) if want_index else rois
 
     def raise_if_error(self):
         st = getattr(self, "last_status", None)
@@ -128,10 +130,12 @@ class RegionProposalNetwork(PlanOwner, nn.Module):
             return {"w2": w2, "w_scale_exp": e, "amax_in": feat_amax, "range_flag": range_flag}
         return {}
 
-    def propose(self, feat: torch.Tensor, img_size, scale=1., want_anchors=False, feat_amax=None, range_flag=None):
+    def propose(self, feat: torch.Tensor, img_size, scale=1., want_anchors=False, feat_amax=None, range_flag=None,
+                want_index=False):
         """feat NHWC [n,h,w,C] -> (fused conv output [n*h*w, pad4(6A)] with loc in columns [0,4A) and score in
         [4A,6A), rois [n,n_post,4], anchors [h*w*A,4] or None).  Four launches, no host sync.  ``feat_amax``: the range words
-        of ``feat`` (engine.Plan.output_amax) - what an fp16x2 choice of the fused conv takes its activation scale from."""
+        of ``feat`` (engine.Plan.output_amax) - what an fp16x2 choice of the fused conv takes its activation scale from.
+        ``want_index``: two more entries, the sort_idx / keep_idx of ``ProposalCreator.select`` (the trainer's backward)."""
         require_cuda(feat, "RegionProposalNetwork")
         n, h, w, _ = feat.shape
         pc, base, n_loc, n_sc = self._pack(feat.device)
@@ -141,6 +145,9 @@ class RegionProposalNetwork(PlanOwner, nn.Module):
         boxes, _, keys, anchor = hip_ops.rpn_decode(fused[:, :n_loc], fused[:, n_loc:n_loc + n_sc], base, n, h, w,
                                                     self.feat_stride, img_size[1], img_size[2],
                                                     self.proposal_layer.min_size * scale, want_anchors=want_anchors)
+        if want_index:
+            rois, sort_idx, keep_idx = self.proposal_layer.select(boxes, keys, want_index=True)
+            return fused, rois, anchor, sort_idx, keep_idx
         return fused, self.proposal_layer.select(boxes, keys), anchor
 
     def autotune(self, feat: torch.Tensor, feat_amax=None, range_flag=None):
