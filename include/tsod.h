@@ -571,6 +571,33 @@ int tsod_wgrad_f32(const float *dy, int64_t M, int32_t N, int32_t dy_pitch, cons
                    int32_t n0, float *dw0, float *db0, int32_t n1, float *dw1, float *db1, int32_t accumulate, void *workspace,
                    size_t workspace_bytes, tsod_stream_t stream);
 
+/* ---- feature gradients: the backward of the RoI head's pooling into the feature map (FasterRCNNTrainer(features=...)) ------
+ * The RoI term of d loss / d feature map, written into (or, accumulate = 1, added to) d_feat [B][Hf][Wf][d_feat_pitch] NHWC:
+ * the arguments of tsod_roi_pool_avg_f32 / tsod_roi_align_avg_f32 plus d_out [B*R][d_out_pitch] = d loss / d (their output).
+ * A gather: one thread owns a (pixel, channel quad) of d_feat and sums what reaches it in a fixed order (RoI groups whose
+ * roi_indices name its image, in group order; the RoIs of a group ascending; bins, then samples and corners, in the forward's
+ * order) - no atomics, bit-identical from run to run.  Any roi_indices mapping; RoIs of an index outside [0, B) contribute 0.
+ * tsod_roi_pool_avg_grad_f32: torchvision's roi_pool backward - bin (ph, pw) gives d_out / (PH PW) to its arg-max pixel
+ *   (recomputed from `feat` by a pre-pass with the forward's rule: from -FLT_MAX, strict '>', h outer, w inner; empty bins and
+ *   bins without a value above -FLT_MAX give nothing).  The arg-max is recorded as a u16 map index: Hf * Wf <= 65535
+ *   (TSOD_ERR_UNSUPPORTED otherwise), B * R <= 65535.  workspace: tsod_roi_pool_avg_grad_workspace_bytes(B, R, C, PH, PW)
+ *   (B*R*PH*PW*C u16 of arg-max record + 16 B per RoI).
+ * tsod_roi_align_avg_grad_f32: torchvision's roi_align backward - sample (iy, ix) of bin (ph, pw) gives w1..w4 x d_out /
+ *   (PH PW count) to its four corners (the forward's positions, [-1, H] x [-1, W] skip, clamps and corner collapse); the
+ *   feature values are not read.  workspace: tsod_roi_align_avg_grad_workspace_bytes(B, R) (16 B per RoI). */
+size_t tsod_roi_pool_avg_grad_workspace_bytes(int32_t B, int32_t R, int32_t C, int32_t PH, int32_t PW);
+int tsod_roi_pool_avg_grad_f32(const float *feat, int32_t B, int32_t Hf, int32_t Wf, int32_t C, int32_t feat_pitch,
+                               const float *rois, const int32_t *roi_indices, int32_t R, float img_h, float img_w,
+                               float spatial_scale, int32_t PH, int32_t PW, const float *d_out, int32_t d_out_pitch, float *d_feat,
+                               int32_t d_feat_pitch, int32_t accumulate, void *workspace, size_t workspace_bytes,
+                               tsod_stream_t stream);
+size_t tsod_roi_align_avg_grad_workspace_bytes(int32_t B, int32_t R);
+int tsod_roi_align_avg_grad_f32(int32_t B, int32_t Hf, int32_t Wf, int32_t C, const float *rois, const int32_t *roi_indices,
+                                int32_t R, float img_h, float img_w, float spatial_scale, int32_t PH, int32_t PW,
+                                int32_t sampling_ratio, int32_t aligned, const float *d_out, int32_t d_out_pitch, float *d_feat,
+                                int32_t d_feat_pitch, int32_t accumulate, void *workspace, size_t workspace_bytes,
+                                tsod_stream_t stream);
+
 /* ---- input step (the step before the path) ----------------------------------------------
  * dataset/dataloader.py:35-44 + dataset/transform.py:14-17: a decoded RGB image becomes an f32 CHW tensor with
  * values 0..255 and is resized to the detector's fixed size by torchvision v2 Resize, i.e. ATen's antialiased

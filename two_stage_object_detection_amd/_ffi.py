@@ -211,6 +211,14 @@ _SIGNATURES = {
     "tsod_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "tsod_wgrad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
+    "tsod_roi_pool_avg_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "tsod_roi_pool_avg_grad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                           c_float, c_float, c_float, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                           c_int32, c_void_p, c_size_t, c_void_p]),
+    "tsod_roi_align_avg_grad_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "tsod_roi_align_avg_grad_f32": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_float, c_float,
+                                            c_float, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                            c_int32, c_void_p, c_size_t, c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

@@ -15,29 +15,6 @@
 
 namespace {
 
-struct RoiGeom {
-    int b, sw, sh, rw, rh;
-};
-
-__device__ __forceinline__ RoiGeom roi_geom(float bidx, float x1, float y1, float x2, float y2, float scale) {
-    RoiGeom g;
-    g.b = (int)bidx;
-    g.sw = (int)roundf(x1 * scale);
-    g.sh = (int)roundf(y1 * scale);
-    const int ew = (int)roundf(x2 * scale);
-    const int eh = (int)roundf(y2 * scale);
-    g.rw = max(ew - g.sw + 1, 1);
-    g.rh = max(eh - g.sh + 1, 1);
-    return g;
-}
-
-__device__ __forceinline__ void bin_range(int p, float bin, int start, int limit, int &lo, int &hi) {
-    lo = (int)floorf((float)p * bin) + start;
-    hi = (int)ceilf((float)(p + 1) * bin) + start;
-    lo = min(max(lo, 0), limit);
-    hi = min(max(hi, 0), limit);
-}
-
 __device__ __forceinline__ float4 max4(float4 m, const float4 v) {
     if (v.x > m.x) m.x = v.x;
     if (v.y > m.y) m.y = v.y;
@@ -63,7 +40,7 @@ roi_pool_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int C, in
                 const float *__restrict__ rois5, float scale, int PH, int PW, float *__restrict__ out) {
     const int k = blockIdx.x;
     const float *r = rois5 + 5l * k;
-    const RoiGeom g = roi_geom(r[0], r[1], r[2], r[3], r[4], scale);
+    const tsod_pool_geom g = tsod_roi_pool_geom(r[0], r[1], r[2], r[3], r[4], scale);
     if (g.b < 0 || g.b >= B) return;
     const float bin_h = (float)g.rh / (float)PH;
     const float bin_w = (float)g.rw / (float)PW;
@@ -72,10 +49,10 @@ roi_pool_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int C, in
     for (int c4 = threadIdx.x; c4 < (C >> 2); c4 += blockDim.x) {
         for (int ph = 0; ph < PH; ++ph) {
             int hs, he;
-            bin_range(ph, bin_h, g.sh, Hf, hs, he);
+            tsod_bin_range(ph, bin_h, g.sh, Hf, hs, he);
             for (int pw = 0; pw < PW; ++pw) {
                 int ws, we;
-                bin_range(pw, bin_w, g.sw, Wf, ws, we);
+                tsod_bin_range(pw, bin_w, g.sw, Wf, ws, we);
                 const float4 m = bin_max(fmap, Wf, pitch, c4, hs, he, ws, we);
                 float *o = out + ((long)k * C + 4 * c4) * bins + ph * PW + pw;
                 o[0] = m.x; o[bins] = m.y; o[2 * bins] = m.z; o[3 * bins] = m.w;
@@ -101,11 +78,8 @@ roi_pool_avg_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int C
     const int k = roi_in_y ? blockIdx.y : blockIdx.x;
     const float4 rr = reinterpret_cast<const float4 *>(rois)[k];
     // nets/classify.py:35-36: divide by the image side, then multiply by the map side
-    const float fx1 = rr.x / img_w * (float)Wf;
-    const float fy1 = rr.y / img_h * (float)Hf;
-    const float fx2 = rr.z / img_w * (float)Wf;
-    const float fy2 = rr.w / img_h * (float)Hf;
-    const RoiGeom g = roi_geom((float)roi_indices[k / R], fx1, fy1, fx2, fy2, scale);
+    const float4 fm = tsod_roi_to_map(rr, img_h, img_w, Hf, Wf);
+    const tsod_pool_geom g = tsod_roi_pool_geom((float)roi_indices[k / R], fm.x, fm.y, fm.z, fm.w, scale);
     if (g.b < 0 || g.b >= B) return;
     const float bin_h = (float)g.rh / (float)PH;
     const float bin_w = (float)g.rw / (float)PW;
@@ -120,7 +94,7 @@ roi_pool_avg_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int C
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         if (live && ph < PH) {
             int hs, he;
-            bin_range(ph, bin_h, g.sh, Hf, hs, he);
+            tsod_bin_range(ph, bin_h, g.sh, Hf, hs, he);
             // Neighbouring bins of a row share at most ONE pixel column (floor / ceil edges of a float bin width): its column maximum is
             // kept from the bin before instead of being read again - a window pixel is read once per bin ROW it belongs to, not once
             // per bin (a 7-bin row read 1.2-2x its width before).  A maximum taken in another order is the same maximum: bit-exact.
@@ -128,7 +102,7 @@ roi_pool_avg_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int C
             float4 kept = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX);
             for (int pw = 0; pw < PW; ++pw) {
                 int ws, we;
-                bin_range(pw, bin_w, g.sw, Wf, ws, we);
+                tsod_bin_range(pw, bin_w, g.sw, Wf, ws, we);
                 float4 m = make_float4(0.f, 0.f, 0.f, 0.f);                   // empty bin
                 if (he > hs && we > ws) {
                     m = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX);
@@ -170,45 +144,17 @@ roi_pool_avg_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int C
 //   sample (iy, ix) of bin (ph, pw): y = start_h + ph * bin_h + (iy + .5) * bin_h / grid_h (x likewise);
 //   outside [-1, H] x [-1, W] -> 0; clamp at 0; low = (int), high = low + 1 (both H-1 at the border, y = low there);
 //   value = hy*hx*v1 + hy*lx*v2 + ly*hx*v3 + ly*lx*v4; bin output = sum over the grid (iy outer, ix inner) / count.
-struct AlignGeom {
-    int b, grid_h, grid_w;
-    float start_h, start_w, bin_h, bin_w, count;
-};
-
-__device__ __forceinline__ AlignGeom align_geom(float bidx, float x1, float y1, float x2, float y2, float scale, int PH,
-                                                int PW, int sampling_ratio, int aligned) {
-    AlignGeom g;
-    g.b = (int)bidx;
-    const float offset = aligned ? 0.5f : 0.f;
-    g.start_w = x1 * scale - offset;
-    g.start_h = y1 * scale - offset;
-    const float end_w = x2 * scale - offset, end_h = y2 * scale - offset;
-    float rw = end_w - g.start_w, rh = end_h - g.start_h;
-    if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
-    g.bin_h = rh / (float)PH;
-    g.bin_w = rw / (float)PW;
-    g.grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / (float)PH);
-    g.grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / (float)PW);
-    g.count = (float)max(g.grid_h * g.grid_w, 1);
-    return g;
-}
-
+// The geometry and the per-axis bilinear rule live in tsod_internal.h (shared with the backward in feature_grads.hip).
 // sum of the grid samples of bin (ph, pw) for one channel quad (not yet divided by count)
 __device__ __forceinline__ float4 align_bin_sum(const float *__restrict__ fmap, int Hf, int Wf, int pitch, int c4,
-                                                const AlignGeom &g, int ph, int pw) {
+                                                const tsod_align_geom &g, int ph, int pw) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int iy = 0; iy < g.grid_h; ++iy) {
-        const float yy = g.start_h + (float)ph * g.bin_h + ((float)iy + .5f) * g.bin_h / (float)g.grid_h;
+        const float yy = TSOD_ALIGN_SAMPLE(g.start_h, g.bin_h, g.grid_h, ph, iy);
         for (int ix = 0; ix < g.grid_w; ++ix) {
-            const float xx = g.start_w + (float)pw * g.bin_w + ((float)ix + .5f) * g.bin_w / (float)g.grid_w;
-            float y = yy, x = xx;
-            if (y < -1.f || y > (float)Hf || x < -1.f || x > (float)Wf) continue;      // contributes 0
-            if (y <= 0.f) y = 0.f;
-            if (x <= 0.f) x = 0.f;
-            int y_low = (int)y, x_low = (int)x, y_high, x_high;
-            if (y_low >= Hf - 1) { y_high = y_low = Hf - 1; y = (float)y_low; } else y_high = y_low + 1;
-            if (x_low >= Wf - 1) { x_high = x_low = Wf - 1; x = (float)x_low; } else x_high = x_low + 1;
-            const float ly = y - (float)y_low, lx = x - (float)x_low, hy = 1.f - ly, hx = 1.f - lx;
+            const float xx = TSOD_ALIGN_SAMPLE(g.start_w, g.bin_w, g.grid_w, pw, ix);
+            TSOD_ALIGN_BILINEAR_OR_CONTINUE(yy, xx, Hf, Wf);
+            const float hy = 1.f - ly, hx = 1.f - lx;
             const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
             const float4 v1 = *reinterpret_cast<const float4 *>(fmap + ((long)y_low * Wf + x_low) * pitch + 4 * c4);
             const float4 v2 = *reinterpret_cast<const float4 *>(fmap + ((long)y_low * Wf + x_high) * pitch + 4 * c4);
@@ -229,7 +175,7 @@ roi_align_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int C, i
                  float scale, int PH, int PW, int sampling_ratio, int aligned, float *__restrict__ out) {
     const int k = blockIdx.x;
     const float *r = rois5 + 5l * k;
-    const AlignGeom g = align_geom(r[0], r[1], r[2], r[3], r[4], scale, PH, PW, sampling_ratio, aligned);
+    const tsod_align_geom g = tsod_roi_align_geom(r[0], r[1], r[2], r[3], r[4], scale, PH, PW, sampling_ratio, aligned);
     if (g.b < 0 || g.b >= B) return;
     const float *fmap = feat + (long)g.b * Hf * Wf * pitch;
     const int bins = PH * PW, quads = C >> 2;
@@ -249,9 +195,9 @@ roi_align_avg_kernel(const float *__restrict__ feat, int B, int Hf, int Wf, int 
     __shared__ float4 rowsum[8][kQuads];
     const int k = roi_in_y ? blockIdx.y : blockIdx.x;      // (channel group fastest: see roi_pool_avg_kernel)
     const float4 rr = reinterpret_cast<const float4 *>(rois)[k];
-    const float fx1 = rr.x / img_w * (float)Wf, fy1 = rr.y / img_h * (float)Hf;
-    const float fx2 = rr.z / img_w * (float)Wf, fy2 = rr.w / img_h * (float)Hf;
-    const AlignGeom g = align_geom((float)roi_indices[k / R], fx1, fy1, fx2, fy2, scale, PH, PW, sampling_ratio, aligned);
+    const float4 fm = tsod_roi_to_map(rr, img_h, img_w, Hf, Wf);
+    const tsod_align_geom g = tsod_roi_align_geom((float)roi_indices[k / R], fm.x, fm.y, fm.z, fm.w, scale, PH, PW, sampling_ratio,
+                                                  aligned);
     if (g.b < 0 || g.b >= B) return;
     const float *fmap = feat + (long)g.b * Hf * Wf * pitch;
     const float nb = (float)(PH * PW);

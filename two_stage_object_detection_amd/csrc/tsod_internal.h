@@ -74,6 +74,72 @@ __device__ __forceinline__ tsod_box tsod_decode_box(float ax1, float ay1, float 
     o.y2 = ncy + 0.5f * nh;
     return o;
 }
+// ---- RoI geometry of roi_pool.hip's forward kernels and feature_grads.hip's backward: one definition, so that the two cannot
+// disagree about which pixels a bin reads.
+// nets/classify.py:35-36: a RoI in image coordinates -> feature-map coordinates (divide by the image side, multiply by the map's)
+__device__ __forceinline__ float4 tsod_roi_to_map(float4 rr, float img_h, float img_w, int Hf, int Wf) {
+    return make_float4(rr.x / img_w * (float)Wf, rr.y / img_h * (float)Hf, rr.z / img_w * (float)Wf, rr.w / img_h * (float)Hf);
+}
+// torchvision RoIPool: round() half away from zero, +1 extents
+struct tsod_pool_geom {
+    int b, sw, sh, rw, rh;
+};
+__device__ __forceinline__ tsod_pool_geom tsod_roi_pool_geom(float bidx, float x1, float y1, float x2, float y2, float scale) {
+    tsod_pool_geom g;
+    g.b = (int)bidx;
+    g.sw = (int)roundf(x1 * scale);
+    g.sh = (int)roundf(y1 * scale);
+    const int ew = (int)roundf(x2 * scale);
+    const int eh = (int)roundf(y2 * scale);
+    g.rw = max(ew - g.sw + 1, 1);
+    g.rh = max(eh - g.sh + 1, 1);
+    return g;
+}
+// bin p of a float bin size: [lo, hi) = [floor(p bin), ceil((p+1) bin)) + start, clamped to [0, limit]
+__device__ __forceinline__ void tsod_bin_range(int p, float bin, int start, int limit, int &lo, int &hi) {
+    lo = (int)floorf((float)p * bin) + start;
+    hi = (int)ceilf((float)(p + 1) * bin) + start;
+    lo = min(max(lo, 0), limit);
+    hi = min(max(hi, 0), limit);
+}
+// torchvision.ops.roi_align (ops/cpu/roi_align_kernel.cpp + roi_align_common.h)
+struct tsod_align_geom {
+    int b, grid_h, grid_w;
+    float start_h, start_w, bin_h, bin_w, count;
+};
+__device__ __forceinline__ tsod_align_geom tsod_roi_align_geom(float bidx, float x1, float y1, float x2, float y2, float scale,
+                                                               int PH, int PW, int sampling_ratio, int aligned) {
+    tsod_align_geom g;
+    g.b = (int)bidx;
+    const float offset = aligned ? 0.5f : 0.f;
+    g.start_w = x1 * scale - offset;
+    g.start_h = y1 * scale - offset;
+    const float end_w = x2 * scale - offset, end_h = y2 * scale - offset;
+    float rw = end_w - g.start_w, rh = end_h - g.start_h;
+    if (!aligned) { rw = fmaxf(rw, 1.f); rh = fmaxf(rh, 1.f); }
+    g.bin_h = rh / (float)PH;
+    g.bin_w = rw / (float)PW;
+    g.grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / (float)PH);
+    g.grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / (float)PW);
+    g.count = (float)max(g.grid_h * g.grid_w, 1);
+    return g;
+}
+// The sample rule as macros, not functions: they expand to the forward's original statements, so roi_pool.hip's kernels keep
+// their instruction stream (a function boundary here changes the register allocation of roi_align_kernel).
+// Coordinate of sample i of bin p along one axis:
+#define TSOD_ALIGN_SAMPLE(start, bin, grid, p, i) ((start) + (float)(p) * (bin) + ((float)(i) + .5f) * (bin) / (float)(grid))
+// The bilinear rule of the sample (yy, xx): `continue` when it lies outside [-1, H] x [-1, W] (it contributes 0); else clamp
+// at 0, low = (int), high = low + 1 (both H - 1 / W - 1 at the border, where the coordinate becomes low) and ly / lx =
+// coordinate - low (the weight of high; 1 - it is the weight of low).  Declares y_low, y_high, x_low, x_high, ly, lx.
+#define TSOD_ALIGN_BILINEAR_OR_CONTINUE(yy, xx, Hf, Wf)                                                          \
+    float y = (yy), x = (xx);                                                                                 \
+    if (y < -1.f || y > (float)(Hf) || x < -1.f || x > (float)(Wf)) continue;                                 \
+    if (y <= 0.f) y = 0.f;                                                                                    \
+    if (x <= 0.f) x = 0.f;                                                                                    \
+    int y_low = (int)y, x_low = (int)x, y_high, x_high;                                                       \
+    if (y_low >= (Hf) - 1) { y_high = y_low = (Hf) - 1; y = (float)y_low; } else y_high = y_low + 1;          \
+    if (x_low >= (Wf) - 1) { x_high = x_low = (Wf) - 1; x = (float)x_low; } else x_high = x_low + 1;          \
+    const float ly = y - (float)y_low, lx = x - (float)x_low
 // fp16x2 activation exponent for a tensor whose abs-max has these bits: 2^e * absmax < 2^15 (fp16 ends at 65504), e in [-24, 24]
 // (zero / subnormal abs-max: 24; inf: -24 - the range flag of the launch then reports the non-finite input)
 __device__ __forceinline__ int tsod_fp16x2_exp_from_bits(unsigned bits) {

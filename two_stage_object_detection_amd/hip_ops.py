@@ -622,6 +622,62 @@ def roi_align_avg_nhwc(feat: torch.Tensor, rois: torch.Tensor, roi_indices: torc
     return out
 
 
+def _grad_target(d_out: torch.Tensor, B: int, Hf: int, Wf: int, C: int, d_feat, what: str):
+    if d_out.dim() != 2 or d_out.stride(1) != 1 or d_out.shape[1] < C or d_out.dtype != torch.float32:
+        raise ValueError(f"{what}: d_out must be a float32 row matrix [B*R, >= {C}], got {tuple(d_out.shape)}")
+    if d_feat is None:
+        return torch.empty((B, Hf, Wf, C), dtype=torch.float32, device=d_out.device)
+    if (d_feat.dim() != 4 or tuple(d_feat.shape[:3]) != (B, Hf, Wf) or d_feat.shape[3] < C or not d_feat.is_contiguous()
+            or d_feat.dtype != torch.float32):
+        raise ValueError(f"{what}: d_feat must be a contiguous float32 [{B},{Hf},{Wf},>={C}] tensor, got {tuple(d_feat.shape)}")
+    return d_feat
+
+
+def roi_pool_avg_grad_nhwc(feat: torch.Tensor, rois: torch.Tensor, roi_indices: torch.Tensor, img_h, img_w, d_out: torch.Tensor,
+                           output_size=(7, 7), spatial_scale=1.0, d_feat=None, accumulate: bool = False) -> torch.Tensor:
+    """The backward of roi_pool_avg_nhwc (tsod_roi_pool_avg_grad_f32): feat [B,Hf,Wf,P] (the forward's input; its first
+    C = d_out's columns channels), rois [B,R,4], roi_indices [B], d_out [B*R, >= C] (row pitch = stride(0)) -> d_feat
+    [B,Hf,Wf,C'] NHWC (``d_feat`` given: written, or with ``accumulate`` added to, in its first C channels)."""
+    require_cuda(feat, "roi_pool_avg_grad")
+    B, Hf, Wf, P = feat.shape
+    R = rois.shape[1]
+    C = P if d_feat is None else min(P, d_feat.shape[3])
+    C = min(C, d_out.shape[1])
+    PH, PW = output_size
+    d_feat = _grad_target(d_out, B, Hf, Wf, C, d_feat, "roi_pool_avg_grad")
+    if rois.shape[0] != B:
+        raise ValueError(f"roi_pool_avg_grad: {rois.shape[0]} RoI groups for {B} feature maps")
+    ws_bytes = lib().tsod_roi_pool_avg_grad_workspace_bytes(B, R, C, PH, PW)
+    ws = ARENA.get(feat.device, ws_bytes)
+    check(lib().tsod_roi_pool_avg_grad_f32(ptr(feat), B, Hf, Wf, C, P, ptr(rois.contiguous()),
+                                           ptr(roi_indices.to(torch.int32).contiguous()), R, float(img_h), float(img_w),
+                                           float(spatial_scale), PH, PW, ptr(d_out), d_out.stride(0), ptr(d_feat), d_feat.shape[3],
+                                           1 if accumulate else 0, ptr(ws), ws_bytes, stream_ptr()), "roi_pool_avg_grad")
+    return d_feat
+
+
+def roi_align_avg_grad_nhwc(feat_shape, rois: torch.Tensor, roi_indices: torch.Tensor, img_h, img_w, d_out: torch.Tensor,
+                            output_size=(7, 7), spatial_scale=1.0, sampling_ratio=2, aligned=False, d_feat=None,
+                            accumulate: bool = False) -> torch.Tensor:
+    """The backward of roi_align_avg_nhwc (tsod_roi_align_avg_grad_f32): ``feat_shape`` = (B, Hf, Wf, C) of the forward's input
+    (its values are not needed), d_out [B*R, >= C] -> d_feat [B,Hf,Wf,C] NHWC (``d_feat`` / ``accumulate`` as for RoIPool)."""
+    require_cuda(d_out, "roi_align_avg_grad")
+    B, Hf, Wf, C = (int(v) for v in feat_shape)
+    C = min(C, d_out.shape[1]) if d_feat is None else min(C, d_out.shape[1], d_feat.shape[3])
+    R = rois.shape[1]
+    PH, PW = output_size
+    d_feat = _grad_target(d_out, B, Hf, Wf, C, d_feat, "roi_align_avg_grad")
+    if rois.shape[0] != B:
+        raise ValueError(f"roi_align_avg_grad: {rois.shape[0]} RoI groups for {B} feature maps")
+    ws_bytes = lib().tsod_roi_align_avg_grad_workspace_bytes(B, R)
+    ws = ARENA.get(d_out.device, ws_bytes)
+    check(lib().tsod_roi_align_avg_grad_f32(B, Hf, Wf, C, ptr(rois.contiguous()), ptr(roi_indices.to(torch.int32).contiguous()), R,
+                                            float(img_h), float(img_w), float(spatial_scale), PH, PW, int(sampling_ratio),
+                                            1 if aligned else 0, ptr(d_out), d_out.stride(0), ptr(d_feat), d_feat.shape[3],
+                                            1 if accumulate else 0, ptr(ws), ws_bytes, stream_ptr()), "roi_align_avg_grad")
+    return d_feat
+
+
 def detections(cls_locs: torch.Tensor, scores: torch.Tensor, rois: torch.Tensor) -> torch.Tensor:
     """[B,R,4*n_class], [B,R,n_class], [B,R,4] -> [B,R,6] (x1,y1,x2,y2,score,class)."""
     require_cuda(scores, "detections")

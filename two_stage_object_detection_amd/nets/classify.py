@@ -96,6 +96,38 @@ class HarNetRoIHead(PlanOwner, nn.Module):
                 torch.cuda.current_stream(dev).synchronize()
         return w2
 
+    def _dgrad_weight(self, dev):
+        """The fused weight transposed, [C, 1, 1, pad4(5*n_class)] (kept in ``_packed_cache``: ``invalidate_packed()`` drops it)."""
+        wt = self._packed_cache.get(("head.dgrad", dev))
+        if wt is None:
+            w = self._pack(dev)[0]
+            wt = w.t().contiguous()
+            wt = self._packed_cache[("head.dgrad", dev)] = wt.view(wt.shape[0], 1, 1, wt.shape[1])
+        return wt
+
+    def fc7_grad(self, d_both: torch.Tensor, wt=None) -> torch.Tensor:
+        """d fc7 [M, C] = d_both [M, pad4(5*n_class)] (d loss / d ``forward_fused``'s fused output, zero pad columns) times the
+        fused weight, on the f32 conv library as a 1x1 GEMM with the transposed weight (K = pad4(5*n_class)).  ``wt``: a
+        ``_dgrad_weight`` kept from the forward (default: the current one)."""
+        require_cuda(d_both, "HarNetRoIHead.fc7_grad")
+        wt = self._dgrad_weight(d_both.device) if wt is None else wt
+        M = d_both.shape[0]
+        if d_both.dim() != 2 or d_both.shape[1] != wt.shape[3] or not d_both.is_contiguous():
+            raise ValueError(f"fc7_grad: d_both must be a contiguous [M, {wt.shape[3]}] matrix, got {tuple(d_both.shape)}")
+        return hip_ops.conv2d_nhwc(d_both.view(1, 1, M, wt.shape[3]), wt, precision=_ffi.PREC_F32).view(M, wt.shape[0])
+
+    def pooled_grad(self, feat, rois, roi_indices, img_size, d_fc7, d_feat=None, accumulate=False):
+        """The backward of ``pooled`` (RoI rescale + RoIPool / RoIAlign + the classifier's mean): d_fc7 [n*R, C] -> d feat NHWC,
+        written into / added to ``d_feat`` when given (tsod_roi_pool_avg_grad_f32 / tsod_roi_align_avg_grad_f32)."""
+        n = feat.shape[0]
+        rois = rois.reshape(n, -1, 4)
+        if isinstance(self.roi, RoIAlign):
+            return hip_ops.roi_align_avg_grad_nhwc(feat.shape, rois, roi_indices, img_size[0], img_size[1], d_fc7,
+                                                   self.roi.output_size, self.roi.spatial_scale, self.roi.sampling_ratio,
+                                                   self.roi.aligned, d_feat=d_feat, accumulate=accumulate)
+        return hip_ops.roi_pool_avg_grad_nhwc(feat, rois, roi_indices, img_size[0], img_size[1], d_fc7, self.roi.output_size,
+                                              self.roi.spatial_scale, d_feat=d_feat, accumulate=accumulate)
+
     def _gemm_kw(self, dev, prec, feat_amax, range_flag, fc7=None):
         """What the fused GEMM's arithmetic needs beside the f32 weights.  fp16x2 scales its input with range words: the
         backbone plan's (``feat_amax``) inside the detector forward; for the staged API (``forward`` / ``forward_nhwc`` /

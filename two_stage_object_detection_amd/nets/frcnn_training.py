@@ -85,17 +85,21 @@ HEAD_PARAMS = ("rpn.loc.weight", "rpn.loc.bias", "rpn.score.weight", "rpn.score.
 
 
 class _HeadLosses(torch.autograd.Function):
-    """The five losses as one differentiable node whose backward is the HIP kernels of csrc/head_grads.hip only.
+    """The five losses as one differentiable node whose backward is HIP kernels only (csrc/head_grads.hip, feature_grads.hip).
 
-    forward(per [4], saved, *the eight head parameters) -> [rpn_loc, rpn_cls, roi_loc, roi_cls, total] (total summed in the
+    forward(per [4], saved, features or None, *params) -> [rpn_loc, rpn_cls, roi_loc, roi_cls, total] (total summed in the
     order of the default path, so the values are identical).  backward: tsod_rpn_losses_grad_f32, tsod_roi_losses_grad_f32,
-    tsod_rpn_roi_scatter_f32 (the indirect term through the proposals), then tsod_wgrad_f32 for the RPN (feature map rows)
-    and for the head (fc7 rows).  It writes / adds the eight ``.grad`` tensors itself (the fused [56,C] / [408,C] results go
-    straight into the reference's parameter shapes) and returns no gradient to autograd, so ``torch.autograd.grad`` on these
-    parameters is not supported - ``.backward()`` is."""
+    tsod_rpn_roi_scatter_f32 (the indirect term through the proposals), then
+      * with ``params`` (head_grads=True): tsod_wgrad_f32 for the RPN (feature map rows) and for the head (fc7 rows), each pair
+        skipped when none of its four parameters requires grad.  It writes / adds the eight ``.grad`` tensors itself (the fused
+        [56,C] / [408,C] results go straight into the reference's parameter shapes) and returns no gradient for them, so
+        ``torch.autograd.grad`` on these parameters is not supported - ``.backward()`` is;
+      * with ``features`` (the caller's feature map, requiring grad): d feat = d rpn_out . W_rpn (1x1 f32 GEMM) + the backward
+        of the head's pooling of d fc7 = d both . W_head (tsod_roi_pool_avg_grad_f32 / tsod_roi_align_avg_grad_f32, adding in
+        place), one NHWC -> NCHW pass, returned to autograd as d features."""
 
     @staticmethod
-    def forward(ctx, per, saved, *params):
+    def forward(ctx, per, saved, features, *params):
         ctx.saved = saved
         ctx.params = params
         return torch.cat([per, (per[0] + per[1] + per[2] + per[3]).view(1)])
@@ -110,9 +114,20 @@ class _HeadLosses(torch.autograd.Function):
         hip_ops.rpn_roi_scatter(d_rpn, d_roi, sv["sample_src"], sv["keep_idx"], sv["sort_idx"], sv["rpn_out"], sv["anchor"],
                                 sv["A"], sv["clamp_x"], sv["clamp_y"])
         feat = sv["feat"]
-        _wgrad_into(d_rpn, feat.view(-1, feat.shape[-1])[:, :params[0].shape[1]], params[0:4])   # (pixel rows may be padded)
-        _wgrad_into(d_both, sv["fc7"], params[4:8])
-        return (None, None) + (None,) * len(params)
+        if params:
+            if any(p.requires_grad for p in params[0:4]):
+                _wgrad_into(d_rpn, feat.view(-1, feat.shape[-1])[:, :params[0].shape[1]], params[0:4])   # (pixel rows may be padded)
+            if any(p.requires_grad for p in params[4:8]):
+                _wgrad_into(d_both, sv["fc7"], params[4:8])
+        d_features = None
+        if ctx.needs_input_grad[2]:
+            n, h, w = feat.shape[:3]
+            d_feat = sv["rpn"].input_grad(d_rpn, n, h, w, wt=sv["rpn_wt"])                     # [n,h,w,C] NHWC
+            d_fc7 = sv["head"].fc7_grad(d_both, wt=sv["head_wt"])
+            sv["head"].pooled_grad(feat, sv["sample_roi"], sv["roi_indices"], sv["head_size"], d_fc7, d_feat=d_feat,
+                                   accumulate=True)
+            d_features = hip_ops.nhwc_to_nchw(d_feat)
+        return (None, None, d_features) + (None,) * len(params)
 
 
 def _wgrad_into(dy, x, params):
@@ -150,6 +165,13 @@ class FasterRCNNTrainer(nn.Module):
     backward reads, so a backward issued after a later forward still gives its own forward's gradients.  The default
     (``head_grads=False``) returns losses that do not require grad.
 
+    ``forward(..., features=f)`` (keyword-only): ``f`` [B, C, h, w] float32 on the GPU (any strides, any autograd history; C =
+    the RPN's in_channels) is the feature map instead of ``feat_extra(imgs)``; ``imgs`` is then used for its shape only
+    (img_size, B).  When grad mode is on and ``f.requires_grad``, the losses are differentiable w.r.t. ``f``: the node returns
+    d f through autograd (``loss.backward()`` or ``torch.autograd.grad(loss, f)``) - the RPN's input GEMM, the head's input
+    GEMM and the RoIPool / RoIAlign + mean backward on HIP, whatever ``head_grads`` is.  No gradient
+    flows through the RoI coordinates into the pooling (as in torchvision); the frozen-backbone check does not apply.
+
     ``forward(imgs, bboxes, labels, scale=1)`` -> (losses, anchors_pred [B,S,4], classes_pred [B,S] int64,
     classes_score_pred [B,S], bboxes[0][None], (labels[0] + 1)[None]) with losses = [rpn_loc, rpn_cls, roi_loc, roi_cls,
     their sum]: zero-dimensional tensors, each summed over the images and divided by their number (:333-342).
@@ -174,9 +196,10 @@ class FasterRCNNTrainer(nn.Module):
       * in-place updates of the eight head parameters (an optimizer step) are detected through their ``_version`` and the
         RPN's and head's packed weight images are rebuilt before the next forward.
 
-    Not provided: backbone gradients and train-mode BatchNorm (fine-tuning the heads on a frozen backbone is what
-    ``head_grads`` covers); gradients w.r.t. the input or through RoIPool / RoIAlign; eval_fn / calculate_metrics (see the
-    module docstring); graph capture and tuning (the forward runs whatever plan the backbone holds)."""
+    Not provided: the HIP backbone's own backward and train-mode BatchNorm (``head_grads`` fine-tunes the heads on a frozen
+    backbone; ``features=`` trains a backbone that has autograd of its own); gradients w.r.t. RoI coordinates; eval_fn /
+    calculate_metrics (see the module docstring); graph capture and tuning (the forward runs whatever plan the backbone
+    holds)."""
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
                  backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False):
@@ -225,20 +248,37 @@ class FasterRCNNTrainer(nn.Module):
         self.rpn.raise_if_error()
         self.feat_extra.raise_if_error()
 
-    def forward(self, imgs, bboxes, labels, scale=1):
+    def _check_features(self, features, B):
+        if not isinstance(features, torch.Tensor):
+            raise TypeError(f"FasterRCNNTrainer.forward: features must be a tensor, got {type(features).__name__}")
+        if features.dtype != torch.float32:
+            raise TypeError(f"FasterRCNNTrainer.forward: features must be float32, got {features.dtype}")
+        require_cuda(features, "FasterRCNNTrainer.forward(features=)")
+        C = self.rpn.score.in_channels
+        if features.dim() != 4 or features.shape[0] != B or features.shape[1] != C:
+            raise ValueError(f"FasterRCNNTrainer.forward: features must be [B={B}, C={C}, h, w] (the RPN's in_channels), got "
+                             f"{tuple(features.shape)}")
+
+    def forward(self, imgs, bboxes, labels, scale=1, *, features=None):
         if self.training:
             raise TsodError("the HIP path implements the inference forward only: call .eval() first")
-        x = torch.stack(list(imgs)) if isinstance(imgs, (list, tuple)) else imgs
-        require_cuda(x, "FasterRCNNTrainer.forward")
-        B = x.shape[0]
+        if features is None:
+            x = torch.stack(list(imgs)) if isinstance(imgs, (list, tuple)) else imgs
+            require_cuda(x, "FasterRCNNTrainer.forward")
+            shape, dev = tuple(x.shape), x.device
+        else:                                                            # imgs: only its shape is used
+            shape = ((len(imgs),) + tuple(imgs[0].shape)) if isinstance(imgs, (list, tuple)) else tuple(imgs.shape)
+            self._check_features(features, shape[0])
+            dev = features.device
+        B = shape[0]
         if len(bboxes) != B or len(labels) != B:
             raise ValueError(f"FasterRCNNTrainer.forward: {B} images, {len(bboxes)} box sets, {len(labels)} label sets")
-        dev = x.device
-        img_size = tuple(x.shape[1:])                                    # (C,H,W): quirk Q1 (RPN), Q2 (head)
-        head_size = img_size if self.head_img_size == "chw" else tuple(x.shape[2:])
+        img_size = shape[1:]                                             # (C,H,W): quirk Q1 (RPN), Q2 (head)
+        head_size = img_size if self.head_img_size == "chw" else shape[2:]
         n_sample = self.proposal_target_creator.n_sample
         grads = self.head_grads and torch.is_grad_enabled()
-        if grads:
+        feat_grad = features is not None and torch.is_grad_enabled() and features.requires_grad
+        if grads and features is None:
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad]
             if frozen:
                 raise TsodError(f"FasterRCNNTrainer(head_grads=True) computes the head parameters' gradients on a frozen "
@@ -246,11 +286,15 @@ class FasterRCNNTrainer(nn.Module):
                                 "trainer.feat_extra.requires_grad_(False)")
         self._refresh_packs()
         with hip_ops.ARENA.scope((self._uid, 0)):
-            feat = self.feat_extra.forward_nhwc(x, 0)
-            plan = self.feat_extra._plan_for(x, 0)
-            feat_amax, flag = (getattr(plan, "output_amax", 0) or None), getattr(plan, "range_flag", None)
+            if features is None:
+                feat = self.feat_extra.forward_nhwc(x, 0)
+                plan = self.feat_extra._plan_for(x, 0)
+                feat_amax, flag = (getattr(plan, "output_amax", 0) or None), getattr(plan, "range_flag", None)
+            else:                    # the caller's map, once to NHWC (an fp16x2 GEMM choice scales it by a tsod_absmax_f32 pass)
+                feat = hip_ops.nchw_to_nhwc(features.detach())
+                feat_amax, flag = None, None
             proposed = self.rpn.propose(feat, img_size, scale, want_anchors=True, feat_amax=feat_amax, range_flag=flag,
-                                        want_index=grads)
+                                        want_index=grads or feat_grad)
             rpn_out, rois, anchor = proposed[:3]
             gt_locs, gt_labels, s_rois, s_locs, s_labels, s_srcs = [], [], [], [], [], []
             for i in range(B):
@@ -259,7 +303,7 @@ class FasterRCNNTrainer(nn.Module):
                 gt_loc, gt_label = self.anchor_target_creator(bbox, anchor)
                 gt_locs.append(gt_loc)
                 gt_labels.append(gt_label)
-                if grads:
+                if grads or feat_grad:
                     s_roi, s_loc, s_label, s_src = self.proposal_target_creator.with_sources(rois[i], bbox, label)
                     s_srcs.append(s_src)
                 else:
@@ -281,22 +325,27 @@ class FasterRCNNTrainer(nn.Module):
             s_locs_all, s_labels_all = torch.stack(s_locs), torch.stack(s_labels)
             anchors_pred, classes_pred, classes_score_pred, roi_loss, roi_status = hip_ops.roi_losses(
                 roi_cls_locs, roi_scores, sample_rois, s_locs_all, s_labels_all, self.roi_sigma)
-            if grads:
-                saved = dict(feat=feat.clone(),           # the plan's buffer: the next forward overwrites it
-                             rpn_out=rpn_out, anchor=anchor, sort_idx=proposed[3], keep_idx=proposed[4],
+            if grads or feat_grad:
+                saved = dict(feat=feat.clone() if features is None else feat,   # (the plan's buffer: the next forward
+                             rpn_out=rpn_out, anchor=anchor, sort_idx=proposed[3], keep_idx=proposed[4],  # overwrites it)
                              gt_loc=gt_loc_all, gt_label=gt_label_all, sample_roi=sample_rois, gt_roi_loc=s_locs_all,
                              gt_roi_label=s_labels_all, sample_src=torch.stack(s_srcs), fc7=fc7, both=both,
                              A=self.rpn.anchor_base.shape[0], n_class=n_sc, rpn_sigma=self.rpn_sigma,
                              roi_sigma=self.roi_sigma, inv_B=1.0 / B, clamp_x=img_size[1], clamp_y=img_size[2])
-            self.feat_extra.publish_range_word(plan)
+                if feat_grad:
+                    saved.update(rpn=self.rpn, head=self.head, rpn_wt=self.rpn._dgrad_weight(dev),
+                                 head_wt=self.head._dgrad_weight(dev), roi_indices=roi_indices, head_size=head_size)
+            if features is None:
+                self.feat_extra.publish_range_word(plan)
         # (one read of the two status words, after the last launch: the reference raises IndexError there)
         bad = rpn_status.sum() + roi_status.sum()
         if int(bad):
             raise IndexError("a target class index is out of bounds for the logits it indexes "
                              "(the reference raises IndexError at nets/frcnn_training.py:274 / 313-331)")
         per = torch.cat([rpn_loss, roi_loss], dim=1).sum(0) / B        # [rpn_loc, rpn_cls, roi_loc, roi_cls]
-        if grads:
-            losses = list(_HeadLosses.apply(per, saved, *self._head_params()).unbind(0))
+        if grads or feat_grad:
+            params = self._head_params() if grads else ()
+            losses = list(_HeadLosses.apply(per, saved, features if feat_grad else None, *params).unbind(0))
         else:
             losses = list(per.unbind(0))
             losses = losses + [sum(losses)]

@@ -113,6 +113,26 @@ class RegionProposalNetwork(PlanOwner, nn.Module):
                 torch.as_tensor(self.anchor_base, dtype=torch.float32).to(dev).contiguous(), n_loc, n_sc)
         return ent
 
+    def _dgrad_weight(self, dev):
+        """The fused weight transposed, [C, 1, 1, pad4(6A)]: the 1x1 conv that maps d (fused output) back to d feat.  Kept in
+        ``_packed_cache`` beside the forward's images, so ``invalidate_packed()`` drops it with them."""
+        wt = self._packed_cache.get(("rpn.dgrad", dev))
+        if wt is None:
+            pc = self._pack(dev)[0]
+            wt = pc.w.reshape(pc.cout, -1).t().contiguous()
+            wt = self._packed_cache[("rpn.dgrad", dev)] = wt.view(wt.shape[0], 1, 1, wt.shape[1])
+        return wt
+
+    def input_grad(self, d_out: torch.Tensor, n: int, h: int, w: int, wt=None) -> torch.Tensor:
+        """d feat [n,h,w,C] NHWC = d_out [n*h*w, pad4(6A)] (d loss / d ``propose``'s fused output, zero pad columns) times the
+        fused weight: the f32 conv library's 1x1 GEMM with the transposed weight (K = pad4(6A)), whatever arithmetic the
+        forward GEMM was tuned to.  ``wt``: a ``_dgrad_weight`` kept from the forward (default: the current one)."""
+        require_cuda(d_out, "RegionProposalNetwork.input_grad")
+        wt = self._dgrad_weight(d_out.device) if wt is None else wt
+        if d_out.dim() != 2 or d_out.shape != (n * h * w, wt.shape[3]) or not d_out.is_contiguous():
+            raise ValueError(f"input_grad: d_out must be a contiguous [{n * h * w}, {wt.shape[3]}] matrix, got {tuple(d_out.shape)}")
+        return hip_ops.conv2d_nhwc(d_out.view(n, h, w, wt.shape[3]), wt, precision=_ffi.PREC_F32)
+
     def _conv_kw(self, pc, prec, feat_amax, range_flag, feat=None):
         """Arguments of the fused conv that depend on the arithmetic: the pre-split weight image kept beside the f32 weights
         (never re-split per call: a constant of a captured graph) and, for fp16x2, the feature map's range words - the
