@@ -83,3 +83,22 @@ def test_cpu_tensors_are_refused():
     from two_stage_object_detection_amd import hip_ops
     with pytest.raises(_ffi.TsodError, match="HIP-only"):
         hip_ops.bbox_iou(torch.zeros(2, 4), torch.zeros(2, 4))
+
+
+def test_library_reads_only_the_known_environment_switches():
+    """The library's behaviour is set by its arguments: the only TSOD_* environment variables it reads are TSOD_XCD_NMAJOR
+    (workgroup placement, results unchanged) in the HIP sources and TSOD_LIB (which build to load) in the package."""
+    pkg = os.path.join(ROOT, "two_stage_object_detection_amd")
+    csrc = os.path.join(pkg, "csrc")
+    hip = set()
+    for name in os.listdir(csrc):
+        if name.endswith((".hip", ".h")):
+            hip |= set(re.findall(r'getenv\(\s*"(TSOD_\w+)"', open(os.path.join(csrc, name)).read()))
+    py = set()
+    for d, _, files in os.walk(pkg):
+        for name in files:
+            if name.endswith(".py"):
+                text = open(os.path.join(d, name)).read()
+                py |= set(re.findall(r'os\.(?:environ\.get\(|environ\[|getenv\()\s*["\'](TSOD_\w+)', text))
+    assert hip == {"TSOD_XCD_NMAJOR"}
+    assert py == {"TSOD_LIB"}

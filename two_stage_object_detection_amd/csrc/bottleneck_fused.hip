@@ -31,13 +31,11 @@
 //   * a wave owns one 32-channel block of the step's 64 and every second pixel block: ONE weight fragment pair per 16-k chunk
 //     feeds up to four activation fragments.
 #include "tsod_internal.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Tile: TH x 16 output pixels, TH = 10 (160 pixels = 5 blocks of 32, halo 12 x 18 = 216 -> 224 rows = 7 blocks) or 8 (128 = 4 blocks,
@@ -75,39 +73,10 @@ struct Params {
     const unsigned *amax_in;
     unsigned *amax_out;
     int *range_flag;
-    int dbg;                   // timing experiments only (TSOD_BN_DBG): 1 no x loads after the first, 2 no residual loads, 4 no weight loads after
-                               // the first two steps, 8 no output stores - wrong results by design, never set by the library's callers
 };
-
-__device__ __forceinline__ float prelu(float v, float a) { return fmaxf(v, 0.f) + a * fminf(v, 0.f); }
-
-// two fp16 pieces of s * x for a pair of elements (split2_pair of conv_igemm_f32.hip: four mixed-precision FMAs; `sc` wave-uniform)
-__device__ __forceinline__ void split2(float x0, float x1, float sc, unsigned &h, unsigned &l) {
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(h), "=&v"(l) : "v"(x0), "v"(x1), "s"(sc));
-}
-
-// three piece products, smallest first: lo*hi, hi*lo, hi*hi
-__device__ __forceinline__ void mfma3(f32x16 &acc, const u32x4 &wh, const u32x4 &wl, const u32x4 &ah, const u32x4 &al) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wl), __builtin_bit_cast(f16x8, ah), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, al), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, ah), acc, 0, 0, 0);
-}
 
 // byte offset of 16-byte slot `slot` of row `row` in the XOR-swizzled 64-byte-row x stage (4 slots per row, 4 rows per bank line)
 __device__ __forceinline__ int off64(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
-
-// workgroup-wide max of a non-negative value through LDS (two barriers); every thread gets it
-__device__ __forceinline__ float block_max(float v, float *scr, int tid) {
-    v = tsod_wave_max(v);
-    __syncthreads();
-    if ((tid & 63) == 0) scr[tid >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(scr[0], scr[1]), fmaxf(scr[2], scr[3]));
-}
 
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned off) {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
@@ -140,7 +109,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
     const int ty = t_in / p.tiles_x, tx = t_in - ty * p.tiles_x;
     const int h0 = ty * TH, w0 = tx * TW;
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, (short)0, (int)p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc((void *)p.out, (short)0, (int)((p.dbg & 8) ? 0u : p.out_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc((void *)p.out, (short)0, (int)p.out_bytes, 0x00020000);
 
     // ---- x scale: the static exponent, or what the input's range words call for (wave-uniform)
     float a_scale = p.a_scale;
@@ -160,7 +129,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
     const int n_steps1 = p.Cin / 32, sps = PROJ ? 2 + n_steps1 : 2, n_steps = n_steps1 + 18 + (p.Cout / 64) * sps;
     const u32x4 *wbase = reinterpret_cast<const u32x4 *>(p.wstream + cb * (W_STEP / 2) + lane * 64);
     auto w_load = [&](int s, WFrag &f) {
-        if (s >= n_steps || ((p.dbg & 4) && s > 2)) return;
+        if (s >= n_steps) return;
         const u32x4 *src = wbase + (size_t)s * (W_STEP / 16);
         f.h[0] = src[0]; f.l[0] = src[1]; f.h[1] = src[2]; f.l[1] = src[3];
     };
@@ -183,7 +152,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
     }
     float4 xr[NX];
     auto x_load = [&](int ks) {
-        if (ks >= n_steps1 || ((p.dbg & 1) && ks > 0)) return;
+        if (ks >= n_steps1) return;
 #pragma unroll
         for (int i = 0; i < NX; ++i) xr[i] = bload4(rs_x, xoff[i] != kOOB ? xoff[i] + (unsigned)ks * 128u : kOOB);
     };
@@ -191,8 +160,8 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
             unsigned h0_, l0_, h1_, l1_;
-            split2(xr[i].x, xr[i].y, a_scale, h0_, l0_);
-            split2(xr[i].z, xr[i].w, a_scale, h1_, l1_);
+            tsod_split2_pair(xr[i].x, xr[i].y, a_scale, h0_, l0_);
+            tsod_split2_pair(xr[i].z, xr[i].w, a_scale, h1_, l1_);
             *reinterpret_cast<uint2 *>(lds + stage * A_STAGE + xdst[i]) = make_uint2(h0_, h1_);
             *reinterpret_cast<uint2 *>(lds + stage * A_STAGE + A_PLANE + xdst[i]) = make_uint2(l0_, l1_);
         }
@@ -230,7 +199,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
                 if (b < nb1) {
                     const u32x4 ah = *reinterpret_cast<const u32x4 *>(lds + xfa[b][c] + stage * A_STAGE);
                     const u32x4 al = *reinterpret_cast<const u32x4 *>(lds + xfa[b][c] + stage * A_STAGE + A_PLANE);
-                    mfma3(acc[b], wf[0].h[c], wf[0].l[c], ah, al);
+                    tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], ah, al);
                 }
             }
         }
@@ -265,19 +234,19 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 chk = fmaf(acc[b][e], 0.f, chk);                 // (NaN once any accumulator is inf / NaN: PReLU's max / min would hide it)
-                const float v = keep * prelu(fmaf(acc[b][e], sv[e], bv[e]), p.slope);
+                const float v = keep * tsod_prelu(fmaf(acc[b][e], sv[e], bv[e]), p.slope);
                 acc[b][e] = v;
                 mx = fmaxf(mx, fabsf(v));
             }
         }
     }
-    mx = block_max(mx, scr, tid);                        // (its barriers also order the x stages' last reads before the y1 writes)
+    mx = tsod_block_max(mx, scr, tid);                   // (its barriers also order the x stages' last reads before the y1 writes)
     const int e1 = tsod_fp16x2_exp_from_bits(__float_as_uint(mx));
     const float ys1 = __uint_as_float((unsigned)(127 + e1) << 23);
     auto y_store = [&](const f32x16 &v, int row, float ysc) {
         unsigned hq[8], lq[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) split2(v[2 * e], v[2 * e + 1], ysc, hq[e], lq[e]);
+        for (int e = 0; e < 8; ++e) tsod_split2_pair(v[2 * e], v[2 * e + 1], ysc, hq[e], lq[e]);
         unsigned char *dst = lds + (row * Y_PITCH + (4 * cb + 2 * hh) * 16);
         *reinterpret_cast<u32x4 *>(dst) = u32x4{hq[0], hq[1], hq[2], hq[3]};
         *reinterpret_cast<u32x4 *>(dst + 16) = u32x4{hq[4], hq[5], hq[6], hq[7]};
@@ -325,7 +294,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
             if (n + 1 < 36) y1_frags(n + 1, af[(n + 1) & 1]);
 #pragma unroll
             for (int b = 0; b < 3; ++b)
-                if (b < nb2) mfma3(acc[b], wf[t % 3].h[c], wf[t % 3].l[c], af[n & 1][b].h, af[n & 1][b].l);
+                if (b < nb2) tsod_mfma3(acc[b], wf[t % 3].h[c], wf[t % 3].l[c], af[n & 1][b].h, af[n & 1][b].l);
             __builtin_amdgcn_sched_barrier(0);           // (the unrolled loop is one basic block: keep the scheduler from hoisting every
                                                          //  later chunk's loads to the top - 400+ live registers, scratch spills)
         }
@@ -349,13 +318,13 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 chk = fmaf(acc[b][e], 0.f, chk);
-                const float v = prelu(fmaf(acc[b][e], sv[e], bv[e]), p.slope);
+                const float v = tsod_prelu(fmaf(acc[b][e], sv[e], bv[e]), p.slope);
                 acc[b][e] = v;
                 mx = fmaxf(mx, fabsf(v));
             }
         }
     }
-    mx = block_max(mx, scr, tid);
+    mx = tsod_block_max(mx, scr, tid);
     const int e2 = tsod_fp16x2_exp_from_bits(__float_as_uint(mx));
     const float ys2 = __uint_as_float((unsigned)(127 + e2) << 23);
 #pragma unroll
@@ -442,7 +411,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
                     y2_frags(2 * st + c, af[c]);
 #pragma unroll
                     for (int b = 0; b < 3; ++b)
-                        if (b < nb2) mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
+                        if (b < nb2) tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
                 }
                 if (st == 1) {
 #pragma unroll
@@ -456,10 +425,10 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
 #pragma unroll
                     for (int b = 0; b < 3; ++b) {
                         unsigned h0_, l0_, h1_, l1_, h2_, l2_, h3_, l3_;
-                        split2(xraw[c][b][0].x, xraw[c][b][0].y, a_scale, h0_, l0_);
-                        split2(xraw[c][b][0].z, xraw[c][b][0].w, a_scale, h1_, l1_);
-                        split2(xraw[c][b][1].x, xraw[c][b][1].y, a_scale, h2_, l2_);
-                        split2(xraw[c][b][1].z, xraw[c][b][1].w, a_scale, h3_, l3_);
+                        tsod_split2_pair(xraw[c][b][0].x, xraw[c][b][0].y, a_scale, h0_, l0_);
+                        tsod_split2_pair(xraw[c][b][0].z, xraw[c][b][0].w, a_scale, h1_, l1_);
+                        tsod_split2_pair(xraw[c][b][1].x, xraw[c][b][1].y, a_scale, h2_, l2_);
+                        tsod_split2_pair(xraw[c][b][1].z, xraw[c][b][1].w, a_scale, h3_, l3_);
                         af[c][b].h = u32x4{h0_, h1_, h2_, h3_};
                         af[c][b].l = u32x4{l0_, l1_, l2_, l3_};
                     }
@@ -468,7 +437,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
                     for (int b = 0; b < 3; ++b)
-                        if (b < nb2) mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
+                        if (b < nb2) tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
             }
             wf[0] = wf[1];
             wf[1] = wf[2];
@@ -493,10 +462,10 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
             float m4 = 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float o0 = prelu(fmaf(t[i].x, sv.x, b4.x), p.slope);
-                const float o1 = prelu(fmaf(t[i].y, sv.y, b4.y), p.slope);
-                const float o2 = prelu(fmaf(t[i].z, sv.z, b4.z), p.slope);
-                const float o3 = prelu(fmaf(t[i].w, sv.w, b4.w), p.slope);
+                const float o0 = tsod_prelu(fmaf(t[i].x, sv.x, b4.x), p.slope);
+                const float o1 = tsod_prelu(fmaf(t[i].y, sv.y, b4.y), p.slope);
+                const float o2 = tsod_prelu(fmaf(t[i].z, sv.z, b4.z), p.slope);
+                const float o3 = tsod_prelu(fmaf(t[i].w, sv.w, b4.w), p.slope);
                 const float m = fmaxf(fmaxf(fabsf(o0), fabsf(o1)), fmaxf(fabsf(o2), fabsf(o3)));
                 m4 = fmaxf(m4, opix[b][i] != kOOB ? m : 0.f);
                 u32x4 o;
@@ -520,7 +489,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
   #pragma unroll
           for (int b = 0; b < 3; ++b)
   #pragma unroll
-              for (int i = 0; i < 4; ++i) res[b][i] = bload4(rs_x, (xpix[b][i] != kOOB && !(p.dbg & 2)) ? xpix[b][i] + chq : kOOB);
+              for (int i = 0; i < 4; ++i) res[b][i] = bload4(rs_x, xpix[b][i] != kOOB ? xpix[b][i] + chq : kOOB);
           y2_frags(0, af[0]);
   #pragma unroll
           for (int n = 0; n < 4; ++n) {
@@ -528,7 +497,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
               if (n + 1 < 4) y2_frags(n + 1, af[(n + 1) & 1]);
   #pragma unroll
               for (int b = 0; b < 3; ++b)
-                  if (b < nb2) mfma3(acc[b], wf[n >> 1].h[n & 1], wf[n >> 1].l[n & 1], af[n & 1][b].h, af[n & 1][b].l);
+                  if (b < nb2) tsod_mfma3(acc[b], wf[n >> 1].h[n & 1], wf[n >> 1].l[n & 1], af[n & 1][b].h, af[n & 1][b].l);
               __builtin_amdgcn_sched_barrier(0);
           }
           const float4 s4 = *reinterpret_cast<const float4 *>(p.bn + 256 + q * 64 + cb * 32 + ep_q * 4);
@@ -552,10 +521,10 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
               float m4 = 0.f;
   #pragma unroll
               for (int i = 0; i < 4; ++i) {
-                  const float o0 = prelu(fmaf(t[i].x, sv.x, b4.x + res[b][i].x), p.slope);
-                  const float o1 = prelu(fmaf(t[i].y, sv.y, b4.y + res[b][i].y), p.slope);
-                  const float o2 = prelu(fmaf(t[i].z, sv.z, b4.z + res[b][i].z), p.slope);
-                  const float o3 = prelu(fmaf(t[i].w, sv.w, b4.w + res[b][i].w), p.slope);
+                  const float o0 = tsod_prelu(fmaf(t[i].x, sv.x, b4.x + res[b][i].x), p.slope);
+                  const float o1 = tsod_prelu(fmaf(t[i].y, sv.y, b4.y + res[b][i].y), p.slope);
+                  const float o2 = tsod_prelu(fmaf(t[i].z, sv.z, b4.z + res[b][i].z), p.slope);
+                  const float o3 = tsod_prelu(fmaf(t[i].w, sv.w, b4.w + res[b][i].w), p.slope);
                   const float m = fmaxf(fmaxf(fabsf(o0), fabsf(o1)), fmaxf(fabsf(o2), fabsf(o3)));
                   m4 = fmaxf(m4, opix[b][i] != kOOB ? m : 0.f);
                   u32x4 o;
@@ -610,9 +579,7 @@ extern "C" int tsod_bottleneck_fp16x2(const tsod_bottleneck_desc *d, const float
         return (double)((tiles + 2 * cus - 1) / (2 * cus)) * mfma_slowest;
     };
     const int n1 = d->Cin / 32, nq = d->Cout / 64, c3 = proj ? 4 + 2 * n1 : 4;           // chunks of a conv3 slice
-    static const int force_th = [] { const char *e = getenv("TSOD_BN_TH"); return e ? atoi(e) : 0; }();
-    const int TH = force_th == 8 || force_th == 10 ? force_th
-                   : (cost(8, 3 * (3 * 2 * n1 + 2 * 36 + 2 * c3 * nq)) < cost(10, 3 * (4 * 2 * n1 + 3 * 36 + 3 * c3 * nq)) ? 8 : 10);
+    const int TH = cost(8, 3 * (3 * 2 * n1 + 2 * 36 + 2 * c3 * nq)) < cost(10, 3 * (4 * 2 * n1 + 3 * 36 + 3 * c3 * nq)) ? 8 : 10;
     p.tiles_x = (d->W + TW - 1) / TW; p.tiles_y = (d->H + TH - 1) / TH;
     TSOD_REQUIRE((uint64_t)d->N * d->H * d->W * d->out_pitch * 4 < 0xFFFFFFF0ull && d->Cin % 64 == 0, TSOD_ERR_UNSUPPORTED);
     p.x_bytes = (unsigned)((uint64_t)d->N * d->H * d->W * d->in_pitch * 4);
@@ -620,8 +587,6 @@ extern "C" int tsod_bottleneck_fp16x2(const tsod_bottleneck_desc *d, const float
     p.slope = d->slope; p.w_exp1 = d->w_exp[0]; p.w_exp2 = d->w_exp[1]; p.w_exp3 = d->w_exp[2];
     p.a_scale = ldexpf(1.f, d->a_scale_exp);
     p.amax_in = d->amax_in; p.amax_out = d->amax_out; p.range_flag = d->range_flag;
-    static const int dbg = [] { const char *e = getenv("TSOD_BN_DBG"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
     const int64_t grid = (int64_t)d->N * p.tiles_x * p.tiles_y;
     TSOD_REQUIRE(grid < 0x7FFFFFFF, TSOD_ERR_UNSUPPORTED);
     if (proj) {

@@ -144,19 +144,6 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &h, uns
     l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
 }
 
-// fp16x2 (TSOD_PREC_FP16X2): two elements as fp16 pieces of sc * x: hi = rne_f16(sc x), lo = rne_f16(sc x - hi) (the product by a
-// power of two and the subtraction are exact in f32, so each piece is ONE rounding of an exact value).  Four instructions per pair
-// on the mixed-precision FMA (v_fma_mixlo/mixhi_f16: f32 x f32 + f16 -> f16, written into one half of the destination): no separate
-// scale multiply, no conversion of hi back to f32, no pack - the form with v_cvt_pk_f16_f32 / v_cvt_f32_f16 / v_sub_f32 took eight,
-// and the split is what the fp16x2 K loops are short of issue slots for (both kernel families; `sc` wave-uniform).
-__device__ __forceinline__ void split2_pair(float x0, float x1, float sc, unsigned &h, unsigned &l) {
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(h), "=&v"(l) : "v"(x0), "v"(x1), "s"(sc));
-}
-
 // channel index inside the (concatenated) Cin -> offset inside the input pixel (select chain, no branches)
 __device__ __forceinline__ int seg_channel(const ConvParams &p, int ci) {
     int ch = p.seg_off[0] + ci;
@@ -674,11 +661,6 @@ __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN), MIN_WAVES) conv_ig
         u_kw = seg0 - u_kh * p.KW;
     }
     auto load_global = [&](float4(&ra)[A_ROWS], float4(&rb)[B_ROWS]) {
-#ifdef TSOD_DIAG_NOLOAD
-        // timing diagnostic only (wrong results): after the first two K-steps no global load is issued, the staged registers
-        // are re-used - what the K loop costs when memory latency is taken out
-        if (kq > kt_begin + 1) { ++kq; k += kBK; return; }
-#endif
         if (p.uniform_tap) {
             // the per-thread part of the address is the constant c4; everything else about this K-step is wave-uniform
             if (kq * kBK >= p.K1) {                   // K-steps past the first source's K: the second source (a 1x1 tap, always in range)
@@ -755,8 +737,8 @@ __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN), MIN_WAVES) conv_ig
         } else {
             unsigned h[2], m[2], l[2];
             if constexpr (PREC == 2) {
-                split2_pair(v.x, v.y, a_scale, h[0], l[0]);
-                split2_pair(v.z, v.w, a_scale, h[1], l[1]);
+                tsod_split2_pair(v.x, v.y, a_scale, h[0], l[0]);
+                tsod_split2_pair(v.z, v.w, a_scale, h[1], l[1]);
                 m[0] = m[1] = 0;
             } else {
                 split3_pair(v.x, v.y, h[0], m[0], l[0]);
@@ -787,9 +769,6 @@ __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN), MIN_WAVES) conv_ig
         }
     };
     auto store_lds = [&](int buf, const float4(&ra)[A_ROWS], const float4(&rb)[B_ROWS]) {
-#ifdef TSOD_DIAG_NOSTORE
-        if (kq > kt_begin + 2) return;        // timing diagnostic only (wrong results): no split / LDS writes after the first steps
-#endif
 #pragma unroll
         for (int i = 0; i < A_ROWS; ++i) store_chunk(buf, 0, r0 + RPP * i, ra[i]);
         store_b(buf, rb);
@@ -991,9 +970,6 @@ __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN), MIN_WAVES) conv_ig
 // (fp16x2, CHAN) a 1x1 filter over several segments, where every 16-byte chunk of a stage has its own place (chunk table).
 // Measurements and the instruction-level findings behind this layout: DESIGN.md 4.3, scripts/micro/bf16x3_dma_probe.hip.
 typedef int v4i32 __attribute__((ext_vector_type(4)));
-#ifdef TSOD_DIAG_NODMA
-__device__ int g_nodma_steps = 3;   // (a load the compiler cannot fold: with a constant here it proves the loop's descriptors null)
-#endif
 
 __device__ __forceinline__ v4i32 dma_rsrc(const void *ptr, unsigned bytes) {
     v4i32 r; const unsigned long long a = (unsigned long long)ptr;
@@ -1001,21 +977,15 @@ __device__ __forceinline__ v4i32 dma_rsrc(const void *ptr, unsigned bytes) {
     return r;
 }
 // one wave-instruction: 64 lanes x 16 bytes from per-lane source offsets to LDS [lds_dst, lds_dst + 1024)
-#ifndef TSOD_DMA_POLICY_A
-#define TSOD_DMA_POLICY_A ""       /* cache policy suffix of the activation / weight DMAs (experiments: " nt", " sc0", " sc1") */
-#endif
-#ifndef TSOD_DMA_POLICY_B
-#define TSOD_DMA_POLICY_B ""
-#endif
 // (the LDS destination = piece base + ring-slot offset is added INTO m0 by the statement itself: one scalar instruction
 //  instead of an add and a move - scalar instructions are what the K loop is short of)
 template <int WEIGHTS = 0>
 __device__ __forceinline__ void dma16(unsigned voff, v4i32 rsrc, unsigned soff, unsigned lds_dst, unsigned slot_off) {
     if (WEIGHTS)
-        asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen" TSOD_DMA_POLICY_B " lds"
+        asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
                      :: "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst), "s"(slot_off) : "memory", "scc");
     else
-        asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen" TSOD_DMA_POLICY_A " lds"
+        asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
                      :: "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst), "s"(slot_off) : "memory", "scc");
 }
 // one wave-instruction: 64 lanes x 4 bytes from per-lane source offsets to LDS [lds_dst, lds_dst + 256) (the range words)
@@ -1038,53 +1008,32 @@ __device__ __forceinline__ void mfma_bf16(f32x16 &c, const bf16x8 &a, const bf16
 //   gap_cvt:  MFMA; pk = rne_bf16x2(x0, x1); t0 = f32(pk.lo); t1 = f32(pk.hi)
 //   gap_sub:  MFMA; r0 = x0 - t0; r1 = x1 - t1 (exact); one LDS fragment read of the next stage
 //   gap_last: MFMA; pk = rne_bf16x2(x0, x1)
-// (DO = false only in the `make halfmfma` timing probe: the statement without its MFMA)
-template <bool DO = true>
 __device__ __forceinline__ void gap_cvt(f32x16 &c, const bf16x8 &a, const bf16x8 &b, float x0, float x1, unsigned &pk, float &t0, float &t1) {
-    if constexpr (DO)
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %4, %5, %0\n\t"
                  "v_cvt_pk_bf16_f32 %1, %6, %7\n\t"
                  "v_lshlrev_b32 %2, 16, %1\n\t"
                  "v_and_b32 %3, 0xffff0000, %1"
                  : "+v"(c), "=&v"(pk), "=&v"(t0), "=&v"(t1) : "v"(a), "v"(b), "v"(x0), "v"(x1));
-    else
-    asm volatile("v_cvt_pk_bf16_f32 %1, %6, %7\n\t"
-                 "v_lshlrev_b32 %2, 16, %1\n\t"
-                 "v_and_b32 %3, 0xffff0000, %1"
-                 : "+v"(c), "=&v"(pk), "=&v"(t0), "=&v"(t1) : "v"(a), "v"(b), "v"(x0), "v"(x1));
 }
-template <int OFF, bool DO = true, typename T>
+template <int OFF, typename T>
 __device__ __forceinline__ void gap_sub(f32x16 &c, const bf16x8 &a, const bf16x8 &b, float &r0, float &r1, float x0, float x1, float t0, float t1,
                                         T &rd, unsigned addr) {
-    if constexpr (DO)
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %4, %5, %0\n\t"
                  "v_sub_f32 %1, %6, %8\n\t"
                  "v_sub_f32 %2, %7, %9\n\t"
                  "ds_read_b128 %3, %10 offset:%11"
                  : "+v"(c), "=&v"(r0), "=&v"(r1), "=&v"(rd) : "v"(a), "v"(b), "v"(x0), "v"(x1), "v"(t0), "v"(t1), "v"(addr), "n"(OFF) : "memory");
-    else
-    asm volatile("v_sub_f32 %1, %6, %8\n\t"
-                 "v_sub_f32 %2, %7, %9\n\t"
-                 "ds_read_b128 %3, %10 offset:%11"
-                 : "+v"(c), "=&v"(r0), "=&v"(r1), "=&v"(rd) : "v"(a), "v"(b), "v"(x0), "v"(x1), "v"(t0), "v"(t1), "v"(addr), "n"(OFF) : "memory");
 }
-template <bool DO = true>
 __device__ __forceinline__ void gap_last(f32x16 &c, const bf16x8 &a, const bf16x8 &b, float x0, float x1, unsigned &pk) {
-    if constexpr (DO)
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %3, %0\n\t"
                  "v_cvt_pk_bf16_f32 %1, %4, %5"
                  : "+v"(c), "=&v"(pk) : "v"(a), "v"(b), "v"(x0), "v"(x1));
-    else
-    asm volatile("v_cvt_pk_bf16_f32 %1, %4, %5" : "+v"(c), "=&v"(pk) : "v"(a), "v"(b), "v"(x0), "v"(x1));
 }
-template <int OFF, bool DO = true, typename T>
+template <int OFF, typename T>
 __device__ __forceinline__ void gap_read(f32x16 &c, const bf16x8 &a, const bf16x8 &b, T &rd, unsigned addr) {
-    if constexpr (DO)
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %3, %0\n\t"
                  "ds_read_b128 %1, %4 offset:%5"
                  : "+v"(c), "=&v"(rd) : "v"(a), "v"(b), "v"(addr), "n"(OFF) : "memory");
-    else
-    asm volatile("ds_read_b128 %1, %4 offset:%5" : "+v"(c), "=&v"(rd) : "v"(a), "v"(b), "v"(addr), "n"(OFF) : "memory");
 }
 
 // ---- "fp16x2" (TSOD_PREC_FP16X2): every operand as TWO fp16 pieces of s * x (hi = rne(s x), lo = rne(s x - hi), s a power of two
@@ -1117,39 +1066,6 @@ __device__ __forceinline__ void gap2_b(f32x16 &c, const bf16x8 &a, const bf16x8 
                  "ds_read_b128 %2, %9 offset:%10"
                  : "+v"(c), "=&v"(l), "=&v"(rd) : "v"(a), "v"(b), "v"(x0), "v"(x1), "s"(sc), "v"(h), "v"(addr), "n"(OFF) : "memory");
 }
-#ifdef TSOD_DIAG_MFMA16
-// timing probe only (make mfma16; wrong results by design): every v_mfma_f32_32x32x16_bf16 of the K loop replaced by TWO
-// v_mfma_f32_16x16x32_bf16 on the same operand registers (the same matrix-pipe cycles and FLOPs, the other shape's register
-// traffic and power), everything else of the loop - DMAs, LDS reads, the activation split - unchanged
-typedef float f32x4p __attribute__((ext_vector_type(4)));
-struct Acc16 { f32x4p lo, hi; };
-__device__ __forceinline__ void mfma_bf16(Acc16 &c, const bf16x8 &a, const bf16x8 &b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %2, %3, %0\n\tv_mfma_f32_16x16x32_bf16 %1, %2, %3, %1" : "+v"(c.lo), "+v"(c.hi) : "v"(a), "v"(b));
-}
-template <bool DO = true>
-__device__ __forceinline__ void gap_cvt(Acc16 &c, const bf16x8 &a, const bf16x8 &b, float x0, float x1, unsigned &pk, float &t0, float &t1) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %5, %6, %0\n\tv_mfma_f32_16x16x32_bf16 %1, %5, %6, %1\n\t"
-                 "v_cvt_pk_bf16_f32 %2, %7, %8\n\tv_lshlrev_b32 %3, 16, %2\n\tv_and_b32 %4, 0xffff0000, %2"
-                 : "+v"(c.lo), "+v"(c.hi), "=&v"(pk), "=&v"(t0), "=&v"(t1) : "v"(a), "v"(b), "v"(x0), "v"(x1));
-}
-template <int OFF, bool DO = true, typename T>
-__device__ __forceinline__ void gap_sub(Acc16 &c, const bf16x8 &a, const bf16x8 &b, float &r0, float &r1, float x0, float x1, float t0, float t1,
-                                        T &rd, unsigned addr) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %5, %6, %0\n\tv_mfma_f32_16x16x32_bf16 %1, %5, %6, %1\n\t"
-                 "v_sub_f32 %2, %7, %9\n\tv_sub_f32 %3, %8, %10\n\tds_read_b128 %4, %11 offset:%12"
-                 : "+v"(c.lo), "+v"(c.hi), "=&v"(r0), "=&v"(r1), "=&v"(rd) : "v"(a), "v"(b), "v"(x0), "v"(x1), "v"(t0), "v"(t1), "v"(addr), "n"(OFF) : "memory");
-}
-template <bool DO = true>
-__device__ __forceinline__ void gap_last(Acc16 &c, const bf16x8 &a, const bf16x8 &b, float x0, float x1, unsigned &pk) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %3, %4, %0\n\tv_mfma_f32_16x16x32_bf16 %1, %3, %4, %1\n\tv_cvt_pk_bf16_f32 %2, %5, %6"
-                 : "+v"(c.lo), "+v"(c.hi), "=&v"(pk) : "v"(a), "v"(b), "v"(x0), "v"(x1));
-}
-template <int OFF, bool DO = true, typename T>
-__device__ __forceinline__ void gap_read(Acc16 &c, const bf16x8 &a, const bf16x8 &b, T &rd, unsigned addr) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %3, %4, %0\n\tv_mfma_f32_16x16x32_bf16 %1, %3, %4, %1\n\tds_read_b128 %2, %5 offset:%6"
-                 : "+v"(c.lo), "+v"(c.hi), "=&v"(rd) : "v"(a), "v"(b), "v"(addr), "n"(OFF) : "memory");
-}
-#endif
 
 constexpr int dma_stage_bytes(int bm, int bk, int bn = 128, int npl = 3) { return bm * bk * 4 + npl * bn * bk * 2; }
 // workgroups of an LDS-DMA tile per CU: two where two rings fit the LDS AND two workgroups' waves stay at two per SIMD (the loop
@@ -1338,9 +1254,6 @@ conv_dma_kernel(const ConvParams p) {
     // tap: block-major).  The K loop is bound by the instructions its two waves per SIMD issue, not by the matrix pipe (one
     // more scalar instruction per stage costs 8 cycles of a 1950-cycle step: measured 1949 -> 2290 cycles with 40 more), so this
     // state is kept to plain scalar integer selects.
-#ifdef TSOD_DIAG_NODMA
-    const int nodma_steps = __builtin_amdgcn_readfirstlane(*(volatile int *)&g_nodma_steps);
-#endif
     // (channel blocks of the block-major order: 32 channels, or a whole stage where a stage is longer than that)
     constexpr int CBLK = BK > 32 ? BK : 32;
     int u_kt = kt_begin, u_kh, u_kw, u_ci, u_cb;
@@ -1360,11 +1273,7 @@ conv_dma_kernel(const ConvParams p) {
     v4i32 u_rs_a = rs_in, u_rs_w = rs_w;
     const int k1_steps = CHAN ? 0x7fffffff : p.K1 / BK;          // (K1 % BK == 0: tile_ok_for; CHAN: no second source, K any multiple of 4)
     auto stage_state = [&]() {
-#ifdef TSOD_DIAG_NODMA
-        const bool live = u_kt < kt_begin + nodma_steps;         // timing probe only (make nodma): null DMAs after the ring's first fill
-#else
         const bool live = u_kt < kt_end;
-#endif
         u_second = u_kt >= k1_steps;                              // second source: a 1x1 tap, always inside the image
         const int d1 = ((u_kh * p.W + u_kw) * p.in_pitch + u_ci) * 4, d2 = (u_kt - k1_steps) * (BK * 4);
         // byte offset of k in a row of the weight image = (k / 8) * 48 = 6 k (k % 8 == 0); first source k = tap * Cin + channel
@@ -1378,9 +1287,6 @@ conv_dma_kernel(const ConvParams p) {
     };
     stage_state();
     auto advance_stage = [&]() {
-#ifdef TSOD_DIAG_NOADVANCE
-        return;                                                  // timing probe only (make noadvance): every stage fetches the first one again
-#endif
         ++u_kt;
         // (selects, not nested updates: written as branches these scalars end up in scratch memory, and a scratch access is a
         //  VMEM operation in the middle of the hand-counted vmcnt)
@@ -1441,16 +1347,10 @@ conv_dma_kernel(const ConvParams p) {
 
     float a_scale_s = p.a_scale;                                  // fp16x2: the activation scale as a scalar operand of the loop's statements
     f32x16 acc[1][TN];
-#ifdef TSOD_DIAG_MFMA16
-    Acc16 pacc[TN];                                               // the probe's accumulators (acc is zeroed behind the loop instead)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) pacc[j].lo = pacc[j].hi = f32x4p{0.f, 0.f, 0.f, 0.f};
-#else
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[0][j][e] = 0.f;
-#endif
 
     // fragment addresses inside a stage: lane (h, r) holds k = 16 wk + 8 h .. + 7 of row r
     const int h = lane >> 5, r = lane & 31;
@@ -1545,26 +1445,17 @@ conv_dma_kernel(const ConvParams p) {
         nxt.a[1] = __builtin_bit_cast(bf16x8, (u32x4{ll[0], ll[1], ll[2], ll[3]}));
       } else {
 #define TSOD_DMA(I) do { if constexpr ((I) < P) issue_piece(std::integral_constant<int, (I)>{}, std::integral_constant<bool, TABLE>{}, slot_off); } while (0)
-#ifdef TSOD_DIAG_MFMA16
-#define TSOD_MF(n) pacc[(n) & 3], cur.a[PA[(n) >> 2]], cur.b[(n) & 3][PB[(n) >> 2]]
-#else
 #define TSOD_MF(n) acc[0][(n) & 3], cur.a[PA[(n) >> 2]], cur.b[(n) & 3][PB[(n) >> 2]]
-#endif
         if constexpr (TABLE) {
             lds_read16<0>(t_e, tab_ptr);                         // oldest of this phase's LDS reads
             tab_ptr += 16;
         }
         lds_read16<0>(raw0, a_addr[0] + soff);
         lds_read16<0>(raw1, a_addr[1] + soff);
-#ifdef TSOD_DIAG_HALFMFMA
-#define TSOD_DO(n) (((n) >> 2) % 2 == 0)     /* timing probe only (make halfmfma): three of the six piece products, 12 MFMAs per phase */
-#else
-#define TSOD_DO(n) true
-#endif
-        gap_read<0 * B_PLANE, TSOD_DO(0)>(TSOD_MF(0), nxt.b[0][0], b_addr[0] + soff);
-        gap_read<0 * B_PLANE, TSOD_DO(1)>(TSOD_MF(1), nxt.b[1][0], b_addr[1] + soff);
-        gap_read<0 * B_PLANE, TSOD_DO(2)>(TSOD_MF(2), nxt.b[2][0], b_addr[2] + soff);
-        gap_read<0 * B_PLANE, TSOD_DO(3)>(TSOD_MF(3), nxt.b[3][0], b_addr[3] + soff);
+        gap_read<0 * B_PLANE>(TSOD_MF(0), nxt.b[0][0], b_addr[0] + soff);
+        gap_read<0 * B_PLANE>(TSOD_MF(1), nxt.b[1][0], b_addr[1] + soff);
+        gap_read<0 * B_PLANE>(TSOD_MF(2), nxt.b[2][0], b_addr[2] + soff);
+        gap_read<0 * B_PLANE>(TSOD_MF(3), nxt.b[3][0], b_addr[3] + soff);
         if constexpr (TABLE) {
             wait_lgkm_for<4>(t_e);                               // the entry, raw0, raw1 have landed (four younger reads may be out)
             const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)t_e.w);
@@ -1585,28 +1476,14 @@ conv_dma_kernel(const ConvParams p) {
             TSOD_DMA(0);
             wait_lgkm<4>();                                     // raw0, raw1 have landed (four younger reads may be out)
         }
-#ifdef TSOD_DIAG_NOSPLIT
-        // timing probe only (make nosplit; wrong results by design): the same MFMAs, LDS reads and DMAs without the VALU work of
-        // the activation split - what a K loop fed with PRE-SPLIT activations could reach
 #define TSOD_SPLIT_GROUP(N0, X0, X1, G, PL, J0, J1)                                                        \
-        mfma_bf16(TSOD_MF(N0));                                                                            \
-        gap_read<PL * B_PLANE>(TSOD_MF(N0 + 1), nxt.b[J0][PL], b_addr[J0] + soff);                         \
-        mfma_bf16(TSOD_MF(N0 + 2));                                                                        \
+        gap_cvt(TSOD_MF(N0), X0, X1, hh[G], t0, t1);                                                       \
+        gap_sub<PL * B_PLANE>(TSOD_MF(N0 + 1), r0, r1, X0, X1, t0, t1, nxt.b[J0][PL], b_addr[J0] + soff);  \
+        gap_cvt(TSOD_MF(N0 + 2), r0, r1, mm[G], t0, t1);                                                   \
         if constexpr (P > 5) TSOD_DMA(1 + 2 * G);                                                          \
-        gap_read<PL * B_PLANE>(TSOD_MF(N0 + 3), nxt.b[J1][PL], b_addr[J1] + soff);                         \
-        mfma_bf16(TSOD_MF(N0 + 4));                                                                        \
-        hh[G] = __float_as_uint(X0) & 0x3f803f80u; mm[G] = __float_as_uint(X1) & 0x3f803f80u; ll[G] = hh[G];   \
+        gap_sub<PL * B_PLANE>(TSOD_MF(N0 + 3), q0, q1, r0, r1, t0, t1, nxt.b[J1][PL], b_addr[J1] + soff);  \
+        gap_last(TSOD_MF(N0 + 4), q0, q1, ll[G]);                                                          \
         if constexpr (P > 5) TSOD_DMA(2 + 2 * G); else TSOD_DMA(1 + G);
-#else
-#define TSOD_SPLIT_GROUP(N0, X0, X1, G, PL, J0, J1)                                                        \
-        gap_cvt<TSOD_DO(N0)>(TSOD_MF(N0), X0, X1, hh[G], t0, t1);                                          \
-        gap_sub<PL * B_PLANE, TSOD_DO(N0 + 1)>(TSOD_MF(N0 + 1), r0, r1, X0, X1, t0, t1, nxt.b[J0][PL], b_addr[J0] + soff);  \
-        gap_cvt<TSOD_DO(N0 + 2)>(TSOD_MF(N0 + 2), r0, r1, mm[G], t0, t1);                                  \
-        if constexpr (P > 5) TSOD_DMA(1 + 2 * G);                                                          \
-        gap_sub<PL * B_PLANE, TSOD_DO(N0 + 3)>(TSOD_MF(N0 + 3), q0, q1, r0, r1, t0, t1, nxt.b[J1][PL], b_addr[J1] + soff);  \
-        gap_last<TSOD_DO(N0 + 4)>(TSOD_MF(N0 + 4), q0, q1, ll[G]);                                         \
-        if constexpr (P > 5) TSOD_DMA(2 + 2 * G); else TSOD_DMA(1 + G);
-#endif
         TSOD_SPLIT_GROUP(4, raw0.x, raw0.y, 0, 2, 0, 1)
         TSOD_SPLIT_GROUP(9, raw0.z, raw0.w, 1, 2, 2, 3)
         TSOD_SPLIT_GROUP(14, raw1.x, raw1.y, 2, 1, 0, 1)
@@ -1645,16 +1522,8 @@ conv_dma_kernel(const ConvParams p) {
             constexpr int SUB = CBLK / BK;
             const int taps = p.KH * p.KW;
             for (int j = tid; j <= nk + S; j += THREADS) {
-#if defined(TSOD_DIAG_NOADVANCE)
-                const int step = kt_begin;
-#else
                 const int step = kt_begin + j;
-#endif
-#if defined(TSOD_DIAG_NODMA)
-                const bool live = j < nodma_steps;
-#else
                 const bool live = step < kt_end;
-#endif
                 u32x4 e = {0u, 0u, 0u, 2u};                       // dead: no row fetches, null weight descriptor
                 if (live) {
                     if (step >= k1_steps) {
@@ -1714,10 +1583,10 @@ conv_dma_kernel(const ConvParams p) {
                 for (int pl = 0; pl < NPL; ++pl) X.b[j][pl] = *reinterpret_cast<const bf16x8 *>(lds + (b_addr[j] - lds0) + pl * B_PLANE);
             unsigned hh[4], mm[4], ll[4];
             if constexpr (NPL == 2) {
-                split2_pair(raw0.x, raw0.y, a_scale_s, hh[0], ll[0]);
-                split2_pair(raw0.z, raw0.w, a_scale_s, hh[1], ll[1]);
-                split2_pair(raw1.x, raw1.y, a_scale_s, hh[2], ll[2]);
-                split2_pair(raw1.z, raw1.w, a_scale_s, hh[3], ll[3]);
+                tsod_split2_pair(raw0.x, raw0.y, a_scale_s, hh[0], ll[0]);
+                tsod_split2_pair(raw0.z, raw0.w, a_scale_s, hh[1], ll[1]);
+                tsod_split2_pair(raw1.x, raw1.y, a_scale_s, hh[2], ll[2]);
+                tsod_split2_pair(raw1.z, raw1.w, a_scale_s, hh[3], ll[3]);
                 mm[0] = mm[1] = mm[2] = mm[3] = 0;
             } else {
                 split3_pair(raw0.x, raw0.y, hh[0], mm[0], ll[0]);
@@ -1780,12 +1649,6 @@ conv_dma_kernel(const ConvParams p) {
             if (__any(bad) && lane == 0) atomicOr(p.range_flag, 1);
         }
     }
-#ifdef TSOD_DIAG_MFMA16
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[0][j][e] = pacc[j].lo[e & 3] + pacc[j].hi[e & 3];
-#endif
     __syncthreads();                                             // no wave reads the ring any more: the epilogue may use it
 #ifdef TSOD_CLOCK_DIAG
     if (dg_on) { const long long c = __builtin_amdgcn_s_memtime(); dg_loop += c - dg_c; dg_c = c; }
@@ -1918,7 +1781,7 @@ pack_weight_fp16x2_kernel(const float *__restrict__ w, int Cout, int K, float sc
         for (int e = 0; e < 4; ++e) {
             const int k = g * 8 + 2 * e;
             unsigned h, l;
-            split2_pair(k < K ? w[n * K + k] : 0.f, k + 1 < K ? w[n * K + k + 1] : 0.f, scale, h, l);
+            tsod_split2_pair(k < K ? w[n * K + k] : 0.f, k + 1 < K ? w[n * K + k + 1] : 0.f, scale, h, l);
             o[e] = h;
             o[4 + e] = l;
         }
@@ -2089,16 +1952,6 @@ int xcd_map_override() {
     static const int v = [] {
         const char *e = getenv("TSOD_XCD_NMAJOR");
         return e == nullptr || *e == 0 ? -1 : (atoi(e) != 0 ? 1 : 0);
-    }();
-    return v;
-}
-
-// TSOD_KSTEP_TAPMAJOR = 1 keeps the LDS-DMA tiles on the weight image's own K-step order, (tap, channels), for experiments
-// (unset: channel blocks outermost wherever a filter has more than one tap, ConvParams::cmajor)
-int kstep_order_override() {
-    static const int v = [] {
-        const char *e = getenv("TSOD_KSTEP_TAPMAJOR");
-        return e != nullptr && atoi(e) != 0 ? 0 : 1;
     }();
     return v;
 }
@@ -2329,9 +2182,8 @@ extern "C" int tsod_conv2d_dual_f32(const tsod_conv2d_desc *d, const float *in, 
     const Sched sc = resolve(d);
     TSOD_REQUIRE(sc.cost < 1e299, TSOD_ERR_UNSUPPORTED);        // the named tile cannot run this problem (LDS-DMA tiles: tile_ok_for)
     p.uniform_tap = (d->n_seg == 1 && p.Cin % kTiles[sc.tile].bk == 0) ? 1 : 0;
-    static const bool no_chan_tab = getenv("TSOD_NO_CHAN_TAB") != nullptr;     // diagnostic: the arithmetic loader for every layer
     p.chan_tab = (kTiles[sc.tile].dma && dma_chan_case(d)) ? 1 : 0;
-    p.pointwise_tab = (!no_chan_tab && !p.uniform_tap && !kTiles[sc.tile].dma && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->stride == 1 &&
+    p.pointwise_tab = (!p.uniform_tap && !kTiles[sc.tile].dma && d->KH == 1 && d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->stride == 1 &&
                        p.c2 == 0 && p.K <= 4 * kChanTab) ? 1 : 0;
     TSOD_REQUIRE(p.c2 == 0 || (p.uniform_tap && p.K1 % kTiles[sc.tile].bk == 0 && p.c2 % kTiles[sc.tile].bk == 0), TSOD_ERR_UNSUPPORTED);
     p.ksteps = (p.K + kTiles[sc.tile].bk - 1) / kTiles[sc.tile].bk;
@@ -2339,7 +2191,7 @@ extern "C" int tsod_conv2d_dual_f32(const tsod_conv2d_desc *d, const float *in, 
     p.dp_tiles = sc.dp_tiles; p.split = sc.split; p.ksteps_per_split = sc.ksteps_per_split; p.sk_q = sc.sk_q;
     p.nmajor = sc.nmajor;
     const int cblk = kTiles[sc.tile].bk > 32 ? kTiles[sc.tile].bk : 32;      // channel block of the block-major K-step order (conv_dma_kernel: CBLK)
-    p.cmajor = (kTiles[sc.tile].dma && d->KH * d->KW > 1 && p.Cin % cblk == 0 && kstep_order_override() != 0) ? 1 : 0;
+    p.cmajor = (kTiles[sc.tile].dma && d->KH * d->KW > 1 && p.Cin % cblk == 0) ? 1 : 0;
     p.ci_wrap = p.cmajor ? cblk : p.Cin;
     if (sc.rem_tiles > 0)
         TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= sc.ws_bytes && tsod_aligned16(workspace), TSOD_ERR_WORKSPACE);

@@ -27,13 +27,11 @@
 //     XOR-ed with the pixel index: conflict-free writes and reads); then the 3x3 / 2 maxima, 256 contiguous bytes per pooled pixel out,
 //     and the abs-max of what was stored into the output's range words.
 #include "tsod_internal.h"
-#include <stdlib.h>
 #include <math.h>
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -64,35 +62,7 @@ struct Params {
     int w_exp;
     unsigned *amax_out;
     int *range_flag;
-    int dbg;                   // timing experiments only (TSOD_STEM_DBG): 1 no GEMM, 2 no BN / PReLU / conv-tile writes, 4 no pool, 8 no patch
-                               // requests and staging after the first - wrong results by design, never set by the library's callers
 };
-
-__device__ __forceinline__ float prelu(float v, float a) { return fmaxf(v, 0.f) + a * fminf(v, 0.f); }
-
-// two fp16 pieces of s * x for a pair of elements (split2_pair of conv_igemm_f32.hip)
-__device__ __forceinline__ void split2(float x0, float x1, float sc, unsigned &h, unsigned &l) {
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(h), "=&v"(l) : "v"(x0), "v"(x1), "s"(sc));
-}
-
-// three piece products, smallest first: lo*hi, hi*lo, hi*hi
-__device__ __forceinline__ void mfma3(f32x16 &acc, const u32x4 &wh, const u32x4 &wl, const u32x4 &ah, const u32x4 &al) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wl), __builtin_bit_cast(f16x8, ah), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, al), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, ah), acc, 0, 0, 0);
-}
-
-__device__ __forceinline__ float block_max(float v, float *scr, int tid) {
-    v = tsod_wave_max(v);
-    __syncthreads();
-    if ((tid & 63) == 0) scr[tid >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(scr[0], scr[1]), fmaxf(scr[2], scr[3]));
-}
 
 struct WFrag { u32x4 h, l; };
 
@@ -182,7 +152,7 @@ __global__ void __launch_bounds__(256, 2) stem_kernel(const Params p) {
 #pragma unroll
         for (int i = 0; i < PER; ++i) mx = fmaxf(mx, fmaxf(fabsf(px[i][0]), fmaxf(fabsf(px[i][1]), fabsf(px[i][2]))));
         // (a NaN pixel is dropped by fmaxf here and poisons its accumulators below: the range flag reports it)
-        mx = block_max(mx, scr, tid);                    // (its first barrier: the previous tile's pool reads are done with the LDS)
+        mx = tsod_block_max(mx, scr, tid);               // (its first barrier: the previous tile's pool reads are done with the LDS)
         const int e_a = tsod_fp16x2_exp_from_bits(__float_as_uint(mx));
         const float a_scale = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((127 + e_a) << 23));
 #pragma unroll
@@ -190,13 +160,13 @@ __global__ void __launch_bounds__(256, 2) stem_kernel(const Params p) {
             const int q = tid_l + 256 * i;
             if (q < SLOTS) {
                 unsigned h0, l0, h1, l1;
-                split2(px[i][0], px[i][1], a_scale, h0, l0);
-                split2(px[i][2], 0.f, a_scale, h1, l1);
+                tsod_split2_pair(px[i][0], px[i][1], a_scale, h0, l0);
+                tsod_split2_pair(px[i][2], 0.f, a_scale, h1, l1);
                 *reinterpret_cast<u32x2 *>(lds + q * 8) = u32x2{h0, h1};
                 *reinterpret_cast<u32x2 *>(lds + PLANE + q * 8) = u32x2{l0, l1};
             }
         }
-        if (t + nwg < n_tiles && !(p.dbg & 8)) request_patch(tile_at(t + nwg));   // lands while this tile is computed
+        if (t + nwg < n_tiles) request_patch(tile_at(t + nwg));   // lands while this tile is computed
         __syncthreads();
 
         // ---- GEMM: acc[b] = conv pixels of block ph + 2 b (columns) x channels 32 cb + pi(rows), K = 224
@@ -216,7 +186,6 @@ __global__ void __launch_bounds__(256, 2) stem_kernel(const Params p) {
         };
         AFrag af[2];
         af[0] = aload(0, 0);
-        if (!(p.dbg & 1))
 #pragma unroll
         for (int c = 0; c < KCH; ++c) {
             // (past the last chunk: the first fragments again, for this workgroup's next tile)
@@ -227,7 +196,7 @@ __global__ void __launch_bounds__(256, 2) stem_kernel(const Params p) {
                 const int n = c * NB + b;
                 if (n + 1 < KCH * NB) af[(n + 1) & 1] = aload((n + 1) / NB, (n + 1) % NB);
                 __builtin_amdgcn_sched_barrier(0);       // (the next fragment's reads and the weight requests stay AHEAD of these MFMAs)
-                mfma3(acc[b], w.h, w.l, af[n & 1].h, af[n & 1].l);
+                tsod_mfma3(acc[b], w.h, w.l, af[n & 1].h, af[n & 1].l);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -242,56 +211,52 @@ __global__ void __launch_bounds__(256, 2) stem_kernel(const Params p) {
         __syncthreads();                                 // every wave is done with the patch: the conv tile goes over it
 
         // ---- BN + PReLU, -inf outside the conv output, into the conv tile: lane = pixel m, channels ch16 + 0..15
-        if (!(p.dbg & 2)) {
-            const float sc = __uint_as_float((unsigned)(127 - e_a - p.w_exp) << 23);
-            float sv[16], bv[16];
+        const float sc = __uint_as_float((unsigned)(127 - e_a - p.w_exp) << 23);
+        float sv[16], bv[16];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const float4 s4 = *reinterpret_cast<const float4 *>(p.bn + ch16_l + 4 * v), b4 = *reinterpret_cast<const float4 *>(p.bn + 64 + ch16_l + 4 * v);
-                sv[4 * v] = s4.x * sc; sv[4 * v + 1] = s4.y * sc; sv[4 * v + 2] = s4.z * sc; sv[4 * v + 3] = s4.w * sc;
-                bv[4 * v] = b4.x; bv[4 * v + 1] = b4.y; bv[4 * v + 2] = b4.z; bv[4 * v + 3] = b4.w;
+        for (int v = 0; v < 4; ++v) {
+            const float4 s4 = *reinterpret_cast<const float4 *>(p.bn + ch16_l + 4 * v), b4 = *reinterpret_cast<const float4 *>(p.bn + 64 + ch16_l + 4 * v);
+            sv[4 * v] = s4.x * sc; sv[4 * v + 1] = s4.y * sc; sv[4 * v + 2] = s4.z * sc; sv[4 * v + 3] = s4.w * sc;
+            bv[4 * v] = b4.x; bv[4 * v + 1] = b4.y; bv[4 * v + 2] = b4.z; bv[4 * v + 3] = b4.w;
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int m = (ph + 2 * b) * 32 + j, cr = m / CW, cc = m - cr * CW;
+            const bool inside = (unsigned)(c0y + cr) < (unsigned)p.OH && (unsigned)(c0x + cc) < (unsigned)p.OW;
+            float v[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                chk = fmaf(acc[b][e], 0.f, chk);     // (NaN once any accumulator is inf / NaN: PReLU's max / min would hide it)
+                v[e] = inside ? tsod_prelu(fmaf(acc[b][e], sv[e], bv[e]), p.slope) : -INFINITY;
             }
+            if (m < NPX) {
+                unsigned char *row = lds + m * CT_PITCH;
+                const int s0 = ch16_l >> 2, sw = m & 15;
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                const int m = (ph + 2 * b) * 32 + j, cr = m / CW, cc = m - cr * CW;
-                const bool inside = (unsigned)(c0y + cr) < (unsigned)p.OH && (unsigned)(c0x + cc) < (unsigned)p.OW;
-                float v[16];
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    chk = fmaf(acc[b][e], 0.f, chk);     // (NaN once any accumulator is inf / NaN: PReLU's max / min would hide it)
-                    v[e] = inside ? prelu(fmaf(acc[b][e], sv[e], bv[e]), p.slope) : -INFINITY;
-                }
-                if (m < NPX) {
-                    unsigned char *row = lds + m * CT_PITCH;
-                    const int s0 = ch16_l >> 2, sw = m & 15;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        *reinterpret_cast<float4 *>(row + (((s0 + q) ^ sw) << 4)) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-                }
+                for (int q = 0; q < 4; ++q)
+                    *reinterpret_cast<float4 *>(row + (((s0 + q) ^ sw) << 4)) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
             }
         }
         __syncthreads();
 
         // ---- 3x3 / 2 maxima: thread = (pooled column g, channel slot s), the tile's TPH rows in turn
-        if (!(p.dbg & 4)) {
-            const int s = tid_l & 15, g = tid_l >> 4;
-            const int gx = tl.p0x + g;
+        const int s = tid_l & 15, g = tid_l >> 4;
+        const int gx = tl.p0x + g;
 #pragma unroll
-            for (int py = 0; py < TPH; ++py) {
-                const int gy = tl.p0y + py;
-                float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        for (int py = 0; py < TPH; ++py) {
+            const int gy = tl.p0y + py;
+            float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
 #pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
+            for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        const int m = (2 * py + dy) * CW + 2 * g + dx;
-                        const float4 v = *reinterpret_cast<const float4 *>(lds + m * CT_PITCH + ((s ^ (m & 15)) << 4));
-                        best.x = fmaxf(best.x, v.x); best.y = fmaxf(best.y, v.y); best.z = fmaxf(best.z, v.z); best.w = fmaxf(best.w, v.w);
-                    }
-                if (gy < p.PH && gx < p.PW) {
-                    *reinterpret_cast<float4 *>(p.out + (((size_t)tl.img * p.PH + gy) * p.PW + gx) * p.out_pitch + 4 * s) = best;
-                    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(best.x), fabsf(best.y)), fmaxf(fabsf(best.z), fabsf(best.w))));
+                for (int dx = 0; dx < 3; ++dx) {
+                    const int m = (2 * py + dy) * CW + 2 * g + dx;
+                    const float4 v = *reinterpret_cast<const float4 *>(lds + m * CT_PITCH + ((s ^ (m & 15)) << 4));
+                    best.x = fmaxf(best.x, v.x); best.y = fmaxf(best.y, v.y); best.z = fmaxf(best.z, v.z); best.w = fmaxf(best.w, v.w);
                 }
+            if (gy < p.PH && gx < p.PW) {
+                *reinterpret_cast<float4 *>(p.out + (((size_t)tl.img * p.PH + gy) * p.PW + gx) * p.out_pitch + 4 * s) = best;
+                amax = fmaxf(amax, fmaxf(fmaxf(fabsf(best.x), fabsf(best.y)), fmaxf(fabsf(best.z), fabsf(best.w))));
             }
         }
     }
@@ -334,8 +299,6 @@ extern "C" int tsod_stem_fp16x2(const tsod_stem_desc *d, const float *x, const v
     // persistent workgroups, two per CU; every workgroup gets the same number of tiles when that is possible (a grid of ceil(tiles / rounds))
     const int64_t slots = 2 * (int64_t)cus, rounds = (tiles + slots - 1) / slots;
     const int64_t grid = (tiles + rounds - 1) / rounds;
-    static const int dbg = [] { const char *e = getenv("TSOD_STEM_DBG"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
     hipLaunchKernelGGL(stem_kernel, dim3((unsigned)grid), dim3(256), 0, tsod_stream(stream), p);
     return tsod_launch_status();
 }

@@ -34,6 +34,14 @@ __device__ __forceinline__ float tsod_wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+// max over a 4-wave workgroup through LDS (`scr`: 4 floats; two barriers); every thread gets it
+__device__ __forceinline__ float tsod_block_max(float v, float *scr, int tid) {
+    v = tsod_wave_max(v);
+    __syncthreads();
+    if ((tid & 63) == 0) scr[tid >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(scr[0], scr[1]), fmaxf(scr[2], scr[3]));
+}
 // Every thread of the workgroup calls this (uniformly) with the largest |value| it stored (>= 0; fmaxf drops NaN, a NaN output
 // shows up in the consumer's range flag instead).  `smem`: >= blockDim.x / 64 floats of LDS; other waves may still be using
 // OTHER parts of the array it belongs to - the first barrier makes the words free, the second publishes them.
@@ -140,6 +148,31 @@ __device__ __forceinline__ tsod_align_geom tsod_roi_align_geom(float bidx, float
     if (y_low >= (Hf) - 1) { y_high = y_low = (Hf) - 1; y = (float)y_low; } else y_high = y_low + 1;          \
     if (x_low >= (Wf) - 1) { x_high = x_low = (Wf) - 1; x = (float)x_low; } else x_high = x_low + 1;          \
     const float ly = y - (float)y_low, lx = x - (float)x_low
+__device__ __forceinline__ float tsod_prelu(float v, float a) { return fmaxf(v, 0.f) + a * fminf(v, 0.f); }
+
+// ---- fp16x2 (TSOD_PREC_FP16X2) pieces, shared by the conv library and the fused stem / bottleneck kernels
+typedef float tsod_f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 tsod_f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int tsod_u32x4 __attribute__((ext_vector_type(4)));
+// two elements as fp16 pieces of sc * x: hi = rne_f16(sc x), lo = rne_f16(sc x - hi) (the product by a power of two and the
+// subtraction are exact in f32, so each piece is ONE rounding of an exact value).  Four instructions per pair on the
+// mixed-precision FMA (v_fma_mixlo/mixhi_f16: f32 x f32 + f16 -> f16, written into one half of the destination): no separate
+// scale multiply, no conversion of hi back to f32, no pack - the form with v_cvt_pk_f16_f32 / v_cvt_f32_f16 / v_sub_f32 took
+// eight, and the split is what the fp16x2 K loops are short of issue slots for (`sc` wave-uniform).
+__device__ __forceinline__ void tsod_split2_pair(float x0, float x1, float sc, unsigned &h, unsigned &l) {
+    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
+        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
+        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+        : "=&v"(h), "=&v"(l) : "v"(x0), "v"(x1), "s"(sc));
+}
+// three piece products, smallest first: lo*hi, hi*lo, hi*hi
+__device__ __forceinline__ void tsod_mfma3(tsod_f32x16 &acc, const tsod_u32x4 &wh, const tsod_u32x4 &wl, const tsod_u32x4 &ah,
+                                           const tsod_u32x4 &al) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tsod_f16x8, wl), __builtin_bit_cast(tsod_f16x8, ah), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tsod_f16x8, wh), __builtin_bit_cast(tsod_f16x8, al), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tsod_f16x8, wh), __builtin_bit_cast(tsod_f16x8, ah), acc, 0, 0, 0);
+}
 // fp16x2 activation exponent for a tensor whose abs-max has these bits: 2^e * absmax < 2^15 (fp16 ends at 65504), e in [-24, 24]
 // (zero / subnormal abs-max: 24; inf: -24 - the range flag of the launch then reports the non-finite input)
 __device__ __forceinline__ int tsod_fp16x2_exp_from_bits(unsigned bits) {

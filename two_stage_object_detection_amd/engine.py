@@ -10,8 +10,6 @@ Data layout in HBM: every activation is NHWC f32, channel pitch a multiple of 4,
 """
 from __future__ import annotations
 
-import os
-
 from collections import OrderedDict
 from ctypes import byref, c_int32
 from typing import Callable, Sequence
@@ -285,9 +283,9 @@ class Plan:
         self.pool.on_alloc = self._new_amax_slot
 
     # -- range words ------------------------------------------------------------------------
-    # False: plans built from now on use the static fp16x2 exponents (calibrate_fp16x2).  TSOD_NO_RANGE_WORDS=1 switches the words off
-    # for A/B timing (scripts/ab_env.sh); the static 2^4 exponent covers the synthetic detector's activations
-    DEFAULT_DYNAMIC_SCALE = os.environ.get("TSOD_NO_RANGE_WORDS", "0") in ("", "0")
+    # False: plans built from now on use the static fp16x2 exponents (calibrate_fp16x2); the static 2^4 exponent covers the
+    # synthetic detector's activations
+    DEFAULT_DYNAMIC_SCALE = True
     AMAX_SLOTS = 320                         # tensors per forward (ResNet-101: ~110, HarDNet-85: ~200); 4 KB each
 
     def _new_amax_slot(self, t: torch.Tensor) -> None:
@@ -1005,7 +1003,7 @@ class PlanOwner:
         """Arithmetic of the dense conv GEMMs: "f32" (v_mfma_f32_32x32x2_f32), "bf16x3" (three exact bf16 pieces per
         operand, six bf16 MFMAs per 16 k: f32-accurate, less matrix-pipe time) or "fp16x2" (two fp16 pieces of 2^e x per operand,
         three fp16 MFMAs per 16 k: f32-accurate for every finite input - e follows each tensor's abs-max per forward through its
-        range words; only with the words switched off (TSOD_NO_RANGE_WORDS / dynamic_scale False) is the static 2^4 and its
+        range words; only with the words switched off (dynamic_scale False) is the static 2^4 and its
         |x| < 4094 range in force; raise_if_error() reports non-finite accumulators either way).  Existing plans are dropped."""
         if precision not in ("f32", "bf16x3", "fp16x2"):
             raise ValueError(precision)
