@@ -598,6 +598,53 @@ int tsod_roi_align_avg_grad_f32(int32_t B, int32_t Hf, int32_t Wf, int32_t C, co
                                 int32_t d_feat_pitch, int32_t accumulate, void *workspace, size_t workspace_bytes,
                                 tsod_stream_t stream);
 
+/* ---- detection mAP: COCOeval's evaluateImg + accumulate, area range "all", no crowd / ignore flags ------
+ * The reference's calculate_metrics (nets/frcnn_training.py:372-565) defines no usable metric; this is the project's own.
+ * IoU is tsod_bbox_iou_f32's expression (eps 1e-8, no +1), compared as IoU >= t in f32.  Three steps:
+ *
+ * tsod_eval_match_f32: one update.  det [B][R][6] = (x1,y1,x2,y2,score,class) rows; image b's candidates are rows j < counts[b]
+ *   (keep == n_kept == NULL) or rows keep[b][j], j < n_kept[b] (tsod_detection_nms_f32's triple; counts == NULL).  Rows with a
+ *   NaN score, a class outside [0, num_classes) or of ignore_class (< 0: none) are dropped.  Per image and class: descending
+ *   score, ties to the lower j, the first max_dets kept; walking them in that order, each detection takes, for every threshold
+ *   t of iou_thr [T] (device, f32) on its own, the not yet matched ground truth of its class with the largest IoU >= t (equal
+ *   IoUs: the higher index).  gt_boxes [B][G][4] (16-byte aligned), gt_labels [B][G] int64, gt_counts [B]; G may be 0 (the
+ *   three may then be NULL); labels outside [0, num_classes) or equal to ignore_class are not counted.
+ *   Appends one tsod_eval_record per surviving detection to records [capacity] at *n_records (device int64, the running
+ *   total, advanced by the call), ordered by image, then class, then the order above; adds each image's counted ground truth
+ *   to npig [num_classes] (device int64, integer atomics).  Records past capacity are dropped: the caller keeps
+ *   capacity >= *n_records + B * R.  workspace: tsod_eval_match_workspace_bytes(B, R).  Limits (TSOD_ERR_UNSUPPORTED beyond):
+ *   B <= 65535, R <= 8192, G <= 1024, T <= 32, num_classes <= 262144.
+ * tsod_sort_pairs_u64: stable ascending LSD radix sort of keys_in [n] on bits [begin_bit, end_bit) with an int32 payload
+ *   (vals_in, or the identity 0..n-1 when NULL) -> keys_out, vals_out (neither may alias an input).  n_dev (device int64, may be
+ *   NULL) makes the live count min(*n_dev, n) without a host read.  8-bit passes of histogram, per-digit scan and scatter;
+ *   ranks inside a tile come from wave ballots in index order.  n <= 2^31 - 4097.  workspace:
+ *   tsod_sort_pairs_workspace_bytes(n).
+ * tsod_eval_accumulate_f64: every record so far (records [capacity], live count *n_records) sorted by (class, descending
+ *   score) with ties in record order, then per (class c, threshold t): integer cumulative TP / FP, precision tp / (tp + fp)
+ *   in f64 made monotone from the right, sampled for k = 0..100 at the first position where 100 tp >= k npig[c] (0 where
+ *   there is none), AP[c][t] = the mean of the 101 samples.  Outputs [num_classes][T]: ap (f64, -1 when npig[c] == 0),
+ *   tp / fp / fn = npig - tp (int64), recall = tp / npig (f64, -1 when npig[c] == 0).  No float atomics, fixed-order sums:
+ *   run to run bit-identical.  workspace: tsod_eval_accumulate_workspace_bytes(capacity, num_classes). */
+typedef struct tsod_eval_record {
+    float score;
+    int32_t cls;
+    uint32_t tp_mask; /* bit t: a true positive at iou_thr[t] */
+} tsod_eval_record;
+size_t tsod_eval_match_workspace_bytes(int32_t B, int32_t R);
+int tsod_eval_match_f32(const float *det, int32_t B, int32_t R, const int32_t *counts, const int32_t *keep, const int32_t *n_kept,
+                        const float *gt_boxes, const int64_t *gt_labels, const int32_t *gt_counts, int32_t G,
+                        const float *iou_thr, int32_t T, int32_t num_classes, int32_t max_dets, int32_t ignore_class,
+                        tsod_eval_record *records, int64_t capacity, int64_t *n_records, int64_t *npig, void *workspace,
+                        size_t workspace_bytes, tsod_stream_t stream);
+size_t tsod_sort_pairs_workspace_bytes(int64_t n);
+int tsod_sort_pairs_u64(const uint64_t *keys_in, const int32_t *vals_in, int64_t n, const int64_t *n_dev, int32_t begin_bit,
+                        int32_t end_bit, uint64_t *keys_out, int32_t *vals_out, void *workspace, size_t workspace_bytes,
+                        tsod_stream_t stream);
+size_t tsod_eval_accumulate_workspace_bytes(int64_t capacity, int32_t num_classes);
+int tsod_eval_accumulate_f64(const tsod_eval_record *records, int64_t capacity, const int64_t *n_records, const int64_t *npig,
+                             int32_t num_classes, int32_t T, double *ap, int64_t *tp, int64_t *fp, int64_t *fn, double *recall,
+                             void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- input step (the step before the path) ----------------------------------------------
  * dataset/dataloader.py:35-44 + dataset/transform.py:14-17: a decoded RGB image becomes an f32 CHW tensor with
  * values 0..255 and is resized to the detector's fixed size by torchvision v2 Resize, i.e. ATen's antialiased

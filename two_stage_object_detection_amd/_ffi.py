@@ -219,6 +219,16 @@ _SIGNATURES = {
     "tsod_roi_align_avg_grad_f32": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                             c_float, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                             c_int32, c_void_p, c_size_t, c_void_p]),
+    "tsod_eval_match_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "tsod_eval_match_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "tsod_sort_pairs_workspace_bytes": (c_size_t, [c_int64]),
+    "tsod_sort_pairs_u64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
+    "tsod_eval_accumulate_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "tsod_eval_accumulate_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

@@ -1,0 +1,616 @@
+// eval_metrics.hip -- detection mAP on the GPU: COCOeval's evaluateImg + accumulate, area "all",
+// no crowd / ignore regions, with an exact integer recall rule.
+//
+//   eval_match_kernel      one workgroup per image: order each class's detections (bitonic sort of (class, score, row) keys in
+//                          LDS), cap at max_dets per class, then the greedy one-to-one match, one wave per class chain: lanes
+//                          over the class's ground truth for the IoUs, then lanes over thresholds, each walking the IoUs for its
+//                          own arg-max (max IoU, then max index).  Records go to a per-image staging slot; per-class GT counts
+//                          are added with integer atomics.
+//   eval_offsets_kernel    one workgroup: exclusive scan of the per-image record counts on top of the device running total
+//   eval_compact_kernel    copies the staged records to their place in the caller's record buffer (update order, image order)
+//   radix_*                stable LSD radix sort of u64 keys + i32 payload: histogram / per-digit row scan / scatter passes of 8
+//                          bits, local ranks from wave ballots in index order (deterministic, no atomics on the output path)
+//   eval_keys_kernel, eval_segments_kernel, eval_ap_kernel
+//                          the accumulate: key = class << 32 | order-inverted score bits, sorted; per-class segments; one
+//                          workgroup per (class, threshold) scans TP over its segment in order, bins each position's f64 precision
+//                          by floor(100 tp / npig) (LDS integer max), and the suffix max over the 101 bins is the envelope sampled
+//                          at the 101 recall points.
+// Every count is an integer; every f64 value comes from one division or a fixed-order sum: two runs give identical bits.
+#include "tsod_internal.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxR = 8192;           // rows per image (the NMS limit); a row index fits the key's 13 low bits
+constexpr int kMaxG = 1024;           // ground-truth boxes per image (LDS: 56 bytes each)
+constexpr int kMaxT = 32;             // thresholds: bits of the TP mask
+constexpr int kMaxClasses = 1 << 18;  // the class field of the per-image key (19 bits, all-ones reserved for padding)
+constexpr int kRadixItems = 16;       // keys per thread per radix tile
+constexpr int kRadixTile = kThreads * kRadixItems;
+constexpr int kApItems = 16;          // positions per thread per chunk of the AP scan
+constexpr float kIouEps = 1e-8f;
+
+__device__ __forceinline__ unsigned desc_score_bits(float s) {
+    unsigned u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0u;                               // -0 == +0
+    const unsigned asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~asc;                                               // ascending bits = descending score
+}
+
+// exclusive prefix over a 256-thread workgroup (4 waves); `scr` >= 4 ints; returns the prefix, *total = the sum
+__device__ __forceinline__ int block_exclusive_scan(int v, int *scr, int *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int other = __shfl_up(incl, o);
+        if (lane >= o) incl += other;
+    }
+    __syncthreads();
+    if (lane == 63) scr[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wave; ++w) before += scr[w];
+    *total = scr[0] + scr[1] + scr[2] + scr[3];
+    return before + incl - v;
+}
+
+// LDS written by some lanes of a wave, then read by others of the same wave
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// lane `l`'s value of v (l wave-uniform)
+__device__ __forceinline__ float lane_value(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+__device__ __forceinline__ long det_row(const int *__restrict__ keep, int b, int R, int j) {
+    if (keep == nullptr) return j;
+    const int r = keep[(long)b * R + j];
+    return (r >= 0 && r < R) ? r : -1;
+}
+
+// ------------------------------------------------------------------------------------------------------ matching
+__global__ void __launch_bounds__(kThreads)
+eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ counts, const int *__restrict__ keep,
+                  const int *__restrict__ n_kept, const float *__restrict__ gt_boxes, const long long *__restrict__ gt_labels,
+                  const int *__restrict__ gt_counts, int G, const float *__restrict__ thr_in, int T, int C, int max_dets,
+                  int ignore_class, int NP, tsod_eval_record *__restrict__ stage, int *__restrict__ stage_counts,
+                  unsigned long long *__restrict__ npig) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);          // [NP]
+    float4 *gbox = reinterpret_cast<float4 *>(keys + NP);                              // [G]
+    int *gcls = reinterpret_cast<int *>(gbox + G);                                     // [G]
+    unsigned *matched = reinterpret_cast<unsigned *>(gcls + G);                          // [G]: bit t = matched at threshold t
+    int *gmatch_list = reinterpret_cast<int *>(matched + G);                           // [4][G]: a wave's class GT list
+    float *gmatch_iou = reinterpret_cast<float *>(gmatch_list + 4 * G);                // [4][G]: and their IoUs
+    unsigned short *comp = reinterpret_cast<unsigned short *>(gmatch_iou + 4 * G);     // [NP]
+    __shared__ float thr[kMaxT];
+    __shared__ int scr[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long drow0 = (long)b * R;
+
+    int n = keep != nullptr ? n_kept[b] : counts[b];
+    n = min(max(n, 0), R);
+    const int gn = G > 0 ? min(max(gt_counts[b], 0), G) : 0;
+    if (tid < T) thr[tid] = thr_in[tid];
+    for (int p = tid; p < NP; p += kThreads) {
+        unsigned long long key = ~0ull;
+        if (p < n) {
+            const long r = det_row(keep, b, R, p);
+            if (r >= 0) {
+                const float *q = det + (drow0 + r) * 6;
+                const float s = q[4], c = q[5];
+                if (!__builtin_isnan(s) && c >= 0.f && c < (float)C) {
+                    const int cls = (int)c;
+                    if (cls != ignore_class)
+                        key = ((unsigned long long)cls << 45) | ((unsigned long long)desc_score_bits(s) << 13) | (unsigned)p;
+                }
+            }
+        }
+        keys[p] = key;
+    }
+    for (int g = tid; g < G; g += kThreads) {
+        int cls = -1;
+        if (g < gn) {
+            gbox[g] = reinterpret_cast<const float4 *>(gt_boxes)[(long)b * G + g];
+            const long long l = gt_labels[(long)b * G + g];
+            if (l >= 0 && l < C && l != ignore_class) {
+                cls = (int)l;
+                atomicAdd(npig + cls, 1ull);
+            }
+        }
+        gcls[g] = cls;
+        matched[g] = 0u;
+    }
+    __syncthreads();
+
+    // ascending bitonic sort of the NP keys: (class, descending score, row); padding (all ones) last
+    for (int k = 2; k <= NP; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < NP; i += kThreads) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const unsigned long long a = keys[i], c = keys[ixj];
+                    if ((a > c) == ((i & k) == 0)) { keys[i] = c; keys[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // survivors: the first max_dets of each class segment; compact index by a block scan over contiguous chunks
+    const int per = (NP + kThreads - 1) / kThreads;
+    const int p0 = min(tid * per, NP), p1 = min(p0 + per, NP);
+    int mine = 0;
+    for (int p = p0; p < p1; ++p) {
+        const unsigned long long key = keys[p];
+        if (key == ~0ull) break;
+        const unsigned long long lo = (key >> 45) << 45;                 // first key of this class
+        int a = 0, z = p;                                                // lower bound of lo in keys[0, p]
+        while (a < z) { const int m = (a + z) >> 1; if (keys[m] < lo) a = m + 1; else z = m; }
+        if (p - a < max_dets) ++mine;
+    }
+    int total = 0;
+    int at = block_exclusive_scan(mine, scr, &total);
+    for (int p = p0; p < p1; ++p) {
+        const unsigned long long key = keys[p];
+        if (key == ~0ull) break;
+        const unsigned long long lo = (key >> 45) << 45;
+        int a = 0, z = p;
+        while (a < z) { const int m = (a + z) >> 1; if (keys[m] < lo) a = m + 1; else z = m; }
+        if (p - a < max_dets) comp[p] = (unsigned short)at++;
+    }
+    if (tid == 0) stage_counts[b] = total;
+    __syncthreads();
+
+    // greedy matching: class segments dealt round-robin to the four waves; a wave walks its chain in order.  Per detection the
+    // lanes first compute its IoU with the class's ground truth (the class's GT list, ascending, built once per segment), then
+    // lane t < T walks that list for threshold t on its own: the largest IoU >= t among the GT not yet matched at t, ties to the
+    // later (higher) index.  matched[g] bit t is written only by lane t of the wave that owns g's class.
+    int *glist = gmatch_list + wave * G;
+    float *giou = gmatch_iou + wave * G;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const float th = lane < T ? thr[lane] : 0.f;
+    int seg = 0;
+    for (int base = 0; base < NP; base += 64) {
+        const int p = base + lane;
+        const unsigned long long key = p < NP ? keys[p] : ~0ull;
+        const bool valid = key != ~0ull;
+        const bool start = valid && (p == 0 || (keys[p - 1] >> 45) != (key >> 45));
+        unsigned long long starts = __ballot(start);
+        if (__ballot(valid) == 0ull) break;
+        while (starts) {
+            const int sl = __builtin_ctzll(starts);
+            starts &= starts - 1;
+            const int s = base + sl;
+            if ((seg++ & 3) != wave) continue;
+            const unsigned long long cls_hi = keys[s] >> 45;
+            const int cls = (int)cls_hi;
+            int nc = 0;
+            for (int g0 = 0; g0 < gn; g0 += 64) {
+                const int g = g0 + lane;
+                const bool in = g < gn && gcls[g] == cls;
+                const unsigned long long bal = __ballot(in);
+                if (in) glist[nc + __popcll(bal & lt)] = g;
+                nc += __popcll(bal);
+            }
+            wave_sync();
+            for (int q0 = 0; q0 < max_dets; q0 += 64) {
+                const int qi = q0 + lane, pq = s + qi;
+                const unsigned long long kq = (qi < max_dets && pq < NP) ? keys[pq] : ~0ull;
+                const bool mine = kq != ~0ull && (kq >> 45) == cls_hi;      // a prefix of the lanes: the keys are sorted
+                const int nv = __popcll(__ballot(mine));
+                float bx = 0.f, by = 0.f, bz = 0.f, bw = 0.f, sc = 0.f;
+                if (mine) {
+                    const float *dq = det + (drow0 + det_row(keep, b, R, (int)(kq & 0x1FFFu))) * 6;
+                    bx = dq[0]; by = dq[1]; bz = dq[2]; bw = dq[3]; sc = dq[4];
+                }
+                for (int qq = 0; qq < nv; ++qq) {
+                    const float4 dbox = make_float4(lane_value(bx, qq), lane_value(by, qq), lane_value(bz, qq), lane_value(bw, qq));
+                    for (int i = lane; i < nc; i += 64) giou[i] = tsod_bbox_iou(dbox, gbox[glist[i]], kIouEps);
+                    wave_sync();
+                    float best = -__builtin_inff();
+                    int bg = -1;
+                    if (lane < T) {
+                        for (int i = 0; i < nc; ++i) {
+                            const float v = giou[i];
+                            const int g = glist[i];
+                            if (v >= th && v >= best && !((matched[g] >> lane) & 1u)) { best = v; bg = g; }
+                        }
+                        if (bg >= 0) atomicOr(&matched[bg], 1u << lane);
+                    }
+                    const unsigned tp = (unsigned)__ballot(bg >= 0);         // lanes >= T never match: bits of thresholds only
+                    if (lane == qq) {
+                        tsod_eval_record rec;
+                        rec.score = sc;
+                        rec.cls = cls;
+                        rec.tp_mask = tp;
+                        stage[drow0 + comp[s + qi]] = rec;
+                    }
+                    wave_sync();
+                }
+                if (nv < 64) break;
+            }
+        }
+    }
+}
+
+// running total += counts, offsets[b] = running total before image b (update order, then image order)
+__global__ void __launch_bounds__(kThreads)
+eval_offsets_kernel(const int *__restrict__ counts, int B, long long *__restrict__ offsets, long long *__restrict__ n_records) {
+    __shared__ int scr[4];
+    long long carry = *n_records;
+    for (int b0 = 0; b0 < B; b0 += kThreads) {
+        const int b = b0 + threadIdx.x;
+        const int v = b < B ? counts[b] : 0;
+        int total = 0;
+        const int ex = block_exclusive_scan(v, scr, &total);
+        if (b < B) offsets[b] = carry + ex;
+        carry += total;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *n_records = carry;
+}
+
+__global__ void __launch_bounds__(kThreads)
+eval_compact_kernel(const tsod_eval_record *__restrict__ stage, const int *__restrict__ counts, const long long *__restrict__ offsets,
+                    int R, tsod_eval_record *__restrict__ records, long long capacity) {
+    const int b = blockIdx.y;
+    const int j = blockIdx.x * kThreads + threadIdx.x;
+    if (j >= counts[b]) return;
+    const long long dst = offsets[b] + j;
+    if (dst < capacity) records[dst] = stage[(long)b * R + j];
+}
+
+// ------------------------------------------------------------------------------------------------------ radix sort
+__device__ __forceinline__ long long live_count(long long n_max, const long long *n_dev) {
+    if (n_dev == nullptr) return n_max;
+    const long long n = *n_dev;
+    return n < 0 ? 0 : (n < n_max ? n : n_max);
+}
+
+__global__ void __launch_bounds__(kThreads)
+radix_hist_kernel(const unsigned long long *__restrict__ keys, long long n_max, const long long *__restrict__ n_dev, int shift,
+                  int nblk, unsigned *__restrict__ hist) {
+    __shared__ unsigned h[256];
+    const long long n = live_count(n_max, n_dev);
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const long long tile = (long long)blockIdx.x * kRadixTile;
+#pragma unroll 4
+    for (int it = 0; it < kRadixItems; ++it) {
+        const long long i = tile + it * kThreads + threadIdx.x;
+        if (i < n) atomicAdd(&h[(unsigned)(keys[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(long)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
+}
+
+// workgroup d: exclusive scan of hist[d][0..nblk) in place, totals[d] = the row's sum
+__global__ void __launch_bounds__(kThreads)
+radix_rowscan_kernel(unsigned *__restrict__ hist, int nblk, unsigned *__restrict__ totals) {
+    __shared__ int scr[4];
+    unsigned *row = hist + (long)blockIdx.x * nblk;
+    unsigned carry = 0;
+    for (int i0 = 0; i0 < nblk; i0 += kThreads) {
+        const int i = i0 + threadIdx.x;
+        const int v = i < nblk ? (int)row[i] : 0;
+        int total = 0;
+        const int ex = block_exclusive_scan(v, scr, &total);
+        if (i < nblk) row[i] = carry + (unsigned)ex;
+        carry += (unsigned)total;
+    }
+    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+}
+
+__global__ void __launch_bounds__(kThreads)
+radix_scatter_kernel(const unsigned long long *__restrict__ keys_in, const int *__restrict__ vals_in, long long n_max,
+                     const long long *__restrict__ n_dev, int shift, int nblk, const unsigned *__restrict__ hist,
+                     const unsigned *__restrict__ totals, unsigned long long *__restrict__ keys_out, int *__restrict__ vals_out) {
+    __shared__ unsigned base[256];
+    __shared__ unsigned running[256];
+    __shared__ unsigned wcnt[4][256];
+    __shared__ int scr[4];
+    const long long n = live_count(n_max, n_dev);
+    const long long tile = (long long)blockIdx.x * kRadixTile;
+    if (tile >= n) return;                                            // uniform per workgroup
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int total = 0;
+    const int ex = block_exclusive_scan((int)totals[tid], scr, &total);
+    base[tid] = (unsigned)ex + hist[(long)tid * nblk + blockIdx.x];
+    running[tid] = 0u;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int it = 0; it < kRadixItems; ++it) {
+        const long long i = tile + it * kThreads + tid;
+        const bool valid = i < n;
+        const unsigned long long key = valid ? keys_in[i] : 0ull;
+        const int val = valid ? (vals_in != nullptr ? vals_in[i] : (int)i) : 0;
+        const unsigned d = (unsigned)(key >> shift) & 255u;
+        unsigned long long peers = __ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long m = __ballot((d >> bit) & 1u);
+            peers &= ((d >> bit) & 1u) ? m : ~m;
+        }
+        wcnt[0][tid] = 0u; wcnt[1][tid] = 0u; wcnt[2][tid] = 0u; wcnt[3][tid] = 0u;
+        __syncthreads();
+        if (valid && (peers & lt) == 0ull) wcnt[wave][d] = (unsigned)__popcll(peers);
+        __syncthreads();
+        if (valid) {
+            unsigned pos = base[d] + running[d] + (unsigned)__popcll(peers & lt);
+            for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
+            keys_out[pos] = key;
+            vals_out[pos] = val;
+        }
+        __syncthreads();
+        running[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+        __syncthreads();
+    }
+}
+
+struct SortWs {
+    unsigned long long *alt_keys;
+    int *alt_vals;
+    unsigned *hist;
+    unsigned *totals;
+    size_t bytes;
+};
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+SortWs sort_ws_layout(void *ws, long long n) {
+    const long long nblk = tsod_cdiv(n, kRadixTile);
+    SortWs w;
+    char *p = static_cast<char *>(ws);
+    size_t off = 0;
+    w.alt_keys = reinterpret_cast<unsigned long long *>(p + off); off += align256((size_t)n * 8);
+    w.alt_vals = reinterpret_cast<int *>(p + off);                off += align256((size_t)n * 4);
+    w.hist = reinterpret_cast<unsigned *>(p + off);               off += align256((size_t)nblk * 256 * 4);
+    w.totals = reinterpret_cast<unsigned *>(p + off);             off += align256(256 * 4);
+    w.bytes = off;
+    return w;
+}
+
+int launch_sort(const unsigned long long *keys_in, const int *vals_in, long long n, const long long *n_dev, int begin_bit,
+                int end_bit, unsigned long long *keys_out, int *vals_out, const SortWs &w, hipStream_t st) {
+    const int nblk = (int)tsod_cdiv(n, kRadixTile);
+    const int passes = (int)tsod_cdiv(end_bit - begin_bit, 8);
+    const unsigned long long *src_k = keys_in;
+    const int *src_v = vals_in;                                      // NULL: the identity payload (first pass only)
+    for (int i = 0; i < passes; ++i) {
+        const bool to_out = ((passes - 1 - i) & 1) == 0;             // the last pass lands in the caller's output
+        unsigned long long *dk = to_out ? keys_out : w.alt_keys;
+        int *dv = to_out ? vals_out : w.alt_vals;
+        const int shift = begin_bit + 8 * i;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nblk), dim3(kThreads), 0, st, src_k, n, n_dev, shift, nblk, w.hist);
+        hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(kThreads), 0, st, w.hist, nblk, w.totals);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(kThreads), 0, st, src_k, src_v, n, n_dev, shift, nblk,
+                           w.hist, w.totals, dk, dv);
+        src_k = dk;
+        src_v = dv;
+    }
+    return tsod_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------------ accumulate
+__global__ void __launch_bounds__(kThreads)
+eval_keys_kernel(const tsod_eval_record *__restrict__ records, long long n_max, const long long *__restrict__ n_dev,
+                 unsigned long long *__restrict__ keys) {
+    const long long n = live_count(n_max, n_dev);
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const tsod_eval_record r = records[i];
+    keys[i] = ((unsigned long long)(unsigned)r.cls << 32) | desc_score_bits(r.score);
+}
+
+// per-class [begin, end) of the sorted keys, and the TP masks in sorted order
+__global__ void __launch_bounds__(kThreads)
+eval_segments_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ perm,
+                     const tsod_eval_record *__restrict__ records, long long n_max, const long long *__restrict__ n_dev,
+                     int *__restrict__ seg_begin, int *__restrict__ seg_end, unsigned *__restrict__ masks) {
+    const long long n = live_count(n_max, n_dev);
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(keys[i] >> 32);
+    if (i == 0 || (int)(keys[i - 1] >> 32) != c) seg_begin[c] = (int)i;
+    if (i == n - 1 || (int)(keys[i + 1] >> 32) != c) seg_end[c] = (int)(i + 1);
+    masks[i] = records[perm[i]].tp_mask;
+}
+
+// workgroup (c, t): TP / FP along the class's sorted segment, the precision envelope and its 101-point sample
+__global__ void __launch_bounds__(kThreads)
+eval_ap_kernel(const unsigned *__restrict__ masks, const int *__restrict__ seg_begin, const int *__restrict__ seg_end,
+               const long long *__restrict__ npig, int T, double *__restrict__ ap, long long *__restrict__ tp_out,
+               long long *__restrict__ fp_out, long long *__restrict__ fn_out, double *__restrict__ recall) {
+    __shared__ unsigned long long bins[101];
+    __shared__ int scr[4];
+    const int c = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
+    const int s = seg_begin[c], e = seg_end[c];
+    const long long np = npig[c];
+    if (tid < 101) bins[tid] = 0ull;
+    long long carry = 0;
+    for (int c0 = s; c0 < e; c0 += kThreads * kApItems) {
+        const int j0 = c0 + tid * kApItems, j1 = min(j0 + kApItems, e);
+        int cnt = 0;
+        for (int j = j0; j < j1; ++j) cnt += (masks[j] >> t) & 1u;
+        int total = 0;
+        const int ex = block_exclusive_scan(cnt, scr, &total);        // (its first barrier also orders the bins' zeroing)
+        if (np > 0) {
+            long long tp = carry + ex;
+            int cur = -1;
+            unsigned long long best = 0ull;
+            for (int j = j0; j < j1; ++j) {
+                tp += (masks[j] >> t) & 1u;
+                const double prec = (double)tp / (double)(j - s + 1);
+                const long long q = (100 * tp) / np;
+                const int bin = q < 100 ? (int)q : 100;
+                if (bin != cur) {
+                    if (cur >= 0) atomicMax(&bins[cur], best);
+                    cur = bin;
+                    best = 0ull;
+                }
+                const unsigned long long pb = (unsigned long long)__double_as_longlong(prec);
+                best = pb > best ? pb : best;
+            }
+            if (cur >= 0) atomicMax(&bins[cur], best);
+        }
+        carry += total;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int k = c * T + t;
+        const long long n = (long long)(e - s);
+        tp_out[k] = carry;
+        fp_out[k] = n - carry;
+        fn_out[k] = np - carry;
+        if (np > 0) {
+            unsigned long long env = 0ull;                            // the envelope, right to left (bits of doubles >= 0)
+            for (int i = 100; i >= 0; --i) {
+                env = bins[i] > env ? bins[i] : env;
+                bins[i] = env;
+            }
+            double sum = 0.0;
+            for (int i = 0; i <= 100; ++i) sum += __longlong_as_double((long long)bins[i]);
+            ap[k] = sum / 101.0;
+            recall[k] = (double)carry / (double)np;
+        } else {
+            ap[k] = -1.0;
+            recall[k] = -1.0;
+        }
+    }
+}
+
+int class_bits(int C) {
+    int bits = 1;
+    while (bits < 31 && (1ll << bits) < (long long)C) ++bits;
+    return bits;
+}
+
+struct AccWs {
+    unsigned long long *keys, *sorted_keys;
+    int *perm;
+    unsigned *masks;
+    int *seg_begin, *seg_end;
+    void *sort_ws;
+    size_t sort_bytes, bytes;
+};
+
+AccWs acc_ws_layout(void *ws, long long capacity, int C) {
+    AccWs w;
+    char *p = static_cast<char *>(ws);
+    size_t off = 0;
+    w.keys = reinterpret_cast<unsigned long long *>(p + off);        off += align256((size_t)capacity * 8);
+    w.sorted_keys = reinterpret_cast<unsigned long long *>(p + off); off += align256((size_t)capacity * 8);
+    w.perm = reinterpret_cast<int *>(p + off);                       off += align256((size_t)capacity * 4);
+    w.masks = reinterpret_cast<unsigned *>(p + off);                 off += align256((size_t)capacity * 4);
+    w.seg_begin = reinterpret_cast<int *>(p + off);                  off += align256((size_t)C * 4);
+    w.seg_end = reinterpret_cast<int *>(p + off);                    off += align256((size_t)C * 4);
+    w.sort_ws = p + off;
+    w.sort_bytes = sort_ws_layout(nullptr, capacity).bytes;
+    off += w.sort_bytes;
+    w.bytes = off;
+    return w;
+}
+
+size_t match_lds_bytes(int NP, int G) { return (size_t)NP * 8 + (size_t)G * (16 + 4 + 4 + 4 * 8) + (size_t)NP * 2; }
+
+}  // namespace
+
+extern "C" size_t tsod_eval_match_workspace_bytes(int32_t B, int32_t R) {
+    if (B <= 0 || R <= 0) return 0;
+    return align256((size_t)B * R * sizeof(tsod_eval_record)) + align256((size_t)B * 4) + align256((size_t)B * 8);
+}
+
+extern "C" int tsod_eval_match_f32(const float *det, int32_t B, int32_t R, const int32_t *counts, const int32_t *keep,
+                                   const int32_t *n_kept, const float *gt_boxes, const int64_t *gt_labels,
+                                   const int32_t *gt_counts, int32_t G, const float *iou_thr, int32_t T, int32_t num_classes,
+                                   int32_t max_dets, int32_t ignore_class, tsod_eval_record *records, int64_t capacity,
+                                   int64_t *n_records, int64_t *npig, void *workspace, size_t workspace_bytes,
+                                   tsod_stream_t stream) {
+    TSOD_REQUIRE(det && iou_thr && records && n_records && npig, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE((keep != nullptr) == (n_kept != nullptr) && (counts != nullptr) != (keep != nullptr), TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(B > 0 && R > 0 && G >= 0 && T > 0 && num_classes > 0 && max_dets > 0 && capacity >= 0, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(G == 0 || (gt_boxes && gt_labels && gt_counts), TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(R <= kMaxR && G <= kMaxG && T <= kMaxT && num_classes <= kMaxClasses && B <= 65535, TSOD_ERR_UNSUPPORTED);
+    TSOD_REQUIRE(G == 0 || tsod_aligned16(gt_boxes), TSOD_ERR_ALIGNMENT);
+    TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_match_workspace_bytes(B, R), TSOD_ERR_WORKSPACE);
+    char *p = static_cast<char *>(workspace);
+    tsod_eval_record *stage = reinterpret_cast<tsod_eval_record *>(p);
+    int *stage_counts = reinterpret_cast<int *>(p + align256((size_t)B * R * sizeof(tsod_eval_record)));
+    long long *offsets = reinterpret_cast<long long *>(p + align256((size_t)B * R * sizeof(tsod_eval_record)) +
+                                                       align256((size_t)B * 4));
+    int NP = 64;
+    while (NP < R) NP <<= 1;
+    const size_t lds = match_lds_bytes(NP, G);
+    hipStream_t st = tsod_stream(stream);
+    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(eval_match_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return TSOD_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(kThreads), lds, st, det, R, counts, keep, n_kept, gt_boxes,
+                       reinterpret_cast<const long long *>(gt_labels), gt_counts, G, iou_thr, T, num_classes, max_dets,
+                       ignore_class, NP, stage, stage_counts, reinterpret_cast<unsigned long long *>(npig));
+    hipLaunchKernelGGL(eval_offsets_kernel, dim3(1), dim3(kThreads), 0, st, stage_counts, B, offsets,
+                       reinterpret_cast<long long *>(n_records));
+    hipLaunchKernelGGL(eval_compact_kernel, dim3((unsigned)tsod_cdiv(R, kThreads), B), dim3(kThreads), 0, st, stage, stage_counts,
+                       offsets, R, records, (long long)capacity);
+    return tsod_launch_status();
+}
+
+extern "C" size_t tsod_sort_pairs_workspace_bytes(int64_t n) {
+    if (n <= 0) return 0;
+    return sort_ws_layout(nullptr, n).bytes;
+}
+
+extern "C" int tsod_sort_pairs_u64(const uint64_t *keys_in, const int32_t *vals_in, int64_t n, const int64_t *n_dev,
+                                   int32_t begin_bit, int32_t end_bit, uint64_t *keys_out, int32_t *vals_out, void *workspace,
+                                   size_t workspace_bytes, tsod_stream_t stream) {
+    TSOD_REQUIRE(keys_in && keys_out && vals_out, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(n > 0 && (const void *)keys_in != (const void *)keys_out && (const void *)vals_in != (const void *)vals_out,
+                 TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(0 <= begin_bit && begin_bit < end_bit && end_bit <= 64, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(n <= (int64_t)INT32_MAX - kRadixTile, TSOD_ERR_UNSUPPORTED);
+    TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_sort_pairs_workspace_bytes(n), TSOD_ERR_WORKSPACE);
+    const SortWs w = sort_ws_layout(workspace, n);
+    return launch_sort(reinterpret_cast<const unsigned long long *>(keys_in), vals_in, n,
+                       reinterpret_cast<const long long *>(n_dev), begin_bit, end_bit,
+                       reinterpret_cast<unsigned long long *>(keys_out), vals_out, w, tsod_stream(stream));
+}
+
+extern "C" size_t tsod_eval_accumulate_workspace_bytes(int64_t capacity, int32_t num_classes) {
+    if (capacity <= 0 || num_classes <= 0) return 0;
+    return acc_ws_layout(nullptr, capacity, num_classes).bytes;
+}
+
+extern "C" int tsod_eval_accumulate_f64(const tsod_eval_record *records, int64_t capacity, const int64_t *n_records,
+                                        const int64_t *npig, int32_t num_classes, int32_t T, double *ap, int64_t *tp,
+                                        int64_t *fp, int64_t *fn, double *recall, void *workspace, size_t workspace_bytes,
+                                        tsod_stream_t stream) {
+    TSOD_REQUIRE(records && n_records && npig && ap && tp && fp && fn && recall, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(capacity > 0 && num_classes > 0 && T > 0, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(T <= kMaxT && num_classes <= kMaxClasses && capacity <= (int64_t)INT32_MAX - kRadixTile, TSOD_ERR_UNSUPPORTED);
+    TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_accumulate_workspace_bytes(capacity, num_classes),
+                 TSOD_ERR_WORKSPACE);
+    const AccWs w = acc_ws_layout(workspace, capacity, num_classes);
+    hipStream_t st = tsod_stream(stream);
+    const long long *nd = reinterpret_cast<const long long *>(n_records);
+    const unsigned grid = (unsigned)tsod_cdiv(capacity, kThreads);
+    if (hipMemsetAsync(w.seg_begin, 0, (size_t)num_classes * 4, st) != hipSuccess ||
+        hipMemsetAsync(w.seg_end, 0, (size_t)num_classes * 4, st) != hipSuccess)
+        return TSOD_ERR_LAUNCH;
+    hipLaunchKernelGGL(eval_keys_kernel, dim3(grid), dim3(kThreads), 0, st, records, (long long)capacity, nd, w.keys);
+    const int rc = launch_sort(w.keys, nullptr, capacity, nd, 0, 32 + class_bits(num_classes), w.sorted_keys, w.perm,
+                               sort_ws_layout(w.sort_ws, capacity), st);
+    if (rc != TSOD_OK) return rc;
+    hipLaunchKernelGGL(eval_segments_kernel, dim3(grid), dim3(kThreads), 0, st, w.sorted_keys, w.perm, records,
+                       (long long)capacity, nd, w.seg_begin, w.seg_end, w.masks);
+    hipLaunchKernelGGL(eval_ap_kernel, dim3((unsigned)num_classes * (unsigned)T), dim3(kThreads), 0, st, w.masks, w.seg_begin,
+                       w.seg_end, reinterpret_cast<const long long *>(npig), T, ap, reinterpret_cast<long long *>(tp),
+                       reinterpret_cast<long long *>(fp), reinterpret_cast<long long *>(fn), recall);
+    return tsod_launch_status();
+}

@@ -190,13 +190,7 @@ bbox_iou_kernel(const float *__restrict__ a, int Na, const float *__restrict__ b
     if (j >= Nb || i >= Na) return;
     const float4 A = reinterpret_cast<const float4 *>(a)[i];
     const float4 Bx = reinterpret_cast<const float4 *>(bq)[j];
-    const float tlx = fmaxf(A.x, Bx.x), tly = fmaxf(A.y, Bx.y);
-    const float brx = fminf(A.z, Bx.z), bry = fminf(A.w, Bx.w);
-    const float w = fmaxf(brx - tlx, 0.f), h = fmaxf(bry - tly, 0.f);
-    const float ai = w * h;
-    const float aa = (A.z - A.x) * (A.w - A.y);
-    const float ab = (Bx.z - Bx.x) * (Bx.w - Bx.y);
-    out[(long)i * Nb + j] = ai / (aa + ab - ai + eps);
+    out[(long)i * Nb + j] = tsod_bbox_iou(A, Bx, eps);
 }
 
 }  // namespace

@@ -148,6 +148,17 @@ __device__ __forceinline__ tsod_align_geom tsod_roi_align_geom(float bidx, float
     if (y_low >= (Hf) - 1) { y_high = y_low = (Hf) - 1; y = (float)y_low; } else y_high = y_low + 1;          \
     if (x_low >= (Wf) - 1) { x_high = x_low = (Wf) - 1; x = (float)x_low; } else x_high = x_low + 1;          \
     const float ly = y - (float)y_low, lx = x - (float)x_low
+// utils/loc_bbox_iou.py:4-27 (bbox_iou, eps in the denominator, no +1) for one pair, op for op: the one expression of
+// tsod_bbox_iou_f32 and tsod_eval_match_f32 (bit-equal under -ffp-contract=off)
+__device__ __forceinline__ float tsod_bbox_iou(const float4 A, const float4 Bx, float eps) {
+    const float tlx = fmaxf(A.x, Bx.x), tly = fmaxf(A.y, Bx.y);
+    const float brx = fminf(A.z, Bx.z), bry = fminf(A.w, Bx.w);
+    const float w = fmaxf(brx - tlx, 0.f), h = fmaxf(bry - tly, 0.f);
+    const float ai = w * h;
+    const float aa = (A.z - A.x) * (A.w - A.y);
+    const float ab = (Bx.z - Bx.x) * (Bx.w - Bx.y);
+    return ai / (aa + ab - ai + eps);
+}
 __device__ __forceinline__ float tsod_prelu(float v, float a) { return fmaxf(v, 0.f) + a * fminf(v, 0.f); }
 
 // ---- fp16x2 (TSOD_PREC_FP16X2) pieces, shared by the conv library and the fused stem / bottleneck kernels

@@ -726,6 +726,80 @@ def filter_detections(det: torch.Tensor, iou_thr: float = 0.1, score_thresh: flo
     return det_sorted, keep, n_kept
 
 
+# ----------------------------------------------------------------------------- detection mAP
+EVAL_RECORD_INTS = 3                 # tsod_eval_record = (score f32, class i32, TP mask u32), one int32 row of three
+EVAL_ARENA = _Arena()                # the evaluator's staging slots and sort / accumulate scratch
+
+
+def _require_cuda_any(t, what: str, dtype) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _ffi.TsodError(f"{what}: this package is a HIP-only path and needs a CUDA/ROCm tensor "
+                             "(the CPU restatement lives under oracle/ and is test infrastructure only)")
+    if t.dtype != dtype:
+        raise _ffi.TsodError(f"{what}: {dtype} required, got {t.dtype}")
+
+
+def sort_pairs_u64(keys: torch.Tensor, vals: torch.Tensor | None = None, begin_bit: int = 0, end_bit: int = 64,
+                   n_dev: torch.Tensor | None = None):
+    """Stable ascending radix sort (tsod_sort_pairs_u64) of keys [n] int64 holding u64 bit patterns on bits
+    [begin_bit, end_bit), with vals [n] int32 (None: 0..n-1).  ``n_dev`` (int64 [1] on the device) limits the live count
+    without a host read; entries past it are left as they are.  -> (keys_sorted [n] int64, vals_sorted [n] int32)."""
+    _require_cuda_any(keys, "sort_pairs_u64", torch.int64)
+    if keys.dim() != 1:
+        raise ValueError(f"sort_pairs_u64: keys must be [n], got {tuple(keys.shape)}")
+    keys = keys.contiguous()
+    n, dev = keys.shape[0], keys.device
+    if vals is not None:
+        _require_cuda_any(vals, "sort_pairs_u64", torch.int32)
+        if tuple(vals.shape) != (n,):
+            raise ValueError(f"sort_pairs_u64: vals {tuple(vals.shape)} for {n} keys")
+        vals = vals.contiguous()
+    keys_out = torch.empty_like(keys)
+    vals_out = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return keys_out, vals_out
+    L = lib()
+    ws_bytes = L.tsod_sort_pairs_workspace_bytes(n)
+    ws = EVAL_ARENA.get(dev, ws_bytes)
+    check(L.tsod_sort_pairs_u64(ptr(keys), ptr(vals), n, ptr(n_dev), int(begin_bit), int(end_bit), ptr(keys_out), ptr(vals_out),
+                                ptr(ws), ws_bytes, stream_ptr()), "sort_pairs_u64")
+    return keys_out, vals_out
+
+
+def eval_match(det: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_counts: torch.Tensor,
+               iou_thr: torch.Tensor, num_classes: int, max_dets: int, ignore_class: int, records: torch.Tensor,
+               n_records: torch.Tensor, npig: torch.Tensor, *, counts=None, keep=None, n_kept=None) -> None:
+    """One update of the evaluator's device state (tsod_eval_match_f32): det [B,R,6] with counts [B] int32 or keep [B,R] +
+    n_kept [B] int32; gt_boxes [B,G,4] f32, gt_labels [B,G] int64, gt_counts [B] int32; iou_thr [T] f32.  Appends to
+    records [capacity,3] int32 at n_records [1] int64 and adds to npig [num_classes] int64, in place."""
+    require_cuda(det, "eval_match")
+    B, R, six = det.shape
+    if six != 6:
+        raise ValueError(f"eval_match: detection records are [B,R,6], got {tuple(det.shape)}")
+    G = gt_boxes.shape[1]
+    L = lib()
+    ws_bytes = L.tsod_eval_match_workspace_bytes(B, R)
+    ws = EVAL_ARENA.get(det.device, ws_bytes)
+    check(L.tsod_eval_match_f32(ptr(det), B, R, ptr(counts), ptr(keep), ptr(n_kept), ptr(gt_boxes) if G else None,
+                                ptr(gt_labels) if G else None, ptr(gt_counts) if G else None, G, ptr(iou_thr),
+                                iou_thr.shape[0], int(num_classes), int(max_dets), int(ignore_class), ptr(records),
+                                records.shape[0], ptr(n_records), ptr(npig), ptr(ws), ws_bytes, stream_ptr()), "eval_match")
+
+
+def eval_accumulate(records: torch.Tensor, n_records: torch.Tensor, npig: torch.Tensor, T: int) -> torch.Tensor:
+    """tsod_eval_accumulate_f64 over every record so far -> one int64 tensor [5, C, T] on the device: the bits of AP (f64),
+    TP, FP, FN, the bits of recall (f64), in that order (one buffer, so the caller reads the results with one copy)."""
+    C = npig.shape[0]
+    out = torch.empty((5, C, T), dtype=torch.int64, device=records.device)
+    L = lib()
+    ws_bytes = L.tsod_eval_accumulate_workspace_bytes(records.shape[0], C)
+    ws = EVAL_ARENA.get(records.device, ws_bytes)
+    check(L.tsod_eval_accumulate_f64(ptr(records), records.shape[0], ptr(n_records), ptr(npig), C, int(T), ptr(out[0]),
+                                     ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(ws), ws_bytes, stream_ptr()),
+          "eval_accumulate")
+    return out
+
+
 # ----------------------------------------------------------------------------- training-side box ops
 def anchor_targets(bbox: torch.Tensor, anchor: torch.Tensor, n_pos: int, n_sample: int, pos_iou_thresh: float,
                    neg_iou_thresh: float):

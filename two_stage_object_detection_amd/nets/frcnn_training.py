@@ -10,9 +10,10 @@ classes produced):
 
 ``FasterRCNNTrainer`` (nets/frcnn_training.py:179-342) is the class the reference's scripts instantiate: its forward runs
 the detector conditioned on ground truth and returns the four losses, their sum and the head's per-RoI predictions
-(pinned by tests/golden/trainer_ref.npz, made by the reference's own class).  Its eval_fn / calculate_metrics are not
-provided: the reference's calculate_metrics has no return statement, loops over an empty range and calls the
-one-argument compute_ap with two arguments, so it returns None or raises TypeError - there is no defined mAP to match.
+(pinned by tests/golden/trainer_ref.npz, made by the reference's own class).  Its ``eval_fn`` / ``calculate_metrics``
+score with the project's own metric (``utils.metrics.DetectionEvaluator``): the reference's
+calculate_metrics loops over an empty range and calls the one-argument compute_ap with two arguments, so there is no
+reference mAP to match.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ from ..models.hardnet import HarNetClassifier
 from .classify import HarNetRoIHead
 from .frcnn import _UID, _make_extractor
 from .rpn import RegionProposalNetwork
+from ..utils.metrics import DetectionEvaluator
 
 
 class AnchorTargetCreator:
@@ -197,9 +199,8 @@ class FasterRCNNTrainer(nn.Module):
         RPN's and head's packed weight images are rebuilt before the next forward.
 
     Not provided: the HIP backbone's own backward and train-mode BatchNorm (``head_grads`` fine-tunes the heads on a frozen
-    backbone; ``features=`` trains a backbone that has autograd of its own); gradients w.r.t. RoI coordinates; eval_fn /
-    calculate_metrics (see the module docstring); graph capture and tuning (the forward runs whatever plan the backbone
-    holds)."""
+    backbone; ``features=`` trains a backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
+    and tuning (the forward runs whatever plan the backbone holds).  ``eval_fn`` / ``calculate_metrics``: see there."""
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
                  backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False):
@@ -351,3 +352,66 @@ class FasterRCNNTrainer(nn.Module):
             losses = losses + [sum(losses)]
         return (losses, anchors_pred, classes_pred, classes_score_pred, torch.unsqueeze(bboxes[0], dim=0),
                 torch.unsqueeze(labels[0] + 1, dim=0))
+
+    # ------------------------------------------------------------------------------------------------------- evaluation
+    def _records(self, anchors_pred, classes_pred, classes_score_pred, nms_iou_threshold):
+        """The head's per-RoI predictions as [B,S,6] detection rows, through the reference's per-class NMS
+        (``hip_ops.filter_detections(per_class=True)``, class 0 = background dropped) -> (det_sorted, keep, n_kept)."""
+        det = torch.cat([anchors_pred.float(), classes_score_pred.float().unsqueeze(-1), classes_pred.float().unsqueeze(-1)],
+                        dim=-1)
+        return hip_ops.filter_detections(det, iou_thr=nms_iou_threshold, per_class=True, background_class=0)
+
+    def eval_fn(self, eval_dataloader, scale=1, nms_iou_threshold=0.7, map_iou_threshold=0.7):
+        """The reference's evaluation leg (nets/frcnn_training.py:347-369, called by train/train.py under
+        ``torch.inference_mode()``) -> (avg_eval_loss, avg_mAP).
+
+        Every batch ``(imgs, bboxes, labels)`` (CPU batches of a reference-style DataLoader are moved to the module's device)
+        runs through ``forward``; its (anchors_pred, classes_score_pred, classes_pred) rows go through the reference's
+        per-class NMS at ``nms_iou_threshold`` and into one ``DetectionEvaluator(n_classes + 1, (map_iou_threshold,),
+        ignore_class=0)`` against each image's own ``labels + 1``.  avg_eval_loss = the mean over batches of ``losses[-1]``
+        (summed on the device, read once); avg_mAP = the evaluator's dataset-level mAP (NaN when no image has ground truth).
+        Both are 0 for an empty loader, as in the reference.
+
+        Deviations from the reference: the metric is one-to-one COCO matching, not "any GT with
+        IoU > t"; classes without ground truth are excluded, not counted as 0; the mAP is over the whole loader, not a mean
+        of per-batch values; every image is scored against its own ground truth, not ``bboxes[0]``.  The predictions come
+        from the ground-truth-conditioned samples of ``forward`` (the reference's design), so the score sees the ground truth
+        it is measured against: ``FasterRCNN.predict`` + ``DetectionEvaluator`` is the honest score of a detector."""
+        self.eval()
+        ev = DetectionEvaluator(self.n_classes + 1, iou_thresholds=(map_iou_threshold,), ignore_class=0)
+        dev = next(self.parameters()).device
+        loss_total, batches = None, 0
+        for imgs, bboxes, labels in eval_dataloader:
+            imgs = [im.to(dev) for im in imgs] if isinstance(imgs, (list, tuple)) else imgs.to(dev)
+            bboxes = [bb.to(dev, torch.float32) for bb in bboxes]
+            labels = [lb.to(dev) for lb in labels]
+            losses, anchors_pred, classes_pred, classes_score_pred = self.forward(imgs, bboxes, labels, scale)[:4]
+            loss = losses[-1].detach()
+            loss_total = loss if loss_total is None else loss_total + loss
+            det_sorted, keep, n_kept = self._records(anchors_pred, classes_pred, classes_score_pred, nms_iou_threshold)
+            ev.update(det_sorted, bboxes, [lb.to(torch.int64) + 1 for lb in labels], keep=keep, n_kept=n_kept)
+            batches += 1
+        if batches == 0:
+            return 0, 0
+        return float(loss_total) / batches, ev.compute()["mAP"]
+
+    def calculate_metrics(self, anchors_pred, classes_pred, classes_score_pred, anchors_gt, classes_gt,
+                          nms_iou_threshold: float = 0.7, map_iou_threshold: float = 0.7):
+        """One batch at one threshold, in the layout of the ``results`` dict the reference builds
+        (nets/frcnn_training.py:372-565): ``{'mAP': float, 'class_metrics': {c: {'AP', 'Recall', 'Precision', 'TP', 'FP',
+        'FN'}}}`` for c = 1..n_classes.  anchors_pred [B,S,4], classes_pred [B,S], classes_score_pred [B,S]; anchors_gt
+        [B,G,4], classes_gt [B,G] (already + 1; pad with -1).  CPU inputs are moved to the module's device.  The metric is
+        ``DetectionEvaluator``'s (``eval_fn`` lists how it deviates from the reference); a class without ground truth has
+        AP and Recall -1 and does not enter the mAP; Precision = TP / (TP + FP) (0 without detections)."""
+        dev = next(self.parameters()).device
+        anchors_pred, classes_pred, classes_score_pred = (t.to(dev) for t in (anchors_pred, classes_pred, classes_score_pred))
+        ev = DetectionEvaluator(self.n_classes + 1, iou_thresholds=(map_iou_threshold,), ignore_class=0)
+        det_sorted, keep, n_kept = self._records(anchors_pred, classes_pred, classes_score_pred, nms_iou_threshold)
+        ev.update(det_sorted, anchors_gt.to(dev, torch.float32), classes_gt.to(dev, torch.int64), keep=keep, n_kept=n_kept)
+        r = ev.compute()
+        results = {"mAP": r["mAP"], "class_metrics": {}}
+        for c in range(1, self.n_classes + 1):
+            tp, fp, fn = int(r["TP"][c, 0]), int(r["FP"][c, 0]), int(r["FN"][c, 0])
+            results["class_metrics"][c] = {"AP": float(r["AP"][c, 0]), "Recall": float(r["recall"][c, 0]),
+                                           "Precision": tp / (tp + fp) if tp + fp > 0 else 0.0, "TP": tp, "FP": fp, "FN": fn}
+        return results

@@ -1,0 +1,235 @@
+"""Detection mAP on HIP: COCO's mAP@[.5:.95] with 101 recall points, computed on the GPU.
+
+The reference's ``calculate_metrics`` (nets/frcnn_training.py:372-565) loops over an empty range and calls the one-argument
+``compute_ap`` with two arguments, so it defines no number to match: the metric is this project's, and it is COCOeval's
+``evaluateImg`` + ``accumulate`` with area range "all" and no crowd / ignore flags:
+
+* per image and class: detections ordered by descending score (ties: the lower row), the first ``max_dets`` kept (the cap
+  is per (image, class), as COCOeval's), each taking the not yet matched ground truth of its class with the largest
+  IoU >= t (equal IoUs: the higher GT index, COCOeval's ``<`` loop), every threshold on its own; IoU is the reference's
+  ``bbox_iou`` (eps 1e-8, no +1) in f32, thresholds are f32;
+* per class and threshold, over everything passed to ``update``: records sorted by descending score (ties: update order,
+  then the image's position in its batch, then the per-image order), integer cumulative TP / FP, f64 precision made
+  monotone from the right, sampled at the first position where ``100 tp >= k npig`` for k = 0..100 (0 where there is
+  none) - an exact integer form of COCO's float ``searchsorted``, which differs from pycocotools only where a recall lands
+  exactly on k/100 - and AP = the mean of the 101 samples;
+* a class without ground truth is excluded (COCO's -1); a class with ground truth and no detection scores 0; mAP is the mean
+  over the (class, threshold) pairs whose class has ground truth (NaN when there is none).
+
+Deliberate deviations from the reference's evident intent: one-to-one matching (the reference counts a detection as a TP
+when any GT of its class has IoU > t); classes without ground truth are excluded (the reference appends 0); the mAP is one
+dataset-level number (the reference averages per-batch values); every image is scored against its own ground truth (the
+reference uses ``bboxes[0]`` only).
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from .. import hip_ops
+from .._ffi import TsodError, require_cuda
+
+COCO_IOU_THRESHOLDS = tuple(float(np.float32(v)) for v in np.linspace(0.5, 0.95, 10))
+MAX_THRESHOLDS = 32
+
+
+def _as_list(x, what):
+    if isinstance(x, torch.Tensor):
+        return None
+    if isinstance(x, (list, tuple)):
+        return list(x)
+    raise TypeError(f"DetectionEvaluator.update: {what} must be a tensor or a list of tensors, got {type(x).__name__}")
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class DetectionEvaluator:
+    """COCO-style detection mAP accumulated on the GPU.
+
+    ``DetectionEvaluator(num_classes, iou_thresholds=0.50:0.95:0.05, max_dets=100, ignore_class=None)``: classes are
+    evaluated in ``[0, num_classes)``; detections of ``ignore_class`` (and ground truth labelled with it) are not counted.
+
+    ``update(det, gt_boxes, gt_labels, *, counts=None, keep=None, n_kept=None)`` takes the detections of a batch as
+      * a padded [B,R,6] tensor of rows (x1,y1,x2,y2,score,class) with ``counts`` [B] (None: all R rows), or
+      * ``postprocess()``'s triple: ``det`` = det_sorted [B,R,6], ``keep`` [B,R], ``n_kept`` [B], or
+      * ``predict()``'s list of [n_i,6] tensors;
+    and the ground truth as lists of [G_i,4] boxes / [G_i] labels or padded [B,G,4] / [B,G] tensors (pad labels with -1).
+    Rows with a NaN score or a class outside the range are dropped.  GPU tensors only; no host synchronisation: the record
+    buffer grows from the host-known upper bound B*R per call.  ``compute()`` reads the results back once and returns a dict
+    (``mAP``, ``AP50`` / ``AP75`` when those thresholds are evaluated, ``AP`` [C,T] f64 with -1 for classes without ground
+    truth, ``recall`` (likewise), ``TP`` / ``FP`` / ``FN`` [C,T] int64, ``npig`` [C] int64, ``iou_thresholds``).  ``reset()``
+    clears the state."""
+
+    def __init__(self, num_classes: int, iou_thresholds=COCO_IOU_THRESHOLDS, max_dets: int = 100, ignore_class=None):
+        thr = [float(np.float32(v)) for v in iou_thresholds]
+        if not 0 < len(thr) <= MAX_THRESHOLDS:
+            raise ValueError(f"DetectionEvaluator: 1 to {MAX_THRESHOLDS} IoU thresholds, got {len(thr)}")
+        if int(num_classes) <= 0 or int(max_dets) <= 0:
+            raise ValueError("DetectionEvaluator: num_classes and max_dets must be positive")
+        self.num_classes = int(num_classes)
+        self.iou_thresholds = tuple(thr)
+        self.max_dets = int(max_dets)
+        self.ignore_class = -1 if ignore_class is None else int(ignore_class)
+        self.reset()
+
+    def reset(self):
+        self._device = None
+        self._records = None            # [capacity, 3] int32: tsod_eval_record rows
+        self._bound = 0                 # host-known upper bound of the live record count
+        self._n = None                  # [1] int64 on the device: the live count
+        self._npig = None               # [C] int64
+        self._thr = None
+
+    # -------------------------------------------------------------------------------------------------------------- state
+    def _state(self, dev):
+        if self._device is None:
+            self._device = dev
+            self._records = torch.empty((0, hip_ops.EVAL_RECORD_INTS), dtype=torch.int32, device=dev)
+            self._n = torch.zeros((1,), dtype=torch.int64, device=dev)
+            self._npig = torch.zeros((self.num_classes,), dtype=torch.int64, device=dev)
+            self._thr = torch.tensor(self.iou_thresholds, dtype=torch.float32, device=dev)
+        elif dev != self._device:
+            raise TsodError(f"DetectionEvaluator: inputs on {dev}, state on {self._device}")
+
+    def _reserve(self, extra: int):
+        need = self._bound + extra
+        cap = self._records.shape[0]
+        if need > cap:
+            grown = torch.empty((max(need, 2 * cap), hip_ops.EVAL_RECORD_INTS), dtype=torch.int32, device=self._device)
+            if self._bound:
+                grown[:self._bound].copy_(self._records[:self._bound])
+            self._records = grown
+
+    # ------------------------------------------------------------------------------------------------------------- inputs
+    def _detections(self, det, counts, keep, n_kept):
+        rows = _as_list(det, "det")
+        if rows is not None:                                              # predict()'s list
+            if counts is not None or keep is not None or n_kept is not None:
+                raise ValueError("DetectionEvaluator.update: counts / keep / n_kept go with a padded det tensor")
+            if not rows:
+                raise ValueError("DetectionEvaluator.update: empty batch")
+            for r in rows:
+                require_cuda(r, "DetectionEvaluator.update")
+                if r.dim() != 2 or r.shape[1] != 6:
+                    raise ValueError(f"DetectionEvaluator.update: detections are [n,6] rows, got {tuple(r.shape)}")
+            dev = rows[0].device
+            R = max(1, max(r.shape[0] for r in rows))
+            padded = torch.zeros((len(rows), R, 6), dtype=torch.float32, device=dev)
+            for b, r in enumerate(rows):
+                padded[b, :r.shape[0]].copy_(r)
+            ns = torch.tensor([r.shape[0] for r in rows], dtype=torch.int32).to(dev, non_blocking=True)
+            return padded, ns, None, None
+        require_cuda(det, "DetectionEvaluator.update")
+        if det.dim() != 3 or det.shape[2] != 6 or det.shape[0] == 0 or det.shape[1] == 0:
+            raise ValueError(f"DetectionEvaluator.update: detections are [B,R,6], got {tuple(det.shape)}")
+        B, R = det.shape[:2]
+        det = det.contiguous()
+        if (keep is None) != (n_kept is None):
+            raise ValueError("DetectionEvaluator.update: keep and n_kept go together")
+        if keep is not None:
+            if counts is not None:
+                raise ValueError("DetectionEvaluator.update: counts or (keep, n_kept), not both")
+            if tuple(keep.shape) != (B, R) or tuple(n_kept.shape) != (B,):
+                raise ValueError(f"DetectionEvaluator.update: keep {tuple(keep.shape)} / n_kept {tuple(n_kept.shape)} for "
+                                 f"detections {tuple(det.shape)}")
+            return det, None, keep.to(det.device, torch.int32).contiguous(), n_kept.to(det.device, torch.int32).contiguous()
+        if counts is None:
+            counts = torch.full((B,), R, dtype=torch.int32, device=det.device)
+        elif tuple(counts.shape) != (B,):
+            raise ValueError(f"DetectionEvaluator.update: counts {tuple(counts.shape)} for {B} images")
+        return det, counts.to(det.device, torch.int32).contiguous(), None, None
+
+    def _ground_truth(self, gt_boxes, gt_labels, B, dev, gt_counts):
+        boxes, labels = _as_list(gt_boxes, "gt_boxes"), _as_list(gt_labels, "gt_labels")
+        if (boxes is None) != (labels is None):
+            raise ValueError("DetectionEvaluator.update: gt_boxes and gt_labels are both lists or both tensors")
+        if boxes is not None:
+            if len(boxes) != B or len(labels) != B:
+                raise ValueError(f"DetectionEvaluator.update: {B} images, {len(boxes)} box sets, {len(labels)} label sets")
+            for bx, lb in zip(boxes, labels):
+                require_cuda(bx, "DetectionEvaluator.update")
+                if not isinstance(lb, torch.Tensor) or not lb.is_cuda:
+                    require_cuda(lb, "DetectionEvaluator.update")
+                if bx.dim() != 2 or bx.shape[1] != 4 or lb.shape != bx.shape[:1]:
+                    raise ValueError(f"DetectionEvaluator.update: ground truth [G,4] / [G], got {tuple(bx.shape)} / "
+                                     f"{tuple(lb.shape)}")
+            G = max(bx.shape[0] for bx in boxes)
+            pb = torch.zeros((B, G, 4), dtype=torch.float32, device=dev)
+            pl = torch.full((B, G), -1, dtype=torch.int64, device=dev)
+            for b in range(B):
+                g = boxes[b].shape[0]
+                pb[b, :g].copy_(boxes[b])
+                pl[b, :g].copy_(labels[b])
+            gc = torch.tensor([bx.shape[0] for bx in boxes], dtype=torch.int32).to(dev, non_blocking=True)
+            return pb, pl, gc
+        require_cuda(gt_boxes, "DetectionEvaluator.update")
+        if not gt_labels.is_cuda:
+            require_cuda(gt_labels, "DetectionEvaluator.update")
+        if gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 4 or tuple(gt_labels.shape) != tuple(gt_boxes.shape[:2]):
+            raise ValueError(f"DetectionEvaluator.update: padded ground truth [B,G,4] / [B,G] for B={B}, got "
+                             f"{tuple(gt_boxes.shape)} / {tuple(gt_labels.shape)}")
+        G = gt_boxes.shape[1]
+        if gt_counts is None:
+            gc = torch.full((B,), G, dtype=torch.int32, device=dev)
+        else:
+            gc = gt_counts.to(dev, torch.int32).contiguous()
+        return _aligned(gt_boxes), gt_labels.to(dev, torch.int64).contiguous(), gc
+
+    def update(self, det, gt_boxes, gt_labels, *, counts=None, keep=None, n_kept=None, gt_counts=None):
+        det, counts, keep, n_kept = self._detections(det, counts, keep, n_kept)
+        B, R = det.shape[:2]
+        dev = det.device
+        gb, gl, gc = self._ground_truth(gt_boxes, gt_labels, B, dev, gt_counts)
+        self._state(dev)
+        self._reserve(B * R)
+        hip_ops.eval_match(det, gb, gl, gc, self._thr, self.num_classes, self.max_dets, self.ignore_class, self._records,
+                           self._n, self._npig, counts=counts, keep=keep, n_kept=n_kept)
+        self._bound += B * R
+
+    # ------------------------------------------------------------------------------------------------------------ results
+    def records(self):
+        """The records so far, in record order, read back to the host (a test / debugging accessor):
+        (score [N] f32, class [N] int32, TP mask [N] uint32) numpy arrays."""
+        if self._device is None:
+            return np.zeros(0, np.float32), np.zeros(0, np.int32), np.zeros(0, np.uint32)
+        n = int(self._n.item())
+        r = self._records[:n].cpu().numpy()
+        return r[:, 0].view(np.float32).copy(), r[:, 1].copy(), r[:, 2].view(np.uint32).copy()
+
+    def compute(self) -> dict:
+        if self._device is None:
+            raise RuntimeError("DetectionEvaluator.compute: nothing was passed to update()")
+        C, T = self.num_classes, len(self.iou_thresholds)
+        self._reserve(1)                                                  # capacity > 0 even when every batch was empty
+        out = hip_ops.eval_accumulate(self._records, self._n, self._npig, T)
+        host = torch.cat([out.view(-1), self._npig]).cpu().numpy()       # the one host read
+        body = host[:5 * C * T].reshape(5, C, T)
+        ap, recall = body[0].view(np.float64), body[4].view(np.float64)
+        npig = host[5 * C * T:]
+        has_gt = npig > 0
+        res = {
+            "mAP": _mean(ap[has_gt].ravel()),
+            "AP": torch.from_numpy(ap.copy()),
+            "recall": torch.from_numpy(recall.copy()),
+            "TP": torch.from_numpy(body[1].copy()),
+            "FP": torch.from_numpy(body[2].copy()),
+            "FN": torch.from_numpy(body[3].copy()),
+            "npig": torch.from_numpy(npig.copy()),
+            "iou_thresholds": self.iou_thresholds,
+        }
+        for name, v in (("AP50", 0.5), ("AP75", 0.75)):
+            for t, thr in enumerate(self.iou_thresholds):
+                if thr == float(np.float32(v)):
+                    res[name] = _mean(ap[has_gt, t])
+        return res
+
+
+def _mean(values) -> float:
+    """Mean of f64 values with one correctly rounded sum (math.fsum): independent of their order; NaN when empty."""
+    values = list(np.asarray(values, dtype=np.float64).ravel())
+    return math.fsum(values) / len(values) if values else float("nan")
