@@ -667,6 +667,63 @@ int tsod_resize_bilinear_aa_u8_f32(const uint8_t *src, int32_t H, int32_t W, int
                                    int32_t OW, float mul, float *out, int64_t stride_y, int64_t stride_x,
                                    int64_t stride_c, int32_t C_out, tsod_stream_t stream);
 
+/* ---- training augmentation: the reference's `transform` (dataset/transform.py:4-12) -----------------
+ * RandomPhotometricDistort -> RandomHorizontalFlip -> ScaleJitter -> Resize -> SanitizeBoundingBoxes on an RGB u8 HWC
+ * image (values 0..255) and its XYXY boxes.  The parameters are drawn on the host; these calls apply them.
+ * tsod_photometric holds one image's colour draws: the ops whose bit is set in `flags` run in torchvision's order
+ * (brightness, contrast if CONTRAST_FIRST, saturation, hue, contrast otherwise, channel permutation).  When any of the
+ * four colour ops is set, the pixel is divided by `white` first, the colour ops clamp into [0, 1], and the result is
+ * multiplied by `white`; white = 1 is the reference (its 0..255 image clamped into [0, 1]), 255 the evident intent.
+ *   tsod_augment_gray_mean_partials  TSOD_AUGMENT_MEAN_PARTS fixed-order partial sums (f64, device) of the grayscale
+ *                                    value of the image as contrast sees it; needed only when CONTRAST is set
+ *   tsod_augment_resize_u8_f32       colour ops + channel permutation + (flip ? mirrored columns : identity) + one
+ *                                    antialiased resize (the tables of tsod_resize_aa_tables_f32, same tap arithmetic as
+ *                                    tsod_resize_bilinear_aa_u8_f32 with mul = 1) into out[oy*stride_y + ox*stride_x +
+ *                                    c*stride_c], c < 3, channels 3..C_out-1 zero.  mean_partials: the output of
+ *                                    tsod_augment_gray_mean_partials for the same image and params (NULL without CONTRAST)
+ *   tsod_resize_bilinear_aa_f32      the same resize from an f32 image src[y*src_stride_y + x*src_stride_x +
+ *                                    c*src_stride_c], c < C <= 4 (the augmentation's second resize)
+ *   tsod_augment_boxes_f32           B images in one launch (one workgroup each).  Image b owns boxes [first, first +
+ *                                    count) of `boxes` [N,4] / `labels` [N]: iparams[b] = {first, count, flip, 0},
+ *                                    fparams[b] = {W, sx1, sy1, sx2, sy2, OW, OH, min_size}.  Per box: flip
+ *                                    (x1, x2) -> (W - x2, W - x1), x *= sx1, y *= sy1, x *= sx2, y *= sy2, then kept iff
+ *                                    x2 - x1 >= min_size, y2 - y1 >= min_size, every coordinate >= 0, x1, x2 <= OW,
+ *                                    y1, y2 <= OH.  Kept boxes and labels are written in order from index `first` of the
+ *                                    outputs; kept[b] = their count.
+ *   tsod_augment_color_host          HOST function: the colour ops and permutation of tsod_photometric on n
+ *                                    interleaved f32 RGB pixels, given contrast's mean (the arithmetic the kernels run) */
+#define TSOD_AUGMENT_MEAN_PARTS 256
+enum {
+    TSOD_AUG_BRIGHTNESS = 1,
+    TSOD_AUG_CONTRAST = 2,
+    TSOD_AUG_SATURATION = 4,
+    TSOD_AUG_HUE = 8,
+    TSOD_AUG_CONTRAST_FIRST = 16,
+    TSOD_AUG_PERMUTE = 32
+};
+typedef struct tsod_photometric {
+    int32_t flags;
+    float brightness, contrast, saturation, hue; /* factors of the ops that are set */
+    float white;                                  /* > 0 */
+    int32_t perm[3];                              /* out[c] = in[perm[c]] when PERMUTE is set; a permutation of 0,1,2 */
+} tsod_photometric;
+int tsod_augment_gray_mean_partials(const uint8_t *src, int32_t H, int32_t W, int64_t src_row_bytes,
+                                    const tsod_photometric *params, double *partials, tsod_stream_t stream);
+int tsod_augment_resize_u8_f32(const uint8_t *src, int32_t H, int32_t W, int64_t src_row_bytes,
+                               const tsod_photometric *params, const double *mean_partials, int32_t flip,
+                               const int32_t *yfirst, const int32_t *ycount, const float *ywt, const int32_t *xfirst,
+                               const int32_t *xcount, const float *xwt, int32_t OH, int32_t OW, float *out,
+                               int64_t stride_y, int64_t stride_x, int64_t stride_c, int32_t C_out, tsod_stream_t stream);
+int tsod_resize_bilinear_aa_f32(const float *src, int32_t H, int32_t W, int32_t C, int64_t src_stride_y,
+                                int64_t src_stride_x, int64_t src_stride_c, const int32_t *yfirst, const int32_t *ycount,
+                                const float *ywt, const int32_t *xfirst, const int32_t *xcount, const float *xwt,
+                                int32_t OH, int32_t OW, float *out, int64_t stride_y, int64_t stride_x, int64_t stride_c,
+                                int32_t C_out, tsod_stream_t stream);
+int tsod_augment_boxes_f32(const float *boxes, const int64_t *labels, int32_t B, const int32_t *iparams,
+                           const float *fparams, float *boxes_out, int64_t *labels_out, int32_t *kept,
+                           tsod_stream_t stream);
+int tsod_augment_color_host(const float *rgb, int64_t n, const tsod_photometric *params, float mean, float *rgb_out);
+
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends
  * `count_per_rank` floats and receives n_ranks * count_per_rank in rank order.  Stream-ordered, no host synchronisation.

@@ -112,6 +112,15 @@ class StemDesc(Structure):
 
 STEM_NCHW, STEM_NHWC4 = 0, 1
 
+AUG_MEAN_PARTS = 256             # TSOD_AUGMENT_MEAN_PARTS
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE, AUG_CONTRAST_FIRST, AUG_PERMUTE = 1, 2, 4, 8, 16, 32
+
+
+class Photometric(Structure):
+    """Mirror of ``tsod_photometric`` (include/tsod.h)."""
+    _fields_ = [("flags", c_int32), ("brightness", c_float), ("contrast", c_float), ("saturation", c_float),
+                ("hue", c_float), ("white", c_float), ("perm", c_int32 * 3)]
+
 # name -> (restype, argtypes); every symbol include/tsod.h declares
 _SIGNATURES = {
     "tsod_status_str": (c_char_p, [c_int]),
@@ -185,6 +194,17 @@ _SIGNATURES = {
     "tsod_resize_bilinear_aa_u8_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int64,
                                                c_int64, c_int64, c_int32, c_void_p]),
+    "tsod_augment_gray_mean_partials": (c_int, [c_void_p, c_int32, c_int32, c_int64, POINTER(Photometric), c_void_p,
+                                                c_void_p]),
+    "tsod_augment_resize_u8_f32": (c_int, [c_void_p, c_int32, c_int32, c_int64, POINTER(Photometric), c_void_p, c_int32,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                           c_int64, c_int64, c_int64, c_int32, c_void_p]),
+    "tsod_resize_bilinear_aa_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                            c_int64, c_int64, c_int64, c_int32, c_void_p]),
+    "tsod_augment_boxes_f32": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "tsod_augment_color_host": (c_int, [c_void_p, c_int64, POINTER(Photometric), c_float, c_void_p]),
     "tsod_detection_keys_f32": (c_int, [c_void_p, c_int64, c_float, c_int32, c_void_p, c_void_p]),
     "tsod_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "tsod_detection_nms_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p,

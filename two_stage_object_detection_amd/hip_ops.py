@@ -13,7 +13,7 @@ from ctypes import byref, c_int32
 import torch
 
 from . import _ffi
-from ._ffi import ACT_NONE, check, lib, make_conv_desc, ptr, require_cuda, stream_ptr
+from ._ffi import ACT_NONE, TsodError, check, lib, make_conv_desc, ptr, require_cuda, stream_ptr
 
 
 # ----------------------------------------------------------------------------- workspace arena
@@ -1057,4 +1057,135 @@ def resize_bilinear_aa(img: torch.Tensor, OH: int, OW: int, layout: str = "nhwc4
     check(lib().tsod_resize_bilinear_aa_u8_f32(ptr(img), H, W, C, img.stride(0), ptr(yf), ptr(yc), ptr(yw), ptr(xf), ptr(xc),
                                                ptr(xw), OH, OW, float(mul), ptr(out), strides[0], strides[1], strides[2],
                                                c_out, stream_ptr()), "resize_bilinear_aa")
+    return out
+
+
+# ----------------------------------------------------------------------------- training augmentation
+def photometric(brightness=None, contrast=None, saturation=None, hue=None, contrast_before: bool = True, perm=None,
+                white: float = 1.0) -> _ffi.Photometric:
+    """The ``tsod_photometric`` of one image's RandomPhotometricDistort draws (None = the op was not drawn)."""
+    p = _ffi.Photometric()
+    flags = 0
+    for bit, name, v in ((_ffi.AUG_BRIGHTNESS, "brightness", brightness), (_ffi.AUG_CONTRAST, "contrast", contrast),
+                         (_ffi.AUG_SATURATION, "saturation", saturation), (_ffi.AUG_HUE, "hue", hue)):
+        if v is not None:
+            flags |= bit
+            setattr(p, name, float(v))
+    if contrast_before:
+        flags |= _ffi.AUG_CONTRAST_FIRST
+    if perm is not None:
+        flags |= _ffi.AUG_PERMUTE
+        p.perm[:] = [int(c) for c in perm]
+    p.flags = flags
+    p.white = float(white)
+    return p
+
+
+def _rgb_u8(img, what):
+    if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise TsodError(f"{what}: a u8 [H,W,3] CUDA/ROCm tensor is required")
+    if img.stride(2) != 1 or img.stride(1) != 3:
+        raise TsodError(f"{what}: pixels must be interleaved and contiguous along a row")
+    return img.shape[0], img.shape[1]
+
+
+def _out_tensor(out, shape, dev, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise TsodError(f"{what}: out must be a contiguous f32 {shape} tensor on {dev}")
+    return out
+
+
+def _layout(layout, C, OH, OW):
+    if layout == "nhwc4":
+        return (OH, OW, 4), (4 * OW, 4, 1), 4
+    if layout == "nchw":
+        return (C, OH, OW), (OW, 1, OH * OW), C
+    raise ValueError(layout)
+
+
+def augment_gray_mean_partials(img: torch.Tensor, params: _ffi.Photometric, out=None) -> torch.Tensor:
+    """u8 [H,W,3] CUDA image -> f64 [TSOD_AUGMENT_MEAN_PARTS] partial sums of contrast's grayscale input (their sum /
+    (H*W) is the mean; ``params`` must draw contrast)."""
+    H, W = _rgb_u8(img, "augment_gray_mean_partials")
+    if out is None:
+        out = torch.empty(_ffi.AUG_MEAN_PARTS, dtype=torch.float64, device=img.device)
+    if tuple(out.shape) != (_ffi.AUG_MEAN_PARTS,) or out.dtype != torch.float64 or out.device != img.device:
+        raise TsodError(f"augment_gray_mean_partials: out must be f64 [{_ffi.AUG_MEAN_PARTS}] on {img.device}")
+    check(lib().tsod_augment_gray_mean_partials(ptr(img), H, W, img.stride(0), byref(params), ptr(out), stream_ptr()),
+          "augment_gray_mean_partials")
+    return out
+
+
+def augment_resize(img: torch.Tensor, OH: int, OW: int, params: _ffi.Photometric, flip: bool, mean_partials=None,
+                   layout: str = "nchw", out=None) -> torch.Tensor:
+    """u8 [H,W,3] CUDA image -> colour ops, channel permutation, optional horizontal flip and one antialiased bilinear
+    resize to f32 (``layout="nchw"`` -> [3,OH,OW], ``"nhwc4"`` -> [OH,OW,4]).  ``mean_partials``: the output of
+    ``augment_gray_mean_partials`` for the same image and params, required when contrast is drawn."""
+    H, W = _rgb_u8(img, "augment_resize")
+    dev = img.device
+    if (params.flags & _ffi.AUG_CONTRAST) and mean_partials is None:
+        raise TsodError("augment_resize: contrast is drawn but mean_partials is missing")
+    yf, yc, yw = resize_tables(H, OH, dev)
+    xf, xc, xw = resize_tables(W, OW, dev)
+    shape, strides, c_out = _layout(layout, 3, OH, OW)
+    out = _out_tensor(out, shape, dev, "augment_resize")
+    check(lib().tsod_augment_resize_u8_f32(ptr(img), H, W, img.stride(0), byref(params), ptr(mean_partials), int(bool(flip)),
+                                           ptr(yf), ptr(yc), ptr(yw), ptr(xf), ptr(xc), ptr(xw), OH, OW, ptr(out),
+                                           strides[0], strides[1], strides[2], c_out, stream_ptr()), "augment_resize")
+    return out
+
+
+def resize_bilinear_aa_f32(src: torch.Tensor, OH: int, OW: int, layout: str = "nchw", out=None) -> torch.Tensor:
+    """f32 [C<=4,H,W] CUDA image -> antialiased-bilinear resized f32 image (``layout`` as ``resize_bilinear_aa``); the
+    same tap tables and tap order as the u8 kernel."""
+    require_cuda(src, "resize_bilinear_aa_f32")
+    if src.dim() != 3 or not 1 <= src.shape[0] <= 4:
+        raise TsodError("resize_bilinear_aa_f32: an f32 [C<=4,H,W] tensor is required")
+    C, H, W = src.shape
+    dev = src.device
+    yf, yc, yw = resize_tables(H, OH, dev)
+    xf, xc, xw = resize_tables(W, OW, dev)
+    shape, strides, c_out = _layout(layout, C, OH, OW)
+    out = _out_tensor(out, shape, dev, "resize_bilinear_aa_f32")
+    check(lib().tsod_resize_bilinear_aa_f32(ptr(src), H, W, C, src.stride(1), src.stride(2), src.stride(0), ptr(yf), ptr(yc),
+                                            ptr(yw), ptr(xf), ptr(xc), ptr(xw), OH, OW, ptr(out), strides[0], strides[1],
+                                            strides[2], c_out, stream_ptr()), "resize_bilinear_aa_f32")
+    return out
+
+
+def augment_boxes(boxes: torch.Tensor, labels: torch.Tensor, iparams: torch.Tensor, fparams: torch.Tensor):
+    """Flip, two scalings and SanitizeBoundingBoxes for B images in one launch.  ``boxes`` f32 [N,4] / ``labels`` i64 [N]
+    on the device; ``iparams`` i32 [B,4] = (first, count, flip, 0), ``fparams`` f32 [B,8] = (W, sx1, sy1, sx2, sy2, OW,
+    OH, min_size).  -> (boxes_out [N,4], labels_out [N], kept i32 [B]): image b's kept boxes at [first, first + kept[b])."""
+    require_cuda(boxes, "augment_boxes")
+    dev = boxes.device
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or not boxes.is_contiguous():
+        raise TsodError("augment_boxes: boxes must be a contiguous f32 [N,4] tensor")
+    if labels.dtype != torch.int64 or labels.shape != (boxes.shape[0],) or labels.device != dev or not labels.is_contiguous():
+        raise TsodError("augment_boxes: labels must be a contiguous i64 [N] tensor on the boxes' device")
+    B = iparams.shape[0]
+    if (iparams.dtype != torch.int32 or tuple(iparams.shape) != (B, 4) or fparams.dtype != torch.float32
+            or tuple(fparams.shape) != (B, 8) or iparams.device != dev or fparams.device != dev
+            or not iparams.is_contiguous() or not fparams.is_contiguous()):
+        raise TsodError("augment_boxes: iparams must be i32 [B,4] and fparams f32 [B,8], contiguous, on the boxes' device")
+    boxes_out = torch.empty_like(boxes)
+    labels_out = torch.empty_like(labels)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().tsod_augment_boxes_f32(ptr(boxes), ptr(labels), B, ptr(iparams), ptr(fparams), ptr(boxes_out),
+                                       ptr(labels_out), ptr(kept), stream_ptr()), "augment_boxes")
+    return boxes_out, labels_out, kept
+
+
+def augment_color_host(rgb, params: _ffi.Photometric, mean: float = 0.0):
+    """HOST: the colour ops and permutation of ``params`` on f32 [..., 3] pixels (a numpy array), given contrast's mean
+    -- the per-pixel arithmetic the kernels run, for checking it without a GPU."""
+    import numpy as np
+    src = np.ascontiguousarray(rgb, dtype=np.float32)
+    if src.shape[-1] != 3:
+        raise ValueError("augment_color_host: pixels must be [..., 3]")
+    out = np.empty_like(src)
+    check(lib().tsod_augment_color_host(src.ctypes.data, src.size // 3, byref(params), float(mean), out.ctypes.data),
+          "augment_color_host")
     return out
