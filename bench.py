@@ -16,7 +16,8 @@ Workloads: N = 1 -> BASELINE.json configs[1] (batch 1); N > 1 -> configs[4] (dat
 over 8 GPUs), weak scaling: every rank processes its own images, value = images of all ranks / max-over-ranks time.
 `--batch` overrides the per-rank batch.
 
-Two schedules are measured and BOTH are reported in the one JSON line:
+Two schedules exist; a plain run times the headline one (in flight, or serial with --in-flight 1), --full measures BOTH and
+reports them in the one JSON line:
   * serial     : one forward at a time on one stream (`serial`: images/s, ms per step = latency of a forward).  The
                  `roofline` object belongs to this schedule: algorithmic conv FLOPs / HIP-event time of one pass over
                  the conv launches in forward order (on their launch stream, tile table tuned for this schedule, cache
@@ -31,6 +32,11 @@ Two schedules are measured and BOTH are reported in the one JSON line:
 Every timed region (exactly K steps between barrier + synchronize on both sides, max over ranks) is run --repeats times
 (default 1, so that --steps K times exactly K steps per schedule); with more, the median repeat is reported, min / max alongside.
 
+A plain run does only what the headline needs: set up, tune, warm up, time the headline schedule, write --dump-outputs if
+asked, print the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, tuning_seconds).  Everything below
+- the serial schedule beside the in-flight headline, the roofline legs, the HBM traffic, the CPU baseline, `parity` against
+the CPU oracle, the N > 1 --check, --dump-layers - runs with --full only.
+
   roofline         : per layer the autotuner picks the arithmetic (--precision auto): f32 MFMA (peak 157.3 TFLOP/s) or bf16x3
                      (three exact bf16 pieces per operand, six bf16 MFMAs per f32 product: peak 2516.8 / 6 = 419.5 TFLOP/s
                      f32-equivalent).  achieved = algorithmic f32 conv FLOPs / kernel time; peak = the FLOP-weighted
@@ -42,7 +48,7 @@ Every timed region (exactly K steps between barrier + synchronize on both sides,
                      child runs of this script (rank 0, N = 1; --no-pmc skips them).
   cpu_baseline     : the CPU oracle (torch CPU ops + C nms / roi_pool restatement of the reference's path) timed on this
                      box's host cores on the same workload (rank 0, N = 1 only).
-  --check          : (N > 1, on by default) the gathered [N*B,300,6] records of the last step are compared on rank 0 with
+  --check          : (N > 1, on by default with --full) the gathered [N*B,300,6] records of the last step are compared on rank 0 with
                      single-GPU forwards of every rank's images, POSITION-WISE (record i of image g against record i: boxes /
                      scores <= 1e-3, classes equal, no unmatched record; `bit_exact` says whether they are even identical):
                      rank 0 tunes the tile tables once and broadcasts them, so every rank sums in the same order.  A
@@ -80,6 +86,9 @@ DUMP_BUDGET_BYTES = 60 << 20                                  # --dump-outputs: 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the serial schedule, the roofline legs (f32 MFMA, "
+                    "bf16x3), the HBM traffic (rocprofv3 --pmc children), the CPU baseline, `parity` against the CPU oracle, the "
+                    "N > 1 --check and --dump-layers; a plain run measures the headline schedule only")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=1, help="how many times the K-step timed region is run (median reported; "
@@ -122,18 +131,18 @@ def parse(argv=None):
                     "(for rocprofv3 --pmc passes: every dispatch then carries its own counter sample)")
     ap.add_argument("--no-fuse-shortcut", action="store_true", help="ResNet: one launch per conv (the projection shortcuts as their "
                     "own GEMMs + residual reads) instead of stacking them into their block's last 1x1 conv (A/B switch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child runs behind roofline.traffic")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and `parity`")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc child runs behind roofline.traffic")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--dump-layers", default=None, help="write the serial plan's conv launches (name, FLOPs, algorithmic bytes, tile, "
-                    "K-slice slab bytes, HIP-event time) as JSON: the per-layer columns of scripts/summarize_pmc.py")
+    ap.add_argument("--dump-layers", default=None, help="with --full: write the serial plan's conv launches (name, FLOPs, algorithmic "
+                    "bytes, tile, K-slice slab bytes, HIP-event time) as JSON: the per-layer columns of scripts/summarize_pmc.py")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the arrays the last timed step returned as "
                     "DIR/<name>.npy (float32 / float64; a fixed seeded sample above 60 MiB in all) for output-by-output comparison "
                     "of two builds")
-    ap.add_argument("--cpu-reps", type=int, default=8)
+    ap.add_argument("--cpu-reps", type=int, default=8, help="--full: timed CPU oracle forwards of the CPU baseline")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--check", action="store_true", default=None, help="N > 1: compare the gathered records with single-GPU forwards "
-                    "on rank 0 (the DEFAULT for N > 1; --no-check skips it)")
+                    "on rank 0 (the DEFAULT for N > 1 with --full; --no-check skips it)")
     ap.add_argument("--no-check", dest="check", action="store_false")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI; the real path) | gloo (rehearsal of "
                     "the N>1 control flow on a box with fewer GPUs than ranks: ranks share devices, gather goes through host)")
@@ -145,6 +154,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.dump_layers and not args.full:
+        ap.error("--dump-layers times every conv launch on its own: it needs --full")
     return args
 
 
@@ -563,7 +574,7 @@ def main(argv=None):
         args.batch = 8 if world > 1 else 1
     B = args.batch
     if args.check is None:
-        args.check = world > 1                              # a driver-run --gpus N validates what it gathers
+        args.check = world > 1 and args.full                # a --full run of --gpus N validates what it gathers
     if args.autotune_in_sequence is None:
         args.autotune_in_sequence = 5 if B < 4 else 0
     if args.autotune_in_flight_refine is None:
@@ -707,7 +718,7 @@ def main(argv=None):
 
         # ---- the f32-MFMA kernels alone (every layer pinned to precision f32): the roofline comparable with round 1
         f32_leg = None
-        if world == 1 and not args.no_autotune and not args.no_graph and args.precision != "f32" and not (tiles_loaded and "f32" not in tiles):
+        if args.full and world == 1 and not args.no_autotune and not args.no_graph and args.precision != "f32" and not (tiles_loaded and "f32" not in tiles):
             if "f32" not in tiles:
                 tiles["f32"] = model.tune(x, precisions=(0,), schedules=("serial",), splits=splits, in_sequence=0, heads=False,
                                           fuse_bottleneck=False)["serial"]
@@ -723,7 +734,7 @@ def main(argv=None):
                                "HIP events); not the timed path when --precision auto picks bf16x3"}
         # ---- the same with the candidates of rounds 2-3 (f32 / bf16x3 per layer, no fp16x2): what the third arithmetic buys
         bf_leg = None
-        if world == 1 and not args.no_autotune and not args.no_graph and 2 in precs and not (tiles_loaded and "bf16x3" not in tiles):
+        if args.full and world == 1 and not args.no_autotune and not args.no_graph and 2 in precs and not (tiles_loaded and "bf16x3" not in tiles):
             if "bf16x3" not in tiles:
                 tiles["bf16x3"] = model.tune(x, precisions=(0, 1), schedules=("serial",), splits=splits,
                                              in_sequence=args.autotune_in_sequence, heads=False, fuse_bottleneck=False)["serial"]
@@ -741,18 +752,19 @@ def main(argv=None):
                               "events): the arithmetic of rounds 2-3, not the timed path when fp16x2 is among the candidates"}
         # ---- schedule 1: strictly serial (one graph, one stream) + the per-kernel roofline that belongs to it
         plan = use_table("serial")
-        conv_ms = conv_event_times(plan)
-        conv_seq_ms = conv_sequence_time(plan)
-        if args.dump_layers and rank == 0:
-            dump_layers(plan, args.dump_layers, conv_ms, conv_in_sequence_times(plan))
-        conv_flops = sum(st.flops for st in plan.gemm_steps)
-        algo_bytes = conv_algorithmic_bytes(plan)
-        precs = [step_precision(st) for st in plan.gemm_steps]
-        has_stem = getattr(plan, "stem_step", None) is not None
-        n_fused = len(plan.fused_steps) - (1 if has_stem else 0)
-        flops_bf = sum(st.flops * (6 if pr == 1 else 3) for st, pr in zip(plan.gemm_steps, precs) if pr >= 1) / 6.0
-        peak_of = {0: F32_MFMA_PEAK_TFLOPS, 1: BF16X3_PEAK_TFLOPS, 2: FP16X2_PEAK_TFLOPS}
-        ideal_ms = sum(st.flops / (peak_of[pr] * 1e12) * 1e3 for st, pr in zip(plan.gemm_steps, precs))
+        precs = [step_precision(st) for st in plan.gemm_steps]            # (the line's dtype)
+        if args.full:
+            conv_ms = conv_event_times(plan)
+            conv_seq_ms = conv_sequence_time(plan)
+            if args.dump_layers and rank == 0:
+                dump_layers(plan, args.dump_layers, conv_ms, conv_in_sequence_times(plan))
+            conv_flops = sum(st.flops for st in plan.gemm_steps)
+            algo_bytes = conv_algorithmic_bytes(plan)
+            has_stem = getattr(plan, "stem_step", None) is not None
+            n_fused = len(plan.fused_steps) - (1 if has_stem else 0)
+            flops_bf = sum(st.flops * (6 if pr == 1 else 3) for st, pr in zip(plan.gemm_steps, precs) if pr >= 1) / 6.0
+            peak_of = {0: F32_MFMA_PEAK_TFLOPS, 1: BF16X3_PEAK_TFLOPS, 2: FP16X2_PEAK_TFLOPS}
+            ideal_ms = sum(st.flops / (peak_of[pr] * 1e12) * 1e3 for st, pr in zip(plan.gemm_steps, precs))
         if args.no_graph:
             n_fly = 1
 
@@ -774,7 +786,7 @@ def main(argv=None):
                 def drain(self):
                     torch.cuda.synchronize()
             serial_server = _Eager()
-        else:
+        elif args.full or n_fly == 1:
             serial_server = InFlightDetector(model, x, depth=1, tiles=tiles["serial"])
 
         def last_step_outputs(srv):
@@ -784,12 +796,14 @@ def main(argv=None):
             if world > 1:
                 arrs["detections_gathered"] = gathered[(srv._next - 1) % n_fly].cpu()
             return arrs
-        serial = timer.measure(make_step(serial_server, 1), args.steps, args.warmup, args.repeats)
-        serial_server.drain()
-        last_outs = last_step_outputs(serial_server) if args.dump_outputs and rank == 0 and n_fly == 1 else None
+        serial, last_outs = None, None
         timed_outs = {}                                                   # what the timed plans computed on x (checked in `parity`)
-        if rank == 0 and not args.no_graph:
-            timed_outs["serial"] = [o.cpu() for o in serial_server.result(serial_server.submit())[:4]]
+        if args.full or n_fly == 1:                                       # (a plain run times the serial schedule when it is the headline)
+            serial = timer.measure(make_step(serial_server, 1), args.steps, args.warmup, args.repeats)
+            serial_server.drain()
+            last_outs = last_step_outputs(serial_server) if args.dump_outputs and rank == 0 and n_fly == 1 else None
+            if args.full and rank == 0 and not args.no_graph:
+                timed_outs["serial"] = [o.cpu() for o in serial_server.result(serial_server.submit())[:4]]
         # ---- schedule 2: --in-flight steps overlapped on as many streams (the default headline)
         if n_fly > 1:
             server = InFlightDetector(model, x, depth=n_fly, tiles=tiles["in_flight"])
@@ -797,13 +811,13 @@ def main(argv=None):
             server.drain()
             if args.dump_outputs and rank == 0:
                 last_outs = last_step_outputs(server)
-            if rank == 0:                                                  # the slot the next request would use
+            if args.full and rank == 0:                                    # the slot the next request would use
                 timed_outs[f"in_flight_slot{server._next % n_fly}"] = [o.cpu() for o in server.result(server.submit())[:4]]
                 server.drain()
         else:
             server, fly = serial_server, serial
         model.raise_if_error()
-        if rank == 0 and args.no_graph:
+        if args.full and rank == 0 and args.no_graph:
             timed_outs["serial_eager"] = [o.cpu() for o in model(x)]
             model.raise_if_error()
 
@@ -828,13 +842,23 @@ def main(argv=None):
     exit_code = 0
     if rank == 0:
         head = fly
-        conv_total_ms = conv_seq_ms                                       # one pass in forward order (agrees with the kernel trace)
-        achieved = conv_flops / (conv_total_ms * 1e-3) / 1e12
-        eff_peak = conv_flops / (ideal_ms * 1e-3) / 1e12               # FLOP-weighted harmonic peak of the layers' arithmetics
         n_bf = sum(1 for pr in precs if pr == 1)
         n_h2 = sum(1 for pr in precs if pr == 2)
-        traffic, traffic_note = (None, "skipped") if (n_gpus > 1 or args.no_pmc) else pmc_traffic(args, tiles, len(conv_ms))
-        step_flops = conv_flops                                           # conv GEMM FLOPs of one step (B images)
+        config = {"workload": f"Full Faster R-CNN {args.backbone} inference forward, batch={B} per GPU, "
+                              f"3x{args.height}x{args.width}, {args.num_classes}+1 classes, 3000->300 proposals"
+                              + (" (BASELINE configs[4]: data-parallel, 8 images per rank)" if world > 1 and B == 8 else ""),
+                  "global_batch": n_gpus * B, "parallelism": f"dp{n_gpus}",
+                  "hip_graph": not args.no_graph, "autotuned_tiles": not args.no_autotune, "steps_in_flight": n_fly,
+                  "timed_step": ("result() of the request that last used the slot (event wait + the slot's range-word read), then submit()"
+                                 if n_fly > 1 else "submit() only: forwards queued back to back on one stream, results collected behind the region"),
+                  # the two schedules side by side (value / ms_per_step above = the in-flight one)
+                  "images_per_s_in_flight": round(n_gpus * B / (head["ms_per_step"] * 1e-3), 3)}
+        if serial is not None:
+            config["images_per_s_serial"] = round(n_gpus * B / (serial["ms_per_step"] * 1e-3), 3)
+            config["ms_per_step_serial"] = round(serial["ms_per_step"], 4)
+        config["tiles_tuned_on"] = "rank 0, broadcast" if world > 1 else "this rank"
+        config["collective"] = None if n_gpus == 1 else (f"tsod_allgather_f32 [{n_gpus * B},300,6] f32 (RCCL)" if args.collective == "tsod" and args.dist_backend == "nccl"
+                                                         else f"all_gather_into_tensor [{n_gpus * B},300,6] f32 ({args.dist_backend})")
         line = {
             "metric": "images/sec Faster R-CNN ResNet-50 @800x1333" if args.backbone == "resnet50"
                       else f"images/sec Faster R-CNN {args.backbone} @{args.height}x{args.width}",
@@ -848,57 +872,52 @@ def main(argv=None):
                                               + "f32 MFMA in the rest",
             "data": "synthetic" + (" (seeded random-init weights; BatchNorm running statistics pre-computed from two seeded images, "
                                    "configs/synthetic_bn_*.npz)" if args.backbone.startswith("hardnet") else ""),
-            "config": {"workload": f"Full Faster R-CNN {args.backbone} inference forward, batch={B} per GPU, "
-                                   f"3x{args.height}x{args.width}, {args.num_classes}+1 classes, 3000->300 proposals"
-                                   + (" (BASELINE configs[4]: data-parallel, 8 images per rank)" if world > 1 and B == 8 else ""),
-                       "global_batch": n_gpus * B, "parallelism": f"dp{n_gpus}",
-                       "hip_graph": not args.no_graph, "autotuned_tiles": not args.no_autotune, "steps_in_flight": n_fly,
-                       "timed_step": ("result() of the request that last used the slot (event wait + the slot's range-word read), then submit()"
-                                      if n_fly > 1 else "submit() only: forwards queued back to back on one stream, results collected behind the region"),
-                       # the two schedules side by side (value / ms_per_step above = the in-flight one)
-                       "images_per_s_in_flight": round(n_gpus * B / (head["ms_per_step"] * 1e-3), 3),
-                       "images_per_s_serial": round(n_gpus * B / (serial["ms_per_step"] * 1e-3), 3),
-                       "ms_per_step_serial": round(serial["ms_per_step"], 4),
-                       "tiles_tuned_on": "rank 0, broadcast" if world > 1 else "this rank",
-                       "collective": None if n_gpus == 1 else (f"tsod_allgather_f32 [{n_gpus * B},300,6] f32 (RCCL)" if args.collective == "tsod" and args.dist_backend == "nccl"
-                                                              else f"all_gather_into_tensor [{n_gpus * B},300,6] f32 ({args.dist_backend})")},
+            "config": config,
             "repeats": {"n": head["n"], "steps_each": head["steps"], "ms_per_step_median": round(head["ms_per_step"], 4),
                         "ms_per_step_min": round(head["min"], 4), "ms_per_step_max": round(head["max"], 4)},
-            "serial": {"images_per_s": round(n_gpus * B / (serial["ms_per_step"] * 1e-3), 3),
-                       "ms_per_step": round(serial["ms_per_step"], 4), "ms_per_step_min": round(serial["min"], 4),
-                       "ms_per_step_max": round(serial["max"], 4), "repeats": serial["n"],
-                       "note": "one forward at a time on one stream (--in-flight 1 semantics) = latency of a step"},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 3), "peak": round(eff_peak, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / eff_peak, 4),
-                         "peak_note": f"f32-equivalent: {n_bf} layers bf16x3 (bf16 dense MFMA {BF16_MFMA_PEAK_TFLOPS} / 6 products = "
-                                      f"{BF16X3_PEAK_TFLOPS:.1f}), "
-                                      + (f"{n_h2} layers fp16x2 (/ 3 products = {FP16X2_PEAK_TFLOPS:.1f}), " if n_h2 else "")
-                                      + f"{len(precs) - n_bf - n_h2} layers f32 MFMA ({F32_MFMA_PEAK_TFLOPS}); FLOP-weighted "
-                                      "harmonic mean, i.e. frac = sum of ideal matrix-pipe times / measured time",
-                         "executed_bf16_mfma_tflops": round(6.0 * flops_bf / (conv_total_ms * 1e-3) / 1e12, 1),
-                         "traffic": None if traffic is None else round(traffic),
-                         "traffic_unit": "HBM bytes per conv launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024 / launches"
-                                         + ("" if traffic_note is None else f" [{traffic_note}]"),
-                         "algorithmic_bytes_per_launch": round(algo_bytes / len(conv_ms)),
-                         "traffic_over_algorithmic": None if traffic is None else round(traffic * len(conv_ms) / algo_bytes, 3),
-                         "kernel": f"conv_igemm_kernel / conv_dma_kernel (implicit GEMM; per layer f32 MFMA, bf16x3 or fp16x2 MFMA, register-staged or "
-                                   f"fed by LDS-DMA)" + (f" + bottleneck_kernel ({n_fused} bottlenecks of layer1 as one launch each)" if n_fused else "")
-                                   + (" + stem_kernel (conv1 + bn1 + PReLU + max pool from the NCHW images as one launch)" if has_stem else "")
-                                   + f", {len(conv_ms)} launches per forward",
-                         "schedule": "serial", "flops_per_forward": conv_flops,
-                         "kernel_ms_per_forward": round(conv_total_ms, 4),
-                         "kernel_ms_measured_as": "HIP events around one pass over the conv launches in forward order (cache state of a "
-                                                  "forward, launch boundaries included); `achieved` / `frac` use it",
-                         "kernel_ms_per_forward_isolated": round(sum(conv_ms), 4),
-                         "isolated_note": "sum over layers of 5 back-to-back repeats of each launch on hot operands (per-layer figures of "
-                                          "--dump-layers / --verbose): the optimistic bound",
-                         "serial_ms_per_step": round(serial["ms_per_step"], 4),
-                         "share_of_serial_step": round(conv_total_ms / serial["ms_per_step"], 4)},
-            "throughput_mode": {"steps_in_flight": n_fly, "conv_tflops_per_step_time": round(step_flops / (head["ms_per_step"] * 1e-3) / 1e12, 3),
-                                "frac_of_peak": round(step_flops / (head["ms_per_step"] * 1e-3) / 1e12 / eff_peak, 4),
-                                "note": "conv FLOPs of a step / ms_per_step of the headline schedule: a whole-step bound "
-                                        "(non-GEMM kernels included in the time), not a per-kernel measurement"},
         }
+        if serial is not None:
+            line["serial"] = {"images_per_s": round(n_gpus * B / (serial["ms_per_step"] * 1e-3), 3),
+                              "ms_per_step": round(serial["ms_per_step"], 4), "ms_per_step_min": round(serial["min"], 4),
+                              "ms_per_step_max": round(serial["max"], 4), "repeats": serial["n"],
+                              "note": "one forward at a time on one stream (--in-flight 1 semantics) = latency of a step"}
+        if args.full:
+            conv_total_ms = conv_seq_ms                                   # one pass in forward order (agrees with the kernel trace)
+            achieved = conv_flops / (conv_total_ms * 1e-3) / 1e12
+            eff_peak = conv_flops / (ideal_ms * 1e-3) / 1e12           # FLOP-weighted harmonic peak of the layers' arithmetics
+            traffic, traffic_note = (None, "skipped") if (n_gpus > 1 or args.no_pmc) else pmc_traffic(args, tiles, len(conv_ms))
+            step_flops = conv_flops                                       # conv GEMM FLOPs of one step (B images)
+            line["roofline"] = {
+                "bound": "mfma", "achieved": round(achieved, 3), "peak": round(eff_peak, 1), "unit": "TFLOP/s",
+                "frac": round(achieved / eff_peak, 4),
+                "peak_note": f"f32-equivalent: {n_bf} layers bf16x3 (bf16 dense MFMA {BF16_MFMA_PEAK_TFLOPS} / 6 products = "
+                             f"{BF16X3_PEAK_TFLOPS:.1f}), "
+                             + (f"{n_h2} layers fp16x2 (/ 3 products = {FP16X2_PEAK_TFLOPS:.1f}), " if n_h2 else "")
+                             + f"{len(precs) - n_bf - n_h2} layers f32 MFMA ({F32_MFMA_PEAK_TFLOPS}); FLOP-weighted "
+                             "harmonic mean, i.e. frac = sum of ideal matrix-pipe times / measured time",
+                "executed_bf16_mfma_tflops": round(6.0 * flops_bf / (conv_total_ms * 1e-3) / 1e12, 1),
+                "traffic": None if traffic is None else round(traffic),
+                "traffic_unit": "HBM bytes per conv launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024 / launches"
+                                + ("" if traffic_note is None else f" [{traffic_note}]"),
+                "algorithmic_bytes_per_launch": round(algo_bytes / len(conv_ms)),
+                "traffic_over_algorithmic": None if traffic is None else round(traffic * len(conv_ms) / algo_bytes, 3),
+                "kernel": f"conv_igemm_kernel / conv_dma_kernel (implicit GEMM; per layer f32 MFMA, bf16x3 or fp16x2 MFMA, register-staged or "
+                          f"fed by LDS-DMA)" + (f" + bottleneck_kernel ({n_fused} bottlenecks of layer1 as one launch each)" if n_fused else "")
+                          + (" + stem_kernel (conv1 + bn1 + PReLU + max pool from the NCHW images as one launch)" if has_stem else "")
+                          + f", {len(conv_ms)} launches per forward",
+                "schedule": "serial", "flops_per_forward": conv_flops,
+                "kernel_ms_per_forward": round(conv_total_ms, 4),
+                "kernel_ms_measured_as": "HIP events around one pass over the conv launches in forward order (cache state of a "
+                                         "forward, launch boundaries included); `achieved` / `frac` use it",
+                "kernel_ms_per_forward_isolated": round(sum(conv_ms), 4),
+                "isolated_note": "sum over layers of 5 back-to-back repeats of each launch on hot operands (per-layer figures of "
+                                 "--dump-layers / --verbose): the optimistic bound",
+                "serial_ms_per_step": round(serial["ms_per_step"], 4),
+                "share_of_serial_step": round(conv_total_ms / serial["ms_per_step"], 4)}
+            line["throughput_mode"] = {"steps_in_flight": n_fly, "conv_tflops_per_step_time": round(step_flops / (head["ms_per_step"] * 1e-3) / 1e12, 3),
+                                       "frac_of_peak": round(step_flops / (head["ms_per_step"] * 1e-3) / 1e12 / eff_peak, 4),
+                                       "note": "conv FLOPs of a step / ms_per_step of the headline schedule: a whole-step bound "
+                                               "(non-GEMM kernels included in the time), not a per-kernel measurement"}
         line["tuning_seconds"] = {"per_rank": all_tuning, "note": "autotune + head tuning wall time before the first timed step"
                                   + (" (rank 0 tunes, the others wait for its broadcast)" if world > 1 else "")}
         if f32_leg is not None:
@@ -908,14 +927,15 @@ def main(argv=None):
         if check is not None:
             line["check"] = check
         parity = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # N = 1: the timed oracle forwards double as the reference of `parity`; N > 1: one untimed oracle forward of rank 0's shard
             ref_outs, cpu = cpu_baseline(sd, args.backbone, x_cpu, args.cpu_reps if n_gpus == 1 else 0)
             if n_gpus == 1:
                 line["cpu_baseline"] = cpu
             parity = parity_of(timed_outs, ref_outs, getattr(cpu_baseline, "exact_outs", None), getattr(cpu_baseline, "cutoff", None),
                                getattr(cpu_baseline, "exact_cutoff", None))
-        line["parity"] = parity
+        if args.full:
+            line["parity"] = parity
         if last_outs is not None:
             line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(last_outs, args.dump_outputs),
                                     "note": "the headline schedule's last timed step: {name: [shape, elements written]}"}

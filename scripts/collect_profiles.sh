@@ -17,18 +17,18 @@ O=$R/gpurun_out/prof_${tag}_$name
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 T=$O/tiles.json
-python3 $R/bench.py --steps 20 --warmup 5 --tiles-file $T --dump-layers $O/layers.json "$@" > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
+python3 $R/bench.py --full --steps 20 --warmup 5 --tiles-file $T --dump-layers $O/layers.json "$@" > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
 tail -1 $O/bench_default.log > $O/bench_default.json
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_serial -- python3 $R/bench.py --steps 20 --warmup 3 --repeats 1 --no-cpu-baseline --no-pmc --in-flight 1 --tiles-file $T "$@" > $O/trace_serial.log 2>&1 || echo "serial trace failed"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_serial -- python3 $R/bench.py --full --steps 20 --warmup 3 --repeats 1 --no-cpu-baseline --no-pmc --in-flight 1 --tiles-file $T "$@" > $O/trace_serial.log 2>&1 || echo "serial trace failed"
 echo "serial trace done"
 if [ "$name" = "b1" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_default -- python3 $R/bench.py --steps 20 --warmup 3 --repeats 1 --no-cpu-baseline --no-pmc --tiles-file $T "$@" > $O/trace_default.log 2>&1 || echo "default trace failed"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_default -- python3 $R/bench.py --full --steps 20 --warmup 3 --repeats 1 --no-cpu-baseline --no-pmc --tiles-file $T "$@" > $O/trace_default.log 2>&1 || echo "default trace failed"
 echo "default trace done"
 fi
 for pass in "sq:SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "fetch:FETCH_SIZE GRBM_GUI_ACTIVE" "write:WRITE_SIZE" "tcc:TCC_HIT_sum TCC_MISS_sum"; do
   n=${pass%%:*}; c=${pass#*:}
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$n -- python3 $R/bench.py --steps 4 --warmup 2 --repeats 1 --no-cpu-baseline --no-pmc --no-graph --in-flight 1 --tiles-file $T "$@" > $O/pmc_$n.log 2>&1 || echo "pmc $n failed"
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$n -- python3 $R/bench.py --full --steps 4 --warmup 2 --repeats 1 --no-cpu-baseline --no-pmc --no-graph --in-flight 1 --tiles-file $T "$@" > $O/pmc_$n.log 2>&1 || echo "pmc $n failed"
   echo "pmc $n done"
 done
 cd $R

@@ -268,6 +268,21 @@ def test_bench_dump_outputs_and_step_count(tmp_path):
     assert sizes <= budget
 
 
+def test_bench_plain_run_and_full():
+    """A plain bench.py run measures the headline only; the serial schedule, rooflines, traffic, CPU baseline, parity, the
+    N > 1 --check and the per-layer dump are behind --full (off by default).  --dump-layers without --full is refused."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert args.full is False and args.check is None and args.dump_layers is None
+    assert bench.parse(["--full"]).full is True
+    assert bench.parse(["--full", "--dump-layers", "layers.json"]).dump_layers == "layers.json"
+    with pytest.raises(SystemExit):
+        bench.parse(["--dump-layers", "layers.json"])
+
+
 def test_head_choices_roundtrip_as_json():
     """FasterRCNN.head_choices / set_head_choices: the pinned (tile, K schedule, arithmetic) of the two GEMMs outside the
     backbone plan travel as plain JSON (bench.py persists them beside the tile table and broadcasts them to every rank)."""
