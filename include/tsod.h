@@ -724,6 +724,52 @@ int tsod_augment_boxes_f32(const float *boxes, const int64_t *labels, int32_t B,
                            tsod_stream_t stream);
 int tsod_augment_color_host(const float *rgb, int64_t n, const tsod_photometric *params, float mean, float *rgb_out);
 
+/* ---- optimizer: one AdamW update of any number of f32 tensors in ONE launch ---------------------------
+ * Replaces torch.optim.AdamW(...).step() [+ zero_grad] of the reference's train/train.py (amsgrad=False, maximize=False,
+ * decoupled weight decay).  Per element, every operation rounded to f32 on its own (the library is built with
+ * -ffp-contract=off), in the order of torch's single-tensor AdamW:
+ *     p = p * decay                                                   decay = 1 - lr * weight_decay
+ *     m = w < 0.5 ? m + (g - m) * w : g - (g - m) * (1 - w)           w = 1 - beta1          (torch's lerp_)
+ *     v = v * beta2 + ((1 - beta2) * g) * g                           (mul_, then addcmul_)
+ *     p = p + ((-step_size) * m) / (sqrt(v) / bias2_sqrt + eps)       (addcdiv_; IEEE divide and sqrt)
+ *     g = 0 when zero_grad is set
+ * tsod_adamw_group holds the scalars of one step for tensors that share hyper-parameters and step count t; the caller
+ * prepares them in double precision and rounds each once to f32.
+ *   tsod_adamw_step_f32       `table` and `chunks` are DEVICE memory.  table[i] describes tensor i; `group` indexes
+ *                             `groups`, a HOST array of n_groups <= TSOD_ADAMW_MAX_GROUPS records that travels by value
+ *                             with the launch (nothing on the host is read after the call returns).  chunks[c] =
+ *                             {tensor, piece}: workgroup c updates elements [piece * TSOD_ADAMW_CHUNK, + TSOD_ADAMW_CHUNK)
+ *                             of that tensor, clipped to its n.  Every element of every tensor must be covered by exactly
+ *                             one chunk; records that point outside the table or the groups are skipped.  16-byte accesses
+ *                             where the four pointers of a chunk are 16-byte aligned, 4-byte ones otherwise.  No atomics:
+ *                             the result does not depend on the schedule.  n_groups > TSOD_ADAMW_MAX_GROUPS:
+ *                             TSOD_ERR_UNSUPPORTED.
+ *   tsod_adamw_step_host_f32  HOST function: the same update over n elements of host arrays (the arithmetic the kernel runs) */
+#define TSOD_ADAMW_CHUNK 2048
+#define TSOD_ADAMW_MAX_GROUPS 32
+typedef struct tsod_adamw_tensor {
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    int64_t n;     /* elements */
+    int32_t group; /* index into groups */
+    int32_t reserved;
+} tsod_adamw_tensor;
+typedef struct tsod_adamw_chunk {
+    int32_t tensor, piece;
+} tsod_adamw_chunk;
+typedef struct tsod_adamw_group {
+    float decay;           /* 1 - lr * weight_decay */
+    float one_minus_beta1; /* lerp weight w */
+    float beta2, one_minus_beta2;
+    float step_size;       /* lr / (1 - beta1^t) */
+    float bias2_sqrt;      /* sqrt(1 - beta2^t) */
+    float eps;
+    float reserved;
+} tsod_adamw_group;
+int tsod_adamw_step_f32(const tsod_adamw_tensor *table, int32_t n_tensors, const tsod_adamw_chunk *chunks, int64_t n_chunks,
+                        const tsod_adamw_group *groups, int32_t n_groups, int32_t zero_grad, tsod_stream_t stream);
+int tsod_adamw_step_host_f32(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                             const tsod_adamw_group *group, int32_t zero_grad);
+
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends
  * `count_per_rank` floats and receives n_ranks * count_per_rank in rank order.  Stream-ordered, no host synchronisation.

@@ -121,6 +121,16 @@ class Photometric(Structure):
     _fields_ = [("flags", c_int32), ("brightness", c_float), ("contrast", c_float), ("saturation", c_float),
                 ("hue", c_float), ("white", c_float), ("perm", c_int32 * 3)]
 
+
+ADAMW_CHUNK, ADAMW_MAX_GROUPS = 2048, 32         # TSOD_ADAMW_CHUNK, TSOD_ADAMW_MAX_GROUPS
+
+
+class AdamWGroup(Structure):
+    """Mirror of ``tsod_adamw_group`` (include/tsod.h): the f32 scalars of one AdamW step."""
+    _fields_ = [("decay", c_float), ("one_minus_beta1", c_float), ("beta2", c_float), ("one_minus_beta2", c_float),
+                ("step_size", c_float), ("bias2_sqrt", c_float), ("eps", c_float), ("reserved", c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/tsod.h declares
 _SIGNATURES = {
     "tsod_status_str": (c_char_p, [c_int]),
@@ -205,6 +215,8 @@ _SIGNATURES = {
     "tsod_augment_boxes_f32": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     "tsod_augment_color_host": (c_int, [c_void_p, c_int64, POINTER(Photometric), c_float, c_void_p]),
+    "tsod_adamw_step_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p]),
+    "tsod_adamw_step_host_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(AdamWGroup), c_int32]),
     "tsod_detection_keys_f32": (c_int, [c_void_p, c_int64, c_float, c_int32, c_void_p, c_void_p]),
     "tsod_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "tsod_detection_nms_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p,

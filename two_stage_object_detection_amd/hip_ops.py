@@ -1189,3 +1189,79 @@ def augment_color_host(rgb, params: _ffi.Photometric, mean: float = 0.0):
     check(lib().tsod_augment_color_host(src.ctypes.data, src.size // 3, byref(params), float(mean), out.ctypes.data),
           "augment_color_host")
     return out
+
+
+# ----------------------------------------------------------------------------- optimizer
+def adamw_group(lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: float) -> _ffi.AdamWGroup:
+    """The scalars of step number ``step`` (1, 2, ...) for tensors that share these hyper-parameters: computed in double
+    precision as torch's single-tensor AdamW computes them, each rounded once to f32 (by ctypes)."""
+    bias1 = 1 - beta1 ** step
+    bias2 = 1 - beta2 ** step
+    return _ffi.AdamWGroup(1 - lr * weight_decay, 1 - beta1, beta2, 1 - beta2, lr / bias1, bias2 ** 0.5, eps, 0.0)
+
+
+def adamw_chunks(numels, chunk: int = _ffi.ADAMW_CHUNK):
+    """HOST: the work list of ``tsod_adamw_step_f32`` for tensors of ``numels`` elements: int32 [n_chunks, 2] rows
+    (tensor, piece), tensor by tensor, piece = 0, 1, ... covering elements [piece * chunk, (piece + 1) * chunk) up to the
+    tensor's end.  An empty tensor gets no row."""
+    import numpy as np
+    numels = np.asarray(numels, dtype=np.int64).reshape(-1)
+    if (numels < 0).any() or chunk <= 0:
+        raise ValueError("adamw_chunks: negative element count or chunk size")
+    pieces = (numels + chunk - 1) // chunk
+    total = int(pieces.sum())
+    if total >= 2 ** 31 or len(numels) >= 2 ** 31:
+        raise TsodError(f"adamw_chunks: {total} chunks do not fit one launch")
+    out = np.empty((total, 2), dtype=np.int32)
+    out[:, 0] = np.repeat(np.arange(len(numels)), pieces)
+    out[:, 1] = np.arange(total) - np.repeat(np.cumsum(pieces) - pieces, pieces)
+    return out
+
+
+def adamw_table(pointers, numels, groups, n_groups: int):
+    """HOST: ``tsod_adamw_tensor`` records as int64 [n, 6] words (param, grad, exp_avg, exp_avg_sq, n, group) from
+    ``pointers`` [n, 4], checked here because the kernel only sees them in device memory: no null or misaligned pointer, no
+    negative count, every group index inside [0, n_groups)."""
+    import numpy as np
+    pointers = np.asarray(pointers, dtype=np.int64).reshape(-1, 4)
+    numels = np.asarray(numels, dtype=np.int64).reshape(-1)
+    groups = np.asarray(groups, dtype=np.int64).reshape(-1)
+    if not (len(pointers) == len(numels) == len(groups)):
+        raise ValueError("adamw_table: pointers, numels and groups differ in length")
+    if (numels < 0).any():
+        raise TsodError("adamw_table: negative element count")
+    if ((pointers == 0).any(axis=1) & (numels > 0)).any() or (pointers & 3).any():      # (an empty tensor has no storage)
+        raise TsodError("adamw_table: null or misaligned tensor pointer")
+    if len(groups) and (groups.min() < 0 or groups.max() >= n_groups):
+        raise TsodError(f"adamw_table: group index outside [0, {n_groups})")
+    table = np.empty((len(pointers), 6), dtype=np.int64)
+    table[:, :4], table[:, 4], table[:, 5] = pointers, numels, groups      # (group in the low int32, reserved = 0)
+    return table
+
+
+def adamw_step(table: torch.Tensor, chunks: torch.Tensor, groups, zero_grad: bool = False) -> None:
+    """One AdamW update of every tensor of ``table`` (device copy of ``adamw_table``) over the work list ``chunks`` (device
+    copy of ``adamw_chunks``) in ONE launch on the current stream.  ``groups``: a sequence of ``adamw_group`` records; they
+    travel by value.  With ``zero_grad`` the gradients are cleared in the same pass."""
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int64 and table.dim() == 2
+            and table.shape[1] == 6 and table.is_contiguous()):
+        raise TsodError("adamw_step: table must be a contiguous int64 [n, 6] CUDA/ROCm tensor (there is no CPU fallback)")
+    if not (isinstance(chunks, torch.Tensor) and chunks.device == table.device and chunks.dtype == torch.int32
+            and chunks.dim() == 2 and chunks.shape[1] == 2 and chunks.is_contiguous()):
+        raise TsodError("adamw_step: chunks must be a contiguous int32 [n_chunks, 2] tensor on the table's device")
+    arr = (_ffi.AdamWGroup * len(groups))(*groups)
+    check(lib().tsod_adamw_step_f32(ptr(table), table.shape[0], ptr(chunks), chunks.shape[0], arr, len(groups),
+                                    int(bool(zero_grad)), stream_ptr()), "adamw_step")
+
+
+def adamw_step_host(param, grad, exp_avg, exp_avg_sq, group: _ffi.AdamWGroup, zero_grad: bool = False) -> None:
+    """HOST: the kernel's per-element update, in place on four contiguous f32 numpy arrays of one size -- for checking the
+    arithmetic without a GPU."""
+    import numpy as np
+    arrays = (param, grad, exp_avg, exp_avg_sq)
+    for a in arrays:
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable
+                and a.size == param.size):
+            raise ValueError("adamw_step_host: four writeable contiguous float32 arrays of one size")
+    check(lib().tsod_adamw_step_host_f32(*(a.ctypes.data for a in arrays), param.size, byref(group), int(bool(zero_grad))),
+          "adamw_step_host")
