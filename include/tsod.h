@@ -448,7 +448,8 @@ int tsod_roi_align_avg_f32(const float *feat, int32_t B, int32_t Hf, int32_t Wf,
                            float *out, int32_t out_pitch, tsod_stream_t stream);
 
 /* Final detection records (nets/frcnn_training.py:311-319): per RoI the arg-max class
- * over all n_class logits (first max wins), its raw logit, and loc2bbox(roi, loc of that class).
+ * over all n_class logits (first max wins; a NaN logit counts as the largest, as in torch.max / torch.argmax: the record's
+ * score is NaN and its class the first NaN's column), its raw logit, and loc2bbox(roi, loc of that class).
  *   cls_locs [K] rows of 4*n_class floats (row pitch loc_pitch), scores [K] rows of n_class (pitch score_pitch) - both may
  *   be column slices of one wider matrix, as the fused head GEMM writes them - rois [K][4]
  *   -> det [K][6] = (x1,y1,x2,y2,score,class). */
@@ -519,7 +520,8 @@ int tsod_proposal_targets_f32(const float *roi, int32_t R, const float *bbox, in
  *   sample_roi / gt_roi_loc [B][S][4], gt_roi_label [B][S] int64 in [0, n_class) ->
  *   anchors_pred [B][S][4] = loc2bbox(sample_roi, cls_loc[row, gt_label]) (the decode of tsod_loc2bbox_f32; NaN rows for an
  *   out-of-range label), classes_pred [B][S] int64 / classes_score_pred [B][S] = arg-max / max of the raw logits (first
- *   maximum wins, quirk Q11), out [B][2] = (loc loss, cls loss over all n_class logits), status [B]. */
+ *   maximum wins, quirk Q11; a row holding a NaN logit gives (the first NaN's column, NaN), as torch.argmax / torch.max, and a
+ *   NaN cls loss), out [B][2] = (loc loss, cls loss over all n_class logits), status [B]. */
 int tsod_rpn_losses_f32(const float *rpn_out, int32_t pitch, int32_t A, int32_t B, int32_t n_pix, const float *gt_loc,
                         const int64_t *gt_label, float sigma, float *out, int32_t *status, tsod_stream_t stream);
 int tsod_roi_losses_f32(const float *cls_locs, int32_t loc_pitch, const float *scores, int32_t score_pitch,

@@ -13,14 +13,15 @@ import re
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+import torch.nn.functional as F  # noqa: F401
+
+from trainer_losses_restated import F32_EPS, bbox2loc, chain_losses, loc2bbox, loc_loss, restated_on_run  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_CLASS = 81
 A = 9
 PARAMS = ("rpn.loc.weight", "rpn.loc.bias", "rpn.score.weight", "rpn.score.bias",
           "head.cls_loc.weight", "head.cls_loc.bias", "head.score.weight", "head.score.bias")
-F32_EPS = torch.finfo(torch.float32).eps
 
 
 @pytest.fixture(scope="module")
@@ -44,53 +45,7 @@ def reference_state_dict():
 
 
 # ------------------------------------------------------------------------------------------------------ the restatement
-def loc_loss(pred, gt, label, sigma=1.0):
-    pos = label > 0
-    d = (gt[pos] - pred[pos]).abs()
-    s2 = sigma ** 2
-    return torch.where(d < 1. / s2, 0.5 * s2 * d ** 2, d - 0.5 / s2).sum() / d.numel()
-
-
-def loc2bbox(src, loc):
-    w, h = src[:, 2] - src[:, 0], src[:, 3] - src[:, 1]
-    cx, cy = src[:, 0] + 0.5 * w, src[:, 1] + 0.5 * h
-    ncx, ncy = loc[:, 0] * w + cx, loc[:, 1] * h + cy
-    nw, nh = torch.exp(loc[:, 2]) * w, torch.exp(loc[:, 3]) * h
-    return torch.stack([ncx - 0.5 * nw, ncy - 0.5 * nh, ncx + 0.5 * nw, ncy + 0.5 * nh], dim=1)
-
-
-def bbox2loc(src, dst):
-    w, h = src[:, 2] - src[:, 0], src[:, 3] - src[:, 1]
-    cx, cy = src[:, 0] + 0.5 * w, src[:, 1] + 0.5 * h
-    bw, bh = dst[:, 2] - dst[:, 0], dst[:, 3] - dst[:, 1]
-    bcx, bcy = dst[:, 0] + 0.5 * bw, dst[:, 1] + 0.5 * bh
-    w = torch.maximum(w, torch.tensor(F32_EPS, dtype=w.dtype))
-    h = torch.maximum(h, torch.tensor(F32_EPS, dtype=h.dtype))
-    return torch.stack([(bcx - cx) / w, (bcy - cy) / h, torch.log(bw / w), torch.log(bh / h)], dim=1)
-
-
-def chain_losses(rpn_locs, rpn_scores, gt_rpn_loc, gt_rpn_label, cls_locs, scores, gt_roi_label, anchor, roi_anchor,
-                 sample_src, sample_gt, bbox, img_size, detach_rois=False):
-    """One image's four losses with autograd through everything the reference differentiates: the RPN outputs directly, and
-    rpn_locs again through roi = clamp(loc2bbox(anchor, loc))[chain] -> cat(roi, bbox)[keep_index] -> bbox2loc's target."""
-    S = gt_roi_label.shape[0]
-    a = roi_anchor.long()
-    roi = loc2bbox(anchor[a].to(rpn_locs.dtype), rpn_locs[a])
-    xs = roi[:, 0::2].clamp(min=0, max=img_size[1])
-    ys = roi[:, 1::2].clamp(min=0, max=img_size[2])
-    roi = torch.stack([xs[:, 0], ys[:, 0], xs[:, 1], ys[:, 1]], dim=1)
-    if detach_rois:
-        roi = roi.detach()
-    cand = torch.cat([roi, bbox.to(roi.dtype)])
-    sample_roi = cand[sample_src.long()]
-    gt_roi_loc = bbox2loc(sample_roi, bbox.to(roi.dtype)[sample_gt.long()])
-    roi_loc = cls_locs.view(S, -1, 4)[torch.arange(S), gt_roi_label]
-    return [loc_loss(rpn_locs, gt_rpn_loc.to(rpn_locs.dtype), gt_rpn_label),
-            F.cross_entropy(rpn_scores, gt_rpn_label, ignore_index=-1),
-            loc_loss(roi_loc, gt_roi_loc, gt_roi_label),
-            F.cross_entropy(scores, gt_roi_label)]
-
-
+# loc_loss, loc2bbox, bbox2loc, chain_losses, restated_on_run: tests/trainer_losses_restated.py (shared with the loss sweep)
 def restated_grads(X, fc7, W, gt_rpn_loc, gt_rpn_label, gt_roi_label, anchor, roi_anchor, sample_src, sample_gt, bbox,
                    img_size, weights=(0, 0, 0, 0, 1), detach_rois=False, dtype=torch.float64):
     """The eight gradients of sum_k weights[k] * loss_k (loss 4 = the total) for one image in ``dtype``: X [h*w, C] the
@@ -426,39 +381,6 @@ def saved_node(losses):
     while not hasattr(node, "saved"):
         node = node.next_functions[0][0]
     return node.saved
-
-
-def restated_on_run(sv, W, bbox, weights=(0, 0, 0, 0, 1)):
-    """float64 autograd on the GPU run's own intermediates (what its autograd node kept): d rpn_out / d both from the
-    restated losses of the kept outputs, then dW = dY^T X in float64."""
-    A_ = sv["A"]
-    rpn_out, both = sv["rpn_out"].cpu().double(), sv["both"].cpu().double()
-    rl = rpn_out[:, :4 * A_].clone().requires_grad_(True)
-    rs = rpn_out[:, 4 * A_:6 * A_].clone().requires_grad_(True)
-    cl = both[:, :4 * N_CLASS].clone().requires_grad_(True)
-    sc = both[:, 4 * N_CLASS:5 * N_CLASS].clone().requires_grad_(True)
-    sort_idx, keep_idx = sv["sort_idx"][0].cpu().long(), sv["keep_idx"][0].cpu().long()
-    roi_anchor = sort_idx[keep_idx]
-    src = sv["sample_src"][0].cpu()
-    sroi = sv["sample_roi"][0].cpu().double()
-    b = bbox.double()
-    tl = torch.maximum(sroi[:, None, :2], b[:, :2])
-    br = torch.minimum(sroi[:, None, 2:], b[:, 2:])
-    inter = (br - tl).clamp(min=0).prod(2)
-    iou = inter / ((sroi[:, 2:] - sroi[:, :2]).prod(1)[:, None] + (b[:, 2:] - b[:, :2]).prod(1) - inter)
-    sample_gt = iou.argmax(1)
-    losses = chain_losses(rl.reshape(-1, 4), rs.reshape(-1, 2), sv["gt_loc"][0].cpu(), sv["gt_label"][0].cpu(), cl, sc,
-                          sv["gt_roi_label"][0].cpu(), sv["anchor"].cpu(), roi_anchor, src, sample_gt, bbox,
-                          (3, sv["clamp_x"], sv["clamp_y"]))
-    losses.append(sum(losses))
-    sum(w * l for w, l in zip(weights, losses) if w).backward()
-    C = W["rpn.loc.weight"].shape[1]
-    X = sv["feat"].cpu().double().reshape(-1, sv["feat"].shape[-1])[:, :C]
-    fc7 = sv["fc7"].cpu().double()
-    g = {"rpn.loc.weight": rl.grad.T @ X, "rpn.loc.bias": rl.grad.sum(0), "rpn.score.weight": rs.grad.T @ X,
-         "rpn.score.bias": rs.grad.sum(0), "head.cls_loc.weight": cl.grad.T @ fc7, "head.cls_loc.bias": cl.grad.sum(0),
-         "head.score.weight": sc.grad.T @ fc7, "head.score.bias": sc.grad.sum(0)}
-    return {k: v.reshape(W[k].shape) for k, v in g.items()}
 
 
 @pytest.mark.gpu

@@ -93,7 +93,8 @@ rpn_losses_kernel(const float *__restrict__ fused, int pitch, int A, long n_pix,
 }
 
 // One workgroup per image, one wave per RoI row (rows w, w + waves, ...): first-max arg-max over the raw logits (quirk
-// Q11, the rule of tsod_detections_f32), log-sum-exp in f64, then lane 0 gathers the gt class's offsets and decodes them.
+// Q11, tsod_wave_argmax: the rule of tsod_detections_f32; a NaN logit wins, as in torch.max, and makes the row's CE NaN),
+// log-sum-exp in f64, then lane 0 gathers the gt class's offsets and decodes them.
 __global__ void __launch_bounds__(kRoiThreads)
 roi_losses_kernel(const float *__restrict__ cls_locs, int loc_pitch, const float *__restrict__ scores, int score_pitch,
                   const float *__restrict__ sample_roi, const float *__restrict__ gt_roi_loc,
@@ -109,18 +110,9 @@ roi_losses_kernel(const float *__restrict__ cls_locs, int loc_pitch, const float
     for (int r = wave; r < S; r += kWaves) {
         const long k = (long)b * S + r;
         const float *s = scores + k * score_pitch;
-        float best = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int c = lane; c < n_class; c += 64) {
-            const float v = s[c];
-            if (bi == 0x7fffffff || v > best) { best = v; bi = c; }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(best, off);
-            const int oi = __shfl_xor(bi, off);
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-        }
-        if (bi == 0x7fffffff) { bi = 0; best = NAN; }         // (a row of NaN logits: NaN, as torch.max)
+        float best;
+        int bi;
+        tsod_wave_argmax(s, n_class, lane, best, bi);
         // every lane holds the same (best, bi); the xor butterfly below leaves the same f64 sum in every lane too
         double e = 0.0;
         for (int c = lane; c < n_class; c += 64) e += exp((double)s[c] - (double)best);

@@ -108,17 +108,9 @@ detections_kernel(const float *__restrict__ cls_locs, int loc_pitch, const float
     const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (k >= K) return;
     const float *s = scores + (long)k * score_pitch;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int c = lane; c < n_class; c += 64) {
-        const float v = s[c];
-        if (bi == 0x7fffffff || v > best) { best = v; bi = c; }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-    }
+    float best;
+    int bi;
+    tsod_wave_argmax(s, n_class, lane, best, bi);
     if (lane == 0) {
         const float *l = cls_locs + (long)k * loc_pitch + bi * 4;
         const float *r = rois + (long)k * 4;

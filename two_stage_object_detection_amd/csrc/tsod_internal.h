@@ -82,6 +82,29 @@ __device__ __forceinline__ tsod_box tsod_decode_box(float ax1, float ay1, float 
     o.y2 = ncy + 0.5f * nh;
     return o;
 }
+// Arg-max / max of one row of n_class logits by one full wave, in torch.max's order (quirk Q11): a NaN is larger than every
+// number, equal values (two NaNs included) go to the lower column.  Every lane returns the same (best, bi): the one rule of
+// tsod_detections_f32 and tsod_roi_losses_f32.
+__device__ __forceinline__ bool tsod_argmax_takes(float v, int c, float best, int bi) {
+    if (c == 0x7fffffff) return false;                           // the other lane held no column
+    if (bi == 0x7fffffff) return true;
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || c < bi);
+    return v > best || (v == best && c < bi);
+}
+__device__ __forceinline__ void tsod_wave_argmax(const float *s, int n_class, int lane, float &best, int &bi) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    for (int c = lane; c < n_class; c += 64) {
+        const float v = s[c];
+        if (tsod_argmax_takes(v, c, best, bi)) { best = v; bi = c; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (tsod_argmax_takes(ov, oi, best, bi)) { best = ov; bi = oi; }
+    }
+}
 // ---- RoI geometry of roi_pool.hip's forward kernels and feature_grads.hip's backward: one definition, so that the two cannot
 // disagree about which pixels a bin reads.
 // nets/classify.py:35-36: a RoI in image coordinates -> feature-map coordinates (divide by the image side, multiply by the map's)
