@@ -86,7 +86,7 @@ def main():
                 byt = src * (2 if name == "all_on" else 1) + 2 * 3 * nh * nw * 4 + OH * OW * 16
             rec = dict(size=f"{H}x{W}", setting=name, jitter=f"{nh}x{nw}", wall_us=round(wall, 2), kernel_us=round(kern, 2),
                        gbps=round(byt / kern / 1e3, 1) if kern > 0 else None,
-                       kernels={k[:60]: round(v, 2) for k, v in per.items()})
+                       kernels={k[:100]: round(v, 2) for k, v in per.items()})
             print(json.dumps(rec), flush=True)
 
 

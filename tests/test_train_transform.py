@@ -259,9 +259,10 @@ def test_photometric_layout_matches_header(tmp_path):
 def test_augment_kernels_use_no_scratch_memory(tmp_path):
     from test_kernel_metadata import _kernel_notes
     kernels = _kernel_notes(tmp_path)
-    aug = {k: v for k, v in kernels.items() if any(s in k for s in ("gray_mean_kernel", "aug_resize_tile_kernel",
-                                                                    "f32_resize_tile_kernel", "aug_resize_flat_kernel",
-                                                                    "boxes_kernel"))}
-    assert len(aug) == 6, sorted(aug)                     # the flat kernel in its u8 and f32 forms
+    aug = {k: v for k, v in kernels.items() if any(s in k for s in ("gray_mean_kernel", "resize_tile_kernel",
+                                                                    "resize_flat_kernel", "boxes_kernel"))}
+    # the tiled and the flat resize, each over its three sources (u8 bytes, augmented u8, strided f32)
+    assert len(aug) == 8, sorted(aug)
+    assert sum(s in k for k in aug for s in ("U8Bytes", "AugU8", "StridedF32")) == 6, sorted(aug)
     bad = {k: v for k, v in aug.items() if v.get("private_segment_fixed_size", 0) != 0 or v.get("vgpr_spill_count", 0) != 0}
     assert not bad, bad

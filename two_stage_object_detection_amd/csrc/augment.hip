@@ -5,23 +5,19 @@
 //   gray_mean_kernel      contrast's grayscale mean: the ops in front of contrast are recomputed from the u8 source
 //                         (never materialised); fixed-order two-level sum (per-workgroup f64 tree, then a second tree
 //                         over TSOD_AUGMENT_MEAN_PARTS partials in every consumer workgroup), no atomics
-//   aug_resize_tile_kernel  colour ops + permutation + mirrored column index applied while the source region is staged
-//                         into LDS (the clamps make the ops nonlinear, so they run on source pixels before any tap),
-//                         then the first antialiased resize out of LDS; the staging and tap order of resize.hip's
-//                         resize_aa_tile_kernel, with the region held as f32 planes instead of u8 bytes
-//   f32_resize_tile_kernel  the second resize, f32 -> f32, same tile, same taps
+//   AugU8                 resize_aa.h's source policy of the first antialiased resize: colour ops + permutation +
+//                         mirrored column index applied while the source region is staged into LDS as three f32
+//                         planes (the clamps make the ops nonlinear, so they run on source pixels before any tap);
+//                         its prologue reduces the mean's partials.  The second resize, f32 -> f32, is resize.hip's.
 //   boxes_kernel          flip, two scalings, sanitize and a stable compaction of boxes + labels, one workgroup per image
 // Compiled with -ffp-contract=off: every expression rounds like the f32 restatement of DESIGN 4.15.
-#include "tsod_internal.h"
-#include <math.h>
+#include "resize_aa.h"
 
 namespace {
 
 constexpr int kParts = TSOD_AUGMENT_MEAN_PARTS;
 constexpr int kColorOps = TSOD_AUG_BRIGHTNESS | TSOD_AUG_CONTRAST | TSOD_AUG_SATURATION | TSOD_AUG_HUE;
 constexpr int kAllFlags = kColorOps | TSOD_AUG_CONTRAST_FIRST | TSOD_AUG_PERMUTE;
-constexpr int kTY = 8, kTX = 32, kThreads = kTY * kTX;   // resize.hip's tile
-constexpr size_t kLdsCap = 64 * 1024;
 
 __host__ __device__ inline float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 
@@ -161,7 +157,8 @@ gray_mean_kernel(const unsigned char *__restrict__ src, int H, int W, long pitch
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
 }
 
-// The second level of the mean: every thread of the workgroup calls it (kThreads == kParts); same tree everywhere.
+// The second level of the mean: every thread of the workgroup calls it; same tree everywhere.
+static_assert(kThreads == kParts, "one partial per thread");
 __device__ float reduce_mean(const double *__restrict__ partials, long n, double *red) {
     red[threadIdx.x] = partials ? partials[threadIdx.x] : 0.0;
     __syncthreads();
@@ -174,194 +171,40 @@ __device__ float reduce_mean(const double *__restrict__ partials, long n, double
     return m;
 }
 
-// Output pixel (ox, oy) of a tile from the staged f32 planes; the tap order of resize.hip.
-__device__ inline void tile_taps(const float *planes, int C, int cap_rows, int cap_cols, int ry0, int rx0,
-                                 const int *__restrict__ yfirst, const int *__restrict__ ycount,
-                                 const int *__restrict__ xfirst, const int *__restrict__ xcount, const float *wx,
-                                 const float *wy, int ox, int oy, float *__restrict__ out, long stride_y,
-                                 long stride_x, long stride_c, int C_out) {
-    const int x0 = xfirst[ox], nx = xcount[ox];
-    const int y0 = yfirst[oy], ny = ycount[oy];
-    const long plane = (long)cap_rows * cap_cols;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < ny; ++j) {
-        const float *row = planes + (long)min(y0 + j - ry0, cap_rows - 1) * cap_cols;
-        float h[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int i = 0; i < nx; ++i) {
-            const float w = wx[i];
-            const int col = min(x0 - rx0 + i, cap_cols - 1);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (c < C) {
-                    const float v = row[c * plane + col] * w;
-                    h[c] = i == 0 ? v : h[c] + v;
-                }
-        }
-        const float w = wy[j];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float v = h[c] * w;
-            acc[c] = j == 0 ? v : acc[c] + v;
-        }
+// The first resize's source: u8 RGB rows through the colour ops, read at the mirrored column when flipped.
+struct AugU8 : F32Planes {
+    const unsigned char *src;
+    int H, W;
+    long pitch;
+    tsod_photometric p;
+    const double *mean_partials;
+    int flip;
+    float mean;                                          // set by prologue()
+    static constexpr int C = 3;
+    static constexpr int kPrologueDoubles = kParts;
+    __device__ void prologue(double *red) {
+        mean = (p.flags & TSOD_AUG_CONTRAST) ? reduce_mean(mean_partials, (long)H * W, red) : 0.f;
     }
-    float *o = out + oy * stride_y + ox * stride_x;
-    if (stride_c == 1 && C_out == 4 && ((stride_x | stride_y) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
-        *reinterpret_cast<float4 *>(o) = make_float4(acc[0], C > 1 ? acc[1] : 0.f, C > 2 ? acc[2] : 0.f, C > 3 ? acc[3] : 0.f);
-        return;
+    __device__ auto src_px(int y, int xf) const {                    // xf: column of the flipped image
+        float c[3];
+        load_rgb(src, pitch, y, flip ? W - 1 - xf : xf, c);
+        aug_color(c, p, mean, false);
+        return [c](int k) { return c[k]; };
     }
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if (c < C_out) o[c * stride_c] = c < C ? acc[c] : 0.f;
-}
-
-struct TileGeom {
-    int oy0, ox0, ry0, rx0, rows, cols;
-};
-
-__device__ inline TileGeom tile_geom(const int *yfirst, const int *ycount, const int *xfirst, const int *xcount, int OH,
-                                     int OW, int cap_rows, int cap_cols) {
-    const int tiles_x = (OW + kTX - 1) / kTX;
-    TileGeom g;
-    g.oy0 = (blockIdx.x / tiles_x) * kTY;
-    g.ox0 = (blockIdx.x % tiles_x) * kTX;
-    const int oyL = min(g.oy0 + kTY, OH) - 1, oxL = min(g.ox0 + kTX, OW) - 1;
-    g.ry0 = yfirst[g.oy0];
-    g.rx0 = xfirst[g.ox0];
-    g.rows = min(yfirst[oyL] + ycount[oyL] - g.ry0, cap_rows);
-    g.cols = min(xfirst[oxL] + xcount[oxL] - g.rx0, cap_cols);
-    return g;
-}
-
-// the tile's weight rows to LDS (resize.hip)
-__device__ inline void stage_weights(float *s_wx, float *s_wy, const float *__restrict__ xwt, int xtaps,
-                                     const float *__restrict__ ywt, int ytaps, int ox0, int oy0, int OW, int OH) {
-    for (int t = threadIdx.x; t < kTX * xtaps; t += kThreads) {
-        const int o = ox0 + t / xtaps;
-        s_wx[t] = o < OW ? xwt[(long)o * xtaps + t % xtaps] : 0.f;
-    }
-    for (int t = threadIdx.x; t < kTY * ytaps; t += kThreads) {
-        const int o = oy0 + t / ytaps;
-        s_wy[t] = o < OH ? ywt[(long)o * ytaps + t % ytaps] : 0.f;
-    }
-}
-
-__global__ void __launch_bounds__(kThreads)
-aug_resize_tile_kernel(const unsigned char *__restrict__ src, int H, int W, long pitch, tsod_photometric p,
-                       const double *__restrict__ mean_partials, int flip, const int *__restrict__ yfirst,
-                       const int *__restrict__ ycount, const float *__restrict__ ywt, int ytaps,
-                       const int *__restrict__ xfirst, const int *__restrict__ xcount, const float *__restrict__ xwt,
-                       int xtaps, int OH, int OW, float *__restrict__ out, long stride_y, long stride_x, long stride_c,
-                       int C_out, int cap_rows, int cap_cols) {
-    extern __shared__ __align__(16) float lds[];        // 3 planes of cap_rows x cap_cols, then the tile's weights
-    // the mean's reduction borrows the front of the same LDS before the staging overwrites it
-    const float mean = (p.flags & TSOD_AUG_CONTRAST) ? reduce_mean(mean_partials, (long)H * W, reinterpret_cast<double *>(lds))
-                                                     : 0.f;
-    const TileGeom g = tile_geom(yfirst, ycount, xfirst, xcount, OH, OW, cap_rows, cap_cols);
-    const long plane = (long)cap_rows * cap_cols;
-    for (int r = threadIdx.x / kTX; r < g.rows; r += kTY)        // a row of the region per 32 threads
-        for (int col = threadIdx.x % kTX; col < g.cols; col += kTX) {
-            const int y = g.ry0 + r, xf = g.rx0 + col;           // xf: column of the flipped image
-            if (y >= H || xf >= W) continue;
-            float c[3];
-            load_rgb(src, pitch, y, flip ? W - 1 - xf : xf, c);
-            aug_color(c, p, mean, false);
-            float *d = lds + (long)r * cap_cols + col;
-            d[0] = c[0];
-            d[plane] = c[1];
-            d[2 * plane] = c[2];
-        }
-    float *s_wx = lds + 3 * plane;
-    float *s_wy = s_wx + kTX * xtaps;
-    stage_weights(s_wx, s_wy, xwt, xtaps, ywt, ytaps, g.ox0, g.oy0, OW, OH);
-    __syncthreads();
-    const int ox = g.ox0 + (threadIdx.x % kTX), oy = g.oy0 + (threadIdx.x / kTX);
-    if (ox >= OW || oy >= OH) return;
-    tile_taps(lds, 3, cap_rows, cap_cols, g.ry0, g.rx0, yfirst, ycount, xfirst, xcount,
-              s_wx + (threadIdx.x % kTX) * xtaps, s_wy + (threadIdx.x / kTX) * ytaps, ox, oy, out, stride_y, stride_x,
-              stride_c, C_out);
-}
-
-__global__ void __launch_bounds__(kThreads)
-f32_resize_tile_kernel(const float *__restrict__ src, int H, int W, int C, long sy, long sx, long sc,
-                       const int *__restrict__ yfirst, const int *__restrict__ ycount, const float *__restrict__ ywt,
-                       int ytaps, const int *__restrict__ xfirst, const int *__restrict__ xcount,
-                       const float *__restrict__ xwt, int xtaps, int OH, int OW, float *__restrict__ out, long stride_y,
-                       long stride_x, long stride_c, int C_out, int cap_rows, int cap_cols) {
-    extern __shared__ __align__(16) float lds[];        // C planes of cap_rows x cap_cols, then the tile's weights
-    const TileGeom g = tile_geom(yfirst, ycount, xfirst, xcount, OH, OW, cap_rows, cap_cols);
-    const long plane = (long)cap_rows * cap_cols;
-    for (int c = 0; c < C; ++c)
-        for (int r = threadIdx.x / kTX; r < g.rows; r += kTY)
+    __device__ void stage(unsigned char *lds, const TileGeom &g, int cap_rows, int cap_cols) const {
+        const long plane = (long)cap_rows * cap_cols;
+        for (int r = threadIdx.x / kTX; r < g.rows; r += kTY)        // a row of the region per 32 threads
             for (int col = threadIdx.x % kTX; col < g.cols; col += kTX) {
-                const int y = g.ry0 + r, x = g.rx0 + col;
-                if (y >= H || x >= W) continue;
-                lds[c * plane + (long)r * cap_cols + col] = src[(long)y * sy + (long)x * sx + (long)c * sc];
+                const int y = g.ry0 + r, xf = g.rx0 + col;
+                if (y >= H || xf >= W) continue;
+                const auto px = src_px(y, xf);
+                float *d = reinterpret_cast<float *>(lds) + (long)r * cap_cols + col;
+                d[0] = px(0);
+                d[plane] = px(1);
+                d[2 * plane] = px(2);
             }
-    float *s_wx = lds + C * plane;
-    float *s_wy = s_wx + kTX * xtaps;
-    stage_weights(s_wx, s_wy, xwt, xtaps, ywt, ytaps, g.ox0, g.oy0, OW, OH);
-    __syncthreads();
-    const int ox = g.ox0 + (threadIdx.x % kTX), oy = g.oy0 + (threadIdx.x / kTX);
-    if (ox >= OW || oy >= OH) return;
-    tile_taps(lds, C, cap_rows, cap_cols, g.ry0, g.rx0, yfirst, ycount, xfirst, xcount,
-              s_wx + (threadIdx.x % kTX) * xtaps, s_wy + (threadIdx.x / kTX) * ytaps, ox, oy, out, stride_y, stride_x,
-              stride_c, C_out);
-}
-
-// Very large down-scales (the region of a tile does not fit the LDS cap): every tap straight from global memory, the
-// colour ops recomputed per tap (same per-pixel arithmetic, so the same values as the tiled form).
-template <bool kU8>
-__global__ void __launch_bounds__(kThreads)
-aug_resize_flat_kernel(const unsigned char *__restrict__ src8, const float *__restrict__ src32, int H, int W, int C,
-                       long sy, long sx, long sc, tsod_photometric p, const double *__restrict__ mean_partials, int flip,
-                       const int *__restrict__ yfirst, const int *__restrict__ ycount, const float *__restrict__ ywt,
-                       int ytaps, const int *__restrict__ xfirst, const int *__restrict__ xcount,
-                       const float *__restrict__ xwt, int xtaps, int OH, int OW, float *__restrict__ out, long stride_y,
-                       long stride_x, long stride_c, int C_out) {
-    __shared__ double red[kParts];
-    const float mean = (kU8 && (p.flags & TSOD_AUG_CONTRAST)) ? reduce_mean(mean_partials, (long)H * W, red) : 0.f;
-    const long total = (long)OH * OW;
-    for (long t = (long)blockIdx.x * kThreads + threadIdx.x; t < total; t += (long)gridDim.x * kThreads) {
-        const int ox = (int)(t % OW), oy = (int)(t / OW);
-        const int x0 = xfirst[ox], nx = xcount[ox];
-        const int y0 = yfirst[oy], ny = ycount[oy];
-        const float *wx = xwt + (long)ox * xtaps;
-        const float *wy = ywt + (long)oy * ytaps;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int j = 0; j < ny; ++j) {
-            float h[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int i = 0; i < nx; ++i) {
-                const float w = wx[i];
-                float px[4] = {0.f, 0.f, 0.f, 0.f};
-                if (kU8) {
-                    const int xf = x0 + i;
-                    load_rgb(src8, sy, y0 + j, flip ? W - 1 - xf : xf, px);
-                    aug_color(px, p, mean, false);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (c < C) px[c] = src32[(long)(y0 + j) * sy + (long)(x0 + i) * sx + (long)c * sc];
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (c < C) {
-                        const float v = px[c] * w;
-                        h[c] = i == 0 ? v : h[c] + v;
-                    }
-            }
-            const float w = wy[j];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float v = h[c] * w;
-                acc[c] = j == 0 ? v : acc[c] + v;
-            }
-        }
-        float *o = out + oy * stride_y + ox * stride_x;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (c < C_out) o[c * stride_c] = c < C ? acc[c] : 0.f;
     }
-}
+};
 
 __global__ void __launch_bounds__(kThreads)
 boxes_kernel(const float *__restrict__ boxes, const long long *__restrict__ labels, const int *__restrict__ iparams,
@@ -416,20 +259,6 @@ boxes_kernel(const float *__restrict__ boxes, const long long *__restrict__ labe
     if (threadIdx.x == 0) kept[b] = base;
 }
 
-// the tiled form's LDS cap (resize.hip's bound on the region a tile touches), in f32 planes
-void tile_caps(int H, int W, int OH, int OW, int C, int *cap_rows, int *cap_cols, size_t *lds) {
-    const int ytaps = tsod_resize_aa_taps(H, OH), xtaps = tsod_resize_aa_taps(W, OW);
-    const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
-    *cap_rows = (int)ceilf((kTY - 1) * sy) + ytaps + 2;
-    *cap_cols = (int)ceilf((kTX - 1) * sx) + xtaps + 2;
-    *lds = ((size_t)C * *cap_rows * *cap_cols + (size_t)(kTX * xtaps + kTY * ytaps)) * sizeof(float);
-}
-
-int flat_blocks(int OH, int OW) {
-    const long total = (long)OH * OW;
-    return (int)((total + kThreads - 1) / kThreads < 8192 ? (total + kThreads - 1) / kThreads : 8192);
-}
-
 }  // namespace
 
 extern "C" int tsod_augment_gray_mean_partials(const uint8_t *src, int32_t H, int32_t W, int64_t src_row_bytes,
@@ -454,54 +283,11 @@ extern "C" int tsod_augment_resize_u8_f32(const uint8_t *src, int32_t H, int32_t
                  TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(src_row_bytes >= (int64_t)W * 3, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(mean_partials || !(params->flags & TSOD_AUG_CONTRAST), TSOD_ERR_INVALID_ARG);
-    const int ytaps = tsod_resize_aa_taps(H, OH), xtaps = tsod_resize_aa_taps(W, OW);
-    int cap_rows, cap_cols;
-    size_t lds;
-    tile_caps(H, W, OH, OW, 3, &cap_rows, &cap_cols, &lds);
-    if (lds <= kLdsCap) {
-        const int tiles = ((OH + kTY - 1) / kTY) * ((OW + kTX - 1) / kTX);
-        lds = lds > kParts * sizeof(double) ? lds : kParts * sizeof(double);
-        hipLaunchKernelGGL(aug_resize_tile_kernel, dim3(tiles), dim3(kThreads), lds, tsod_stream(stream), src, H, W,
-                           (long)src_row_bytes, *params, mean_partials, flip, yfirst, ycount, ywt, ytaps, xfirst, xcount,
-                           xwt, xtaps, OH, OW, out, (long)stride_y, (long)stride_x, (long)stride_c, C_out, cap_rows,
-                           cap_cols);
-        return tsod_launch_status();
-    }
-    hipLaunchKernelGGL(aug_resize_flat_kernel<true>, dim3(flat_blocks(OH, OW)), dim3(kThreads), 0, tsod_stream(stream),
-                       src, (const float *)nullptr, H, W, 3, (long)src_row_bytes, 3L, 1L, *params, mean_partials, flip,
-                       yfirst, ycount, ywt, ytaps, xfirst, xcount, xwt, xtaps, OH, OW, out, (long)stride_y,
-                       (long)stride_x, (long)stride_c, C_out);
-    return tsod_launch_status();
-}
-
-extern "C" int tsod_resize_bilinear_aa_f32(const float *src, int32_t H, int32_t W, int32_t C, int64_t src_stride_y,
-                                           int64_t src_stride_x, int64_t src_stride_c, const int32_t *yfirst,
-                                           const int32_t *ycount, const float *ywt, const int32_t *xfirst,
-                                           const int32_t *xcount, const float *xwt, int32_t OH, int32_t OW, float *out,
-                                           int64_t stride_y, int64_t stride_x, int64_t stride_c, int32_t C_out,
-                                           tsod_stream_t stream) {
-    TSOD_REQUIRE(src && yfirst && ycount && ywt && xfirst && xcount && xwt && out, TSOD_ERR_INVALID_ARG);
-    TSOD_REQUIRE(H > 0 && W > 0 && OH > 0 && OW > 0 && C >= 1 && C <= 4 && C_out >= C && C_out <= 4, TSOD_ERR_INVALID_ARG);
-    TSOD_REQUIRE(src_stride_y >= 0 && src_stride_x >= 0 && src_stride_c >= 0, TSOD_ERR_INVALID_ARG);
-    const int ytaps = tsod_resize_aa_taps(H, OH), xtaps = tsod_resize_aa_taps(W, OW);
-    int cap_rows, cap_cols;
-    size_t lds;
-    tile_caps(H, W, OH, OW, C, &cap_rows, &cap_cols, &lds);
-    if (lds <= kLdsCap) {
-        const int tiles = ((OH + kTY - 1) / kTY) * ((OW + kTX - 1) / kTX);
-        hipLaunchKernelGGL(f32_resize_tile_kernel, dim3(tiles), dim3(kThreads), lds, tsod_stream(stream), src, H, W, C,
-                           (long)src_stride_y, (long)src_stride_x, (long)src_stride_c, yfirst, ycount, ywt, ytaps, xfirst,
-                           xcount, xwt, xtaps, OH, OW, out, (long)stride_y, (long)stride_x, (long)stride_c, C_out,
-                           cap_rows, cap_cols);
-        return tsod_launch_status();
-    }
-    tsod_photometric none = {};
-    none.white = 1.f;
-    hipLaunchKernelGGL(aug_resize_flat_kernel<false>, dim3(flat_blocks(OH, OW)), dim3(kThreads), 0, tsod_stream(stream),
-                       (const unsigned char *)nullptr, src, H, W, C, (long)src_stride_y, (long)src_stride_x,
-                       (long)src_stride_c, none, (const double *)nullptr, 0, yfirst, ycount, ywt, ytaps, xfirst, xcount,
-                       xwt, xtaps, OH, OW, out, (long)stride_y, (long)stride_x, (long)stride_c, C_out);
-    return tsod_launch_status();
+    AugU8 a;
+    a.src = src, a.H = H, a.W = W, a.pitch = (long)src_row_bytes;
+    a.p = *params, a.mean_partials = mean_partials, a.flip = flip, a.mean = 0.f;
+    return launch_resize(a, H, W, yfirst, ycount, ywt, xfirst, xcount, xwt, OH, OW, 1.0f, out, stride_y, stride_x, stride_c,
+                         C_out, stream);
 }
 
 extern "C" int tsod_augment_boxes_f32(const float *boxes, const int64_t *labels, int32_t B, const int32_t *iparams,

@@ -1033,6 +1033,32 @@ def resize_tables(n_in: int, n_out: int, device):
     return t
 
 
+def _out_tensor(out, shape, dev, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise TsodError(f"{what}: out must be a contiguous f32 {shape} tensor on {dev}")
+    return out
+
+
+def _layout(layout, C, OH, OW):
+    if layout == "nhwc4":
+        return (OH, OW, 4), (4 * OW, 4, 1), 4
+    if layout == "nchw":
+        return (C, OH, OW), (OW, 1, OH * OW), C
+    raise ValueError(layout)
+
+
+def _resize(fn, what: str, src: tuple, H, W, C, OH, OW, mid: tuple, layout, out, dev):
+    """One call of a resize entry point: its source arguments, the two axes' tap tables, OH, OW, ``mid``, the output
+    of ``layout`` with its strides and channel count, the stream."""
+    tables = [ptr(t) for n_in, n_out in ((H, OH), (W, OW)) for t in resize_tables(n_in, n_out, dev)]
+    shape, strides, c_out = _layout(layout, C, OH, OW)
+    out = _out_tensor(out, shape, dev, what)
+    check(fn(*src, *tables, OH, OW, *mid, ptr(out), *strides, c_out, stream_ptr()), what)
+    return out
+
+
 def resize_bilinear_aa(img: torch.Tensor, OH: int, OW: int, layout: str = "nhwc4", mul: float = 1.0, out=None):
     """u8 [H,W,C<=4] CUDA image -> antialiased-bilinear resized f32 image: ``layout="nhwc4"`` -> [OH,OW,4] (extra channels
     zero), ``"nchw"`` -> [C,OH,OW]  (dataset/transform.py:14-17 on the GPU)."""
@@ -1041,23 +1067,8 @@ def resize_bilinear_aa(img: torch.Tensor, OH: int, OW: int, layout: str = "nhwc4
     H, W, C = img.shape
     if not 1 <= C <= 4 or img.stride(2) != 1 or img.stride(1) != C:
         raise TsodError("resize_bilinear_aa: pixels must be interleaved and contiguous along a row")
-    dev = img.device
-    yf, yc, yw = resize_tables(H, OH, dev)
-    xf, xc, xw = resize_tables(W, OW, dev)
-    if layout == "nhwc4":
-        shape, strides, c_out = (OH, OW, 4), (4 * OW, 4, 1), 4
-    elif layout == "nchw":
-        shape, strides, c_out = (C, OH, OW), (OW, 1, OH * OW), C
-    else:
-        raise ValueError(layout)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise TsodError(f"resize_bilinear_aa: out must be a contiguous f32 {shape} tensor on {dev}")
-    check(lib().tsod_resize_bilinear_aa_u8_f32(ptr(img), H, W, C, img.stride(0), ptr(yf), ptr(yc), ptr(yw), ptr(xf), ptr(xc),
-                                               ptr(xw), OH, OW, float(mul), ptr(out), strides[0], strides[1], strides[2],
-                                               c_out, stream_ptr()), "resize_bilinear_aa")
-    return out
+    return _resize(lib().tsod_resize_bilinear_aa_u8_f32, "resize_bilinear_aa", (ptr(img), H, W, C, img.stride(0)), H, W, C,
+                   OH, OW, (float(mul),), layout, out, img.device)
 
 
 # ----------------------------------------------------------------------------- training augmentation
@@ -1089,22 +1100,6 @@ def _rgb_u8(img, what):
     return img.shape[0], img.shape[1]
 
 
-def _out_tensor(out, shape, dev, what):
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise TsodError(f"{what}: out must be a contiguous f32 {shape} tensor on {dev}")
-    return out
-
-
-def _layout(layout, C, OH, OW):
-    if layout == "nhwc4":
-        return (OH, OW, 4), (4 * OW, 4, 1), 4
-    if layout == "nchw":
-        return (C, OH, OW), (OW, 1, OH * OW), C
-    raise ValueError(layout)
-
-
 def augment_gray_mean_partials(img: torch.Tensor, params: _ffi.Photometric, out=None) -> torch.Tensor:
     """u8 [H,W,3] CUDA image -> f64 [TSOD_AUGMENT_MEAN_PARTS] partial sums of contrast's grayscale input (their sum /
     (H*W) is the mean; ``params`` must draw contrast)."""
@@ -1127,14 +1122,9 @@ def augment_resize(img: torch.Tensor, OH: int, OW: int, params: _ffi.Photometric
     dev = img.device
     if (params.flags & _ffi.AUG_CONTRAST) and mean_partials is None:
         raise TsodError("augment_resize: contrast is drawn but mean_partials is missing")
-    yf, yc, yw = resize_tables(H, OH, dev)
-    xf, xc, xw = resize_tables(W, OW, dev)
-    shape, strides, c_out = _layout(layout, 3, OH, OW)
-    out = _out_tensor(out, shape, dev, "augment_resize")
-    check(lib().tsod_augment_resize_u8_f32(ptr(img), H, W, img.stride(0), byref(params), ptr(mean_partials), int(bool(flip)),
-                                           ptr(yf), ptr(yc), ptr(yw), ptr(xf), ptr(xc), ptr(xw), OH, OW, ptr(out),
-                                           strides[0], strides[1], strides[2], c_out, stream_ptr()), "augment_resize")
-    return out
+    return _resize(lib().tsod_augment_resize_u8_f32, "augment_resize",
+                   (ptr(img), H, W, img.stride(0), byref(params), ptr(mean_partials), int(bool(flip))), H, W, 3, OH, OW, (),
+                   layout, out, dev)
 
 
 def resize_bilinear_aa_f32(src: torch.Tensor, OH: int, OW: int, layout: str = "nchw", out=None) -> torch.Tensor:
@@ -1144,15 +1134,9 @@ def resize_bilinear_aa_f32(src: torch.Tensor, OH: int, OW: int, layout: str = "n
     if src.dim() != 3 or not 1 <= src.shape[0] <= 4:
         raise TsodError("resize_bilinear_aa_f32: an f32 [C<=4,H,W] tensor is required")
     C, H, W = src.shape
-    dev = src.device
-    yf, yc, yw = resize_tables(H, OH, dev)
-    xf, xc, xw = resize_tables(W, OW, dev)
-    shape, strides, c_out = _layout(layout, C, OH, OW)
-    out = _out_tensor(out, shape, dev, "resize_bilinear_aa_f32")
-    check(lib().tsod_resize_bilinear_aa_f32(ptr(src), H, W, C, src.stride(1), src.stride(2), src.stride(0), ptr(yf), ptr(yc),
-                                            ptr(yw), ptr(xf), ptr(xc), ptr(xw), OH, OW, ptr(out), strides[0], strides[1],
-                                            strides[2], c_out, stream_ptr()), "resize_bilinear_aa_f32")
-    return out
+    return _resize(lib().tsod_resize_bilinear_aa_f32, "resize_bilinear_aa_f32",
+                   (ptr(src), H, W, C, src.stride(1), src.stride(2), src.stride(0)), H, W, C, OH, OW, (), layout, out,
+                   src.device)
 
 
 def augment_boxes(boxes: torch.Tensor, labels: torch.Tensor, iparams: torch.Tensor, fparams: torch.Tensor):
