@@ -600,6 +600,36 @@ int tsod_roi_align_avg_grad_f32(int32_t B, int32_t Hf, int32_t Wf, int32_t C, co
                                 int32_t d_feat_pitch, int32_t accumulate, void *workspace, size_t workspace_bytes,
                                 tsod_stream_t stream);
 
+/* ---- the HarDNet tail's backward: depthwise 3x3 and the grouped pair 1x1 ---------------------------
+ * NHWC f32 with pixel pitches and channel offsets like the forwards; no float atomics, bit-identical from run to run: the
+ * parameter gradients are per-workgroup partial sums over pixel slices (slice count and in-workgroup tree fixed by the shape),
+ * added in slice order by a second launch.
+ * tsod_dwconv3x3_grad_f32: backward of y = relu?(scale[c] * dwconv3x3(x, w)[c] + shift[c]) (tsod_dwconv3x3_f32's arguments;
+ *   scale / shift NULL = 1 / 0).  dy [N][OH][OW][dy_pitch]; g = dy * [y > 0] with relu (the mask is recomputed from x with the
+ *   forward's tap order), else dy.
+ *     dx [N][H][W][dx_pitch] (NULL: skipped) = scale * sum over the outputs that read the pixel of w[dh][dw] * g, dh then dw
+ *        ascending: a gather by the thread that owns the pixel's channel quad; accumulate = 1 adds to what is there.
+ *     dw [3][3][C] = scale[c] * sum_pixels g * x_tap;  dscale [C] = sum g * dwconv3x3(x, w) (may be NULL; must be NULL when scale
+ *        is NULL);  dshift [C] = sum g.
+ *     dw and dshift NULL together (then dscale NULL and dx not): no parameter gradient is computed - without relu the dx gather is
+ *        the only launch and no workspace is read.
+ *   workspace: tsod_dwconv3x3_grad_workspace_bytes(N, H, W, C, stride, relu_dx) - the partials, and with relu_dx (= relu and a
+ *   non-NULL dx) room for g, which the dx gather reads.  16-byte aligned pointers, C / pitches / offsets multiples of 4.
+ * tsod_gconv1x1_pair_grad_f32: backward of tsod_gconv1x1_pair_f32.  d_out [pixels][d_out_pitch];
+ *   d_in [pixels][d_in_pitch] (columns [0, 2G): d_in[2g + j] = w[g][j] * d_out[g]), dw [G][2] = sum_pixels d_out[g] * in[2g + j],
+ *   dbias [G] = sum_pixels d_out[g]; each of the three may be NULL (skipped).  in / d_in 8-byte aligned with even pitches.
+ *   workspace: tsod_gconv1x1_pair_grad_workspace_bytes(pixels, G). */
+size_t tsod_dwconv3x3_grad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t relu_dx);
+int tsod_dwconv3x3_grad_f32(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t in_pitch, int32_t in_off,
+                            const float *w, const float *scale, const float *shift, int32_t stride, int32_t relu,
+                            const float *dy, int32_t dy_pitch, int32_t dy_off, float *dx, int32_t dx_pitch, int32_t dx_off,
+                            int32_t accumulate, float *dw, float *dscale, float *dshift, void *workspace,
+                            size_t workspace_bytes, tsod_stream_t stream);
+size_t tsod_gconv1x1_pair_grad_workspace_bytes(int64_t pixels, int32_t G);
+int tsod_gconv1x1_pair_grad_f32(const float *in, int64_t pixels, int32_t G, int32_t in_pitch, const float *w,
+                                const float *d_out, int32_t d_out_pitch, float *d_in, int32_t d_in_pitch, float *dw,
+                                float *dbias, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- detection mAP: COCOeval's evaluateImg + accumulate, area range "all", no crowd / ignore flags ------
  * The reference's calculate_metrics (nets/frcnn_training.py:372-565) defines no usable metric; this is the project's own.
  * IoU is tsod_bbox_iou_f32's expression (eps 1e-8, no +1), compared as IoU >= t in f32.  Three steps:

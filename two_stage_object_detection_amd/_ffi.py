@@ -251,6 +251,13 @@ _SIGNATURES = {
     "tsod_roi_align_avg_grad_f32": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                             c_float, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                             c_int32, c_void_p, c_size_t, c_void_p]),
+    "tsod_dwconv3x3_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "tsod_dwconv3x3_grad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                        c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                        c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_gconv1x1_pair_grad_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "tsod_gconv1x1_pair_grad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_eval_match_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "tsod_eval_match_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,

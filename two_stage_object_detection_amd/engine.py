@@ -1160,7 +1160,11 @@ class PlanOwner:
                 raise TsodError("the HIP path implements the inference forward only: call .eval() first")
             return self.build_plan(shape[0], shape[2], shape[3], device)
         # slot: independent buffer sets for forwards in flight concurrently (the packed weights are shared)
-        return self._cached_plan((shape, device, slot), build)
+        return self._cached_plan((shape, device, slot) + tuple(self._plan_variant()), build)
+
+    def _plan_variant(self) -> tuple:
+        """Extra plan-cache key of an owner whose build_plan depends on a mode of the module (HarDNet's train_tail)."""
+        return ()
 
     def _plan_for(self, x, slot: int = 0) -> "Plan":
         _ffi.require_cuda(x, type(self).__name__ + ".forward")

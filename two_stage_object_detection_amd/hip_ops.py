@@ -11,6 +11,7 @@ import threading
 from ctypes import byref, c_int32
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _ffi
 from ._ffi import ACT_NONE, TsodError, check, lib, make_conv_desc, ptr, require_cuda, stream_ptr
@@ -417,8 +418,15 @@ def maxpool3x3s2_nhwc(x: torch.Tensor) -> torch.Tensor:
 
 def dwconv3x3_nhwc(x: torch.Tensor, w33c: torch.Tensor, scale=None, shift=None, stride=1, relu=False, C=None,
                    in_off=0, out=None, out_off=0) -> torch.Tensor:
-    """Depthwise 3x3 pad 1 on channels [in_off, in_off+C) of x [N,H,W,P]; w33c is [3,3,C]."""
+    """Depthwise 3x3 pad 1 on channels [in_off, in_off+C) of x [N,H,W,P]; w33c is [3,3,C].
+
+    Differentiable in x, w33c, scale and shift (``_DWConv3x3``: tsod_dwconv3x3_grad_f32) when grad mode is on, one of them
+    requires grad and the call is on whole tensors (no C / in_off / out / out_off); a call with any of those keeps the plain,
+    non-differentiable path whatever requires grad, as before."""
     require_cuda(x, "dwconv3x3")
+    whole = C is None and not in_off and out is None and not out_off and x.shape[3] == w33c.shape[2]
+    if whole and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w33c, scale, shift)):
+        return _DWConv3x3.apply(x, w33c, scale, shift, int(stride), bool(relu))
     N, H, W, P = x.shape
     C = w33c.shape[2] if C is None else C
     OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -441,8 +449,105 @@ def gconv3x3_nhwc(x: torch.Tensor, w_packed: torch.Tensor, groups: int, scale=No
     return out
 
 
+def dwconv3x3_grad(x, w33c, scale, shift, stride, relu, dy, *, want_dx=True, want_params=True, dx=None, accumulate=False,
+                   in_off=0):
+    """The backward of ``dwconv3x3_nhwc`` (tsod_dwconv3x3_grad_f32) -> (dx or None, dw [3,3,C], dscale [C] or None, dshift [C]).
+    x [N,H,W,P] (channels [in_off, in_off+C)), dy [N,OH,OW,C] contiguous.  ``dx`` [N,H,W,C]: written, or added to with
+    ``accumulate``; allocated when ``want_dx`` and none is given.  ``want_params`` False: dx only (dw, dscale, dshift None;
+    without a ReLU that is the gather launch alone)."""
+    require_cuda(x, "dwconv3x3_grad")
+    N, H, W, P = x.shape
+    C = w33c.shape[2]
+    dy = dy.contiguous()
+    dev = x.device
+    if dx is None and want_dx:
+        dx, accumulate = torch.empty((N, H, W, C), dtype=torch.float32, device=dev), False
+    dw = torch.empty((3, 3, C), dtype=torch.float32, device=dev) if want_params else None
+    dscale = torch.empty(C, dtype=torch.float32, device=dev) if want_params and scale is not None else None
+    dshift = torch.empty(C, dtype=torch.float32, device=dev) if want_params else None
+    L = lib()
+    ws_bytes = L.tsod_dwconv3x3_grad_workspace_bytes(N, H, W, C, int(stride), 1 if relu and dx is not None else 0)
+    ws = ARENA.get(dev, ws_bytes)
+    check(L.tsod_dwconv3x3_grad_f32(ptr(x), N, H, W, C, P, int(in_off), ptr(w33c), ptr(scale), ptr(shift), int(stride),
+                                    1 if relu else 0, ptr(dy), dy.shape[3], 0, ptr(dx), 0 if dx is None else dx.shape[3], 0,
+                                    1 if accumulate else 0, ptr(dw), ptr(dscale), ptr(dshift), ptr(ws), ws_bytes, stream_ptr()),
+          "dwconv3x3_grad")
+    return dx, dw, dscale, dshift
+
+
+class _DWConv3x3(torch.autograd.Function):
+    """``dwconv3x3_nhwc`` as an autograd node: forward tsod_dwconv3x3_f32, backward tsod_dwconv3x3_grad_f32 (one call gives
+    all four gradients; d x is skipped when not asked for, the others are dropped)."""
+
+    @staticmethod
+    def forward(ctx, x, w33c, scale, shift, stride, relu):
+        xd, wd = x.detach().contiguous(), w33c.detach().contiguous()
+        sc = None if scale is None else scale.detach().contiguous()
+        sh = None if shift is None else shift.detach().contiguous()
+        ctx.save_for_backward(xd, wd, sc, sh)
+        ctx.stride, ctx.relu = stride, relu
+        with torch.no_grad():
+            return dwconv3x3_nhwc(xd, wd, sc, sh, stride, relu)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, w, sc, sh = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dw, dscale, dshift = dwconv3x3_grad(x, w, sc, sh, ctx.stride, ctx.relu, gy, want_dx=need[0],
+                                                want_params=any(need[1:4]))
+        return (dx if need[0] else None, dw if need[1] else None, dscale if need[2] else None,
+                dshift if need[3] and sh is not None else None, None, None)
+
+
+def gconv1x1_pair_grad(x, w_g2, d_out, *, want_dx=True, want_dw=True, want_dbias=True):
+    """The backward of ``gconv1x1_pair_nhwc`` (tsod_gconv1x1_pair_grad_f32) -> (d x [..., 2G], dw [G,2], dbias [G]; None where
+    not wanted).  x [..., P] with P >= 2G, d_out [..., G] contiguous."""
+    require_cuda(x, "gconv1x1_pair_grad")
+    G, P = w_g2.shape[0], x.shape[-1]
+    pixels = x.numel() // P
+    d_out = d_out.contiguous()
+    dev = x.device
+    dx = torch.empty(tuple(x.shape[:-1]) + (2 * G,), dtype=torch.float32, device=dev) if want_dx else None
+    dw = torch.empty((G, 2), dtype=torch.float32, device=dev) if want_dw else None
+    db = torch.empty(G, dtype=torch.float32, device=dev) if want_dbias else None
+    L = lib()
+    ws_bytes = L.tsod_gconv1x1_pair_grad_workspace_bytes(pixels, G)
+    ws = ARENA.get(dev, ws_bytes)
+    check(L.tsod_gconv1x1_pair_grad_f32(ptr(x), pixels, G, P, ptr(w_g2), ptr(d_out), G, ptr(dx), 2 * G, ptr(dw), ptr(db), ptr(ws),
+                                        ws_bytes, stream_ptr()), "gconv1x1_pair_grad")
+    return dx, dw, db
+
+
+class _GConv1x1Pair(torch.autograd.Function):
+    """``gconv1x1_pair_nhwc`` as an autograd node (tsod_gconv1x1_pair_f32 / tsod_gconv1x1_pair_grad_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, w_g2, bias):
+        xd, wd = x.detach().contiguous(), w_g2.detach().contiguous()
+        bd = None if bias is None else bias.detach().contiguous()
+        ctx.save_for_backward(xd, wd)
+        ctx.has_bias = bias is not None
+        with torch.no_grad():
+            return gconv1x1_pair_nhwc(xd, wd, bd)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dw, db = gconv1x1_pair_grad(x, w, gy, want_dx=need[0], want_dw=need[1], want_dbias=need[2] and ctx.has_bias)
+        return dx, dw, db
+
+
 def gconv1x1_pair_nhwc(x: torch.Tensor, w_g2: torch.Tensor, bias=None) -> torch.Tensor:
+    """nn.Conv2d(2G, G, 1, groups=G) on NHWC x [N,H,W,P >= 2G]; w_g2 is [G,2].  Differentiable in x, w_g2 and bias
+    (``_GConv1x1Pair``) when grad mode is on, one of them requires grad and x has exactly 2G channels (a wider x keeps the
+    plain, non-differentiable path, as before)."""
     require_cuda(x, "gconv1x1_pair")
+    if x.shape[3] == 2 * w_g2.shape[0] and torch.is_grad_enabled() and \
+            any(t is not None and t.requires_grad for t in (x, w_g2, bias)):
+        return _GConv1x1Pair.apply(x, w_g2, bias)
     N, H, W, P = x.shape
     G = w_g2.shape[0]
     out = torch.empty((N, H, W, G), dtype=torch.float32, device=x.device)

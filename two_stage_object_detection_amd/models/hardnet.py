@@ -19,10 +19,11 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .. import hip_ops
 from .._ffi import ACT_NONE, ACT_RELU6, TsodError, lib, ptr, require_cuda
-from ..engine import PackedConv, Plan, PlanOwner, fold_bn
+from ..engine import PackedConv, Plan, PlanOwner, fold_bn, stage_input
 
 
 def _pad4(c: int) -> int:
@@ -159,7 +160,40 @@ class _RawConv:
         return H, W
 
 
+class _TailGrads(torch.autograd.Function):
+    """The feature map of a ``train_tail`` forward as an autograd node over the six tail tensors.
+
+    forward(saved, *params) hands out the map the plan computed; backward runs tsod_gconv1x1_pair_grad_f32 and
+    tsod_dwconv3x3_grad_f32 twice on the node's OWN copies of the three tail inputs and of the packed weights of its forward,
+    and returns the six gradients in torch's parameter layouts (autograd adds them into ``.grad``)."""
+
+    @staticmethod
+    def forward(ctx, saved, *params):
+        ctx.saved = saved
+        return saved.pop("out")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        sv, need = ctx.saved, ctx.needs_input_grad[1:]
+        g = hip_ops.nchw_to_nhwc(gy) if sv["nchw"] else gy.contiguous()
+        (x0, off0), (a, _), (b, _) = sv["inputs"]
+        (w1, _, sh1, _), (w2, _, sh2, _), (wg, bias) = sv["packs"]
+        d_b, d_wg, d_bias = hip_ops.gconv1x1_pair_grad(b, wg, g, want_dw=need[4], want_dbias=need[5])
+        d_a, d_w2, _, d_sh2 = hip_ops.dwconv3x3_grad(a, w2, None, sh2, 2, False, d_b)
+        _, d_w1, _, d_sh1 = hip_ops.dwconv3x3_grad(x0, w1, None, sh1, 2, True, d_a, want_dx=False, in_off=off0)
+        C = sv["C"]
+
+        def conv_weight(d):                                   # [3][3][C_pad] -> torch's [C,1,3,3]
+            return d[:, :, :C].reshape(9, C).t().reshape(C, 1, 3, 3)
+        grads = (conv_weight(d_w1), d_sh1[:C], conv_weight(d_w2), d_sh2[:C],
+                 None if d_wg is None else d_wg.view(-1, 2, 1, 1), d_bias)
+        return (None,) + tuple(d if n else None for d, n in zip(grads, need))
+
+
 class HarDNetFeatureExtraction(PlanOwner, nn.Module):
+    _train_tail = False          # train_tail(): the last four modules of ``base`` are differentiable (default off)
+
     def __init__(self, depth_wise=True, arch=39):
         super().__init__()
         cfg = _ARCH[arch if arch in (39, 85) else 68]          # any other value = HarDNet-68, like the reference
@@ -191,6 +225,86 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         self._init_plan_owner()
         self.out_channels = 512
 
+    # -- the trainable tail ---------------------------------------------
+    def _tail_indices(self):
+        """Indices in ``base`` of the tail's three layers: dw3x3 s2 (+ ReLU), dw3x3 s2, grouped pair 1x1."""
+        n = len(self.base)
+        return n - 4, n - 2, n - 1
+
+    def tail_parameters(self):
+        """The six tail tensors, in the order of ``base``: two depthwise (weight, bias) pairs, the pair conv's weight, bias."""
+        return [p for i in self._tail_indices() for p in (self.base[i].weight, self.base[i].bias)]
+
+    def train_tail(self, enabled: bool = True):
+        """Make the last four modules of ``base`` (the two depthwise 3x3 stride-2 convs, the ReLU between them and the grouped
+        1x1) differentiable: while on, with grad mode enabled and the module in eval(), the feature map that ``forward`` /
+        ``forward_nhwc`` return carries an autograd node whose backward (HIP kernels, csrc/dw_grads.hip) gives the gradients
+        of the six tail tensors.  The forward's launches and values are unchanged; nothing is returned for the input or the
+        body's parameters.  In-place updates of the six tensors (an optimizer step) are noticed through their ``_version``
+        and the tail's packed weights refreshed before the next forward of ANY kind (grad mode on or off, ``train_tail``
+        switched off again included), from the first ``train_tail(True)`` on.
+
+        Memory: a ``train_tail`` forward keeps its three tail inputs out of the plan's buffer pool and the node copies
+        them - the first is the trunk's stride-4 output, N x H/4 x W/4 x 1024 floats (92 MB at 600x600 batch 1, 2.2 GB at
+        800x1333 batch 8), held until the node is freed; the plan for grad mode off is a second plan of the same shape."""
+        self._train_tail = bool(enabled)
+        return self
+
+    def _tail_active(self) -> bool:
+        return self._train_tail and torch.is_grad_enabled()
+
+    def _plan_variant(self):
+        return ("train_tail",) if self._tail_active() else ()
+
+    def _refresh_tail_packs(self):
+        """Rewrite the tail's packed weights (and only those) in place when one of the six tensors changed since they were
+        last known to match: plans and graphs keep their pointers; an autograd node of an earlier forward holds copies."""
+        if not self._train_tail and "_tail_versions" not in self.__dict__:
+            return                                               # train_tail was never on: today's contract (invalidate_packed)
+        versions = tuple(p._version for p in self.tail_parameters())
+        if versions == self.__dict__.get("_tail_versions"):
+            return
+        i1, i2, ip = self._tail_indices()
+        for (name, device), pack in list(self._packed_cache.items()):
+            if name in (f"base.{i1}", f"base.{i2}"):
+                new = self._dw_params(self.base[i1 if name == f"base.{i1}" else i2], None, device)
+            elif name == f"base.{ip}":
+                new = self._pair_params(self.base[ip], device)
+            else:
+                continue
+            with torch.inference_mode():                      # (the packs may have been made under inference mode)
+                for old, t in zip(pack, new):
+                    if isinstance(old, torch.Tensor):
+                        old.copy_(t)
+        self.__dict__["_tail_versions"] = versions
+
+    def _forward_tail(self, x, slot, nchw):
+        if self.training:
+            raise TsodError("the HIP path implements the inference forward only: call .eval() first")
+        self._refresh_tail_packs()
+        plan = self._plan_for(x, slot)
+        stage_input(plan, x)
+        plan.run()
+        self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
+        out = plan.output_nhwc
+        saved = dict(out=hip_ops.nhwc_to_nchw(out) if nchw else out.clone(), nchw=nchw,
+                     inputs=[(t.clone(), off) for t, off in plan.tail_inputs],
+                     packs=[tuple(t.clone() if isinstance(t, torch.Tensor) else t for t in pack) for pack in plan.tail_packs],
+                     C=self.base[self._tail_indices()[0]].weight.shape[0])
+        return _TailGrads.apply(saved, *self.tail_parameters())
+
+    def forward_nhwc(self, x, slot: int = 0):
+        if self._tail_active():
+            return self._forward_tail(x, slot, nchw=False)
+        self._refresh_tail_packs()
+        return super().forward_nhwc(x, slot)
+
+    @staticmethod
+    def _pair_params(m: nn.Conv2d, device):
+        G = m.out_channels
+        return (m.weight.detach().float().view(G, 2).contiguous().to(device),
+                None if m.bias is None else m.bias.detach().float().to(device))
+
     # -- plan (cache, invalidation, lookup: engine.PlanOwner) -----------------------------------
     @staticmethod
     def _dw_params(conv: nn.Conv2d, bn, device):
@@ -217,6 +331,10 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         mods = list(self.base)
         x4 = plan.pool.alloc((N, H, W, 4))
         plan.input_nhwc = x4
+        # train_tail: the tail's three inputs stay out of the pool (the autograd node copies them after the run) and the
+        # packs are listed for it; the launches are the same
+        tail = self._tail_active()
+        plan.tail_inputs, plan.tail_packs = [], []
 
         def dest_for(next_idx, C, h, w):
             """Where the tensor feeding module ``next_idx`` must be written: slice 0 of the next
@@ -232,6 +350,7 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
             n, h, w_, P = src.shape
             plan.call(L.tsod_dwconv3x3_amax_f32, ptr(src), n, h, w_, cp, P, src_off, ptr(w33), ptr(scale), ptr(shift), stride,
                       1 if relu else 0, ptr(dst), dst.shape[3], dst_off, plan.amax_ptr(dst) or None, keep=(src, dst, w33, scale, shift))
+            return w33, scale, shift, cp
 
         # --- stem: 3x3 s2 conv (3 -> c0, input padded to 4 channels), 1x1 conv, dw3x3 s2
         m0, m1, m2 = mods[0], mods[1], mods[2]
@@ -301,20 +420,26 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 s = m.stride[0]
                 nh, nw = (h - 1) // s + 1, (w - 1) // s + 1
                 dst = plan.pool.alloc((N, nh, nw, _pad4(cur_C)))
-                emit_dw(cur, cur_off, cur_C, m, None, s, relu, dst, 0, f"base.{i}")
-                plan.pool.release(cur)
+                pack = emit_dw(cur, cur_off, cur_C, m, None, s, relu, dst, 0, f"base.{i}")
+                if tail:
+                    plan.tail_inputs.append((cur, cur_off))
+                    plan.tail_packs.append(pack)
+                else:
+                    plan.pool.release(cur)
                 cur, cur_off, h, w = dst, 0, nh, nw
                 i += 2 if relu else 1
             elif isinstance(m, nn.Conv2d) and m.kernel_size == (1, 1) and m.groups == m.out_channels \
                     and m.in_channels == 2 * m.out_channels:
                 G = m.out_channels
-                wg, bias = plan.packed(f"base.{i}", lambda m=m: (
-                    m.weight.detach().float().view(G, 2).contiguous().to(device),
-                    None if m.bias is None else m.bias.detach().float().to(device)))
+                wg, bias = plan.packed(f"base.{i}", lambda m=m: self._pair_params(m, device))
                 dst = plan.pool.alloc((N, h, w, G))
                 plan.call(L.tsod_gconv1x1_pair_amax_f32, ptr(cur), N * h * w, G, cur.shape[3], ptr(wg), ptr(bias), ptr(dst), G,
                           plan.amax_ptr(dst) or None, keep=(cur, dst, wg, bias))
-                plan.pool.release(cur)
+                if tail:
+                    plan.tail_inputs.append((cur, cur_off))
+                    plan.tail_packs.append((wg, bias))
+                else:
+                    plan.pool.release(cur)
                 cur, cur_off, cur_C = dst, 0, G
                 i += 1
             else:
@@ -324,6 +449,8 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         return plan.finalize()
 
     def forward(self, x):
+        if self._tail_active():
+            return self._forward_tail(x, 0, nchw=True)
         return hip_ops.nhwc_to_nchw(self.forward_nhwc(x))
 
 

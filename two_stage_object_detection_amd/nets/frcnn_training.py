@@ -198,15 +198,28 @@ class FasterRCNNTrainer(nn.Module):
       * in-place updates of the eight head parameters (an optimizer step) are detected through their ``_version`` and the
         RPN's and head's packed weight images are rebuilt before the next forward.
 
-    Not provided: the HIP backbone's own backward and train-mode BatchNorm (``head_grads`` fine-tunes the heads on a frozen
-    backbone; ``features=`` trains a backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
+    ``backbone_grads="tail"`` (keyword-only, HarDNet backbones; default None = everything above): with ``features=None`` and
+    grad mode on, ``forward`` switches ``feat_extra.train_tail`` on, takes the feature map with the tail's autograd node and
+    continues on the ``features=`` path, so ``losses[-1].backward()`` also fills ``.grad`` of the six tail tensors
+    (``feat_extra.tail_parameters()``: the two depthwise 3x3 stride-2 convs and the grouped 1x1 the reference adds on top of
+    HarDNet, which no pretrained checkpoint holds) - the backward of tsod_gconv1x1_pair_f32 and tsod_dwconv3x3_f32 on HIP
+    (DESIGN.md section 4.17).  The frozen-backbone check then applies to every backbone parameter except those six.
+
+    Not provided: the backward of the HIP backbone below its tail and train-mode BatchNorm (``head_grads`` fine-tunes the heads
+    on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail; ``features=`` trains a backbone that has autograd
+    of its own); gradients w.r.t. RoI coordinates; graph capture
     and tuning (the forward runs whatever plan the backbone holds).  ``eval_fn`` / ``calculate_metrics``: see there."""
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
-                 backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False):
+                 backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False, backbone_grads=None):
         super().__init__()
         if head_img_size not in ("chw", "hw"):
             raise ValueError(f"head_img_size must be 'chw' (the reference's) or 'hw', got {head_img_size!r}")
+        if backbone_grads not in (None, "tail"):
+            raise ValueError(f"backbone_grads must be None or 'tail', got {backbone_grads!r}")
+        if backbone_grads == "tail" and not str(backbone).startswith("hardnet"):
+            raise ValueError(f"backbone_grads='tail' trains the HarDNet tail (the last four modules of feat_extra.base); "
+                             f"backbone {backbone!r} has none")
         self.feat_extra, feat_ch, native_stride = _make_extractor(backbone)
         self.feat_stride = native_stride if (feat_stride == 16 and native_stride != 16) else feat_stride
         self.rpn_sigma = 1
@@ -223,6 +236,7 @@ class FasterRCNNTrainer(nn.Module):
         self.backbone = backbone
         self.head_img_size = head_img_size
         self.head_grads = bool(head_grads)
+        self.backbone_grads = backbone_grads
         self.__dict__["_uid"] = next(_UID)          # scratch ownership, as FasterRCNN's
         self.__dict__["_head_versions"] = None
 
@@ -278,14 +292,24 @@ class FasterRCNNTrainer(nn.Module):
         head_size = img_size if self.head_img_size == "chw" else shape[2:]
         n_sample = self.proposal_target_creator.n_sample
         grads = self.head_grads and torch.is_grad_enabled()
-        feat_grad = features is not None and torch.is_grad_enabled() and features.requires_grad
-        if grads and features is None:
+        tail = self.backbone_grads == "tail" and features is None and torch.is_grad_enabled()
+        if tail:
+            ours = {id(p) for p in self.feat_extra.tail_parameters()}
+            frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
+            if frozen:
+                raise TsodError(f"FasterRCNNTrainer(backbone_grads='tail') reaches the six tail tensors of the backbone only "
+                                f"(feat_extra.tail_parameters()); every other backbone parameter must be frozen, but "
+                                f"feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad")
+        elif grads and features is None:
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad]
             if frozen:
                 raise TsodError(f"FasterRCNNTrainer(head_grads=True) computes the head parameters' gradients on a frozen "
                                 f"backbone, but feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad: call "
                                 "trainer.feat_extra.requires_grad_(False)")
         self._refresh_packs()
+        if tail:                     # the map with the tail's autograd node; from here on the features= path
+            features = self.feat_extra.train_tail(True)(x)
+        feat_grad = features is not None and torch.is_grad_enabled() and features.requires_grad
         with hip_ops.ARENA.scope((self._uid, 0)):
             if features is None:
                 feat = self.feat_extra.forward_nhwc(x, 0)
