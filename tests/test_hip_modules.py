@@ -578,6 +578,60 @@ def test_in_flight_detector_blames_the_request_at_fault(dev):
     assert mirror is not None and mirror[0].is_pinned() and int(mirror[0].abs().sum()) == 0
 
 
+@pytest.mark.parametrize("backbone,shape", [("resnet50", (1, 3, 160, 224)), ("hardnet39", (1, 3, 96, 128))])
+def test_plans_are_built_on_their_owners_range_word_and_exponents(dev, backbone, shape):
+    """A plan is wired when it is BUILT, nothing is patched in afterwards: straight after ``_plan_for`` (no forward) it carries its
+    slot, the owner's ONE exponent table and the owner's range word of that slot; every fp16x2 conv descriptor and every
+    one-launch descriptor points at that word; every conv is bound to the two-source entry, the second source null exactly where
+    the descriptor has none; and an exponent put into the owner's table shows up in the descriptors of a REBUILT plan."""
+    from two_stage_object_detection_amd import _ffi
+    from two_stage_object_detection_amd.engine import FP16X2_A_SCALE_EXP, FusedStep
+    if backbone == "resnet50":
+        from two_stage_object_detection_amd.models.resnet import resnet50
+        owner = resnet50(include_top=False)
+    else:
+        from two_stage_object_detection_amd.models.hardnet import HarDNetFeatureExtraction
+        owner = HarDNetFeatureExtraction(depth_wise=True, arch=39)
+    owner = owner.to(dev).eval()
+    owner.set_conv_precision("fp16x2")
+    if backbone == "resnet50":
+        owner.set_fuse_bottleneck(True, projection=True)
+        owner.set_fuse_stem(True)
+    x = _img(shape).to(dev)
+    dual = _ffi.lib().tsod_conv2d_dual_f32
+
+    def wired(plan, slot):
+        assert plan.slot == slot
+        assert plan.a_exps is owner.__dict__["_a_exps"]
+        assert plan.range_flag.data_ptr() == owner._range_word(dev, slot).data_ptr()
+        assert plan.conv_steps and all(int(st.desc.precision) == _ffi.PREC_FP16X2 for st in plan.conv_steps)
+        for st in plan.gemm_steps:
+            if isinstance(st, FusedStep) or int(st.desc.precision) == _ffi.PREC_FP16X2:
+                assert st.desc.range_flag == plan.range_flag.data_ptr(), st.name
+        for st in plan.conv_steps:
+            assert st.fn is dual, st.name
+            assert (not st.args[2]) == (st.desc.c2 == 0), st.name               # in2 of tsod_conv2d_dual_f32(desc, in, in2, ...)
+
+    for slot in (0, 3):
+        wired(owner._plan_for(x, slot), slot)
+    plan = owner._plan_for(x, 0)
+    assert owner._range_word(dev, 0).data_ptr() != owner._range_word(dev, 3).data_ptr()
+    if backbone == "resnet50":                                                   # both kinds of conv step, all three one-launch steps
+        assert {st.desc.c2 == 0 for st in plan.conv_steps} == {True, False}
+        assert plan.stem_step is not None and len(plan.fused_steps) == 4
+    names = [plan.conv_steps[1].name] + [st.name for st in plan.fused_steps if st.x is not None][:1]
+    for name in names:
+        owner._a_exps[name] = 2
+    owner.drop_plan()
+    for slot in (0, 3):
+        plan = owner._plan_for(x, slot)
+        wired(plan, slot)
+        for st in plan.gemm_steps:
+            if hasattr(st.desc, "a_scale_exp"):                                  # (the stem has none: its pixel scale is each tile's own)
+                assert int(st.desc.a_scale_exp) == (2 if st.name in names else FP16X2_A_SCALE_EXP), st.name
+    owner.raise_if_error()                                                       # (nothing was launched: the words are clean)
+
+
 @pytest.mark.parametrize("backbone", ["resnet50", "hardnet39"])
 def test_images_too_small_for_300_proposals_raise_like_the_reference(dev, synth, backbone):
     """A 32x32 / 64x96 image has fewer anchors than n_post: the reference's pad (nets/rpn.py:65-69) raises IndexError,

@@ -364,3 +364,32 @@ def make_conv_desc(*, N, H, W, in_pitch, segs, Cout, out_pitch, out_off=0, KH=1,
     if src2 is not None:
         d.c2, d.in2_pitch, d.in2_off, d.stride2, d.H2, d.W2 = (int(v) for v in src2)
     return d
+
+
+def make_bottleneck_desc(*, N, H, W, Cin, in_pitch, Cout, out_pitch, slope, w_exps, projection=False, Cmid=64,
+                         a_scale_exp=4, range_flag=None, amax_in=None, amax_out=None) -> BottleneckDesc:
+    """The descriptor of tsod_bottleneck_fp16x2; ``range_flag`` / ``amax_*`` are raw device pointers (0 / None: none)."""
+    d = BottleneckDesc()
+    d.N, d.H, d.W, d.Cin, d.in_pitch, d.Cmid, d.Cout, d.out_pitch = N, H, W, Cin, in_pitch, Cmid, Cout, out_pitch
+    d.projection = 1 if projection else 0
+    d.slope = float(slope)
+    for k in range(3):
+        d.w_exp[k] = int(w_exps[k])
+    d.a_scale_exp = int(a_scale_exp)
+    d.range_flag, d.amax_in, d.amax_out = range_flag or None, amax_in or None, amax_out or None
+    return d
+
+
+def stem_out_hw(H, W):
+    """(oh, ow, ph, pw): the map after ResNet's 7x7/2 conv (pad 3) and after its 3x3/2 max pool (pad 1)."""
+    oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return oh, ow, (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
+
+
+def make_stem_desc(*, N, H, W, in_layout, out_pitch, slope, w_exp, range_flag=None, amax_out=None) -> StemDesc:
+    """The descriptor of tsod_stem_fp16x2; ``range_flag`` / ``amax_out`` are raw device pointers (0 / None: none)."""
+    d = StemDesc()
+    d.N, d.H, d.W, d.in_layout, d.out_pitch = N, H, W, in_layout, out_pitch
+    d.slope, d.w_exp = float(slope), int(w_exp)
+    d.range_flag, d.amax_out = range_flag or None, amax_out or None
+    return d

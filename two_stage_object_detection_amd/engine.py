@@ -10,6 +10,7 @@ Data layout in HBM: every activation is NHWC f32, channel pitch a multiple of 4,
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 from ctypes import byref, c_int32
 from typing import Callable, Sequence
@@ -109,8 +110,7 @@ class FusedBottleneckWeights:
         self.stream, self.w_exps = hip_ops.pack_bottleneck_wstream(w1, w2, w3, projection=self.projection)
         self.bn = torch.cat(bn).to(device)
         self.slope = prelu_slope(blk.relu)
-        if not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(self.stream.device).synchronize()
+        _publish(self.stream)
 
 
 class FusedStemWeights:
@@ -122,8 +122,7 @@ class FusedStemWeights:
         self.wfrag, self.w_exp = hip_ops.pack_stem_wfrag(conv.weight.detach().float().to(device))
         self.bn = torch.cat(fold_bn(bn)).to(device)
         self.slope = prelu_slope(relu)
-        if not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(self.wfrag.device).synchronize()
+        _publish(self.wfrag)
 
 
 class FusedStep:
@@ -140,18 +139,23 @@ def step_precision(st) -> int:
     return int(st.precision) if isinstance(st, FusedStep) else int(st.desc.precision)
 
 
+def _publish(t: torch.Tensor) -> torch.Tensor:
+    """Wait until a freshly packed weight image is complete, BEFORE it is stored where others find it: the image is shared by
+    every plan, in-flight slot and stream of its owner, so a consumer on ANOTHER stream must never see it half written (one host
+    wait per image, at build time; illegal - and never needed, the warm-up forwards of a capture run first - while the stream
+    is being captured)."""
+    if not torch.cuda.is_current_stream_capturing():
+        torch.cuda.current_stream(t.device).synchronize()
+    return t
+
+
 def weights_bf16x3(pc) -> torch.Tensor:
     """The pre-split bf16x3 image of a packed layer's weights (PackedConv or a compatible holder), made on first use and
     kept beside the f32 weights."""
     w3 = getattr(pc, "w3", None)
     if w3 is None:
         from . import hip_ops
-        w3 = pc.w3 = hip_ops.pack_conv_weight_bf16x3(pc.w)
-        # the image is shared by every plan, in-flight slot and stream of the owner: it must be complete before a consumer on
-        # ANOTHER stream can see the attribute (one host wait per layer, at build time; illegal - and never needed, the
-        # warm-up forwards of a capture run first - while the stream is being captured)
-        if not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(w3.device).synchronize()
+        w3 = pc.w3 = _publish(hip_ops.pack_conv_weight_bf16x3(pc.w))
     return w3
 
 
@@ -168,7 +172,6 @@ def new_range_flag(device) -> torch.Tensor:
 def fp16x2_activation_exp(absmax: float, headroom_bits: int = 4) -> int:
     """The fp16x2 activation exponent e for a tensor of that abs-max: 2^e * absmax <= 65504 / 2^headroom_bits, clamped to
     [-24, 8] (8 for an all-zero or non-finite measurement: the guard decides at run time)."""
-    import math
     if absmax == 0.0 or not math.isfinite(absmax):
         return 8
     return max(-24, min(8, int(math.floor(math.log2(65504.0 / (absmax * (1 << headroom_bits)))))))
@@ -181,9 +184,7 @@ def weights_fp16x2(pc):
     if hit is None:
         from . import hip_ops
         e = hip_ops.fp16x2_weight_scale_exp(pc.w)
-        hit = pc.w2 = (hip_ops.pack_conv_weight_fp16x2(pc.w, e), e)
-        if not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(pc.w.device).synchronize()
+        hit = pc.w2 = (_publish(hip_ops.pack_conv_weight_fp16x2(pc.w, e)), e)
     return hit
 
 
@@ -235,27 +236,38 @@ def _merge_adjacent(segs):
 
 # --------------------------------------------------------------------------- plan
 class ConvStep:
-    __slots__ = ("desc", "args", "name", "flops", "ws_bytes", "pc", "fn", "w_index", "ws_index", "range_flag", "x", "x2", "exps")
+    """One tsod_conv2d_dual_f32 launch of a plan: args = [desc, in, in2 (null: one source), w, scale, shift, residual, out,
+    workspace, workspace bytes]."""
+    __slots__ = ("desc", "args", "name", "flops", "ws_bytes", "pc", "fn", "plan", "x", "x2")
+    W_ARG, WS_ARG = 3, 8                     # positions of the weight image and of (workspace, its size) in ``args``
 
     def choose(self, tile: int, split_k: int, precision: int):
-        """Pin (tile, K-slice schedule, arithmetic); the weight argument follows the arithmetic (f32 or pre-split bf16x3)."""
+        """Pin (tile, K-slice schedule, arithmetic); the weight argument follows the arithmetic (f32 or a pre-split image)."""
         d = self.desc
         d.tile, d.split_k, d.precision = int(tile), int(split_k), int(precision)
         if precision == _ffi.PREC_FP16X2:
             w2, e = weights_fp16x2(self.pc)
-            d.a_scale_exp, d.w_scale_exp = int(self.exps.get(self.name, FP16X2_A_SCALE_EXP)), int(e)
-            d.range_flag = ptr(self.range_flag)                  # the owner's word: PlanOwner.raise_if_error reads it
-            self.args[self.w_index] = ptr(w2)
+            d.a_scale_exp, d.w_scale_exp = int(self.plan.a_exps.get(self.name, FP16X2_A_SCALE_EXP)), int(e)
+            d.range_flag = ptr(self.plan.range_flag)             # the owner's word: PlanOwner.raise_if_error reads it
+            self.args[self.W_ARG] = ptr(w2)
         else:
-            self.args[self.w_index] = ptr(weights_bf16x3(self.pc)) if precision == _ffi.PREC_BF16X3 else ptr(self.pc.w)
+            self.args[self.W_ARG] = ptr(weights_bf16x3(self.pc)) if precision == _ffi.PREC_BF16X3 else ptr(self.pc.w)
+
+    def args_on(self, ws: torch.Tensor) -> list:
+        """The step's arguments as they stand now, with ``ws`` as the K-slice workspace (timing on a buffer that is not the plan's)."""
+        a = list(self.args)
+        a[self.WS_ARG], a[self.WS_ARG + 1] = ptr(ws), ws.numel()
+        return a
 
 
 class Plan:
-    def __init__(self, device, packed: dict | None = None):
+    def __init__(self, device, packed: dict | None = None, *, range_flag=None, a_exps: dict | None = None, slot: int = 0,
+                 on_calibrated=None, precision: int = 0):
         self.device = torch.device(device)
         self.pool = BufferPool(self.device)
         self._packed = packed if packed is not None else {}   # the owner's packed-weight cache (shared by all its plans)
-        self.precision = 0                   # default arithmetic of the plan's dense convs (_ffi.PREC_F32 / PREC_BF16X3)
+        self.precision = int(precision)      # default arithmetic of the plan's dense convs (_ffi.PREC_*)
+        self.slot = int(slot)                # the in-flight slot the plan serves (PlanOwner: whose range word it reports into)
         self._retired: list = []             # outgrown workspaces: graphs captured earlier still hold their pointers
         self.steps: list[list] = []          # [cfunc, [args...]]
         self.conv_steps: list[ConvStep] = []
@@ -264,16 +276,16 @@ class Plan:
         self.stem_step = None                # the one-launch stem (tsod_stem_fp16x2), whose input pointer stage_input binds per forward
         self._bound_input = None
         self.keep: list = []                 # keeps descriptors / tensors alive
-        self._ws_slots: list[tuple[list, int, int, int]] = []   # (args, ptr index, size index, bytes)
         self.workspace: torch.Tensor | None = None
         self.graph = None
         # fp16x2 layers OR 1 into this word when a launch ends with non-finite accumulators (include/tsod.h: range_flag);
-        # a PlanOwner hands its plans one word per (device, in-flight slot) out of a tensor of its own (see _cached_plan): the word
-        # survives plan eviction, and checking all of an owner's words costs one small read per device
-        self.range_flag = new_range_flag(self.device)
-        self.a_exps: dict = {}               # layer name -> fp16x2 activation exponent (calibrate_fp16x2); the owner shares ONE dict among its plans
+        # a PlanOwner hands its plans one word per (device, in-flight slot) out of a tensor of its own (PlanOwner._new_plan): the
+        # word survives plan eviction, and checking all of an owner's words costs one small read per device
+        self.range_flag = new_range_flag(self.device) if range_flag is None else range_flag
+        # layer name -> fp16x2 activation exponent (calibrate_fp16x2); the owner shares ONE dict among its plans
+        self.a_exps: dict = {} if a_exps is None else a_exps
         self.flops = 0
-        self.on_calibrated = None
+        self.on_calibrated = on_calibrated   # (the owner: a graph captured at detector level holds the old exponents)
         # Range words (include/tsod.h): every tensor the pool hands out gets a fresh set; producers add their outputs' abs-max,
         # fp16x2 convs take their activation scale from the words of their input(s) - per forward, inside the launches.
         self.dynamic_scale = bool(self.DEFAULT_DYNAMIC_SCALE)
@@ -373,19 +385,13 @@ class Plan:
                            tile=tile, split_k=split_k, precision=precision,
                            src2=None if x2 is None else (pc.c2, x2.shape[3], 0, stride2, x2.shape[1], x2.shape[2]))
         d.amax_in, d.amax_in2, d.amax_out = self.amax_ptr(x) or None, self.amax_ptr(x2) or None, self.amax_ptr(out) or None
-        args = [byref(d), ptr(x), ptr(weights_bf16x3(pc)) if precision == _ffi.PREC_BF16X3 else ptr(pc.w), ptr(pc.scale),
-                ptr(pc.shift), ptr(residual), ptr(out), 0, 0]
-        if x2 is not None:
-            args.insert(2, ptr(x2))                               # tsod_conv2d_dual_f32(desc, in, in2, w, ...)
-        self.steps.append([lib().tsod_conv2d_dual_f32 if x2 is not None else lib().tsod_conv2d_f32, args])
+        args = [byref(d), ptr(x), ptr(x2), None, ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(out), 0, 0]
+        self.steps.append([lib().tsod_conv2d_dual_f32, args])
         st = ConvStep()
-        st.desc, st.args, st.name, st.pc = d, args, name, pc
-        st.range_flag = self.range_flag
-        st.x, st.x2, st.exps = x, x2, self.a_exps                 # (the inputs: Plan.calibrate_fp16x2 measures their range)
+        st.desc, st.args, st.name, st.pc, st.plan = d, args, name, pc, self
+        st.x, st.x2 = x, x2                                       # (the inputs: Plan.calibrate_fp16x2 measures their range)
         st.fn = self.steps[-1][0]
-        st.w_index, st.ws_index = (3, 8) if x2 is not None else (2, 7)
-        if precision == _ffi.PREC_FP16X2:                         # (weight image, scale exponents, range flag: choose() sets them)
-            st.choose(tile, split_k, precision)
+        st.choose(tile, split_k, precision)                       # (weight image; fp16x2: scale exponents and range word too)
         st.flops = 2 * N * OH * OW * getattr(pc, "cout_real", pc.cout) * pc.kh * pc.kw_logical * pc.cin_src   # algorithmic
         st.ws_bytes = 0
         self.conv_steps.append(st)
@@ -400,15 +406,10 @@ class Plan:
         N, H, W, P = x.shape
         proj = bool(getattr(fb, "projection", False))
         assert tuple(out.shape[:3]) == (N, H, W) and (proj or fb.cin == fb.cout)
-        d = _ffi.BottleneckDesc()
-        d.N, d.H, d.W, d.Cin, d.in_pitch, d.Cmid, d.Cout, d.out_pitch = N, H, W, fb.cin, P, fb.cmid, fb.cout, out.shape[3]
-        d.projection = 1 if proj else 0
-        d.slope = float(fb.slope)
-        for k in range(3):
-            d.w_exp[k] = int(fb.w_exps[k])
-        d.a_scale_exp = int(self.a_exps.get(name, FP16X2_A_SCALE_EXP))
-        d.range_flag = ptr(self.range_flag)
-        d.amax_in, d.amax_out = self.amax_ptr(x) or None, self.amax_ptr(out) or None
+        d = _ffi.make_bottleneck_desc(N=N, H=H, W=W, Cin=fb.cin, in_pitch=P, Cmid=fb.cmid, Cout=fb.cout, out_pitch=out.shape[3],
+                                      slope=fb.slope, w_exps=fb.w_exps, projection=proj,
+                                      a_scale_exp=self.a_exps.get(name, FP16X2_A_SCALE_EXP), range_flag=ptr(self.range_flag),
+                                      amax_in=self.amax_ptr(x), amax_out=self.amax_ptr(out))
         args = [byref(d), ptr(x), ptr(fb.stream), ptr(fb.bn), ptr(out)]
         self.steps.append([lib().tsod_bottleneck_fp16x2, args])
         px = N * H * W
@@ -426,14 +427,11 @@ class Plan:
         """images [N,3,H,W] (NCHW) or NHWC4Images -> out [N,PH,PW,64]: conv1 + bn1 + PReLU + max pool as ONE launch
         (tsod_stem_fp16x2; the pixel scale is each tile's own).  The images are whatever ``stage_input`` bound last: the launch
         reads them where the caller holds them - no layout pass, no copy."""
-        d = _ffi.StemDesc()
-        d.N, d.H, d.W, d.in_layout, d.out_pitch = N, H, W, _ffi.STEM_NHWC4, out.shape[3]
-        d.slope, d.w_exp = float(fs.slope), int(fs.w_exp)
-        d.range_flag = ptr(self.range_flag)
-        d.amax_out = self.amax_ptr(out) or None
+        d = _ffi.make_stem_desc(N=N, H=H, W=W, in_layout=_ffi.STEM_NHWC4, out_pitch=out.shape[3], slope=fs.slope, w_exp=fs.w_exp,
+                                range_flag=ptr(self.range_flag), amax_out=self.amax_ptr(out))
         args = [byref(d), ptr(self.input_nhwc), ptr(fs.wfrag), ptr(fs.bn), ptr(out)]
         self.steps.append([lib().tsod_stem_fp16x2, args])
-        oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        oh, ow, _, _ = _ffi.stem_out_hw(H, W)
         flops = 2 * N * oh * ow * 64 * 147
         alg = 4 * (N * H * W * 3 + out.shape[0] * out.shape[1] * out.shape[2] * 64 + 64 * 147)
         st = FusedStep(name, self.steps[-1][0], args, d, flops, alg)
@@ -474,8 +472,7 @@ class Plan:
                 self._retired.append(self.workspace)
             self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
         for st in self.conv_steps:
-            st.args[st.ws_index] = ptr(self.workspace)
-            st.args[st.ws_index + 1] = self.workspace.numel()
+            st.args[:] = st.args_on(self.workspace)              # (in place: self.steps launches this very list)
         self.graph = None
         return self
 
@@ -486,7 +483,6 @@ class Plan:
         to [-24, 8].  Without it every layer uses 2^4 (|x| < 4094); with it a model whose activations are larger (or much
         smaller) than the synthetic detector's gets exponents that fit, with 16x headroom for other inputs - and the range guard
         (include/tsod.h: range_flag) still watches every launch.  Returns {layer name: (absmax, exponent)}."""
-        import math
         stage_input(self, x)
         by_args = {id(st.args): st for st in self.conv_steps}
         by_args.update({id(st.args): st for st in self.fused_steps if st.x is not None})     # (one-launch bottlenecks: the static path's exponent of x)
@@ -619,8 +615,7 @@ class Plan:
             def time_candidate(tile, split, prec, n_reps):
                 """elapsed ms per launch of this candidate (None: the library refuses it)"""
                 st.choose(tile, split, prec)
-                args = list(st.args)
-                args[st.ws_index], args[st.ws_index + 1] = ptr(big), big.numel()
+                args = st.args_on(big)
                 s = stream_ptr()
                 conv_fn = st.fn
                 rc = conv_fn(*args, s)          # warm
@@ -642,9 +637,7 @@ class Plan:
                     for _ in range(n_reps):
                         rc |= conv_fn(*args, s)
                         for ci, st2 in enumerate(side):
-                            a2 = list(args)
-                            a2[st.ws_index] = ptr(bigs[ci + 1])
-                            rc |= conv_fn(*a2, st2.cuda_stream)
+                            rc |= conv_fn(*st.args_on(bigs[ci + 1]), st2.cuda_stream)
                     for st2 in side:
                         cur.wait_stream(st2)
                     e1.record()
@@ -757,11 +750,6 @@ class Plan:
         (HIP events around that one launch, median of ``reps`` passes); the other layers run their current choice."""
         import statistics
         s = stream_ptr()
-
-        def args_of(st):
-            a = list(st.args)
-            a[st.ws_index], a[st.ws_index + 1] = ptr(big), big.numel()
-            return a
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         out = []
         for i, st in enumerate(self.conv_steps):
@@ -769,7 +757,7 @@ class Plan:
             timed = []
             for tile, split, prec in cands:
                 st.choose(tile, split, prec)
-                all_args = [args_of(t) for t in self.conv_steps]
+                all_args = [t.args_on(big) for t in self.conv_steps]
                 ts = []
                 rc = 0
                 for _ in range(reps + 1):
@@ -846,15 +834,7 @@ class InFlightMeter:
 
     def args(self):
         """the launches of every plan as they stand now (call again after a choose()), on the meter's own workspaces"""
-        out = []
-        for pl, big in zip(self.plans, self.bigs):
-            rows = []
-            for st in pl.conv_steps:
-                a = list(st.args)
-                a[st.ws_index], a[st.ws_index + 1] = ptr(big), big.numel()
-                rows.append((st.fn, a))
-            out.append(rows)
-        return out
+        return [[(st.fn, st.args_on(big)) for st in pl.conv_steps] for pl, big in zip(self.plans, self.bigs)]
 
     def measure(self, args=None):
         import statistics
@@ -1046,7 +1026,7 @@ class PlanOwner:
         """Copy the plan's range word to the host mirror (one thread, stream-ordered, capturable): last launch of a detector forward."""
         m = self._range_mirror(plan.device)
         if m is not None:
-            slot = int(getattr(plan, "slot", 0)) % self.RANGE_WORDS
+            slot = plan.slot % self.RANGE_WORDS
             check(lib().tsod_word_publish_i32(ptr(plan.range_flag), m[1] + 4 * slot, stream_ptr()), "word_publish")
 
     def raise_if_error(self, slot=None):
@@ -1117,36 +1097,26 @@ class PlanOwner:
         st["_plans"], st["_packed_cache"], st["_range_words"], st["_range_mirrors"] = OrderedDict(), {}, {}, {}
         return st
 
+    def _new_plan(self, device, slot: int = 0) -> "Plan":
+        """An empty plan of this owner for (device, in-flight slot), wired from the start to what the owner's plans share: the
+        packed weights, the slot's range word (it survives plan eviction), the ONE table of fp16x2 activation exponents by layer
+        name, and the default arithmetic.  ``build_plan`` starts from it."""
+        return Plan(device, self._packed_cache, range_flag=self._range_word(device, slot),
+                    a_exps=self.__dict__.setdefault("_a_exps", {}), slot=slot, on_calibrated=self._bump_version,
+                    precision={"f32": _ffi.PREC_F32, "bf16x3": _ffi.PREC_BF16X3, "fp16x2": _ffi.PREC_FP16X2}[self.conv_precision])
+
     def _cached_plan(self, key, build: Callable):
         plans = self._plans
         plan = plans.get(key)
         if plan is None:
             plan = plans[key] = build()
-            shared = self.__dict__.setdefault("_a_exps", {})      # fp16x2 activation exponents by layer name, for every plan of this owner
-            if isinstance(plan, Plan):
-                # the owner's range word of (the plan's device, its in-flight slot): survives plan eviction
-                slot = key[2] if isinstance(key, tuple) and len(key) > 2 and isinstance(key[2], int) else 0
-                flag = self._range_word(plan.device, slot)
-                assert flag.device == plan.device
-                plan.slot = slot
-                plan.a_exps = shared
-                plan.range_flag = flag
-                plan.on_calibrated = self._bump_version           # (a graph captured at detector level holds the old exponents)
-                for st in plan.conv_steps:
-                    st.exps = shared
-                    st.range_flag = flag
-                    if int(st.desc.precision) == _ffi.PREC_FP16X2:    # (built in that arithmetic: choose() ran before the dict was shared)
-                        st.desc.a_scale_exp = int(shared.get(st.name, FP16X2_A_SCALE_EXP))
-                        st.desc.range_flag = ptr(flag)
-                for st in plan.fused_steps:
-                    st.desc.range_flag = ptr(flag)
             while len(plans) > max(1, int(self.max_plans)):
                 plans.popitem(last=False)
         else:
             plans.move_to_end(key)
         return plan
 
-    # -- the backbones' plan lookup (build_plan(N, H, W, device) is theirs) ---------------------
+    # -- the backbones' plan lookup (build_plan(N, H, W, device, slot) is theirs) ---------------
     def _plan_for_shape(self, shape, device, slot: int = 0) -> "Plan":
         device = torch.device(device)
         if device.type != "cuda":
@@ -1158,7 +1128,7 @@ class PlanOwner:
         def build():
             if self.training:
                 raise TsodError("the HIP path implements the inference forward only: call .eval() first")
-            return self.build_plan(shape[0], shape[2], shape[3], device)
+            return self.build_plan(shape[0], shape[2], shape[3], device, slot)
         # slot: independent buffer sets for forwards in flight concurrently (the packed weights are shared)
         return self._cached_plan((shape, device, slot) + tuple(self._plan_variant()), build)
 

@@ -134,7 +134,6 @@ def pack_conv_weight_bf16x3(w_packed: torch.Tensor) -> torch.Tensor:
 def fp16x2_weight_scale_exp(w_packed: torch.Tensor) -> int:
     """The power of two that brings max |w| just below 2^14 (fp16's largest finite value is 65504; the low pieces of weights
     scaled like this stay out of its subnormals): the ``w_scale_exp`` of pack_conv_weight_fp16x2 and of the conv descriptor."""
-    import math
     m = float(w_packed.abs().max())
     return 0 if m == 0.0 or not math.isfinite(m) else max(-40, min(40, int(math.floor(math.log2(16384.0 / m)))))
 
@@ -169,10 +168,8 @@ def _w3_for(w_packed: torch.Tensor) -> torch.Tensor:
         if len(_W3_CACHE) >= 64:
             _W3_CACHE.clear()
         base = w_packed._base if w_packed._base is not None else w_packed
-        w3 = pack_conv_weight_bf16x3(w_packed)
-        if not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(w3.device).synchronize()      # complete before another stream can hit the entry
-        hit = _W3_CACHE[key] = (base, w3)
+        from .engine import _publish
+        hit = _W3_CACHE[key] = (base, _publish(pack_conv_weight_bf16x3(w_packed)))
     return hit[1]
 
 
@@ -277,14 +274,9 @@ def bottleneck_fused(x: torch.Tensor, wstream: torch.Tensor, w_exps, bn: torch.T
     N, H, W, P = x.shape
     if out is None:
         out = torch.empty((N, H, W, cout), dtype=torch.float32, device=x.device)
-    d = _ffi.BottleneckDesc()
-    d.N, d.H, d.W, d.Cin, d.in_pitch, d.Cmid, d.Cout, d.out_pitch = N, H, W, cout if cin is None else cin, P, 64, cout, out.shape[3]
-    d.projection = 0 if cin is None else 1
-    d.slope = float(slope)
-    for k in range(3):
-        d.w_exp[k] = int(w_exps[k])
-    d.a_scale_exp = int(a_scale_exp)
-    d.range_flag, d.amax_in, d.amax_out = ptr(range_flag) or None, _word_ptr(amax_in), _word_ptr(amax_out)
+    d = _ffi.make_bottleneck_desc(N=N, H=H, W=W, Cin=cout if cin is None else cin, in_pitch=P, Cout=cout, out_pitch=out.shape[3],
+                                  slope=slope, w_exps=w_exps, projection=cin is not None, a_scale_exp=a_scale_exp,
+                                  range_flag=ptr(range_flag), amax_in=_word_ptr(amax_in), amax_out=_word_ptr(amax_out))
     check(lib().tsod_bottleneck_fp16x2(byref(d), ptr(x), ptr(wstream), ptr(bn), ptr(out), stream_ptr()), "bottleneck_fused")
     return out
 
@@ -320,14 +312,11 @@ def stem_fused(x, wfrag: torch.Tensor, w_exp: int, bn: torch.Tensor, slope: floa
         N, H, W, _ = t.shape
     else:
         N, _, H, W = t.shape
-    oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    ph, pw = (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
+    _, _, ph, pw = _ffi.stem_out_hw(H, W)
     if out is None:
         out = torch.empty((N, ph, pw, 64), dtype=torch.float32, device=t.device)
-    d = _ffi.StemDesc()
-    d.N, d.H, d.W, d.in_layout, d.out_pitch = N, H, W, (_ffi.STEM_NHWC4 if nhwc4 else _ffi.STEM_NCHW), out.shape[3]
-    d.slope, d.w_exp = float(slope), int(w_exp)
-    d.range_flag, d.amax_out = ptr(range_flag) or None, _word_ptr(amax_out)
+    d = _ffi.make_stem_desc(N=N, H=H, W=W, in_layout=_ffi.STEM_NHWC4 if nhwc4 else _ffi.STEM_NCHW, out_pitch=out.shape[3],
+                            slope=slope, w_exp=w_exp, range_flag=ptr(range_flag), amax_out=_word_ptr(amax_out))
     check(lib().tsod_stem_fp16x2(byref(d), ptr(t), ptr(wfrag), ptr(bn), ptr(out), stream_ptr()), "stem_fused")
     return out
 

@@ -321,12 +321,11 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
             shift = _padded(conv.bias.detach(), cp) if conv.bias is not None else None
         return (w.to(device), None if scale is None else scale.to(device), None if shift is None else shift.to(device), cp)
 
-    def build_plan(self, N, H, W, device) -> Plan:
+    def build_plan(self, N, H, W, device, slot=0) -> Plan:
         if not self.depth_wise:
             raise TsodError("depth_wise=False HarDNet (max-pool variant) has no HIP path; the reference only "
                             "uses depth_wise=True")
-        plan = Plan(device, self._packed_cache)
-        plan.precision = {"f32": 0, "bf16x3": 1, "fp16x2": 2}[self.conv_precision]
+        plan = self._new_plan(device, slot)
         L = lib()
         mods = list(self.base)
         x4 = plan.pool.alloc((N, H, W, 4))

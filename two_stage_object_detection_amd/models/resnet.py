@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip_ops
-from .._ffi import ACT_NONE, ACT_PRELU, TsodError, lib, ptr, require_cuda
+from .._ffi import ACT_NONE, ACT_PRELU, TsodError, lib, ptr, require_cuda, stem_out_hw
 from ..engine import FusedBottleneckWeights, FusedShortcutConv, FusedStemWeights, PackedConv, Plan, PlanOwner, prelu_slope
 
 
@@ -175,18 +175,16 @@ class ResNet(PlanOwner, nn.Module):
         return nn.Sequential(*blocks)
 
     # -- plan (cache, invalidation, lookup: engine.PlanOwner) -----------------------------------
-    def build_plan(self, N, H, W, device) -> Plan:
+    def build_plan(self, N, H, W, device, slot=0) -> Plan:
         """Launch plan for a [N,3,H,W] input: NCHW->NHWC4, 7x7 stem as a 7x8x4 implicit GEMM with
         BN+PReLU, 3x3/s2 max pool, then the residual stages."""
-        plan = Plan(device, self._packed_cache)
-        plan.precision = {"f32": 0, "bf16x3": 1, "fp16x2": 2}[self.conv_precision]
+        plan = self._new_plan(device, slot)
         plan.fuse_shortcut = bool(self.fuse_shortcut)
         plan.fuse_bottleneck = bool(self.fuse_bottleneck)
         plan.fuse_projection = bool(self.fuse_projection)
         x4 = plan.pool.alloc((N, H, W, 4))
         plan.input_nhwc = x4
-        oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        ph, pw = (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
+        oh, ow, ph, pw = stem_out_hw(H, W)
         if self.fuse_stem and tuple(self.conv1.weight.shape) == (64, 3, 7, 7):
             # conv1 + bn1 + PReLU + max pool as ONE launch that reads the images where stage_input finds them (NCHW or NHWC4):
             # no layout pass, the 64-channel conv output never leaves the CU (tsod_stem_fp16x2)

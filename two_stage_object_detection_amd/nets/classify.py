@@ -13,7 +13,7 @@ from torch import nn
 
 from .. import _ffi, hip_ops
 from .._ffi import TsodError, require_cuda
-from ..engine import PlanOwner
+from ..engine import PlanOwner, _publish
 from ..models.hardnet import HarNetClassifier
 
 
@@ -80,9 +80,7 @@ class HarNetRoIHead(PlanOwner, nn.Module):
         not be re-split - and baked into a captured graph - on every call)."""
         w3 = self._packed_cache.get(("head.w3", dev))
         if w3 is None:
-            w3 = self._packed_cache[("head.w3", dev)] = hip_ops.pack_conv_weight_bf16x3(self._pack(dev)[0])
-            if not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream(dev).synchronize()       # complete before another slot's stream uses it
+            w3 = self._packed_cache[("head.w3", dev)] = _publish(hip_ops.pack_conv_weight_bf16x3(self._pack(dev)[0]))
         return w3
 
     def _w2(self, dev):
@@ -91,9 +89,7 @@ class HarNetRoIHead(PlanOwner, nn.Module):
         if w2 is None:
             w = self._pack(dev)[0]
             e = hip_ops.fp16x2_weight_scale_exp(w)
-            w2 = self._packed_cache[("head.w2", dev)] = (hip_ops.pack_conv_weight_fp16x2(w.view(w.shape[0], 1, 1, w.shape[1]), e), e)
-            if not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream(dev).synchronize()
+            w2 = self._packed_cache[("head.w2", dev)] = (_publish(hip_ops.pack_conv_weight_fp16x2(w.view(w.shape[0], 1, 1, w.shape[1]), e)), e)
         return w2
 
     def _dgrad_weight(self, dev):
