@@ -630,6 +630,47 @@ int tsod_gconv1x1_pair_grad_f32(const float *in, int64_t pixels, int32_t G, int3
                                 const float *d_out, int32_t d_out_pitch, float *d_in, int32_t d_in_pitch, float *dw,
                                 float *dbias, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
 
+/* ---- the backward of a HarDNet 1x1 ConvLayer --------------------------------------------------------
+ * y[m][o] = relu6(scale[o] * sum_k w[o][k] x[m][k] + shift[o]) on pixel rows m: x is gathered from channel segments of an NHWC
+ * buffer [M][x_pitch] (tsod_pw_segs: buffer offset, padded width - both multiples of 4 - and real width of every segment, in the
+ * K order of w [N][K], K = the sum of the padded widths, zero columns at the pad channels), BN folded into scale / shift [N].
+ * No float atomics; bit-identical from run to run.
+ * tsod_dwconv3x3_grad_act_f32: tsod_dwconv3x3_grad_f32 (same arguments, same workspace query, same dw / dscale / dshift) whose
+ *   dx gather keeps a value only where the x pixel it owns has 0 < x < 6: with x = a ConvLayer's output this dx is that layer's
+ *   masked gradient g, one pass saved.
+ * tsod_relu6_grad_mask_f32: g [rows][g_pitch] = dy [rows][dy_pitch] (columns [dy_off, dy_off + C)) * [0 < y < 6], y
+ *   [rows][y_pitch] the forward's output (both comparisons strict: torch's hardtanh backward).  16-byte aligned, C / pitches /
+ *   dy_off multiples of 4.
+ * tsod_pw_wgrad_f32: dWraw = g^T x_gathered on v_mfma_f32_32x32x2_f32 (g [M][g_pitch], N columns), M cut into slices whose
+ *   partial tiles a finishing launch adds in slice order; it writes dw [n_real][sum of real widths] = scale[o] * dWraw (pad
+ *   rows and columns dropped), dscale [n_real] = sum_k w[o][k] * dWraw[o][k], dshift [n_real] = sum_m g[m][o]; each of the
+ *   three may be NULL (not all).  Slices: enough for about 512 workgroups, at least 64 row pairs each, and never more slab
+ *   floats than M (N + K), the operands.  workspace: tsod_pw_wgrad_workspace_bytes(M, N, K).
+ * tsod_pw_dgrad_f32: dx [M][dx_pitch] columns of every segment with want != 0 (=, or accumulate = 1: +=)
+ *   sum_o (g[m][o] * scale[o]) * w[o][k], o ascending, the old value added last; pad columns of a wanted segment are written as
+ *   exact zeros, segments with want == 0 and everything between segments are not touched.  N, g_pitch multiples of 4. */
+#define TSOD_PW_MAX_SEGMENTS 16
+typedef struct tsod_pw_segs {
+    int32_t n_seg;
+    int32_t off[TSOD_PW_MAX_SEGMENTS];  /* first channel in the buffer */
+    int32_t len[TSOD_PW_MAX_SEGMENTS];  /* padded width */
+    int32_t real[TSOD_PW_MAX_SEGMENTS]; /* real width, 1..len */
+    int32_t want[TSOD_PW_MAX_SEGMENTS]; /* tsod_pw_dgrad_f32: this segment's dx is wanted */
+} tsod_pw_segs;
+int tsod_dwconv3x3_grad_act_f32(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t in_pitch, int32_t in_off,
+                                const float *w, const float *scale, const float *shift, int32_t stride, int32_t relu,
+                                const float *dy, int32_t dy_pitch, int32_t dy_off, float *dx, int32_t dx_pitch, int32_t dx_off,
+                                int32_t accumulate, float *dw, float *dscale, float *dshift, void *workspace,
+                                size_t workspace_bytes, tsod_stream_t stream);
+int tsod_relu6_grad_mask_f32(const float *y, int64_t rows, int32_t C, int32_t y_pitch, const float *dy, int32_t dy_pitch,
+                             int32_t dy_off, float *g, int32_t g_pitch, tsod_stream_t stream);
+size_t tsod_pw_wgrad_workspace_bytes(int64_t M, int32_t N, int32_t K);
+int tsod_pw_wgrad_f32(const float *g, int64_t M, int32_t N, int32_t g_pitch, const float *x, int32_t x_pitch,
+                      const tsod_pw_segs *segs, const float *w, const float *scale, int32_t n_real, float *dw, float *dscale,
+                      float *dshift, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+int tsod_pw_dgrad_f32(const float *g, int64_t M, int32_t N, int32_t g_pitch, const float *w, const float *scale,
+                      const tsod_pw_segs *segs, float *dx, int32_t dx_pitch, int32_t accumulate, tsod_stream_t stream);
+
 /* ---- detection mAP: COCOeval's evaluateImg + accumulate, area range "all", no crowd / ignore flags ------
  * The reference's calculate_metrics (nets/frcnn_training.py:372-565) defines no usable metric; this is the project's own.
  * IoU is tsod_bbox_iou_f32's expression (eps 1e-8, no +1), compared as IoU >= t in f32.  Three steps:

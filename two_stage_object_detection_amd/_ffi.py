@@ -122,6 +122,15 @@ class Photometric(Structure):
                 ("hue", c_float), ("white", c_float), ("perm", c_int32 * 3)]
 
 
+PW_MAX_SEGMENTS = 16             # TSOD_PW_MAX_SEGMENTS
+
+
+class PwSegs(Structure):
+    """Mirror of ``tsod_pw_segs`` (include/tsod.h): the channel segments a 1x1 ConvLayer gathers its K from."""
+    _fields_ = [("n_seg", c_int32), ("off", c_int32 * PW_MAX_SEGMENTS), ("len", c_int32 * PW_MAX_SEGMENTS),
+                ("real", c_int32 * PW_MAX_SEGMENTS), ("want", c_int32 * PW_MAX_SEGMENTS)]
+
+
 ADAMW_CHUNK, ADAMW_MAX_GROUPS = 2048, 32         # TSOD_ADAMW_CHUNK, TSOD_ADAMW_MAX_GROUPS
 
 
@@ -258,6 +267,16 @@ _SIGNATURES = {
     "tsod_gconv1x1_pair_grad_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "tsod_gconv1x1_pair_grad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
                                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_dwconv3x3_grad_act_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                            c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                            c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_relu6_grad_mask_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32,
+                                         c_void_p]),
+    "tsod_pw_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "tsod_pw_wgrad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, POINTER(PwSegs), c_void_p, c_void_p,
+                                  c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_pw_dgrad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, POINTER(PwSegs), c_void_p, c_int32,
+                                  c_int32, c_void_p]),
     "tsod_eval_match_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "tsod_eval_match_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,

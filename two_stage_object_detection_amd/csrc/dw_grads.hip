@@ -1,6 +1,7 @@
 // dw_grads.hip -- the backward of the HarDNet tail's two layer kinds:
 //
 //   tsod_dwconv3x3_grad_f32       y = relu?(scale * dwconv3x3(x, w) + shift)   (pool_layout.hip: dwconv3x3_kernel)
+//   tsod_dwconv3x3_grad_act_f32   the same, dx masked by the ReLU6 window of x (x = a 1x1 ConvLayer's output: section 4.18)
 //   tsod_gconv1x1_pair_grad_f32   out[g] = w[g][0] in[2g] + w[g][1] in[2g+1] + bias[g]   (gconv1x1_pair_kernel)
 //
 // NHWC f32, one float4 of channels (one group of the pair conv) per lane.  No float atomics: the parameter gradients are
@@ -148,12 +149,13 @@ dwconv3x3_grad_combine_kernel(const float *__restrict__ partials, int S, int C, 
 }
 
 // dx: the thread that owns an input pixel's channel quad adds w[dh][dw] * g[oh][ow] over the outputs that read it
-// (ih = oh * STRIDE - 1 + dh), dh then dw ascending, then takes the scale.
+// (ih = oh * STRIDE - 1 + dh), dh then dw ascending, then takes the scale.  `xact` (tsod_dwconv3x3_grad_act_f32): x is the
+// ReLU6 output of the layer before, and the thread keeps its sum only where 0 < x < 6 (that layer's masked gradient).
 template <int STRIDE>
 __global__ void __launch_bounds__(kThreads)
 dwconv3x3_grad_input_kernel(const float *__restrict__ g, int g_pitch, int g_off, int N, int H, int W, int C4, int OH, int OW,
                             const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ dx,
-                            int dx_pitch, int dx_off, int accumulate) {
+                            int dx_pitch, int dx_off, int accumulate, const float *__restrict__ xact, int x_pitch, int x_off) {
     const long total = (long)N * H * W * C4;
     const int C = C4 * 4;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
@@ -182,6 +184,13 @@ dwconv3x3_grad_input_kernel(const float *__restrict__ g, int g_pitch, int g_off,
         if (scale) {
             const float4 s = *reinterpret_cast<const float4 *>(scale + 4 * c4);
             acc.x *= s.x; acc.y *= s.y; acc.z *= s.z; acc.w *= s.w;
+        }
+        if (xact) {
+            const float4 v = *reinterpret_cast<const float4 *>(xact + (((long)n * H + ih) * W + iw) * x_pitch + x_off + 4 * c4);
+            acc.x = (v.x > 0.f && v.x < 6.f) ? acc.x : 0.f;
+            acc.y = (v.y > 0.f && v.y < 6.f) ? acc.y : 0.f;
+            acc.z = (v.z > 0.f && v.z < 6.f) ? acc.z : 0.f;
+            acc.w = (v.w > 0.f && v.w < 6.f) ? acc.w : 0.f;
         }
         float4 *dst = reinterpret_cast<float4 *>(dx + (((long)n * H + ih) * W + iw) * dx_pitch + dx_off + 4 * c4);
         if (accumulate) {
@@ -253,12 +262,12 @@ extern "C" size_t tsod_dwconv3x3_grad_workspace_bytes(int32_t N, int32_t H, int3
     return partials + (relu_dx ? (size_t)pixels * C * sizeof(float) : 0);    // [partials | g = masked dy, for the dx gather]
 }
 
-extern "C" int tsod_dwconv3x3_grad_f32(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t in_pitch,
-                                       int32_t in_off, const float *w, const float *scale, const float *shift,
-                                       int32_t stride, int32_t relu, const float *dy, int32_t dy_pitch, int32_t dy_off,
-                                       float *dx, int32_t dx_pitch, int32_t dx_off, int32_t accumulate, float *dw,
-                                       float *dscale, float *dshift, void *workspace, size_t workspace_bytes,
-                                       tsod_stream_t stream) {
+// both entry points; `act_dx`: the dx gather masks with the ReLU6 window of the x pixel it owns
+static int dwconv3x3_grad(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t in_pitch, int32_t in_off,
+                          const float *w, const float *scale, const float *shift, int32_t stride, int32_t relu, const float *dy,
+                          int32_t dy_pitch, int32_t dy_off, float *dx, int32_t dx_pitch, int32_t dx_off, int32_t accumulate,
+                          float *dw, float *dscale, float *dshift, void *workspace, size_t workspace_bytes,
+                          tsod_stream_t stream, bool act_dx) {
     TSOD_REQUIRE(x && w && dy, TSOD_ERR_INVALID_ARG);
     // the parameter gradients come together (dscale optional), or not at all: then only dx is computed
     const bool params = dw != nullptr;
@@ -301,18 +310,39 @@ extern "C" int tsod_dwconv3x3_grad_f32(const float *x, int32_t N, int32_t H, int
         hipLaunchKernelGGL(dwconv3x3_grad_combine_kernel, dim3((unsigned)((kDwQuantities * C + kThreads - 1) / kThreads)),
                            dim3(kThreads), 0, st, partials, geo.S, C, scale, dw, dscale, dshift);
     if (dx) {
+        const float *xact = act_dx ? x : nullptr;
         const float *g = g_ws ? g_ws : dy;
         const int g_pitch = g_ws ? C : dy_pitch, g_off = g_ws ? 0 : dy_off;
         const long total = (long)N * H * W * (C / 4);
         const unsigned blocks = (unsigned)((total + kThreads - 1) / kThreads < 16384 ? (total + kThreads - 1) / kThreads : 16384);
         if (stride == 1)
             hipLaunchKernelGGL(dwconv3x3_grad_input_kernel<1>, dim3(blocks), dim3(kThreads), 0, st, g, g_pitch, g_off, N, H, W,
-                               C / 4, OH, OW, w, scale, dx, dx_pitch, dx_off, accumulate);
+                               C / 4, OH, OW, w, scale, dx, dx_pitch, dx_off, accumulate, xact, in_pitch, in_off);
         else
             hipLaunchKernelGGL(dwconv3x3_grad_input_kernel<2>, dim3(blocks), dim3(kThreads), 0, st, g, g_pitch, g_off, N, H, W,
-                               C / 4, OH, OW, w, scale, dx, dx_pitch, dx_off, accumulate);
+                               C / 4, OH, OW, w, scale, dx, dx_pitch, dx_off, accumulate, xact, in_pitch, in_off);
     }
     return tsod_launch_status();
+}
+
+extern "C" int tsod_dwconv3x3_grad_f32(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t in_pitch,
+                                       int32_t in_off, const float *w, const float *scale, const float *shift,
+                                       int32_t stride, int32_t relu, const float *dy, int32_t dy_pitch, int32_t dy_off,
+                                       float *dx, int32_t dx_pitch, int32_t dx_off, int32_t accumulate, float *dw,
+                                       float *dscale, float *dshift, void *workspace, size_t workspace_bytes,
+                                       tsod_stream_t stream) {
+    return dwconv3x3_grad(x, N, H, W, C, in_pitch, in_off, w, scale, shift, stride, relu, dy, dy_pitch, dy_off, dx, dx_pitch,
+                          dx_off, accumulate, dw, dscale, dshift, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int tsod_dwconv3x3_grad_act_f32(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t in_pitch,
+                                           int32_t in_off, const float *w, const float *scale, const float *shift,
+                                           int32_t stride, int32_t relu, const float *dy, int32_t dy_pitch, int32_t dy_off,
+                                           float *dx, int32_t dx_pitch, int32_t dx_off, int32_t accumulate, float *dw,
+                                           float *dscale, float *dshift, void *workspace, size_t workspace_bytes,
+                                           tsod_stream_t stream) {
+    return dwconv3x3_grad(x, N, H, W, C, in_pitch, in_off, w, scale, shift, stride, relu, dy, dy_pitch, dy_off, dx, dx_pitch,
+                          dx_off, accumulate, dw, dscale, dshift, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" size_t tsod_gconv1x1_pair_grad_workspace_bytes(int64_t pixels, int32_t G) {

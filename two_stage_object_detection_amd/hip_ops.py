@@ -439,11 +439,12 @@ def gconv3x3_nhwc(x: torch.Tensor, w_packed: torch.Tensor, groups: int, scale=No
 
 
 def dwconv3x3_grad(x, w33c, scale, shift, stride, relu, dy, *, want_dx=True, want_params=True, dx=None, accumulate=False,
-                   in_off=0):
+                   in_off=0, dy_off=0, act_dx=False):
     """The backward of ``dwconv3x3_nhwc`` (tsod_dwconv3x3_grad_f32) -> (dx or None, dw [3,3,C], dscale [C] or None, dshift [C]).
-    x [N,H,W,P] (channels [in_off, in_off+C)), dy [N,OH,OW,C] contiguous.  ``dx`` [N,H,W,C]: written, or added to with
-    ``accumulate``; allocated when ``want_dx`` and none is given.  ``want_params`` False: dx only (dw, dscale, dshift None;
-    without a ReLU that is the gather launch alone)."""
+    x [N,H,W,P] (channels [in_off, in_off+C)), dy [N,OH,OW,>= dy_off + C] contiguous (channels [dy_off, dy_off+C)).  ``dx``
+    [N,H,W,C]: written, or added to with ``accumulate``; allocated when ``want_dx`` and none is given.  ``want_params`` False:
+    dx only (dw, dscale, dshift None; without a ReLU that is the gather launch alone).  ``act_dx``: x is a ReLU6 output and dx
+    is kept only where 0 < x < 6 (tsod_dwconv3x3_grad_act_f32: the masked gradient of the layer that made x)."""
     require_cuda(x, "dwconv3x3_grad")
     N, H, W, P = x.shape
     C = w33c.shape[2]
@@ -457,11 +458,90 @@ def dwconv3x3_grad(x, w33c, scale, shift, stride, relu, dy, *, want_dx=True, wan
     L = lib()
     ws_bytes = L.tsod_dwconv3x3_grad_workspace_bytes(N, H, W, C, int(stride), 1 if relu and dx is not None else 0)
     ws = ARENA.get(dev, ws_bytes)
-    check(L.tsod_dwconv3x3_grad_f32(ptr(x), N, H, W, C, P, int(in_off), ptr(w33c), ptr(scale), ptr(shift), int(stride),
-                                    1 if relu else 0, ptr(dy), dy.shape[3], 0, ptr(dx), 0 if dx is None else dx.shape[3], 0,
-                                    1 if accumulate else 0, ptr(dw), ptr(dscale), ptr(dshift), ptr(ws), ws_bytes, stream_ptr()),
-          "dwconv3x3_grad")
+    fn = L.tsod_dwconv3x3_grad_act_f32 if act_dx else L.tsod_dwconv3x3_grad_f32
+    check(fn(ptr(x), N, H, W, C, P, int(in_off), ptr(w33c), ptr(scale), ptr(shift), int(stride), 1 if relu else 0, ptr(dy),
+             dy.shape[3], int(dy_off), ptr(dx), 0 if dx is None else dx.shape[3], 0, 1 if accumulate else 0, ptr(dw), ptr(dscale),
+             ptr(dshift), ptr(ws), ws_bytes, stream_ptr()), "dwconv3x3_grad")
     return dx, dw, dscale, dshift
+
+
+def pw_segs(segs, real=None, want=None) -> _ffi.PwSegs:
+    """``tsod_pw_segs`` from [(channel offset, padded width), ...], the real widths (default: the padded ones) and the
+    per-segment "dx wanted" switches (default: all)."""
+    if not 1 <= len(segs) <= _ffi.PW_MAX_SEGMENTS:
+        raise ValueError(f"pw_segs: 1..{_ffi.PW_MAX_SEGMENTS} segments, got {len(segs)}")
+    sg = _ffi.PwSegs()
+    sg.n_seg = len(segs)
+    for i, (off, ln) in enumerate(segs):
+        sg.off[i], sg.len[i] = int(off), int(ln)
+        sg.real[i] = int(ln if real is None else real[i])
+        sg.want[i] = 1 if want is None or want[i] else 0
+    return sg
+
+
+def relu6_grad_mask(y: torch.Tensor, dy: torch.Tensor, dy_off: int = 0) -> torch.Tensor:
+    """g = dy[..., dy_off:dy_off + C] * [0 < y < 6] (tsod_relu6_grad_mask_f32); y [..., C] and dy [..., P] contiguous."""
+    require_cuda(y, "relu6_grad_mask")
+    y, dy = y.contiguous(), dy.contiguous()
+    C = y.shape[-1]
+    g = torch.empty_like(y)
+    check(lib().tsod_relu6_grad_mask_f32(ptr(y), y.numel() // C, C, C, ptr(dy), dy.shape[-1], int(dy_off), ptr(g), C, stream_ptr()),
+          "relu6_grad_mask")
+    return g
+
+
+def conv1x1_bn_relu6_grad(x, segs, w, scale, y, dy, *, seg_real=None, seg_want=None, cout=None, dy_off=0, dx=None,
+                          accumulate=False, want_dx=True, want_dw=True, want_dscale=True, want_dshift=True):
+    """The backward of a 1x1 ConvLayer y = relu6(scale * (w . gather(x, segs)) + shift) ->
+    (dx or None, dW [cout, sum(seg_real)] or None, dscale [cout] or None, dshift [cout] or None).
+
+    x [..., P]: the NHWC buffer the forward gathered from; ``segs`` [(channel offset, padded width)] in the K order of ``w``
+    [cout_pad, K] (or [cout_pad,1,1,K]; zero columns at pad channels), ``seg_real`` the real widths (default: no padding),
+    ``cout`` the real output channels (default cout_pad).  ``scale`` [cout_pad]: the folded BN scale.  ``y`` [..., cout_pad]: the
+    forward's saved output, the ReLU6 mask is taken from it (strict 0 < y < 6); ``y`` None: ``dy`` is already the masked
+    gradient g (what ``dwconv3x3_grad(act_dx=True)`` returns).  dy [..., >= dy_off + cout_pad] contiguous.
+    ``dx`` [..., Pd] (default: zeros like x, written): segments with ``seg_want`` (default all) are written, or added to with
+    ``accumulate``, at the offsets of ``segs``; their pad channels become exact zeros; nothing else is touched; segments nobody
+    wants are not computed.  Launches: the mask pass (with ``y``), tsod_pw_wgrad_f32 when any of dW / dscale / dshift is wanted,
+    tsod_pw_dgrad_f32 when ``want_dx``."""
+    require_cuda(x, "conv1x1_bn_relu6_grad")
+    dev = x.device
+    w2 = w.reshape(w.shape[0], -1)
+    if not (x.is_contiguous() and w2.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("conv1x1_bn_relu6_grad: x, w and scale must be contiguous")
+    n_pad, K = w2.shape
+    cout = n_pad if cout is None else int(cout)
+    sg = pw_segs(segs, seg_real, seg_want)
+    if sum(ln for _, ln in segs) != K:
+        raise ValueError(f"conv1x1_bn_relu6_grad: the segments add up to {sum(ln for _, ln in segs)} columns, w has {K}")
+    P = x.shape[-1]
+    M = x.numel() // P
+    if y is not None:
+        g = relu6_grad_mask(y, dy, dy_off)
+    else:
+        g = dy.contiguous()
+        if dy_off or g.shape[-1] != n_pad:
+            raise ValueError("conv1x1_bn_relu6_grad: a masked gradient (y=None) must be a contiguous [..., cout_pad] tensor")
+    if g.numel() != M * n_pad:
+        raise ValueError(f"conv1x1_bn_relu6_grad: {M} pixel rows of x, gradient of shape {tuple(g.shape)}")
+    L = lib()
+    k_real = sum(sg.real[i] for i in range(sg.n_seg))
+    dw = torch.empty((cout, k_real), dtype=torch.float32, device=dev) if want_dw else None
+    dscale = torch.empty(cout, dtype=torch.float32, device=dev) if want_dscale else None
+    dshift = torch.empty(cout, dtype=torch.float32, device=dev) if want_dshift else None
+    if want_dw or want_dscale or want_dshift:
+        ws_bytes = L.tsod_pw_wgrad_workspace_bytes(M, n_pad, K)
+        ws = ARENA.get(dev, ws_bytes)
+        check(L.tsod_pw_wgrad_f32(ptr(g), M, n_pad, n_pad, ptr(x), P, byref(sg), ptr(w2), ptr(scale), cout, ptr(dw), ptr(dscale),
+                                  ptr(dshift), ptr(ws), ws_bytes, stream_ptr()), "pw_wgrad")
+    if want_dx:
+        if dx is None:
+            dx, accumulate = torch.zeros_like(x), False
+        if not dx.is_contiguous() or dx.numel() // dx.shape[-1] != M:
+            raise ValueError("conv1x1_bn_relu6_grad: dx must be a contiguous buffer with x's pixel rows")
+        check(L.tsod_pw_dgrad_f32(ptr(g), M, n_pad, n_pad, ptr(w2), ptr(scale), byref(sg), ptr(dx), dx.shape[-1],
+                                  1 if accumulate else 0, stream_ptr()), "pw_dgrad")
+    return (dx if want_dx else None), dw, dscale, dshift
 
 
 class _DWConv3x3(torch.autograd.Function):

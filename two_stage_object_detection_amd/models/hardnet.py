@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .. import hip_ops
+from .. import _ffi, hip_ops
 from .._ffi import ACT_NONE, ACT_RELU6, TsodError, lib, ptr, require_cuda
 from ..engine import PackedConv, Plan, PlanOwner, fold_bn, stage_input
 
@@ -191,8 +191,109 @@ class _TailGrads(torch.autograd.Function):
         return (None,) + tuple(d if n else None for d, n in zip(grads, need))
 
 
+def _bn_stats(bn, C_pad, device):
+    """(running mean, 1 / sqrt(running var + eps)) of an eval-mode BatchNorm, padded to ``C_pad`` with zeros: what turns
+    (dscale, dshift) into the gradients of ``weight`` / ``bias`` (scale = weight * inv, shift = bias - mean * scale)."""
+    inv = 1.0 / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    return _padded(bn.running_mean.detach(), C_pad).to(device), _padded(inv, C_pad).to(device)
+
+
+def _bn_grads(dscale, dshift, stats, C):
+    """d weight = (dscale - mean * dshift) * inv, d bias = dshift (DESIGN.md section 4.17's folding rule), on [C] vectors."""
+    mean, inv = stats
+    return (dscale[:C] - mean[:C] * dshift[:C]) * inv[:C], dshift[:C]
+
+
+def _conv33_weight(d, C):                                     # [3][3][C_pad] -> torch's [C,1,3,3]
+    return d[:, :, :C].reshape(9, C).t().reshape(C, 1, 3, 3)
+
+
+class _BlockGrads(torch.autograd.Function):
+    """The feature map of a ``train_blocks(n >= 1)`` forward as an autograd node over ``trainable_parameters()`` (DESIGN.md
+    section 4.18): the tail's backward of ``_TailGrads``, whose first depthwise conv now also returns the masked gradient of
+    the last transition layer (tsod_dwconv3x3_grad_act_f32), then per HarDBlock from the last one down: the transition's
+    tsod_pw_wgrad_f32 / tsod_pw_dgrad_f32 into a zeroed block-shaped gradient buffer, the layers in descending order (depthwise
+    backward with the fused ReLU6 mask, then the 1x1's wgrad and dgrad into the slices it gathered from, added in that order),
+    and the ``DWConvLayer`` in front of the block.  Everything runs on the node's own copies (``ctx.saved``)."""
+
+    @staticmethod
+    def forward(ctx, saved, *params):
+        ctx.saved = saved
+        return saved.pop("out")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        sv = ctx.saved
+        need = dict(zip(sv["names"], ctx.needs_input_grad[1:]))
+        out = {}
+
+        def wants(prefix):
+            return need[prefix + ".weight"], need[prefix + ".bias"]
+
+        def dw_layer(prefix, x, pack, stats, C, stride, dy, dy_off):
+            """backward of a DWConvLayer whose input x is a ReLU6 output -> that layer's masked gradient"""
+            w33, sc, sh = pack
+            want = need[prefix + ".dwconv.weight"] or any(wants(prefix + ".norm"))
+            g, d_w, d_sc, d_sh = hip_ops.dwconv3x3_grad(x, w33, sc, sh, stride, False, dy, want_params=want, dy_off=dy_off,
+                                                        act_dx=True)
+            if want:
+                out[prefix + ".dwconv.weight"] = _conv33_weight(d_w, C)
+                out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = _bn_grads(d_sc, d_sh, stats, C)
+            return g
+
+        def pw_layer(prefix, buf, lay, g, dbuf, want_seg):
+            """backward of a 1x1 ConvLayer from its masked gradient g: parameter gradients, and dx added into dbuf"""
+            want_w, (want_g, want_b) = need[prefix + ".conv.weight"], wants(prefix + ".norm")
+            _, d_w, d_sc, d_sh = hip_ops.conv1x1_bn_relu6_grad(
+                buf, lay["segs"], lay["w"], lay["scale"], None, g, seg_real=lay["seg_real"], seg_want=want_seg, cout=lay["cout"],
+                dx=dbuf, accumulate=True, want_dx=any(want_seg), want_dw=want_w, want_dscale=want_g, want_dshift=want_g or want_b)
+            if want_w:
+                out[prefix + ".conv.weight"] = d_w.view(d_w.shape[0], d_w.shape[1], 1, 1)
+            if want_g or want_b:
+                zero = d_sh if d_sc is None else d_sc
+                out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = _bn_grads(zero, d_sh, lay["bn"], lay["cout"])
+
+        # ---- the tail (section 4.17), with the last transition's mask fused into its first layer's dx gather
+        g0 = hip_ops.nchw_to_nhwc(gy) if sv["nchw"] else gy.contiguous()
+        (x0, off0), (a, _), (b, _) = sv["inputs"]
+        (w1, _, sh1, _), (w2, _, sh2, _), (wg, bias) = sv["packs"]
+        i1, i2, ip = sv["tail_indices"]
+        d_b, d_wg, d_bias = hip_ops.gconv1x1_pair_grad(b, wg, g0, want_dw=need[f"base.{ip}.weight"], want_dbias=need[f"base.{ip}.bias"])
+        d_a, d_w2, _, d_sh2 = hip_ops.dwconv3x3_grad(a, w2, None, sh2, 2, False, d_b)
+        g, d_w1, _, d_sh1 = hip_ops.dwconv3x3_grad(x0, w1, None, sh1, 2, True, d_a, in_off=off0, act_dx=True)
+        C = sv["C"]
+        out.update({f"base.{i1}.weight": _conv33_weight(d_w1, C), f"base.{i1}.bias": d_sh1[:C],
+                    f"base.{i2}.weight": _conv33_weight(d_w2, C), f"base.{i2}.bias": d_sh2[:C],
+                    f"base.{ip}.weight": None if d_wg is None else d_wg.view(-1, 2, 1, 1), f"base.{ip}.bias": d_bias})
+
+        # ---- the blocks, last first; g = the masked gradient of the block's transition layer
+        blocks = sv["blocks"]
+        for bi in range(len(blocks) - 1, -1, -1):
+            blk = blocks[bi]
+            first, buf = bi == 0, blk["buf"]
+            dbuf = torch.zeros_like(buf)
+            tr = blk["transition"]
+            pw_layer(f"base.{tr['index']}", buf, tr, g, dbuf, [not (first and k == 0) for k in tr["slices"]])
+            for li in range(len(blk["layers"]), 0, -1):
+                lay = blk["layers"][li - 1]
+                prefix = f"base.{blk['index']}.layers.{li - 1}"
+                g = dw_layer(prefix + ".layer2", lay["y"], lay["dw"], lay["dw_bn"], lay["cout"], 1, dbuf, lay["off"])
+                pw_layer(prefix + ".layer1", buf, lay, g, dbuf, [not (first and k == 0) for k in lay["slices"]])
+            if first:
+                break
+            prev = blocks[bi - 1]["transition"]
+            down = blk["down"]
+            if down is not None:                                  # the DWConvLayer between the blocks
+                g = dw_layer(f"base.{down['index']}", prev["y"], down["dw"], down["dw_bn"], prev["cout"], down["stride"], dbuf, 0)
+            else:                                                 # the transition wrote slice 0 itself
+                g = hip_ops.relu6_grad_mask(prev["y"], dbuf, 0)
+        return (None,) + tuple(out.get(k) if n else None for k, n in need.items())
+
+
 class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     _train_tail = False          # train_tail(): the last four modules of ``base`` are differentiable (default off)
+    _train_blocks = 0            # train_blocks(n): ... and the last n HarDBlocks with their transition layers (default 0)
 
     def __init__(self, depth_wise=True, arch=39):
         super().__init__()
@@ -248,19 +349,156 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         them - the first is the trunk's stride-4 output, N x H/4 x W/4 x 1024 floats (92 MB at 600x600 batch 1, 2.2 GB at
         800x1333 batch 8), held until the node is freed; the plan for grad mode off is a second plan of the same shape."""
         self._train_tail = bool(enabled)
+        if not enabled:
+            self._train_blocks = 0
         return self
+
+    # -- the trainable HarDBlocks (DESIGN.md section 4.18) -----------------------------------------
+    def _block_indices(self):
+        return [i for i, m in enumerate(self.base) if isinstance(m, HarDBlock)]
+
+    def _section_start(self, n: int) -> int:
+        """Index in ``base`` of the earliest of the last ``n`` HarDBlocks."""
+        return self._block_indices()[-n]
+
+    def train_blocks(self, n: int):
+        """Make the tail AND the last ``n`` HarDBlocks differentiable - every ``CombConvLayer`` of those blocks, each block's
+        transition ``ConvLayer`` and any ``DWConvLayer`` between them; ``n = 0`` is ``train_tail(True)``'s state, ``n`` larger
+        than the number of HarDBlocks raises ValueError.  The stem (``base.0`` - ``base.2``) is never reached, and BatchNorm
+        stays in eval mode: its ``weight`` / ``bias`` get gradients through the folded scale / shift, its running statistics
+        are constants.  Contract as ``train_tail``: eval() only; with grad mode on the feature map carries an autograd node
+        (``_BlockGrads``; HIP kernels of csrc/pw_grads.hip and csrc/dw_grads.hip) that gives the gradients of
+        ``trainable_parameters()`` and nothing for the input; the forward runs the same launches on a plan of its own (another
+        plan-cache key) and returns the same bits; in-place updates of the trainable tensors are noticed through their
+        ``_version`` before the next forward of any kind and every packed image derived from a changed layer (gathered f32
+        weight, folded scale / shift, bf16x3 / fp16x2 image) is rewritten in place - plans keep their pointers.
+
+        ``f.grad_fn.saved`` is the dict the backward reads (the node's own copies, so forwards and backwards interleave in any
+        order): ``inputs`` / ``packs`` / ``C`` as ``train_tail``; ``names``: the parameter names in ``trainable_parameters()``
+        order; ``blocks``: per trainable HarDBlock in ``base`` order a dict ``index``, ``buf`` (the block buffer
+        [N,h,w,P]: slice 0 = the block's input, slice i = layer i's output), ``layers`` (per layer: ``y`` = the 1x1's output
+        [N,h,w,cout_pad], ``off`` / ``cout`` = its slice, ``segs`` / ``seg_real`` / ``slices`` = what it gathers, ``w`` /
+        ``scale`` = its packed weight and folded scale, ``dw`` = the depthwise pack), ``transition`` (the same keys for the
+        block's transition layer, ``y`` its output, ``index`` its place in ``base``) and ``down`` (the ``DWConvLayer`` in front
+        of the block, or None).
+
+        Memory: the plan keeps the section's block buffers, 1x1 outputs and transition outputs out of its pool and the node
+        copies them, per block N x h x w x (P + sum of the layers' padded widths + the transition's width) floats: for
+        ``n = 1``, HarDNet-39, 600 x 600, batch 1 that is 150 x 150 pixels x (1 628 + 988 + 1 024) channels x 4 B = 328 MB,
+        twice (plan and node), plus one zeroed gradient buffer of the block buffer's size per block during the backward."""
+        n = int(n)
+        if n < 0 or n > len(self._block_indices()):
+            raise ValueError(f"train_blocks: n must be 0..{len(self._block_indices())} (the HarDBlocks of this backbone), got {n}")
+        self._train_tail, self._train_blocks = True, n
+        self.__dict__["_blocks_watch"] = max(n, self.__dict__.get("_blocks_watch", 0))
+        return self
+
+    def trainable_parameters(self):
+        """The parameters the feature map's autograd node reaches, in ``base`` order: with ``train_blocks(n >= 1)`` everything
+        from the earliest of the last ``n`` HarDBlocks on (conv weights, BN ``weight`` / ``bias``), then the six tail tensors;
+        otherwise ``tail_parameters()``."""
+        return [p for _, p in self._trainable_named()]
+
+    def _trainable_named(self):
+        if not self._train_blocks:
+            i1, i2, ip = self._tail_indices()
+            return [(f"base.{i}.{k}", getattr(self.base[i], k)) for i in (i1, i2, ip) for k in ("weight", "bias")]
+        return [(f"base.{i}.{k}", p) for i in range(self._section_start(self._train_blocks), len(self.base))
+                for k, p in self.base[i].named_parameters()]
 
     def _tail_active(self) -> bool:
         return self._train_tail and torch.is_grad_enabled()
 
+    def _blocks_active(self) -> int:
+        return self._train_blocks if self._tail_active() else 0
+
     def _plan_variant(self):
+        if self._blocks_active():
+            return ("train_blocks", self._blocks_active())
         return ("train_tail",) if self._tail_active() else ()
+
+    def _refresh_block_packs(self):
+        """Rewrite in place the packed images of every layer of the widest section ``train_blocks`` was ever given whose
+        parameters changed since they were last known to match (``_refresh_tail_packs`` for the body)."""
+        n = self.__dict__.get("_blocks_watch", 0)
+        if not n:
+            return
+        seen = self.__dict__.setdefault("_block_versions", {})
+        stale = []
+        for i in range(self._section_start(n), self._tail_indices()[0]):
+            m = self.base[i]
+            units = [(f"base.{i}", m)] if not isinstance(m, HarDBlock) else \
+                [(f"base.{i}.layers.{l}.{k}", getattr(comb, k)) for l, comb in enumerate(m.layers) for k in ("layer1", "layer2")]
+            for name, mod in units:
+                v = tuple(p._version for p in mod.parameters())
+                if seen.get(name) != v:
+                    seen[name] = v
+                    stale.append(name)
+        for name in stale:
+            for (key, device), old in list(self._packed_cache.items()):
+                if key != name:
+                    continue
+                with torch.inference_mode():                  # (the packs may have been made under inference mode)
+                    if isinstance(old, _RawConv):
+                        self._rewrite_raw_conv(old, self._pw_pack(name, device))
+                    else:
+                        parts = name.split(".")
+                        mod = self.base[int(parts[1])] if len(parts) == 2 else self.base[int(parts[1])].layers[int(parts[3])].layer2
+                        for o, t in zip(old, self._dw_params(mod.dwconv, mod.norm, device)):
+                            if isinstance(o, torch.Tensor):
+                                o.copy_(t)
+
+    def _rewrite_raw_conv(self, old, new):
+        """``new``'s images into ``old``'s storage.  The fp16x2 exponent is part of every launch descriptor that reads the
+        image: it is kept while the new weights fit it (graphs stay valid); otherwise the descriptors of every plan follow and
+        captured graphs of those plans are dropped (they hold the old exponent by value)."""
+        old.w.copy_(new.w)
+        old.scale.copy_(new.scale)
+        old.shift.copy_(new.shift)
+        if getattr(old, "w3", None) is not None:
+            old.w3.copy_(hip_ops.pack_conv_weight_bf16x3(old.w))
+        if getattr(old, "w2", None) is not None:
+            img, e = old.w2
+            top = float(old.w.abs().max()) * 2.0 ** e
+            if not (2.0 ** 12 <= top < 2.0 ** 15):             # (packed for just below 2^14; fp16 ends at 65504)
+                e = hip_ops.fp16x2_weight_scale_exp(old.w)
+                for plan in self._plans.values():
+                    for st in plan.conv_steps:
+                        if st.pc is old and int(st.desc.precision) == _ffi.PREC_FP16X2:
+                            st.desc.w_scale_exp = int(e)
+                            plan.graph = None
+                self._bump_version()
+            img.copy_(hip_ops.pack_conv_weight_fp16x2(old.w, e))
+            old.w2 = (img, e)
+
+    def _pw_pack(self, name, device):
+        """The packed form of the 1x1 ConvLayer ``name`` (a HarDBlock layer's ``layer1`` or a transition layer): the weight
+        gathered to the padded slices it reads, BN folded, padded to 4 output channels."""
+        parts = name.split(".")
+        if len(parts) == 2:                                       # transition: base.<i>, the block is the HarDBlock before it
+            i = int(parts[1])
+            bi = max(b for b in self._block_indices() if b < i)
+            blk, tr = self.base[bi], self.base[i]
+            real = blk.slice_table()[0]
+            outs = blk.output_slices()
+            wg = _gathered_weight(tr.conv.weight, [real[k] for k in outs], tr.conv.weight.shape[0])
+            sc, sh = fold_bn(tr.norm)
+            return _RawConv(wg, sc, sh, device, ACT_RELU6, cin_real=sum(real[k] for k in outs))
+        blk, li = self.base[int(parts[1])], int(parts[3]) + 1
+        real = blk.slice_table()[0]
+        comb, link = blk.layers[li - 1], blk.links[li - 1]
+        cout, cp = real[li], _pad4(real[li])
+        wg = _gathered_weight(comb.layer1.conv.weight, [real[k] for k in link], cp)
+        sc, sh = fold_bn(comb.layer1.norm)
+        return _RawConv(wg, _padded(sc, cp), _padded(sh, cp), device, ACT_RELU6, cin_real=sum(real[k] for k in link),
+                        cout_real=cout)
 
     def _refresh_tail_packs(self):
         """Rewrite the tail's packed weights (and only those) in place when one of the six tensors changed since they were
         last known to match: plans and graphs keep their pointers; an autograd node of an earlier forward holds copies."""
         if not self._train_tail and "_tail_versions" not in self.__dict__:
             return                                               # train_tail was never on: today's contract (invalidate_packed)
+        self._refresh_block_packs()
         versions = tuple(p._version for p in self.tail_parameters())
         if versions == self.__dict__.get("_tail_versions"):
             return
@@ -291,7 +529,21 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                      inputs=[(t.clone(), off) for t, off in plan.tail_inputs],
                      packs=[tuple(t.clone() if isinstance(t, torch.Tensor) else t for t in pack) for pack in plan.tail_packs],
                      C=self.base[self._tail_indices()[0]].weight.shape[0])
-        return _TailGrads.apply(saved, *self.tail_parameters())
+        if not self._train_blocks:
+            return _TailGrads.apply(saved, *self.tail_parameters())
+
+        def layer_copy(rec):
+            rc = rec["rc"]
+            return dict(index=rec["index"], off=rec["off"], cout=rec["cout"], segs=rec["segs"], seg_real=rec["seg_real"],
+                        slices=rec["slices"], w=rc.w.view(rc.cout, -1).clone(), scale=rc.scale.clone(), bn=rec["bn"],
+                        y=None if rec["y"] is None else rec["y"][..., rec["y_off"]:rec["y_off"] + rc.cout].clone(),
+                        dw=None if rec["dw"] is None else tuple(t.clone() for t in rec["dw"][:3]), dw_bn=rec["dw_bn"])
+        saved.update(tail_indices=self._tail_indices(), names=[k for k, _ in self._trainable_named()],
+                     blocks=[dict(index=b["index"], buf=b["buf"].clone(), layers=[layer_copy(r) for r in b["layers"]],
+                                  transition=layer_copy(b["transition"]),
+                                  down=None if b["down"] is None else dict(b["down"], dw=tuple(t.clone() for t in b["down"]["dw"][:3])))
+                             for b in plan.block_records])
+        return _BlockGrads.apply(saved, *self.trainable_parameters())
 
     def forward_nhwc(self, x, slot: int = 0):
         if self._tail_active():
@@ -334,6 +586,8 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         # packs are listed for it; the launches are the same
         tail = self._tail_active()
         plan.tail_inputs, plan.tail_packs = [], []
+        section = self._section_start(self._blocks_active()) if self._blocks_active() else None
+        plan.block_records, pending_down = [], None
 
         def dest_for(next_idx, C, h, w):
             """Where the tensor feeding module ``next_idx`` must be written: slice 0 of the next
@@ -374,44 +628,61 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 real, offs, P = m.slice_table()
                 assert cur.shape[3] == P and cur_C == real[0]
                 buf = cur
+                # train_blocks: a block of the section keeps its buffer, its 1x1 outputs and its transition's output out of
+                # the pool (the autograd node copies them after the run); the launches are the same
+                rec = None
+                if section is not None and i >= section:
+                    rec = dict(index=i, buf=buf, layers=[], transition=None, down=pending_down)
+                    plan.block_records.append(rec)
+                pending_down = None
+
+                def pw_record(name, rc, slices, y, y_off, off, bn, dw=None, dw_bn=None):
+                    return dict(index=int(name.split(".")[1]), rc=rc, slices=list(slices), segs=[(offs[k], _pad4(real[k])) for k in slices],
+                                seg_real=[real[k] for k in slices], cout=rc.cout_real, y=y, y_off=y_off, off=off, dw=dw, dw_bn=dw_bn,
+                                bn=plan.packed(name + ".bn", lambda: _bn_stats(bn, rc.cout, device)))
                 for li, comb in enumerate(m.layers, start=1):
                     link = m.links[li - 1]
                     segs = [(offs[k], _pad4(real[k])) for k in link]
                     cout, cp = real[li], _pad4(real[li])
-                    def make_layer1(comb=comb, link=link, cp=cp, cout=cout):
-                        wg = _gathered_weight(comb.layer1.conv.weight, [real[k] for k in link], cp)
-                        sc, sh = fold_bn(comb.layer1.norm)
-                        return _RawConv(wg, _padded(sc, cp), _padded(sh, cp), device, ACT_RELU6,
-                                        cin_real=sum(real[k] for k in link), cout_real=cout)
-                    rc = plan.packed(f"base.{i}.layers.{li - 1}.layer1", make_layer1)
+                    name = f"base.{i}.layers.{li - 1}.layer1"
+                    rc = plan.packed(name, lambda name=name: self._pw_pack(name, device))
                     tmp = plan.pool.alloc((N, h, w, cp))
-                    plan.conv(rc, buf, tmp, segs=segs, name=f"base.{i}.layers.{li - 1}.layer1")
-                    emit_dw(tmp, 0, cout, comb.layer2.dwconv, comb.layer2.norm, 1, False, buf, offs[li],
-                            f"base.{i}.layers.{li - 1}.layer2")
-                    plan.pool.release(tmp)
+                    plan.conv(rc, buf, tmp, segs=segs, name=name)
+                    pack = emit_dw(tmp, 0, cout, comb.layer2.dwconv, comb.layer2.norm, 1, False, buf, offs[li],
+                                   f"base.{i}.layers.{li - 1}.layer2")
+                    if rec is not None:
+                        rec["layers"].append(pw_record(name, rc, link, tmp, 0, offs[li], comb.layer1.norm, pack, plan.packed(
+                            f"base.{i}.layers.{li - 1}.layer2.bn", lambda comb=comb, cp=cp: _bn_stats(comb.layer2.norm, cp, device))))
+                    else:
+                        plan.pool.release(tmp)
                 # transition 1x1 conv gathers the block's output slices (oldest first)
                 outs = m.output_slices()
                 i += 1
                 if isinstance(mods[i], nn.Dropout):
                     i += 1
                 tr = mods[i]
-                def make_transition(tr=tr, outs=outs):
-                    wg = _gathered_weight(tr.conv.weight, [real[k] for k in outs], tr.conv.weight.shape[0])
-                    sc, sh = fold_bn(tr.norm)
-                    return _RawConv(wg, sc, sh, device, ACT_RELU6, cin_real=sum(real[k] for k in outs))
-                rc = plan.packed(f"base.{i}", make_transition)
+                rc = plan.packed(f"base.{i}", lambda name=f"base.{i}": self._pw_pack(name, device))
                 dst, dst_off = dest_for(i + 1, rc.cout, h, w)
                 if isinstance(mods[i + 1], DWConvLayer):          # "downsample" dw3x3 at stride 1 follows
                     plan.pool.release(dst)
                     dst, dst_off = plan.pool.alloc((N, h, w, rc.cout)), 0
                 plan.conv(rc, buf, dst, segs=[(offs[k], _pad4(real[k])) for k in outs], out_off=dst_off, name=f"base.{i}")
-                plan.pool.release(buf)
+                if rec is not None:
+                    # (the last block's transition output is the tail's first input: its mask is taken there)
+                    last = not any(isinstance(later, HarDBlock) for later in mods[i + 1:])
+                    rec["transition"] = pw_record(f"base.{i}", rc, outs, None if last else dst, dst_off, 0, tr.norm)
+                else:
+                    plan.pool.release(buf)
                 cur, cur_off, cur_C = dst, dst_off, rc.cout
                 i += 1
             elif isinstance(m, DWConvLayer):
                 dst, dst_off = dest_for(i + 1, cur_C, h, w)
-                emit_dw(cur, cur_off, cur_C, m.dwconv, m.norm, m.dwconv.stride[0], False, dst, dst_off, f"base.{i}")
-                plan.pool.release(cur)
+                pack = emit_dw(cur, cur_off, cur_C, m.dwconv, m.norm, m.dwconv.stride[0], False, dst, dst_off, f"base.{i}")
+                if section is not None and i > section:           # between two blocks of the section: its input stays
+                    pending_down = dict(index=i, dw=pack, stride=m.dwconv.stride[0], dw_bn=plan.packed(
+                        f"base.{i}.bn", lambda m=m, cp=pack[3]: _bn_stats(m.norm, cp, device)))
+                else:
+                    plan.pool.release(cur)
                 cur, cur_off = dst, dst_off
                 i += 1
             elif isinstance(m, nn.Conv2d) and m.groups == m.in_channels and m.kernel_size == (3, 3):

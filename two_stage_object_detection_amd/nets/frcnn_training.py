@@ -205,9 +205,14 @@ class FasterRCNNTrainer(nn.Module):
     HarDNet, which no pretrained checkpoint holds) - the backward of tsod_gconv1x1_pair_f32 and tsod_dwconv3x3_f32 on HIP
     (DESIGN.md section 4.17).  The frozen-backbone check then applies to every backbone parameter except those six.
 
-    Not provided: the backward of the HIP backbone below its tail and train-mode BatchNorm (``head_grads`` fine-tunes the heads
-    on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail; ``features=`` trains a backbone that has autograd
-    of its own); gradients w.r.t. RoI coordinates; graph capture
+    ``backbone_grads=n`` (an int >= 1, at most the backbone's HarDBlocks): the same with ``feat_extra.train_blocks(n)`` - the
+    tail plus the last ``n`` HarDBlocks, their transition layers and the ``DWConvLayer``s between them
+    (``feat_extra.trainable_parameters()``, BN ``weight`` / ``bias`` included).  BatchNorm stays in eval
+    mode and the stem is never reached.
+
+    Not provided: the backward of the HIP backbone's stem and train-mode BatchNorm (``head_grads`` fine-tunes the heads
+    on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks; ``features=`` trains a
+    backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
     and tuning (the forward runs whatever plan the backbone holds).  ``eval_fn`` / ``calculate_metrics``: see there."""
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
@@ -215,12 +220,16 @@ class FasterRCNNTrainer(nn.Module):
         super().__init__()
         if head_img_size not in ("chw", "hw"):
             raise ValueError(f"head_img_size must be 'chw' (the reference's) or 'hw', got {head_img_size!r}")
-        if backbone_grads not in (None, "tail"):
-            raise ValueError(f"backbone_grads must be None or 'tail', got {backbone_grads!r}")
-        if backbone_grads == "tail" and not str(backbone).startswith("hardnet"):
-            raise ValueError(f"backbone_grads='tail' trains the HarDNet tail (the last four modules of feat_extra.base); "
-                             f"backbone {backbone!r} has none")
+        n_blocks = backbone_grads if isinstance(backbone_grads, int) and not isinstance(backbone_grads, bool) else None
+        if backbone_grads not in (None, "tail") and (n_blocks is None or n_blocks < 1):
+            raise ValueError(f"backbone_grads must be None, 'tail' or a number of HarDBlocks >= 1, got {backbone_grads!r}")
+        if backbone_grads is not None and not str(backbone).startswith("hardnet"):
+            raise ValueError(f"backbone_grads={backbone_grads!r} trains the HarDNet tail (the last four modules of "
+                             f"feat_extra.base) and the HarDBlocks before it; backbone {backbone!r} has none")
         self.feat_extra, feat_ch, native_stride = _make_extractor(backbone)
+        if n_blocks is not None and n_blocks > len(self.feat_extra._block_indices()):
+            raise ValueError(f"backbone_grads={n_blocks}: backbone {backbone!r} has {len(self.feat_extra._block_indices())} "
+                             "HarDBlocks")
         self.feat_stride = native_stride if (feat_stride == 16 and native_stride != 16) else feat_stride
         self.rpn_sigma = 1
         self.roi_sigma = 1
@@ -292,8 +301,15 @@ class FasterRCNNTrainer(nn.Module):
         head_size = img_size if self.head_img_size == "chw" else shape[2:]
         n_sample = self.proposal_target_creator.n_sample
         grads = self.head_grads and torch.is_grad_enabled()
-        tail = self.backbone_grads == "tail" and features is None and torch.is_grad_enabled()
-        if tail:
+        tail = self.backbone_grads is not None and features is None and torch.is_grad_enabled()
+        if tail and self.backbone_grads != "tail":
+            ours = {id(p) for p in self.feat_extra.train_blocks(self.backbone_grads).trainable_parameters()}
+            frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
+            if frozen:
+                raise TsodError(f"FasterRCNNTrainer(backbone_grads={self.backbone_grads}) reaches the backbone's tail and last "
+                                f"{self.backbone_grads} HarDBlocks only (feat_extra.trainable_parameters()); every other backbone "
+                                f"parameter must be frozen, but feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad")
+        elif tail:
             ours = {id(p) for p in self.feat_extra.tail_parameters()}
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
             if frozen:
@@ -308,7 +324,8 @@ class FasterRCNNTrainer(nn.Module):
                                 "trainer.feat_extra.requires_grad_(False)")
         self._refresh_packs()
         if tail:                     # the map with the tail's autograd node; from here on the features= path
-            features = self.feat_extra.train_tail(True)(x)
+            features = (self.feat_extra.train_tail(True) if self.backbone_grads == "tail"
+                        else self.feat_extra.train_blocks(self.backbone_grads))(x)
         feat_grad = features is not None and torch.is_grad_enabled() and features.requires_grad
         with hip_ops.ARENA.scope((self._uid, 0)):
             if features is None:
