@@ -671,6 +671,25 @@ int tsod_pw_wgrad_f32(const float *g, int64_t M, int32_t N, int32_t g_pitch, con
 int tsod_pw_dgrad_f32(const float *g, int64_t M, int32_t N, int32_t g_pitch, const float *w, const float *scale,
                       const tsod_pw_segs *segs, float *dx, int32_t dx_pitch, int32_t accumulate, tsod_stream_t stream);
 
+/* ---- the parameter gradients of HarDNet's first layer ----------------------------------------------
+ * y[n][oh][ow][o] = relu6(scale[o] * sum_{kh,kw,c} w[o][kh][kw][c] x4[n][oh s - 1 + kh][ow s - 1 + kw][c] + shift[o]), s = stride
+ * (1 or 2), pad 1, OH = (H - 1) / s + 1, OW = (W - 1) / s + 1.  x4 [N][H][W][4] (channel 3 is padding and is never read), y
+ * [N][OH][OW][Cout_pad] the forward's saved output, dy [N][OH][OW][dy_pitch] (columns [dy_off, dy_off + Cout_pad)), w
+ * [Cout_pad][3][3][4] the unscaled weight, scale [Cout_pad].  Cout_pad a multiple of 4, at most 64.  There is no dx.
+ * tsod_conv3x3_wgrad_f32: g = dy * [0 < y < 6] (both strict) taken from y inside the kernel; dWraw = sum_{n,oh,ow} g * patch on
+ *   v_mfma_f32_32x32x2_f32 over slices of whole output rows (at most 512 slices, at least 256 pixel pairs each; the shape alone
+ *   fixes them), a finishing launch adds the slices in slice order and writes dw [Cout_pad][3][3][4] = scale[o] * dWraw, dscale
+ *   [Cout_pad] = sum over the 27 real taps of w * dWraw (ascending kh, kw, c), dshift [Cout_pad] = sum g.  Rows o >= Cout_real
+ *   and channel 3 of dw are exact zeros.  Each of the three may be NULL (not all).  No float atomics; bit-identical from run
+ *   to run.  16-byte aligned pointers; dy_pitch and dy_off multiples of 4.
+ *   workspace: tsod_conv3x3_wgrad_workspace_bytes(N, H, W, Cout_pad, stride) = slices * 32 ceil(Cout_pad / 32) * 33 floats; 0
+ *   for a shape the entry point refuses. */
+size_t tsod_conv3x3_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t Cout_pad, int32_t stride);
+int tsod_conv3x3_wgrad_f32(const float *x4, int32_t N, int32_t H, int32_t W, const float *y, const float *dy, int32_t dy_pitch,
+                           int32_t dy_off, const float *w, const float *scale, int32_t Cout_pad, int32_t Cout_real,
+                           int32_t stride, float *dw, float *dscale, float *dshift, void *workspace, size_t workspace_bytes,
+                           tsod_stream_t stream);
+
 /* ---- detection mAP: COCOeval's evaluateImg + accumulate, area range "all", no crowd / ignore flags ------
  * The reference's calculate_metrics (nets/frcnn_training.py:372-565) defines no usable metric; this is the project's own.
  * IoU is tsod_bbox_iou_f32's expression (eps 1e-8, no +1), compared as IoU >= t in f32.  Three steps:

@@ -1,0 +1,160 @@
+"""The stem backward's C ABI, the public switches of section 4.19 and the float64 restatement the GPU tests lean on: everything
+here runs without a GPU."""
+import ctypes
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from stem_grads_restated import STEM_NAMES, backbone_reference, conv3x3_layer_reference, stem_forward_plain  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _lib():
+    from two_stage_object_detection_amd import _ffi
+    if not os.path.exists(_ffi.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return _ffi, _ffi.lib()
+
+
+def test_exports_exist_in_header_binding_and_library():
+    _ffi, L = _lib()
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tsod.h")).read(), flags=re.S)
+    raw = ctypes.CDLL(_ffi.LIB_PATH)
+    for name, n_args in (("tsod_conv3x3_wgrad_workspace_bytes", 5), ("tsod_conv3x3_wgrad_f32", 19)):
+        decl = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", text, flags=re.S)
+        assert decl is not None, name
+        assert len(decl.group(1).split(",")) == n_args == len(_ffi._SIGNATURES[name][1]), name
+        assert hasattr(raw, name) and name in _ffi.EXPORTED_SYMBOLS, name
+    assert L.tsod_version() == 242
+
+
+def _status(L, rc):
+    return L.tsod_status_str(rc).decode().upper()
+
+
+def test_argument_errors():
+    """The entry point refuses bad arguments on the host, before any launch (the pointers are never dereferenced)."""
+    _, L = _lib()
+    A, odd = 0x10000, 0x10004                                   # a 16-byte aligned address and a misaligned one
+    ws = L.tsod_conv3x3_wgrad_workspace_bytes(2, 13, 18, 24, 2)
+    assert ws > 0
+
+    def call(x4=A, N=2, H=13, W=18, y=A, dy=A, dy_pitch=24, dy_off=0, w=A, scale=A, cp=24, cr=24, stride=2, dw=A, dsc=A, dsh=A,
+             wsp=A, wsb=ws):
+        return L.tsod_conv3x3_wgrad_f32(x4, N, H, W, y, dy, dy_pitch, dy_off, w, scale, cp, cr, stride, dw, dsc, dsh, wsp, wsb, None)
+
+    for null in ("x4", "y", "dy", "w", "scale"):
+        assert "INVALID" in _status(L, call(**{null: None})), null
+    assert "INVALID" in _status(L, call(dw=None, dsc=None, dsh=None))                 # nothing wanted
+    for mis in ("x4", "y", "dy", "w"):
+        assert "ALIGN" in _status(L, call(**{mis: odd})), mis
+    assert "ALIGN" in _status(L, call(dy_pitch=26))                                   # pitch not a multiple of 4
+    assert "ALIGN" in _status(L, call(dy_pitch=32, dy_off=6))
+    assert "ALIGN" in _status(L, call(cp=22, cr=22, dy_pitch=24))                     # Cout_pad not a multiple of 4
+    assert "INVALID" in _status(L, call(dy_pitch=20))                                 # pitch below Cout_pad
+    assert "INVALID" in _status(L, call(dy_pitch=24, dy_off=4))                       # the offset runs past the pitch
+    assert "INVALID" in _status(L, call(cr=25))                                       # Cout_real > Cout_pad
+    assert "INVALID" in _status(L, call(cr=0))
+    assert "INVALID" in _status(L, call(stride=3))
+    assert "INVALID" in _status(L, call(stride=0))
+    assert "INVALID" in _status(L, call(N=0))
+    assert "WORKSPACE" in _status(L, call(wsb=ws - 4))
+    assert "WORKSPACE" in _status(L, call(wsp=None))
+    assert "WORKSPACE" in _status(L, call(wsp=odd))
+    assert call(cp=128, cr=128, dy_pitch=128) != 0                                    # wider than the kernel's two tiles
+
+
+def test_workspace_query_follows_the_slice_rule():
+    """Slices are whole output rows: at most 512 of them, at least 256 pixel pairs each; 33 floats per padded output channel."""
+    _, L = _lib()
+    q = L.tsod_conv3x3_wgrad_workspace_bytes
+
+    def slices(N, H, W, stride):
+        OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+        rows, ppr = N * OH, (OW + 1) // 2
+        per = max(-(-rows // 512), -(-256 // ppr))
+        return -(-rows // per)
+    assert q(0, 8, 8, 24, 2) == 0 and q(1, 0, 8, 24, 2) == 0 and q(1, 8, 0, 24, 2) == 0 and q(1, 8, 8, 0, 2) == 0
+    assert q(1, 8, 8, 24, 3) == 0 and q(1, 8, 8, 22, 2) == 0 and q(1, 8, 8, 128, 2) == 0
+    for N, H, W, s in ((2, 13, 18, 2), (1, 8, 7, 2), (2, 9, 9, 1), (2, 151, 201, 2), (1, 600, 600, 2), (8, 800, 1333, 2)):
+        for cp, tiles in ((24, 1), (32, 1), (48, 2), (64, 2)):
+            assert q(N, H, W, cp, s) == slices(N, H, W, s) * tiles * 32 * 33 * 4, (N, H, W, s, cp)
+    assert slices(2, 13, 18, 2) == 1 and slices(2, 151, 201, 2) == 26 and slices(1, 600, 600, 2) == 150
+    assert slices(8, 800, 1333, 2) == 458
+
+
+@pytest.mark.parametrize("arch", [39, 68])
+def test_train_full_and_backbone_grads_arguments(arch):
+    from two_stage_object_detection_amd.models.hardnet import HarDNetFeatureExtraction
+    from two_stage_object_detection_amd.nets.frcnn_training import FasterRCNNTrainer
+    m = HarDNetFeatureExtraction(depth_wise=True, arch=arch)
+    keys = list(m.state_dict())
+    n_blocks = len(m._block_indices())
+    assert m.train_full() is m and m._train_tail and m._train_blocks == n_blocks
+    assert [id(p) for p in m.trainable_parameters()] == [id(p) for p in m.parameters()]
+    names = [k for k, _ in m._trainable_named()]
+    assert names[:9] == STEM_NAMES and names == [k for k, _ in m.named_parameters()]
+    assert list(m.state_dict()) == keys
+    # train_blocks(all) stays "everything but the stem"; one more keeps raising
+    assert len(m.train_blocks(n_blocks).trainable_parameters()) == len(list(m.parameters())) - 9
+    with pytest.raises(ValueError, match="train_blocks"):
+        m.train_blocks(n_blocks + 1)
+    m.train_full()
+    assert m.train_tail(False)._train_blocks == 0 and not m._train_tail and not m._train_full
+    assert [id(p) for p in m.trainable_parameters()] == [id(p) for p in m.tail_parameters()]
+    if arch == 39:
+        assert FasterRCNNTrainer("train", 20, backbone_grads="full").backbone_grads == "full"
+        with pytest.raises(ValueError, match="backbone_grads"):
+            FasterRCNNTrainer("train", 20, backbone="resnet50", backbone_grads="full")
+        with pytest.raises(ValueError, match="backbone_grads"):
+            FasterRCNNTrainer("train", 20, backbone_grads="all")
+
+
+def _seed_bn(mods):
+    for mod in mods:
+        if isinstance(mod, torch.nn.BatchNorm2d):
+            mod.running_mean.normal_(0, 0.2)
+            mod.running_var.uniform_(0.5, 1.5)
+            mod.weight.data.uniform_(0.5, 1.5)
+            mod.bias.data.normal_(0, 0.3)
+
+
+def test_restatement_against_plain_autograd_of_the_stem():
+    """backbone_reference, fed the plain forward's own float64 outputs as the 'saved' ones, is plain autograd of the modules."""
+    from two_stage_object_detection_amd.models.hardnet import ConvLayer, DWConvLayer
+    torch.manual_seed(5)
+    c0, c1 = 6, 10
+    m0, m1, m2 = ConvLayer(3, c0, 3, stride=2).double().eval(), ConvLayer(c0, c1, 1).double().eval(), DWConvLayer(c1, stride=2).double().eval()
+    _seed_bn([mod for m in (m0, m1, m2) for mod in m.modules()])
+    x = torch.randn(2, 3, 9, 12, dtype=torch.float64) * 2
+    params = dict([(f"base.{i}.{k}", p) for i, m in enumerate((m0, m1, m2)) for k, p in m.named_parameters()])
+    assert list(params) == STEM_NAMES
+    y0, y1, out = stem_forward_plain(m0, m1, m2, x)
+    gy = torch.randn(out.shape, dtype=torch.float64)
+    plain = torch.autograd.grad(out, list(params.values()), gy)
+    with torch.no_grad():
+        y0, y1, out = stem_forward_plain(m0, m1, m2, x)
+    assert sum(int(((y <= 0) | (y >= 6)).sum()) for y in (y0, y1)) > 0                  # (the mask is exercised)
+    ref = backbone_reference(dict(m0=m0, m1=m1, m2=m2, x=x, y0=y0, y1=y1, out=out), [], None, gy)
+    assert list(ref) == STEM_NAMES
+    for (name, p), g in zip(params.items(), plain):
+        got, T, n = ref[name]
+        assert got.shape == p.shape and n > 0 and bool((T >= got.abs() * (1 - 1e-12)).all()), name
+        assert float((got - g).abs().max()) <= 1e-12 * float(g.abs().max()), name
+    # the first layer alone, in its folded form, against the same autograd
+    inv = 1.0 / torch.sqrt(m0.norm.running_var + m0.norm.eps)
+    scale = (m0.norm.weight * inv).detach()
+    shift = (m0.norm.bias - m0.norm.running_mean * scale).detach()
+    y0g = m0(x)
+    d0 = torch.autograd.grad(m2(m1(y0g)), y0g, gy)[0]
+    one = conv3x3_layer_reference(x, m0.conv.weight, scale, shift, y0, d0, 2)
+    dsc, dsh = one["dscale"][0], one["dshift"][0]
+    assert float((one["dw"][0] - plain[0]).abs().max()) <= 1e-12 * float(plain[0].abs().max())
+    assert float(((dsc - m0.norm.running_mean * dsh) * inv - plain[1]).abs().max()) <= 1e-12 * max(1.0, float(plain[1].abs().max()))
+    assert float((dsh - plain[2]).abs().max()) <= 1e-12 * float(plain[2].abs().max())

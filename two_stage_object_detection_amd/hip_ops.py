@@ -544,6 +544,45 @@ def conv1x1_bn_relu6_grad(x, segs, w, scale, y, dy, *, seg_real=None, seg_want=N
     return (dx if want_dx else None), dw, dscale, dshift
 
 
+def conv3x3_bn_relu6_grad(x4, w, scale, y, dy, *, stride=2, cout=None, dy_off=0, want_dw=True, want_dscale=True,
+                          want_dshift=True, raw=False):
+    """The parameter gradients of HarDNet's first layer y = relu6(scale * conv3x3(x4, w, stride, pad 1) + shift) (DESIGN.md
+    section 4.19; tsod_conv3x3_wgrad_f32) -> (dW [cout,3,3,3] in torch's layout or None, dscale [cout] or None, dshift [cout]
+    or None).  There is no dx: the image has no gradient.
+
+    x4 [N,H,W,4]: the image padded to four channels (channel 3 is never read).  w [cout_pad,3,3,4]: the unscaled packed weight,
+    scale [cout_pad] the folded BN scale, ``cout`` the real output channels (default cout_pad).  y [N,OH,OW,cout_pad]: the
+    forward's saved output, the ReLU6 mask is taken from it inside the kernel (strict 0 < y < 6).  dy [N,OH,OW,>= dy_off +
+    cout_pad] contiguous (channels [dy_off, dy_off + cout_pad)).  ``raw``: the kernel's own padded outputs instead, dW
+    [cout_pad,3,3,4] and [cout_pad] vectors (pad rows and channel 3 are exact zeros)."""
+    require_cuda(x4, "conv3x3_bn_relu6_grad")
+    if not (x4.is_contiguous() and w.is_contiguous() and scale.is_contiguous() and y.is_contiguous() and dy.is_contiguous()):
+        raise ValueError("conv3x3_bn_relu6_grad: x4, w, scale, y and dy must be contiguous")
+    N, H, W, P = x4.shape
+    cp = w.shape[0]
+    if P != 4 or tuple(w.shape[1:]) != (3, 3, 4):
+        raise ValueError(f"conv3x3_bn_relu6_grad: x4 must be [N,H,W,4] and w [cout_pad,3,3,4], got {tuple(x4.shape)}, {tuple(w.shape)}")
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if tuple(y.shape) != (N, OH, OW, cp) or tuple(dy.shape[:3]) != (N, OH, OW):
+        raise ValueError(f"conv3x3_bn_relu6_grad: y {tuple(y.shape)} / dy {tuple(dy.shape)} do not match [{N},{OH},{OW},{cp}]")
+    if not (want_dw or want_dscale or want_dshift):
+        raise ValueError("conv3x3_bn_relu6_grad: nothing is wanted")
+    cout = cp if cout is None else int(cout)
+    dev = x4.device
+    dw = torch.empty((cp, 3, 3, 4), dtype=torch.float32, device=dev) if want_dw else None
+    dscale = torch.empty(cp, dtype=torch.float32, device=dev) if want_dscale else None
+    dshift = torch.empty(cp, dtype=torch.float32, device=dev) if want_dshift else None
+    L = lib()
+    ws_bytes = L.tsod_conv3x3_wgrad_workspace_bytes(N, H, W, cp, int(stride))
+    ws = ARENA.get(dev, ws_bytes) if ws_bytes else None
+    check(L.tsod_conv3x3_wgrad_f32(ptr(x4), N, H, W, ptr(y), ptr(dy), dy.shape[3], int(dy_off), ptr(w), ptr(scale), cp, cout,
+                                   int(stride), ptr(dw), ptr(dscale), ptr(dshift), ptr(ws), ws_bytes, stream_ptr()), "conv3x3_wgrad")
+    if raw:
+        return dw, dscale, dshift
+    return (None if dw is None else dw[:cout, :, :, :3].permute(0, 3, 1, 2).contiguous(),
+            None if dscale is None else dscale[:cout], None if dshift is None else dshift[:cout])
+
+
 class _DWConv3x3(torch.autograd.Function):
     """``dwconv3x3_nhwc`` as an autograd node: forward tsod_dwconv3x3_f32, backward tsod_dwconv3x3_grad_f32 (one call gives
     all four gradients; d x is skipped when not asked for, the others are dropped)."""

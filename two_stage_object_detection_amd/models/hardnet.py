@@ -268,18 +268,19 @@ class _BlockGrads(torch.autograd.Function):
                     f"base.{ip}.weight": None if d_wg is None else d_wg.view(-1, 2, 1, 1), f"base.{ip}.bias": d_bias})
 
         # ---- the blocks, last first; g = the masked gradient of the block's transition layer
-        blocks = sv["blocks"]
+        blocks, stem = sv["blocks"], sv.get("stem")
         for bi in range(len(blocks) - 1, -1, -1):
             blk = blocks[bi]
             first, buf = bi == 0, blk["buf"]
             dbuf = torch.zeros_like(buf)
             tr = blk["transition"]
-            pw_layer(f"base.{tr['index']}", buf, tr, g, dbuf, [not (first and k == 0) for k in tr["slices"]])
+            skip0 = first and stem is None                        # the first block's input slice: wanted by the stem only
+            pw_layer(f"base.{tr['index']}", buf, tr, g, dbuf, [not (skip0 and k == 0) for k in tr["slices"]])
             for li in range(len(blk["layers"]), 0, -1):
                 lay = blk["layers"][li - 1]
                 prefix = f"base.{blk['index']}.layers.{li - 1}"
                 g = dw_layer(prefix + ".layer2", lay["y"], lay["dw"], lay["dw_bn"], lay["cout"], 1, dbuf, lay["off"])
-                pw_layer(prefix + ".layer1", buf, lay, g, dbuf, [not (first and k == 0) for k in lay["slices"]])
+                pw_layer(prefix + ".layer1", buf, lay, g, dbuf, [not (skip0 and k == 0) for k in lay["slices"]])
             if first:
                 break
             prev = blocks[bi - 1]["transition"]
@@ -288,12 +289,28 @@ class _BlockGrads(torch.autograd.Function):
                 g = dw_layer(f"base.{down['index']}", prev["y"], down["dw"], down["dw_bn"], prev["cout"], down["stride"], dbuf, 0)
             else:                                                 # the transition wrote slice 0 itself
                 g = hip_ops.relu6_grad_mask(prev["y"], dbuf, 0)
+        # ---- the stem (section 4.19): base.2 reads slice 0 of the first block's gradient, base.1 is a one-segment 1x1 layer,
+        # base.0 has parameter gradients only (tsod_conv3x3_wgrad_f32 takes its mask from the saved output)
+        if stem is not None:
+            lay1 = stem["base1"]
+            g = dw_layer("base.2", lay1["y"], stem["dw"], stem["dw_bn"], lay1["cout"], 2, dbuf, 0)
+            d0 = torch.zeros_like(stem["y0"])
+            pw_layer("base.1", stem["y0"], lay1, g, d0, [True])
+            want_w, (want_g, want_b) = need["base.0.conv.weight"], wants("base.0.norm")
+            if want_w or want_g or want_b:
+                c0 = stem["y0"].shape[3]
+                d_w, d_sc, d_sh = hip_ops.conv3x3_bn_relu6_grad(stem["x4"], stem["w0"], stem["scale0"], stem["y0"], d0, stride=2,
+                                                                want_dw=want_w, want_dscale=want_g, want_dshift=True)
+                out["base.0.conv.weight"] = d_w
+                out["base.0.norm.weight"], out["base.0.norm.bias"] = _bn_grads(d_sh if d_sc is None else d_sc, d_sh,
+                                                                               stem["bn0"], c0)
         return (None,) + tuple(out.get(k) if n else None for k, n in need.items())
 
 
 class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     _train_tail = False          # train_tail(): the last four modules of ``base`` are differentiable (default off)
     _train_blocks = 0            # train_blocks(n): ... and the last n HarDBlocks with their transition layers (default 0)
+    _train_full = False          # train_full(): ... and the stem, base.0 - base.2: every parameter (default off)
 
     def __init__(self, depth_wise=True, arch=39):
         super().__init__()
@@ -350,7 +367,7 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         800x1333 batch 8), held until the node is freed; the plan for grad mode off is a second plan of the same shape."""
         self._train_tail = bool(enabled)
         if not enabled:
-            self._train_blocks = 0
+            self._train_blocks, self._train_full = 0, False
         return self
 
     # -- the trainable HarDBlocks (DESIGN.md section 4.18) -----------------------------------------
@@ -364,7 +381,8 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     def train_blocks(self, n: int):
         """Make the tail AND the last ``n`` HarDBlocks differentiable - every ``CombConvLayer`` of those blocks, each block's
         transition ``ConvLayer`` and any ``DWConvLayer`` between them; ``n = 0`` is ``train_tail(True)``'s state, ``n`` larger
-        than the number of HarDBlocks raises ValueError.  The stem (``base.0`` - ``base.2``) is never reached, and BatchNorm
+        than the number of HarDBlocks raises ValueError.  The stem (``base.0`` - ``base.2``) is never reached (``train_full``
+        adds it), and BatchNorm
         stays in eval mode: its ``weight`` / ``bias`` get gradients through the folded scale / shift, its running statistics
         are constants.  Contract as ``train_tail``: eval() only; with grad mode on the feature map carries an autograd node
         (``_BlockGrads``; HIP kernels of csrc/pw_grads.hip and csrc/dw_grads.hip) that gives the gradients of
@@ -389,8 +407,31 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         n = int(n)
         if n < 0 or n > len(self._block_indices()):
             raise ValueError(f"train_blocks: n must be 0..{len(self._block_indices())} (the HarDBlocks of this backbone), got {n}")
-        self._train_tail, self._train_blocks = True, n
+        self._train_tail, self._train_blocks, self._train_full = True, n, False
         self.__dict__["_blocks_watch"] = max(n, self.__dict__.get("_blocks_watch", 0))
+        return self
+
+    # -- the whole backbone ------------------------------------------------
+    def train_full(self):
+        """``train_blocks(all the HarDBlocks)`` plus the stem: ``base.0`` (3x3 stride-2 ConvLayer on the image), ``base.1`` (1x1
+        ConvLayer) and ``base.2`` (stride-2 DWConvLayer).  ``trainable_parameters()`` is then every parameter of the module in
+        ``base`` order.  The contract is ``train_blocks``' otherwise: eval() only, BatchNorm folded (``weight`` / ``bias`` get
+        gradients through the folded scale / shift), a plan of its own that runs the same launches and returns the same bits,
+        nothing for the image, in-place updates noticed through ``_version`` before the next forward of any kind and every
+        image the packed ``base.0`` / ``base.1`` hold (f32 pack, folded scale / shift, bf16x3 and fp16x2 images) and
+        ``base.2``'s depthwise pack rewritten in place.  ``train_blocks(n)`` goes back to "everything but the stem",
+        ``train_tail(False)`` switches everything off.
+
+        ``f.grad_fn.saved`` gains ``stem``: ``x4`` (the image as the plan staged it, [N,H,W,4]), ``y0`` (``base.0``'s output),
+        ``w0`` / ``scale0`` / ``bn0`` (its packed weight [c0,3,3,4], folded scale, BN statistics), ``base1`` (``base.1`` with the
+        keys of a block layer, ``y`` its output) and ``dw`` / ``dw_bn`` (``base.2``'s depthwise pack and BN statistics).
+
+        Memory on top of ``train_blocks(all)``: N x H x W x 4 floats of image and N x H/2 x W/2 x (c0 + c1) floats of stem
+        outputs, twice (plan and node), plus one gradient buffer of ``base.0``'s output during the backward: HarDNet-39 at
+        600 x 600, batch 1: 5.8 + 25.9 MB; at 800 x 1333, batch 8: 137 + 615 MB."""
+        self.train_blocks(len(self._block_indices()))
+        self._train_full = True
+        self.__dict__["_stem_watch"] = True
         return self
 
     def trainable_parameters(self):
@@ -403,8 +444,8 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         if not self._train_blocks:
             i1, i2, ip = self._tail_indices()
             return [(f"base.{i}.{k}", getattr(self.base[i], k)) for i in (i1, i2, ip) for k in ("weight", "bias")]
-        return [(f"base.{i}.{k}", p) for i in range(self._section_start(self._train_blocks), len(self.base))
-                for k, p in self.base[i].named_parameters()]
+        first = 0 if self._train_full else self._section_start(self._train_blocks)
+        return [(f"base.{i}.{k}", p) for i in range(first, len(self.base)) for k, p in self.base[i].named_parameters()]
 
     def _tail_active(self) -> bool:
         return self._train_tail and torch.is_grad_enabled()
@@ -412,7 +453,12 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     def _blocks_active(self) -> int:
         return self._train_blocks if self._tail_active() else 0
 
+    def _full_active(self) -> bool:
+        return self._train_full and self._blocks_active() > 0
+
     def _plan_variant(self):
+        if self._full_active():
+            return ("train_full",)
         if self._blocks_active():
             return ("train_blocks", self._blocks_active())
         return ("train_tail",) if self._tail_active() else ()
@@ -425,7 +471,8 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
             return
         seen = self.__dict__.setdefault("_block_versions", {})
         stale = []
-        for i in range(self._section_start(n), self._tail_indices()[0]):
+        first = 0 if self.__dict__.get("_stem_watch") else self._section_start(n)     # (train_full was on: the stem too)
+        for i in range(first, self._tail_indices()[0]):
             m = self.base[i]
             units = [(f"base.{i}", m)] if not isinstance(m, HarDBlock) else \
                 [(f"base.{i}.layers.{l}.{k}", getattr(comb, k)) for l, comb in enumerate(m.layers) for k in ("layer1", "layer2")]
@@ -439,7 +486,9 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 if key != name:
                     continue
                 with torch.inference_mode():                  # (the packs may have been made under inference mode)
-                    if isinstance(old, _RawConv):
+                    if isinstance(old, PackedConv):           # the stem's base.0 / base.1
+                        self._rewrite_raw_conv(old, self._stem_pack(name, device))
+                    elif isinstance(old, _RawConv):
                         self._rewrite_raw_conv(old, self._pw_pack(name, device))
                     else:
                         parts = name.split(".")
@@ -470,6 +519,14 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 self._bump_version()
             img.copy_(hip_ops.pack_conv_weight_fp16x2(old.w, e))
             old.w2 = (img, e)
+
+    def _stem_pack(self, name, device):
+        """The packed form of ``base.0`` (3x3 stride 2, the image padded to 4 channels) or ``base.1`` (1x1)."""
+        if name == "base.0":
+            m0 = self.base[0]
+            return PackedConv(m0.conv.weight, device, bn=m0.norm, stride=2, pad=1, act=ACT_RELU6, cin_pad=4)
+        m1 = self.base[1]
+        return PackedConv(m1.conv.weight, device, bn=m1.norm, act=ACT_RELU6)
 
     def _pw_pack(self, name, device):
         """The packed form of the 1x1 ConvLayer ``name`` (a HarDBlock layer's ``layer1`` or a transition layer): the weight
@@ -543,6 +600,14 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                                   transition=layer_copy(b["transition"]),
                                   down=None if b["down"] is None else dict(b["down"], dw=tuple(t.clone() for t in b["down"]["dw"][:3])))
                              for b in plan.block_records])
+        if plan.stem_record is not None:
+            sr = plan.stem_record
+            pc0, pc1 = sr["pc0"], sr["pc1"]
+            saved["stem"] = dict(
+                x4=plan.input_nhwc.clone(), y0=sr["y0"].clone(), w0=pc0.w.clone(), scale0=pc0.scale.clone(), bn0=sr["bn0"],
+                base1=dict(index=1, off=0, cout=pc1.cout, segs=[(0, pc1.cin)], seg_real=[pc1.cin], slices=[0],
+                           w=pc1.w.view(pc1.cout, -1).clone(), scale=pc1.scale.clone(), bn=sr["bn1"], y=sr["y1"].clone()),
+                dw=tuple(t.clone() for t in sr["dw"][:3]), dw_bn=sr["dw_bn"])
         return _BlockGrads.apply(saved, *self.trainable_parameters())
 
     def forward_nhwc(self, x, slot: int = 0):
@@ -588,6 +653,8 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         plan.tail_inputs, plan.tail_packs = [], []
         section = self._section_start(self._blocks_active()) if self._blocks_active() else None
         plan.block_records, pending_down = [], None
+        full = self._full_active()
+        plan.stem_record = None
 
         def dest_for(next_idx, C, h, w):
             """Where the tensor feeding module ``next_idx`` must be written: slice 0 of the next
@@ -607,17 +674,26 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
 
         # --- stem: 3x3 s2 conv (3 -> c0, input padded to 4 channels), 1x1 conv, dw3x3 s2
         m0, m1, m2 = mods[0], mods[1], mods[2]
-        pc0 = plan.packed("base.0", lambda: PackedConv(m0.conv.weight, device, bn=m0.norm, stride=2, pad=1, act=ACT_RELU6,
-                                                       cin_pad=4))
+        pc0 = plan.packed("base.0", lambda: self._stem_pack("base.0", device))
         h, w = pc0.out_hw(H, W)
         t0 = plan.conv(pc0, x4, plan.pool.alloc((N, h, w, pc0.cout)), name="base.0")
-        pc1 = plan.packed("base.1", lambda: PackedConv(m1.conv.weight, device, bn=m1.norm, act=ACT_RELU6))
+        pc1 = plan.packed("base.1", lambda: self._stem_pack("base.1", device))
         t1 = plan.conv(pc1, t0, plan.pool.alloc((N, h, w, pc1.cout)), name="base.1")
-        plan.pool.release(t0)
+        if not full:
+            plan.pool.release(t0)
         h2, w2 = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         cur, cur_off = dest_for(3, pc1.cout, h2, w2)
-        emit_dw(t1, 0, pc1.cout, m2.dwconv, m2.norm, 2, False, cur, cur_off, "base.2")
-        plan.pool.release(t1)
+        pack2 = emit_dw(t1, 0, pc1.cout, m2.dwconv, m2.norm, 2, False, cur, cur_off, "base.2")
+        if full:
+            # train_full: the stem's two outputs stay out of the pool (the autograd node copies them and the staged image after
+            # the run); the launches are the same
+            plan.stem_record = dict(
+                y0=t0, y1=t1, pc0=pc0, pc1=pc1, dw=pack2,
+                bn0=plan.packed("base.0.bn", lambda: _bn_stats(m0.norm, pc0.cout, device)),
+                bn1=plan.packed("base.1.bn", lambda: _bn_stats(m1.norm, pc1.cout, device)),
+                dw_bn=plan.packed("base.2.bn", lambda: _bn_stats(m2.norm, pack2[3], device)))
+        else:
+            plan.pool.release(t1)
         cur_C = pc1.cout
         h, w = h2, w2
 

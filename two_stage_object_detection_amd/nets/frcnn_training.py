@@ -210,8 +210,12 @@ class FasterRCNNTrainer(nn.Module):
     (``feat_extra.trainable_parameters()``, BN ``weight`` / ``bias`` included).  BatchNorm stays in eval
     mode and the stem is never reached.
 
-    Not provided: the backward of the HIP backbone's stem and train-mode BatchNorm (``head_grads`` fine-tunes the heads
-    on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks; ``features=`` trains a
+    ``backbone_grads="full"``: the same with ``feat_extra.train_full()`` - every parameter of the backbone, the stem
+    (``base.0`` - ``base.2``) included; the frozen-backbone check has nothing left to refuse.
+
+    Not provided: train-mode BatchNorm and the ResNet backbones' backward (``head_grads`` fine-tunes the heads
+    on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks, ``"full"`` the whole
+    HarDNet; ``features=`` trains a
     backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
     and tuning (the forward runs whatever plan the backbone holds).  ``eval_fn`` / ``calculate_metrics``: see there."""
 
@@ -221,8 +225,8 @@ class FasterRCNNTrainer(nn.Module):
         if head_img_size not in ("chw", "hw"):
             raise ValueError(f"head_img_size must be 'chw' (the reference's) or 'hw', got {head_img_size!r}")
         n_blocks = backbone_grads if isinstance(backbone_grads, int) and not isinstance(backbone_grads, bool) else None
-        if backbone_grads not in (None, "tail") and (n_blocks is None or n_blocks < 1):
-            raise ValueError(f"backbone_grads must be None, 'tail' or a number of HarDBlocks >= 1, got {backbone_grads!r}")
+        if backbone_grads not in (None, "tail", "full") and (n_blocks is None or n_blocks < 1):
+            raise ValueError(f"backbone_grads must be None, 'tail', 'full' or a number of HarDBlocks >= 1, got {backbone_grads!r}")
         if backbone_grads is not None and not str(backbone).startswith("hardnet"):
             raise ValueError(f"backbone_grads={backbone_grads!r} trains the HarDNet tail (the last four modules of "
                              f"feat_extra.base) and the HarDBlocks before it; backbone {backbone!r} has none")
@@ -302,7 +306,9 @@ class FasterRCNNTrainer(nn.Module):
         n_sample = self.proposal_target_creator.n_sample
         grads = self.head_grads and torch.is_grad_enabled()
         tail = self.backbone_grads is not None and features is None and torch.is_grad_enabled()
-        if tail and self.backbone_grads != "tail":
+        if tail and self.backbone_grads == "full":
+            self.feat_extra.train_full()                                 # every backbone parameter: nothing left to refuse
+        elif tail and self.backbone_grads != "tail":
             ours = {id(p) for p in self.feat_extra.train_blocks(self.backbone_grads).trainable_parameters()}
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
             if frozen:
@@ -325,6 +331,7 @@ class FasterRCNNTrainer(nn.Module):
         self._refresh_packs()
         if tail:                     # the map with the tail's autograd node; from here on the features= path
             features = (self.feat_extra.train_tail(True) if self.backbone_grads == "tail"
+                        else self.feat_extra.train_full() if self.backbone_grads == "full"
                         else self.feat_extra.train_blocks(self.backbone_grads))(x)
         feat_grad = features is not None and torch.is_grad_enabled() and features.requires_grad
         with hip_ops.ARENA.scope((self._uid, 0)):
