@@ -171,3 +171,34 @@ def test_fused_mask_of_the_depthwise_backward(dev, stride):
     assert all(torch.equal(a, b) for a, b in zip(sliced, fused))
     if stride == 1:
         assert torch.equal(hip_ops.relu6_grad_mask(x, wide, 4), dy * mask)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,segs,pitch,slices", [
+    (999, 40, [(0, 72)], 72, 8),                       # one tile, a ragged last row pair, N and K short of the tile
+    (2001, 100, [(0, 100), (160, 132)], 296, 16),      # 2 x 2 tiles, a k-tile that straddles the hole (the operand cap: 20)
+])
+def test_wgrad_tile_is_one_tile_for_both_entry_points(dev, M, N, segs, pitch, slices):
+    """tsod_pw_wgrad_f32 (scale = 1, an already masked gradient) and tsod_wgrad_f32 on the contiguous gathered X run the same
+    tile (csrc/grad_reduce.h) over the same slices: dW and dshift / db are equal bit for bit.  Columns outside the segments
+    hold NaN: they are never read."""
+    from two_stage_object_detection_amd import hip_ops
+    from two_stage_object_detection_amd._ffi import lib
+    gen = torch.Generator().manual_seed(14)
+    K = sum(ln for _, ln in segs)
+    x = torch.full((M, pitch), float("nan"))
+    for o, ln in segs:
+        x[:, o:o + ln] = torch.randn(M, ln, generator=gen)
+    xg = torch.cat([x[:, o:o + ln] for o, ln in segs], 1).contiguous()
+    g = torch.randn(M, N, generator=gen)
+    w = torch.randn(N, K, generator=gen)
+    n_pad, k_pad = -(-N // 64) * 64, -(-K // 128) * 128
+    assert lib().tsod_pw_wgrad_workspace_bytes(M, N, K) == lib().tsod_wgrad_workspace_bytes(M, N, K) \
+        == slices * n_pad * (k_pad + 1) * 4, "both entry points must cut M into the same slices"
+    _, dw, _, dshift = hip_ops.conv1x1_bn_relu6_grad(x.to(dev), segs, w.to(dev), torch.ones(N, device=dev), None, g.to(dev),
+                                                     want_dx=False)
+    dw0, db0 = torch.empty(N, K, device=dev), torch.empty(N, device=dev)
+    hip_ops.wgrad(g.to(dev), xg.to(dev), dw0, db0)
+    assert torch.isfinite(dw).all() and torch.isfinite(dshift).all()
+    assert torch.equal(dw, dw0), "dW"
+    assert torch.equal(dshift, db0), "dshift / db0"

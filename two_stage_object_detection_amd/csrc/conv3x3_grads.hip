@@ -10,11 +10,9 @@
 // reach a result.  No float atomics; slices, the in-workgroup tree and the finishing sums depend on the shape only, so the
 // results are bit-identical from run to run.  The tap reads of x4 overlap (2.25x at stride 2, 9x at stride 1); they are left to
 // L1 / L2: a wave's 27 columns of one output pixel lie in three 48-byte runs of x4, and the next pair's runs share a cache line.
-#include "tsod_internal.h"
+#include "grad_reduce.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWaves = 8, kThreads = 64 * kWaves;
 constexpr int kCols = 32;                                            // 27 real (tap, channel) columns in one MFMA tile
@@ -53,15 +51,14 @@ inline bool conv3_wgrad_shape_ok(int64_t N, int64_t H, int64_t W, int cout_pad, 
 // D = A B on v_mfma_f32_32x32x2_f32 with two output pixels as K: A = g^T (32 o x 2 pixels: lane l holds o = l & 31 of pixel
 // l >> 5), B = the patches (2 pixels x 32 columns: lane l holds column l & 31 = 3 tap + c, tap = 3 kh + kw, of pixel l >> 5;
 // columns 27..31 are zeros).  A workgroup of 8 waves owns one slice of output rows and all OT tiles of 32 output channels; wave
-// v takes the pairs v, v + 8, ... of every row.  The waves are summed through LDS as a fixed tree (4..7 -> 0..3, 2..3 -> 0..1,
-// 1 -> 0), the two pixel halves of a column sum last.
+// v takes the pairs v, v + 8, ... of every row.  The waves are summed by tsod_wave_tree_sum (4..7 -> 0..3, 2..3 -> 0..1, 1 -> 0),
+// the two pixel halves of a column sum last.
 template <int OT>
 __global__ void __launch_bounds__(kThreads)
 conv3x3_wgrad_partial_kernel(const float *__restrict__ x4, int H, int W, const float *__restrict__ y, const float *__restrict__ dy,
                              int dy_pitch, int dy_off, int cout_pad, int stride, Conv3WgradShape sh, float *__restrict__ part,
                              float *__restrict__ part_b) {
-    constexpr int kAcc = OT * 17;                                       // per lane: OT x 16 tile values + OT column sums
-    __shared__ float lds[(kWaves / 2) * kAcc * 64];
+    __shared__ float lds[(kWaves / 2) * (OT * 17) * 64];                // per lane: OT x 16 tile values + OT column sums
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
     const int tap = c / 3, ch = c - 3 * tap, kh = tap / 3, kw = tap - 3 * kh;
@@ -69,7 +66,7 @@ conv3x3_wgrad_partial_kernel(const float *__restrict__ x4, int H, int W, const f
     bool o_ok[OT];
 #pragma unroll
     for (int t = 0; t < OT; ++t) o_ok[t] = 32 * t + c < cout_pad;
-    f32x16 acc[OT];
+    tsod_f32x16 acc[OT];
     float bsum[OT];
 #pragma unroll
     for (int t = 0; t < OT; ++t) {
@@ -101,7 +98,7 @@ conv3x3_wgrad_partial_kernel(const float *__restrict__ x4, int H, int W, const f
                     if (ok && o_ok[t]) {
                         const float yv = yrow[ow * cout_pad + 32 * t];
                         const float d = drow[ow * dy_pitch + 32 * t];
-                        a[t][u] = (yv > 0.f && yv < 6.f) ? d : 0.f;
+                        a[t][u] = tsod_relu6_open(yv) ? d : 0.f;
                     }
                 }
             }
@@ -114,29 +111,7 @@ conv3x3_wgrad_partial_kernel(const float *__restrict__ x4, int H, int W, const f
                 }
         }
     }
-#pragma unroll
-    for (int lo = kWaves / 2; lo >= 1; lo >>= 1) {
-        if (wave >= lo && wave < 2 * lo) {
-            float *dst = lds + (wave - lo) * (kAcc * 64);
-#pragma unroll
-            for (int t = 0; t < OT; ++t) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dst[(t * 17 + r) * 64 + lane] = acc[t][r];
-                dst[(t * 17 + 16) * 64 + lane] = bsum[t];
-            }
-        }
-        __syncthreads();
-        if (wave < lo) {
-            const float *src = lds + wave * (kAcc * 64);
-#pragma unroll
-            for (int t = 0; t < OT; ++t) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][r] += src[(t * 17 + r) * 64 + lane];
-                bsum[t] += src[(t * 17 + 16) * 64 + lane];
-            }
-        }
-        __syncthreads();
-    }
+    tsod_wave_tree_sum<kWaves, OT, OT>(acc, bsum, lds, wave, lane);
     if (wave != 0) return;
     float *out = part + (long)blockIdx.x * (OT * 32 * kCols);
     float *out_b = part_b + (long)blockIdx.x * (OT * 32);
@@ -150,21 +125,6 @@ conv3x3_wgrad_partial_kernel(const float *__restrict__ x4, int H, int W, const f
         const float both = bsum[t] + __shfl_xor(bsum[t], 32);
         if (h == 0) out_b[32 * t + c] = both;
     }
-}
-
-// src[0], src[stride], ... (count values) added in that order; 16 loads are in flight at a time, the adds stay serial
-__device__ inline float sum_in_slice_order(const float *__restrict__ src, long stride, int count) {
-    float sum = 0.f;
-    int z = 0;
-    for (; z + 16 <= count; z += 16) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = src[(z + u) * stride];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) sum += v[u];
-    }
-    for (; z < count; ++z) sum += src[z * stride];
-    return sum;
 }
 
 // One workgroup of 64 threads per output row o of the padded weight.  Thread t < 36 owns dW[o][t >> 2][t & 3]: dWraw = the
@@ -181,7 +141,7 @@ conv3x3_wgrad_finish_kernel(const float *__restrict__ part, const float *__restr
         const int k = t >> 2, ch = t & 3;
         const bool live = real && ch < 3;
         float raw = 0.f;
-        if (live && (dw || dscale)) raw = sum_in_slice_order(part + (long)o * kCols + 3 * k + ch, (long)o_pad * kCols, splits);
+        if (live && (dw || dscale)) raw = tsod_sum_in_slice_order(part + (long)o * kCols + 3 * k + ch, (long)o_pad * kCols, splits);
         if (dw) dw[o * 36 + t] = live ? scale[o] * raw : 0.f;
         if (live && dscale) prod[3 * k + ch] = w[o * 36 + t] * raw;
     }
@@ -193,7 +153,7 @@ conv3x3_wgrad_finish_kernel(const float *__restrict__ part, const float *__restr
         dscale[o] = s;
     }
     if (t == 63 && dshift) {
-        dshift[o] = real ? sum_in_slice_order(part_b + o, o_pad, splits) : 0.f;
+        dshift[o] = real ? tsod_sum_in_slice_order(part_b + o, o_pad, splits) : 0.f;
     }
 }
 

@@ -8,7 +8,7 @@
 // sums over pixels, computed as [pixel slice][quantity][channel] partials (a slice = one workgroup's share of the pixels,
 // summed inside the workgroup by a fixed tree) which a second launch adds in slice order; the input gradient is a gather
 // with a fixed tap order.  Slice count and tree depend on the shape only, so results are bit-identical from run to run.
-#include "tsod_internal.h"
+#include "grad_reduce.h"
 
 namespace {
 
@@ -141,8 +141,7 @@ dwconv3x3_grad_combine_kernel(const float *__restrict__ partials, int S, int C, 
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= kDwQuantities * C) return;
     const int i = t / C, c = t % C;
-    float sum = 0.f;
-    for (int s = 0; s < S; ++s) sum += partials[((long)s * kDwQuantities + i) * C + c];
+    const float sum = tsod_sum_in_slice_order(partials + (long)i * C + c, (long)kDwQuantities * C, S);
     if (i < 9) dw[i * C + c] = scale ? sum * scale[c] : sum;
     else if (i == 9) { if (dscale) dscale[c] = sum; }
     else dshift[c] = sum;
@@ -187,10 +186,7 @@ dwconv3x3_grad_input_kernel(const float *__restrict__ g, int g_pitch, int g_off,
         }
         if (xact) {
             const float4 v = *reinterpret_cast<const float4 *>(xact + (((long)n * H + ih) * W + iw) * x_pitch + x_off + 4 * c4);
-            acc.x = (v.x > 0.f && v.x < 6.f) ? acc.x : 0.f;
-            acc.y = (v.y > 0.f && v.y < 6.f) ? acc.y : 0.f;
-            acc.z = (v.z > 0.f && v.z < 6.f) ? acc.z : 0.f;
-            acc.w = (v.w > 0.f && v.w < 6.f) ? acc.w : 0.f;
+            acc = tsod_relu6_keep(acc, v);
         }
         float4 *dst = reinterpret_cast<float4 *>(dx + (((long)n * H + ih) * W + iw) * dx_pitch + dx_off + 4 * c4);
         if (accumulate) {
@@ -241,8 +237,7 @@ gconv1x1_pair_grad_combine_kernel(const float *__restrict__ partials, int S, int
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 3 * G) return;
     const int i = t / G, g = t % G;
-    float sum = 0.f;
-    for (int s = 0; s < S; ++s) sum += partials[((long)s * 3 + i) * G + g];
+    const float sum = tsod_sum_in_slice_order(partials + (long)i * G + g, 3L * G, S);
     if (i < 2) { if (dw) dw[2 * g + i] = sum; }
     else if (dbias) dbias[g] = sum;
 }
@@ -250,7 +245,6 @@ gconv1x1_pair_grad_combine_kernel(const float *__restrict__ partials, int S, int
 inline bool dw_grad_shape_ok(int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride) {
     return N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && (stride == 1 || stride == 2);
 }
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -258,7 +252,7 @@ extern "C" size_t tsod_dwconv3x3_grad_workspace_bytes(int32_t N, int32_t H, int3
     if (!dw_grad_shape_ok(N, H, W, C, stride)) return 0;
     const long pixels = (long)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);
     const red_geom g = reduction_geometry(pixels, C / 4);
-    const size_t partials = align256((size_t)g.S * kDwQuantities * C * sizeof(float));
+    const size_t partials = tsod_align_up((size_t)g.S * kDwQuantities * C * sizeof(float), 256);
     return partials + (relu_dx ? (size_t)pixels * C * sizeof(float) : 0);    // [partials | g = masked dy, for the dx gather]
 }
 
@@ -296,7 +290,7 @@ static int dwconv3x3_grad(const float *x, int32_t N, int32_t H, int32_t W, int32
     TSOD_REQUIRE(geo.QB <= 65535, TSOD_ERR_UNSUPPORTED);
     float *partials = static_cast<float *>(workspace);
     float *g_ws = (relu && dx) ? reinterpret_cast<float *>(static_cast<char *>(workspace) +
-                                                           align256((size_t)geo.S * kDwQuantities * C * sizeof(float)))
+                                                           tsod_align_up((size_t)geo.S * kDwQuantities * C * sizeof(float), 256))
                                : nullptr;
     hipStream_t st = tsod_stream(stream);
     const dim3 rgrid((unsigned)geo.S, (unsigned)geo.QB);
@@ -348,7 +342,7 @@ extern "C" int tsod_dwconv3x3_grad_act_f32(const float *x, int32_t N, int32_t H,
 extern "C" size_t tsod_gconv1x1_pair_grad_workspace_bytes(int64_t pixels, int32_t G) {
     if (pixels <= 0 || G <= 0) return 0;
     const red_geom g = reduction_geometry((long)pixels, G);
-    return align256((size_t)g.S * 3 * G * sizeof(float));
+    return tsod_align_up((size_t)g.S * 3 * G * sizeof(float), 256);
 }
 
 extern "C" int tsod_gconv1x1_pair_grad_f32(const float *in, int64_t pixels, int32_t G, int32_t in_pitch, const float *w,

@@ -360,17 +360,16 @@ struct SortWs {
     size_t bytes;
 };
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 SortWs sort_ws_layout(void *ws, long long n) {
     const long long nblk = tsod_cdiv(n, kRadixTile);
     SortWs w;
     char *p = static_cast<char *>(ws);
     size_t off = 0;
-    w.alt_keys = reinterpret_cast<unsigned long long *>(p + off); off += align256((size_t)n * 8);
-    w.alt_vals = reinterpret_cast<int *>(p + off);                off += align256((size_t)n * 4);
-    w.hist = reinterpret_cast<unsigned *>(p + off);               off += align256((size_t)nblk * 256 * 4);
-    w.totals = reinterpret_cast<unsigned *>(p + off);             off += align256(256 * 4);
+    w.alt_keys = reinterpret_cast<unsigned long long *>(p + off); off += tsod_align_up((size_t)n * 8, 256);
+    w.alt_vals = reinterpret_cast<int *>(p + off);                off += tsod_align_up((size_t)n * 4, 256);
+    w.hist = reinterpret_cast<unsigned *>(p + off);               off += tsod_align_up((size_t)nblk * 256 * 4, 256);
+    w.totals = reinterpret_cast<unsigned *>(p + off);             off += tsod_align_up(256 * 4, 256);
     w.bytes = off;
     return w;
 }
@@ -503,12 +502,12 @@ AccWs acc_ws_layout(void *ws, long long capacity, int C) {
     AccWs w;
     char *p = static_cast<char *>(ws);
     size_t off = 0;
-    w.keys = reinterpret_cast<unsigned long long *>(p + off);        off += align256((size_t)capacity * 8);
-    w.sorted_keys = reinterpret_cast<unsigned long long *>(p + off); off += align256((size_t)capacity * 8);
-    w.perm = reinterpret_cast<int *>(p + off);                       off += align256((size_t)capacity * 4);
-    w.masks = reinterpret_cast<unsigned *>(p + off);                 off += align256((size_t)capacity * 4);
-    w.seg_begin = reinterpret_cast<int *>(p + off);                  off += align256((size_t)C * 4);
-    w.seg_end = reinterpret_cast<int *>(p + off);                    off += align256((size_t)C * 4);
+    w.keys = reinterpret_cast<unsigned long long *>(p + off);        off += tsod_align_up((size_t)capacity * 8, 256);
+    w.sorted_keys = reinterpret_cast<unsigned long long *>(p + off); off += tsod_align_up((size_t)capacity * 8, 256);
+    w.perm = reinterpret_cast<int *>(p + off);                       off += tsod_align_up((size_t)capacity * 4, 256);
+    w.masks = reinterpret_cast<unsigned *>(p + off);                 off += tsod_align_up((size_t)capacity * 4, 256);
+    w.seg_begin = reinterpret_cast<int *>(p + off);                  off += tsod_align_up((size_t)C * 4, 256);
+    w.seg_end = reinterpret_cast<int *>(p + off);                    off += tsod_align_up((size_t)C * 4, 256);
     w.sort_ws = p + off;
     w.sort_bytes = sort_ws_layout(nullptr, capacity).bytes;
     off += w.sort_bytes;
@@ -522,7 +521,8 @@ size_t match_lds_bytes(int NP, int G) { return (size_t)NP * 8 + (size_t)G * (16 
 
 extern "C" size_t tsod_eval_match_workspace_bytes(int32_t B, int32_t R) {
     if (B <= 0 || R <= 0) return 0;
-    return align256((size_t)B * R * sizeof(tsod_eval_record)) + align256((size_t)B * 4) + align256((size_t)B * 8);
+    return tsod_align_up((size_t)B * R * sizeof(tsod_eval_record), 256) + tsod_align_up((size_t)B * 4, 256) +
+           tsod_align_up((size_t)B * 8, 256);
 }
 
 extern "C" int tsod_eval_match_f32(const float *det, int32_t B, int32_t R, const int32_t *counts, const int32_t *keep,
@@ -540,9 +540,9 @@ extern "C" int tsod_eval_match_f32(const float *det, int32_t B, int32_t R, const
     TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_match_workspace_bytes(B, R), TSOD_ERR_WORKSPACE);
     char *p = static_cast<char *>(workspace);
     tsod_eval_record *stage = reinterpret_cast<tsod_eval_record *>(p);
-    int *stage_counts = reinterpret_cast<int *>(p + align256((size_t)B * R * sizeof(tsod_eval_record)));
-    long long *offsets = reinterpret_cast<long long *>(p + align256((size_t)B * R * sizeof(tsod_eval_record)) +
-                                                       align256((size_t)B * 4));
+    int *stage_counts = reinterpret_cast<int *>(p + tsod_align_up((size_t)B * R * sizeof(tsod_eval_record), 256));
+    long long *offsets = reinterpret_cast<long long *>(p + tsod_align_up((size_t)B * R * sizeof(tsod_eval_record), 256) +
+                                                       tsod_align_up((size_t)B * 4, 256));
     int NP = 64;
     while (NP < R) NP <<= 1;
     const size_t lds = match_lds_bytes(NP, G);

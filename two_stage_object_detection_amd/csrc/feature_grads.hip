@@ -262,7 +262,6 @@ roi_align_gather_kernel(int B, int Hf, int Wf, int C, const float *__restrict__ 
     }
 }
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 dim3 gather_grid(int B, int Hf, int Wf, int C) {
     const long strips = (long)B * Hf * ((Wf + kStrip - 1) / kStrip);
@@ -274,7 +273,7 @@ dim3 gather_grid(int B, int Hf, int Wf, int C) {
 extern "C" size_t tsod_roi_pool_avg_grad_workspace_bytes(int32_t B, int32_t R, int32_t C, int32_t PH, int32_t PW) {
     if (B <= 0 || R <= 0 || C <= 0 || PH <= 0 || PW <= 0) return 0;
     const size_t K = (size_t)B * R;
-    return align16(K * sizeof(int4)) + K * (size_t)PH * PW * C * sizeof(uint16_t);
+    return tsod_align_up(K * sizeof(int4), 16) + K * (size_t)PH * PW * C * sizeof(uint16_t);
 }
 
 extern "C" int tsod_roi_pool_avg_grad_f32(const float *feat, int32_t B, int32_t Hf, int32_t Wf, int32_t C, int32_t feat_pitch,
@@ -293,7 +292,7 @@ extern "C" int tsod_roi_pool_avg_grad_f32(const float *feat, int32_t B, int32_t 
                  workspace_bytes >= tsod_roi_pool_avg_grad_workspace_bytes(B, R, C, PH, PW), TSOD_ERR_WORKSPACE);
     hipStream_t s = tsod_stream(stream);
     int4 *ext = static_cast<int4 *>(workspace);
-    uint16_t *rec = reinterpret_cast<uint16_t *>(static_cast<char *>(workspace) + align16((size_t)B * R * sizeof(int4)));
+    uint16_t *rec = reinterpret_cast<uint16_t *>(static_cast<char *>(workspace) + tsod_align_up((size_t)B * R * sizeof(int4), 16));
     hipLaunchKernelGGL(roi_pool_argmax_kernel, dim3((unsigned)tsod_cdiv(C / 4, kQuadsPerWave), B * R), dim3(256), 0, s, feat, B,
                        Hf, Wf, C, feat_pitch, rois, roi_indices, R, img_h, img_w, spatial_scale, PH, PW, ext, rec);
     hipLaunchKernelGGL(roi_pool_gather_kernel, gather_grid(B, Hf, Wf, C), dim3(256), 0, s, B, Hf, Wf, C, rois, roi_indices, R,

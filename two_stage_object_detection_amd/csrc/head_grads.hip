@@ -18,7 +18,7 @@
 // its M-slices in slice order in a second launch.
 // Empty sets follow torch's autograd: no positive -> the loc term gives zero gradients (the NaN loss has an empty
 // regression_diff); no counted row -> the CE term gives zero; |d| == 0 -> abs's zero subgradient.
-#include "tsod_internal.h"
+#include "grad_reduce.h"
 #include <math.h>
 
 namespace {
@@ -244,150 +244,19 @@ scatter_kernel(const float *__restrict__ d_sample_roi, const int32_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------- wgrad
-// dW[n][k] = sum_m dY[m][n] X[m][k] as D = A B with A = dY^T (32 n x 2 m), B = X (2 m x 32 k) on v_mfma_f32_32x32x2_f32:
-// lane l holds A[n = l & 31][m = l >> 5] and B[m = l >> 5][k = l & 31] (cdna_hip_programming.md section 3).  A workgroup
-// (4 waves) owns a 64 n x 128 k tile over one M-slice; every wave runs m-pairs w, w + 4, ... of the slice with 2 x 4
-// accumulators: one 16-byte load of X per lane feeds four MFMAs whose B columns are k0 + 4c + e (c = l & 31, e = 0..3),
-// so the k of accumulator e, C/D column c, is k0 + 4c + e.  C/D rows: (r & 3) + 8 (r >> 2) + 4 (l >> 5).
-// The four waves are summed in LDS in a fixed tree ((w0 + w2) + (w1 + w3)), the slice's partial tile goes to its own slab,
-// and wgrad_combine_kernel adds the slabs in slice order: bit-identical results run to run.  db comes from the k-tile-0
-// workgroups as f32 lane sums of the A operand, summed in the same fixed orders.
-constexpr int kWgThreads = 256;
-constexpr int kWgN = 64, kWgK = 128;
-constexpr int kMinPairsPerSlice = 64;
-constexpr int kTargetWorkgroups = 512;
-constexpr int kUnroll = 8;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct WgradShape {
-    int n_tiles, k_tiles, splits, pairs_per_split;
-    long n_pad, k_pad;
-};
-
-__host__ __device__ inline WgradShape wgrad_shape(long M, int N, int K) {
-    WgradShape s;
-    s.n_tiles = (N + kWgN - 1) / kWgN;
-    s.k_tiles = (K + kWgK - 1) / kWgK;
-    const long pairs = (M + 1) / 2;
-    const long tiles = (long)s.n_tiles * s.k_tiles;
-    long splits = (kTargetWorkgroups + tiles - 1) / tiles;
-    const long cap = (pairs + kMinPairsPerSlice - 1) / kMinPairsPerSlice;
-    if (splits > cap) splits = cap;
-    if (splits < 1) splits = 1;
-    s.pairs_per_split = (int)((pairs + splits - 1) / splits);
-    s.splits = (int)((pairs + s.pairs_per_split - 1) / s.pairs_per_split);
-    if (s.splits < 1) s.splits = 1;
-    s.n_pad = (long)s.n_tiles * kWgN;
-    s.k_pad = (long)s.k_tiles * kWgK;
-    return s;
-}
-
+// grad_reduce.h's tile with X read as it lies: gathered column k is column k.  wgrad_combine_kernel adds the slices' slabs in
+// slice order: bit-identical results run to run.
 __global__ void __launch_bounds__(kWgThreads)
 wgrad_partial_kernel(const float *__restrict__ dy, long M, int N, int dy_pitch, const float *__restrict__ x, int K, int x_pitch,
-                     WgradShape sh, float *__restrict__ part, float *__restrict__ part_b) {
-    __shared__ float lds[2 * 128 * 64];                               // 2 waves x 128 accumulators x 64 lanes (64 KiB)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tile = blockIdx.x, split = blockIdx.y;
-    const int nt = tile / sh.k_tiles, kt = tile - nt * sh.k_tiles;
-    const int n0 = nt * kWgN, k0 = kt * kWgK;
-    const int c = lane & 31, h = lane >> 5;
-    const long p_begin = (long)split * sh.pairs_per_split;
-    long p_end = p_begin + sh.pairs_per_split;
-    const long pairs = (M + 1) / 2;
-    if (p_end > pairs) p_end = pairs;
-    const bool k_ok = k0 + 4 * c < K;                                  // K % 4 == 0: a quad is all in or all out
-    const bool n_ok0 = n0 + c < N, n_ok1 = n0 + 32 + c < N;
-    const bool want_b = kt == 0;
-    f32x16 acc[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][e][r] = 0.f;
-    float bsum0 = 0.f, bsum1 = 0.f;
-    // kUnroll m-pairs of loads in flight per wave before their MFMAs (the loop is otherwise bound by the load latency)
-    for (long p0 = p_begin + wave; p0 < p_end; p0 += 4 * kUnroll) {
-        float4 xv[kUnroll];
-        float a0[kUnroll], a1[kUnroll];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const long p = p0 + 4 * u;
-            const long m = 2 * p + h;
-            xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            a0[u] = a1[u] = 0.f;
-            if (p < p_end && m < M) {
-                if (k_ok) xv[u] = *reinterpret_cast<const float4 *>(x + m * x_pitch + k0 + 4 * c);
-                const float *yr = dy + m * dy_pitch + n0;
-                if (n_ok0) a0[u] = yr[c];
-                if (n_ok1) a1[u] = yr[32 + c];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].x, acc[0][0], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].x, acc[1][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].y, acc[0][1], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].y, acc[1][1], 0, 0, 0);
-            acc[0][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].z, acc[0][2], 0, 0, 0);
-            acc[1][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].z, acc[1][2], 0, 0, 0);
-            acc[0][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].w, acc[0][3], 0, 0, 0);
-            acc[1][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].w, acc[1][3], 0, 0, 0);
-            if (want_b) { bsum0 += a0[u]; bsum1 += a1[u]; }
-        }
-    }
-    // fixed-order tree over the 4 waves: round 1 waves 2, 3 -> 0, 1; round 2 wave 1 -> 0
-#pragma unroll
-    for (int round = 0; round < 2; ++round) {
-        const int lo = round == 0 ? 2 : 1;                             // waves [lo, 2 lo) store, waves [0, lo) add
-        if (wave >= lo && wave < 2 * lo) {
-            float *dst = lds + (wave - lo) * (128 * 64);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) dst[((t * 4 + e) * 16 + r) * 64 + lane] = acc[t][e][r];
-        }
-        __syncthreads();
-        if (wave < lo) {
-            const float *src = lds + wave * (128 * 64);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[t][e][r] += src[((t * 4 + e) * 16 + r) * 64 + lane];
-        }
-        __syncthreads();
-    }
-    float *bl = lds;                                                   // the bias: lane halves, then waves in order
-    if (want_b) {
-        bsum0 += __shfl_xor(bsum0, 32);
-        bsum1 += __shfl_xor(bsum1, 32);
-        if (h == 0) { bl[wave * 64 + c] = bsum0; bl[wave * 64 + 32 + c] = bsum1; }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    float *out = part + (long)split * sh.n_pad * sh.k_pad;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long n = n0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-            *reinterpret_cast<float4 *>(out + n * sh.k_pad + k0 + 4 * c) =
-                make_float4(acc[t][0][r], acc[t][1][r], acc[t][2][r], acc[t][3][r]);
-        }
-    if (want_b) {
-        const float v = ((bl[lane] + bl[64 + lane]) + (bl[128 + lane] + bl[192 + lane]));
-        part_b[(long)split * sh.n_pad + n0 + lane] = v;
-    }
+                     tsod_wgrad_plan sh, float *__restrict__ part, float *__restrict__ part_b) {
+    __shared__ float lds[kWgLdsFloats];
+    // K % 4 == 0: a quad is all in or all out
+    tsod_wgrad_tile(dy, M, N, dy_pitch, x, x_pitch, [K](int k) { return k < K ? k : -1; }, sh, part, part_b, lds);
 }
 
 // dW rows [0, n0) -> dw0 / db0, rows [n0, n0 + n1) -> dw1 / db1 (row pitch K); the slabs are summed in slice order.
 __global__ void __launch_bounds__(256)
-wgrad_combine_kernel(const float *__restrict__ part, const float *__restrict__ part_b, WgradShape sh, int K, int n0, int n1,
+wgrad_combine_kernel(const float *__restrict__ part, const float *__restrict__ part_b, tsod_wgrad_plan sh, int K, int n0, int n1,
                      float *__restrict__ dw0, float *__restrict__ db0, float *__restrict__ dw1, float *__restrict__ db1,
                      int accumulate) {
     const long per_row = (long)K + 1;                                  // K weights + the bias
@@ -395,21 +264,13 @@ wgrad_combine_kernel(const float *__restrict__ part, const float *__restrict__ p
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int n = (int)(i / per_row);
         const int k = (int)(i - (long)n * per_row);
-        float s = 0.f;
+        float s;
         float *dst;
         if (k < K) {
-            const float *src = part + (long)n * sh.k_pad + k;
-            const long stride = (long)sh.n_pad * sh.k_pad;
-            for (int z0 = 0; z0 < sh.splits; z0 += 8) {                 // 8 loads in flight, summed in slice order
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = z0 + u < sh.splits ? src[(long)(z0 + u) * stride] : 0.f;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += v[u];
-            }
+            s = tsod_sum_in_slice_order(part + (long)n * sh.k_pad + k, sh.n_pad * sh.k_pad, sh.splits);
             dst = n < n0 ? dw0 + (long)n * K + k : dw1 + (long)(n - n0) * K + k;
         } else {
-            for (int z = 0; z < sh.splits; ++z) s += part_b[(long)z * sh.n_pad + n];
+            s = tsod_sum_in_slice_order(part_b + n, sh.n_pad, sh.splits);
             dst = n < n0 ? (db0 ? db0 + n : nullptr) : (db1 ? db1 + (n - n0) : nullptr);
             if (dst == nullptr) continue;
         }
@@ -463,8 +324,7 @@ extern "C" int tsod_rpn_roi_scatter_f32(const float *d_sample_roi, const int32_t
 
 extern "C" size_t tsod_wgrad_workspace_bytes(int64_t M, int32_t N, int32_t K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const WgradShape s = wgrad_shape(M, N, K);
-    return (size_t)s.splits * (size_t)s.n_pad * (size_t)(s.k_pad + 1) * sizeof(float);
+    return tsod_wgrad_plan_bytes(tsod_wgrad_plan_of(M, N, K, false));
 }
 
 extern "C" int tsod_wgrad_f32(const float *dy, int64_t M, int32_t N, int32_t dy_pitch, const float *x, int32_t K,
@@ -476,9 +336,9 @@ extern "C" int tsod_wgrad_f32(const float *dy, int64_t M, int32_t N, int32_t dy_
     TSOD_REQUIRE(tsod_aligned16(x), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace && workspace_bytes >= tsod_wgrad_workspace_bytes(M, N, K) && tsod_aligned16(workspace),
                  TSOD_ERR_WORKSPACE);
-    const WgradShape sh = wgrad_shape(M, N, K);
+    const tsod_wgrad_plan sh = tsod_wgrad_plan_of(M, N, K, false);
     float *part = static_cast<float *>(workspace);
-    float *part_b = part + (size_t)sh.splits * sh.n_pad * sh.k_pad;
+    float *part_b = tsod_wgrad_plan_bias(sh, part);
     hipStream_t s = tsod_stream(stream);
     hipLaunchKernelGGL(wgrad_partial_kernel, dim3(sh.n_tiles * sh.k_tiles, sh.splits), dim3(kWgThreads), 0, s,
                        dy, (long)M, N, dy_pitch, x, K, x_pitch, sh, part, part_b);

@@ -9,11 +9,9 @@
 //
 // No float atomics.  The M-slices' partial tiles are added in slice order; slice count, in-workgroup trees and the k order of a
 // row's dscale depend on the shape only, so results are bit-identical from run to run.
-#include "tsod_internal.h"
+#include "grad_reduce.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // gathered column k (over the padded segment widths, in segment order) -> channel of the buffer, or -1 past the end
 __host__ __device__ inline int pw_buffer_column(const tsod_pw_segs &sg, int k) {
@@ -44,160 +42,28 @@ relu6_grad_mask_kernel(const float *__restrict__ y, long rows, int C4, int y_pit
         const long m = t / C4;
         const int c = 4 * (int)(t - m * C4);
         const float4 v = *reinterpret_cast<const float4 *>(y + m * y_pitch + c);
-        float4 d = *reinterpret_cast<const float4 *>(dy + m * dy_pitch + dy_off + c);
-        d.x = (v.x > 0.f && v.x < 6.f) ? d.x : 0.f;
-        d.y = (v.y > 0.f && v.y < 6.f) ? d.y : 0.f;
-        d.z = (v.z > 0.f && v.z < 6.f) ? d.z : 0.f;
-        d.w = (v.w > 0.f && v.w < 6.f) ? d.w : 0.f;
-        *reinterpret_cast<float4 *>(g + m * g_pitch + c) = d;
+        const float4 d = *reinterpret_cast<const float4 *>(dy + m * dy_pitch + dy_off + c);
+        *reinterpret_cast<float4 *>(g + m * g_pitch + c) = tsod_relu6_keep(d, v);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- wgrad
-// The tile of head_grads.hip's wgrad (a workgroup of 4 waves owns 64 n x 128 k over one M-slice, every wave m-pairs w, w + 4,
-// ... with 2 x 4 accumulators, waves summed through LDS as (w0 + w2) + (w1 + w3)) with two differences: a lane's 16-byte load
-// of X goes to the buffer channel its gathered k maps to, and the slice count is bounded by the operands (pw_wgrad_shape).
-constexpr int kWgThreads = 256;
-constexpr int kWgN = 64, kWgK = 128;
-constexpr int kMinPairsPerSlice = 64;
-constexpr int kTargetWorkgroups = 512;
-constexpr int kUnroll = 8;
-
-struct PwWgradShape {
-    int n_tiles, k_tiles, splits, pairs_per_split;
-    long n_pad, k_pad;
-};
-
-// splits = what fills about 512 workgroups, but never more slabs than the operands are large: splits * n_pad * k_pad <=
-// M * (N + K) floats (g and x together), and at least 64 m-pairs per slice.  1024 x 732 at 150 x 150 pixels: 6 slices, 18.9 MB
-// of slabs beside 158 MB of operands; the same layer at 874 rows: one slice.
-__host__ __device__ inline PwWgradShape pw_wgrad_shape(long M, int N, int K) {
-    PwWgradShape s;
-    s.n_tiles = (N + kWgN - 1) / kWgN;
-    s.k_tiles = (K + kWgK - 1) / kWgK;
-    s.n_pad = (long)s.n_tiles * kWgN;
-    s.k_pad = (long)s.k_tiles * kWgK;
-    const long pairs = (M + 1) / 2;
-    const long tiles = (long)s.n_tiles * s.k_tiles;
-    long splits = (kTargetWorkgroups + tiles - 1) / tiles;
-    const long cap_rows = (pairs + kMinPairsPerSlice - 1) / kMinPairsPerSlice;
-    const long cap_bytes = M * ((long)N + K) / (s.n_pad * s.k_pad);
-    if (splits > cap_rows) splits = cap_rows;
-    if (splits > cap_bytes) splits = cap_bytes;
-    if (splits < 1) splits = 1;
-    s.pairs_per_split = (int)((pairs + splits - 1) / splits);
-    s.splits = (int)((pairs + s.pairs_per_split - 1) / s.pairs_per_split);
-    if (s.splits < 1) s.splits = 1;
-    return s;
-}
-
+// grad_reduce.h's tile with a lane's 16-byte load of X going to the buffer channel its gathered k maps to; the slice count is
+// also bounded by the operands (tsod_wgrad_plan_of's cap_by_operands).
 __global__ void __launch_bounds__(kWgThreads)
 pw_wgrad_partial_kernel(const float *__restrict__ g, long M, int N, int g_pitch, const float *__restrict__ x, int K, int x_pitch,
-                        tsod_pw_segs sg, PwWgradShape sh, float *__restrict__ part, float *__restrict__ part_b) {
-    __shared__ float lds[2 * 128 * 64];                               // 2 waves x 128 accumulators x 64 lanes (64 KiB)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tile = blockIdx.x, split = blockIdx.y;
-    const int nt = tile / sh.k_tiles, kt = tile - nt * sh.k_tiles;
-    const int n0 = nt * kWgN, k0 = kt * kWgK;
-    const int c = lane & 31, h = lane >> 5;
-    const long p_begin = (long)split * sh.pairs_per_split;
-    long p_end = p_begin + sh.pairs_per_split;
-    const long pairs = (M + 1) / 2;
-    if (p_end > pairs) p_end = pairs;
+                        tsod_pw_segs sg, tsod_wgrad_plan sh, float *__restrict__ part, float *__restrict__ part_b) {
+    __shared__ float lds[kWgLdsFloats];
     // segment widths are multiples of 4: a quad of gathered columns lies in one segment, or past K
-    const int xcol = k0 + 4 * c < K ? pw_buffer_column(sg, k0 + 4 * c) : -1;
-    const bool n_ok0 = n0 + c < N, n_ok1 = n0 + 32 + c < N;
-    const bool want_b = kt == 0;
-    f32x16 acc[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][e][r] = 0.f;
-    float bsum0 = 0.f, bsum1 = 0.f;
-    for (long p0 = p_begin + wave; p0 < p_end; p0 += 4 * kUnroll) {
-        float4 xv[kUnroll];
-        float a0[kUnroll], a1[kUnroll];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const long p = p0 + 4 * u;
-            const long m = 2 * p + h;
-            xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            a0[u] = a1[u] = 0.f;
-            if (p < p_end && m < M) {
-                if (xcol >= 0) xv[u] = *reinterpret_cast<const float4 *>(x + m * x_pitch + xcol);
-                const float *yr = g + m * g_pitch + n0;
-                if (n_ok0) a0[u] = yr[c];
-                if (n_ok1) a1[u] = yr[32 + c];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].x, acc[0][0], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].x, acc[1][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].y, acc[0][1], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].y, acc[1][1], 0, 0, 0);
-            acc[0][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].z, acc[0][2], 0, 0, 0);
-            acc[1][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].z, acc[1][2], 0, 0, 0);
-            acc[0][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], xv[u].w, acc[0][3], 0, 0, 0);
-            acc[1][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], xv[u].w, acc[1][3], 0, 0, 0);
-            if (want_b) { bsum0 += a0[u]; bsum1 += a1[u]; }
-        }
-    }
-    // fixed-order tree over the 4 waves: round 1 waves 2, 3 -> 0, 1; round 2 wave 1 -> 0 (lane-contiguous LDS rows: no conflicts)
-#pragma unroll
-    for (int round = 0; round < 2; ++round) {
-        const int lo = round == 0 ? 2 : 1;
-        if (wave >= lo && wave < 2 * lo) {
-            float *dst = lds + (wave - lo) * (128 * 64);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) dst[((t * 4 + e) * 16 + r) * 64 + lane] = acc[t][e][r];
-        }
-        __syncthreads();
-        if (wave < lo) {
-            const float *src = lds + wave * (128 * 64);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[t][e][r] += src[((t * 4 + e) * 16 + r) * 64 + lane];
-        }
-        __syncthreads();
-    }
-    float *bl = lds;
-    if (want_b) {
-        bsum0 += __shfl_xor(bsum0, 32);
-        bsum1 += __shfl_xor(bsum1, 32);
-        if (h == 0) { bl[wave * 64 + c] = bsum0; bl[wave * 64 + 32 + c] = bsum1; }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    float *out = part + (long)split * sh.n_pad * sh.k_pad;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long n = n0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-            *reinterpret_cast<float4 *>(out + n * sh.k_pad + k0 + 4 * c) =
-                make_float4(acc[t][0][r], acc[t][1][r], acc[t][2][r], acc[t][3][r]);
-        }
-    if (want_b) {
-        const float v = ((bl[lane] + bl[64 + lane]) + (bl[128 + lane] + bl[192 + lane]));
-        part_b[(long)split * sh.n_pad + n0 + lane] = v;
-    }
+    tsod_wgrad_tile(g, M, N, g_pitch, x, x_pitch, [&](int k) { return k < K ? pw_buffer_column(sg, k) : -1; }, sh, part, part_b,
+                    lds);
 }
 
 // One workgroup per real output row o.  Thread t walks k = t, t + 256, ...: dWraw[o][k] = the slabs in slice order,
 // dW = scale[o] * dWraw at the real columns, and w[o][k] * dWraw[o][k] summed per thread in ascending k, then over the threads
 // by a binary tree (t += 128, 64, ... 1): dscale[o].  dshift[o] = the slices' column sums in slice order.
 __global__ void __launch_bounds__(256)
-pw_wgrad_finish_kernel(const float *__restrict__ part, const float *__restrict__ part_b, PwWgradShape sh, int K, int k_real,
+pw_wgrad_finish_kernel(const float *__restrict__ part, const float *__restrict__ part_b, tsod_wgrad_plan sh, int K, int k_real,
                        tsod_pw_segs sg, const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ dw,
                        float *__restrict__ dscale, float *__restrict__ dshift) {
     __shared__ float lds[256];
@@ -207,9 +73,7 @@ pw_wgrad_finish_kernel(const float *__restrict__ part, const float *__restrict__
     float dot = 0.f;
     if (dw || dscale) {
         for (int k = tid; k < K; k += 256) {
-            const float *src = part + (long)o * sh.k_pad + k;
-            float raw = 0.f;
-            for (int z = 0; z < sh.splits; ++z) raw += src[(long)z * stride];
+            const float raw = tsod_sum_in_slice_order(part + (long)o * sh.k_pad + k, stride, sh.splits);
             if (dw) {
                 const int kr = pw_real_column(sg, k);
                 if (kr >= 0) dw[(long)o * k_real + kr] = s * raw;
@@ -226,11 +90,7 @@ pw_wgrad_finish_kernel(const float *__restrict__ part, const float *__restrict__
         }
         if (tid == 0) dscale[o] = lds[0];
     }
-    if (dshift && tid == 0) {
-        float b = 0.f;
-        for (int z = 0; z < sh.splits; ++z) b += part_b[(long)z * sh.n_pad + o];
-        dshift[o] = b;
-    }
+    if (dshift && tid == 0) dshift[o] = tsod_sum_in_slice_order(part_b + o, sh.n_pad, sh.splits);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- dgrad
@@ -270,7 +130,7 @@ pw_dgrad_kernel(const float *__restrict__ g, long M, int N, int g_pitch, const f
             k0 += sg.len[s];
         }
     }
-    f32x16 acc[4];
+    tsod_f32x16 acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -350,8 +210,7 @@ extern "C" int tsod_relu6_grad_mask_f32(const float *y, int64_t rows, int32_t C,
 
 extern "C" size_t tsod_pw_wgrad_workspace_bytes(int64_t M, int32_t N, int32_t K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const PwWgradShape s = pw_wgrad_shape(M, N, K);
-    return (size_t)s.splits * (size_t)s.n_pad * (size_t)(s.k_pad + 1) * sizeof(float);
+    return tsod_wgrad_plan_bytes(tsod_wgrad_plan_of(M, N, K, true));
 }
 
 extern "C" int tsod_pw_wgrad_f32(const float *g, int64_t M, int32_t N, int32_t g_pitch, const float *x, int32_t x_pitch,
@@ -364,10 +223,10 @@ extern "C" int tsod_pw_wgrad_f32(const float *g, int64_t M, int32_t N, int32_t g
     TSOD_REQUIRE((x_pitch & 3) == 0 && pw_segs_aligned(segs) && tsod_aligned16(x), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace && tsod_aligned16(workspace) && workspace_bytes >= tsod_pw_wgrad_workspace_bytes(M, N, K),
                  TSOD_ERR_WORKSPACE);
-    const PwWgradShape sh = pw_wgrad_shape(M, N, K);
+    const tsod_wgrad_plan sh = tsod_wgrad_plan_of(M, N, K, true);
     TSOD_REQUIRE(sh.splits <= 65535, TSOD_ERR_UNSUPPORTED);
     float *part = static_cast<float *>(workspace);
-    float *part_b = part + (size_t)sh.splits * sh.n_pad * sh.k_pad;
+    float *part_b = tsod_wgrad_plan_bias(sh, part);
     hipStream_t st = tsod_stream(stream);
     hipLaunchKernelGGL(pw_wgrad_partial_kernel, dim3(sh.n_tiles * sh.k_tiles, sh.splits), dim3(kWgThreads), 0, st, g, (long)M, N,
                        g_pitch, x, K, x_pitch, *segs, sh, part, part_b);

@@ -226,7 +226,6 @@ proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__re
     if (tid == 0) { counts[0] = S; counts[1] = pos_len; counts[2] = neg_len; counts[3] = bad ? 1 : 0; }
 }
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // utils/loc_bbox_iou.py:63-88 as a stand-alone op: one thread per box pair
 __global__ void __launch_bounds__(256)
@@ -239,7 +238,7 @@ bbox2loc_kernel(const float4 *__restrict__ src, const float4 *__restrict__ dst, 
 
 extern "C" size_t tsod_anchor_targets_workspace_bytes(int32_t A, int32_t G) {
     if (A <= 0 || G < 0) return 0;
-    return align16((size_t)A * 4) + align16((size_t)(G > 0 ? G : 1) * 4) + 16;
+    return tsod_align_up((size_t)A * 4, 16) + tsod_align_up((size_t)(G > 0 ? G : 1) * 4, 16) + 16;
 }
 
 extern "C" int tsod_anchor_targets_f32(const float *anchor, int32_t A, const float *bbox, int32_t G, float pos_iou_thresh,
@@ -252,8 +251,8 @@ extern "C" int tsod_anchor_targets_f32(const float *anchor, int32_t A, const flo
                  TSOD_ERR_WORKSPACE);
     char *ws = static_cast<char *>(workspace);
     float *max_iou = reinterpret_cast<float *>(ws);
-    int *gt_argmax = reinterpret_cast<int *>(ws + align16((size_t)A * 4));
-    int *flag = reinterpret_cast<int *>(ws + align16((size_t)A * 4) + align16((size_t)(G > 0 ? G : 1) * 4));
+    int *gt_argmax = reinterpret_cast<int *>(ws + tsod_align_up((size_t)A * 4, 16));
+    int *flag = reinterpret_cast<int *>(ws + tsod_align_up((size_t)A * 4, 16) + tsod_align_up((size_t)(G > 0 ? G : 1) * 4, 16));
     hipStream_t s = tsod_stream(stream);
     const float4 *a4 = reinterpret_cast<const float4 *>(anchor), *g4 = reinterpret_cast<const float4 *>(bbox);
     hipLaunchKernelGGL(rowmax_kernel, dim3((A + 255) / 256), dim3(256), 0, s, a4, A, (const float4 *)nullptr, 0, g4, G, 1e-8f,
@@ -268,7 +267,7 @@ extern "C" int tsod_anchor_targets_f32(const float *anchor, int32_t A, const flo
 
 extern "C" size_t tsod_proposal_targets_workspace_bytes(int32_t R, int32_t G, int32_t n_sample) {
     if (R < 0 || G < 0 || R + G <= 0 || n_sample <= 0) return 0;
-    return 2 * align16((size_t)(R + G) * 4) + align16((size_t)n_sample * 4);
+    return 2 * tsod_align_up((size_t)(R + G) * 4, 16) + tsod_align_up((size_t)n_sample * 4, 16);
 }
 
 static int proposal_targets(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
@@ -286,8 +285,8 @@ static int proposal_targets(const float *roi, int32_t R, const float *bbox, int3
     const int N = R + G;
     char *ws = static_cast<char *>(workspace);
     float *max_iou = reinterpret_cast<float *>(ws);
-    int *assign = reinterpret_cast<int *>(ws + align16((size_t)N * 4));
-    int *neg_orig = reinterpret_cast<int *>(ws + 2 * align16((size_t)N * 4));
+    int *assign = reinterpret_cast<int *>(ws + tsod_align_up((size_t)N * 4, 16));
+    int *neg_orig = reinterpret_cast<int *>(ws + 2 * tsod_align_up((size_t)N * 4, 16));
     hipStream_t s = tsod_stream(stream);
     const float4 *r4 = reinterpret_cast<const float4 *>(roi), *g4 = reinterpret_cast<const float4 *>(bbox);
     // roi = torch.cat((roi, bbox)) (:133) is never materialised: candidate n >= R is gt box n - R

@@ -16,6 +16,8 @@ static inline bool tsod_aligned16(const void *p) { return (reinterpret_cast<uint
 
 static inline int64_t tsod_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+static inline size_t tsod_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
 #define TSOD_REQUIRE(cond, code) \
     do {                         \
         if (!(cond)) return (code); \
