@@ -90,7 +90,7 @@ def test_train_full_output_unchanged_and_all_gradients_match_f64(dev, size):
     full = {k: p.grad.clone() for k, p in m.named_parameters()}
     for p in m.parameters():
         p.grad = None
-    m.train_blocks(len(m._block_indices()))(x).backward(gy)
+    m.train_blocks(m.n_blocks)(x).backward(gy)
     for k, p in m.named_parameters():
         assert (p.grad is None) if k in STEM_NAMES else torch.equal(p.grad, full[k]), k
     assert ("train_full",) in {k[3:] for k in m._plans}

@@ -109,7 +109,7 @@ def test_train_blocks_and_backbone_grads_arguments():
         m.train_blocks(5)
     with pytest.raises(ValueError, match="train_blocks"):
         m.train_blocks(-1)
-    assert m.train_blocks(0) is m and m._train_tail and m._train_blocks == 0
+    assert m.train_blocks(0) is m and m.train_mode == "tail"
     assert [id(p) for p in m.trainable_parameters()] == [id(p) for p in m.tail_parameters()]
     m.train_blocks(1)
     names = [k for k, _ in m._trainable_named()]
@@ -121,7 +121,7 @@ def test_train_blocks_and_backbone_grads_arguments():
     assert [k for k, _ in m._trainable_named()][0] == "base.9.layers.0.layer1.conv.weight"
     assert any(k.startswith("base.11.dwconv") for k, _ in m._trainable_named())
     assert len(m.train_blocks(4).trainable_parameters()) == len(list(m.parameters())) - 9     # everything but the stem
-    assert m.train_tail(False)._train_blocks == 0 and not m._train_tail
+    assert m.train_tail(False).train_mode is None
     with pytest.raises(ValueError, match="backbone_grads"):
         FasterRCNNTrainer("train", 20, backbone_grads=-1)
     with pytest.raises(ValueError, match="backbone_grads"):

@@ -95,8 +95,8 @@ def test_train_full_and_backbone_grads_arguments(arch):
     from two_stage_object_detection_amd.nets.frcnn_training import FasterRCNNTrainer
     m = HarDNetFeatureExtraction(depth_wise=True, arch=arch)
     keys = list(m.state_dict())
-    n_blocks = len(m._block_indices())
-    assert m.train_full() is m and m._train_tail and m._train_blocks == n_blocks
+    n_blocks = m.n_blocks
+    assert m.train_full() is m and m.train_mode == "full"
     assert [id(p) for p in m.trainable_parameters()] == [id(p) for p in m.parameters()]
     names = [k for k, _ in m._trainable_named()]
     assert names[:9] == STEM_NAMES and names == [k for k, _ in m.named_parameters()]
@@ -106,7 +106,7 @@ def test_train_full_and_backbone_grads_arguments(arch):
     with pytest.raises(ValueError, match="train_blocks"):
         m.train_blocks(n_blocks + 1)
     m.train_full()
-    assert m.train_tail(False)._train_blocks == 0 and not m._train_tail and not m._train_full
+    assert m.train_tail(False).train_mode is None
     assert [id(p) for p in m.trainable_parameters()] == [id(p) for p in m.tail_parameters()]
     if arch == 39:
         assert FasterRCNNTrainer("train", 20, backbone_grads="full").backbone_grads == "full"

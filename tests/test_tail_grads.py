@@ -255,13 +255,13 @@ def test_train_tail_adds_no_state():
     from two_stage_object_detection_amd.models.hardnet import HarDNetFeatureExtraction
     m = HarDNetFeatureExtraction(depth_wise=True, arch=39)
     keys = list(m.state_dict())
-    assert m._train_tail is False
+    assert m.train_mode is None
     m.train_tail(True)
     assert list(m.state_dict()) == keys
     assert len(m.tail_parameters()) == 6 and sum(p.numel() for p in m.tail_parameters()) == 2 * (9216 + 1024) + 1024 + 512
     for clone in (pickle.loads(pickle.dumps(m)), copy.deepcopy(m)):
-        assert clone._train_tail is True and list(clone.state_dict()) == keys
+        assert clone.train_mode == "tail" and list(clone.state_dict()) == keys
     other = HarDNetFeatureExtraction(depth_wise=True, arch=39)
     other.load_state_dict(m.state_dict(), strict=True)
-    assert other._train_tail is False
-    assert m.train_tail(False)._train_tail is False
+    assert other.train_mode is None
+    assert m.train_tail(False).train_mode is None

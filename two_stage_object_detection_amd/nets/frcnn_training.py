@@ -231,9 +231,8 @@ class FasterRCNNTrainer(nn.Module):
             raise ValueError(f"backbone_grads={backbone_grads!r} trains the HarDNet tail (the last four modules of "
                              f"feat_extra.base) and the HarDBlocks before it; backbone {backbone!r} has none")
         self.feat_extra, feat_ch, native_stride = _make_extractor(backbone)
-        if n_blocks is not None and n_blocks > len(self.feat_extra._block_indices()):
-            raise ValueError(f"backbone_grads={n_blocks}: backbone {backbone!r} has {len(self.feat_extra._block_indices())} "
-                             "HarDBlocks")
+        if n_blocks is not None and n_blocks > self.feat_extra.n_blocks:
+            raise ValueError(f"backbone_grads={n_blocks}: backbone {backbone!r} has {self.feat_extra.n_blocks} HarDBlocks")
         self.feat_stride = native_stride if (feat_stride == 16 and native_stride != 16) else feat_stride
         self.rpn_sigma = 1
         self.roi_sigma = 1
@@ -306,33 +305,20 @@ class FasterRCNNTrainer(nn.Module):
         n_sample = self.proposal_target_creator.n_sample
         grads = self.head_grads and torch.is_grad_enabled()
         tail = self.backbone_grads is not None and features is None and torch.is_grad_enabled()
-        if tail and self.backbone_grads == "full":
-            self.feat_extra.train_full()                                 # every backbone parameter: nothing left to refuse
-        elif tail and self.backbone_grads != "tail":
-            ours = {id(p) for p in self.feat_extra.train_blocks(self.backbone_grads).trainable_parameters()}
+        if tail or (grads and features is None):                         # what the mode does not reach must be frozen
+            ours = {id(p) for p in self.feat_extra.set_train_mode(self.backbone_grads).trainable_parameters()} if tail else ()
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
             if frozen:
-                raise TsodError(f"FasterRCNNTrainer(backbone_grads={self.backbone_grads}) reaches the backbone's tail and last "
-                                f"{self.backbone_grads} HarDBlocks only (feat_extra.trainable_parameters()); every other backbone "
-                                f"parameter must be frozen, but feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad")
-        elif tail:
-            ours = {id(p) for p in self.feat_extra.tail_parameters()}
-            frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
-            if frozen:
-                raise TsodError(f"FasterRCNNTrainer(backbone_grads='tail') reaches the six tail tensors of the backbone only "
-                                f"(feat_extra.tail_parameters()); every other backbone parameter must be frozen, but "
-                                f"feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad")
-        elif grads and features is None:
-            frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad]
-            if frozen:
-                raise TsodError(f"FasterRCNNTrainer(head_grads=True) computes the head parameters' gradients on a frozen "
-                                f"backbone, but feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad: call "
-                                "trainer.feat_extra.requires_grad_(False)")
+                why = ("(head_grads=True) computes the head parameters' gradients on a frozen backbone, but" if not tail else
+                       "(backbone_grads='tail') reaches the six tail tensors of the backbone only (feat_extra.tail_parameters()); "
+                       "every other backbone parameter must be frozen, but" if self.backbone_grads == "tail" else
+                       f"(backbone_grads={self.backbone_grads}) reaches the backbone's tail and last {self.backbone_grads} HarDBlocks "
+                       "only (feat_extra.trainable_parameters()); every other backbone parameter must be frozen, but")
+                raise TsodError(f"FasterRCNNTrainer{why} feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad"
+                                + ("" if tail else ": call trainer.feat_extra.requires_grad_(False)"))
         self._refresh_packs()
-        if tail:                     # the map with the tail's autograd node; from here on the features= path
-            features = (self.feat_extra.train_tail(True) if self.backbone_grads == "tail"
-                        else self.feat_extra.train_full() if self.backbone_grads == "full"
-                        else self.feat_extra.train_blocks(self.backbone_grads))(x)
+        if tail:                     # the map with the backbone's autograd node; from here on the features= path
+            features = self.feat_extra(x)
         feat_grad = features is not None and torch.is_grad_enabled() and features.requires_grad
         with hip_ops.ARENA.scope((self._uid, 0)):
             if features is None:
