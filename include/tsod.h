@@ -690,6 +690,41 @@ int tsod_conv3x3_wgrad_f32(const float *x4, int32_t N, int32_t H, int32_t W, con
                            int32_t stride, float *dw, float *dscale, float *dshift, void *workspace, size_t workspace_bytes,
                            tsod_stream_t stream);
 
+/* ---- train-mode BatchNorm ------------------------------------------------------------------------
+ * NHWC f32 rows [M][ld]; every tensor's channels are [off, off + C_pad) of its rows, C_pad a multiple of 4, C_real <= C_pad
+ * real channels; pad channels of every output are written as exact zeros and never reach a real channel.  16-byte aligned
+ * pointers, pitches and offsets multiples of 4 (TSOD_ERR_ALIGNMENT); NULL required pointers, M < 2 (torch refuses one value
+ * per channel in training mode, so do these), C_real outside 1..C_pad or a slice beyond its pitch: TSOD_ERR_INVALID_ARG.  Sums
+ * are kept in f64; a workgroup reduces TSOD_BN_ROWS_PER_WORKGROUP rows, its partials go to the workspace and a second stage
+ * adds them in an order the shape alone fixes: no float atomics, bit-identical from run to run.
+ * workspace (both entry points that take one): tsod_bn_train_workspace_bytes(M, C_pad); 0 for a shape they refuse.
+ * tsod_bn_stats_f32: mean [C_pad], invstd [C_pad] = 1 / sqrt(var + eps) with the biased variance var (centred squares per
+ *   workgroup, Chan's merge across them - never E[x^2] - E[x]^2), scale = gamma * invstd, shift = beta - mean * scale; gamma,
+ *   beta [C_real].  scale and shift are [2][C_pad] floats: row 0 the f32 value (the folded epilogue's), row 1 the f32
+ *   remainder of the f64 value - where |mean| invstd >> 1 the terms of scale * z + shift cancel and one f32 each would show
+ *   in y.  running_mean / running_var [C_real] (each may be NULL) are updated in place: (1 - momentum) * old + momentum *
+ *   (mean | var * M / (M - 1)); num_batches_tracked (one int64, may be NULL) is incremented.
+ * tsod_bn_apply_f32: y = act(scale * z + shift), act TSOD_ACT_NONE or TSOD_ACT_RELU6 (else TSOD_ERR_UNSUPPORTED); scale,
+ *   shift [2][C_pad] as above (value + remainder, added in f64, the result rounded once); amax_out: the range words of y's
+ *   tensor (NULL: none), see "Range words".  M >= 1.
+ * tsod_bn_train_grad_f32: g = the gradient of the BatchNorm's output (a ReLU6 mask already applied), z the saved input, mean /
+ *   invstd [C_pad] what tsod_bn_stats_f32 gave, gamma [C_real], xhat = (z - mean) * invstd: dgamma [C_pad] = sum g xhat, dbeta
+ *   [C_pad] = sum g, dz = gamma * invstd * (g - dbeta / M - xhat * dgamma / M).  Three launches: the workgroups' partial sums,
+ *   their sum, the elementwise pass. */
+#define TSOD_BN_ROWS_PER_WORKGROUP 128
+size_t tsod_bn_train_workspace_bytes(int64_t M, int32_t C_pad);
+int tsod_bn_stats_f32(const float *z, int64_t M, int32_t C_real, int32_t C_pad, int32_t ld, int32_t off, const float *gamma,
+                      const float *beta, double eps, double momentum, float *running_mean, float *running_var,
+                      int64_t *num_batches_tracked, float *mean, float *invstd, float *scale, float *shift, void *workspace,
+                      size_t workspace_bytes, tsod_stream_t stream);
+int tsod_bn_apply_f32(const float *z, int64_t M, int32_t C_real, int32_t C_pad, int32_t z_ld, int32_t z_off, const float *scale,
+                      const float *shift, int32_t act, float *y, int32_t y_ld, int32_t y_off, uint32_t *amax_out,
+                      tsod_stream_t stream);
+int tsod_bn_train_grad_f32(const float *g, int32_t g_ld, int32_t g_off, const float *z, int32_t z_ld, int32_t z_off, int64_t M,
+                           int32_t C_real, int32_t C_pad, const float *mean, const float *invstd, const float *gamma, float *dz,
+                           int32_t dz_ld, int32_t dz_off, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                           tsod_stream_t stream);
+
 /* ---- detection mAP: COCOeval's evaluateImg + accumulate, area range "all", no crowd / ignore flags ------
  * The reference's calculate_metrics (nets/frcnn_training.py:372-565) defines no usable metric; this is the project's own.
  * IoU is tsod_bbox_iou_f32's expression (eps 1e-8, no +1), compared as IoU >= t in f32.  Three steps:

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 from typing import NamedTuple
 
 import torch
@@ -132,6 +132,7 @@ class PwSegs(Structure):
 
 
 ADAMW_CHUNK, ADAMW_MAX_GROUPS = 2048, 32         # TSOD_ADAMW_CHUNK, TSOD_ADAMW_MAX_GROUPS
+BN_ROWS_PER_WORKGROUP = 128                      # TSOD_BN_ROWS_PER_WORKGROUP: the rows one workgroup of bn_train.hip reduces
 
 
 class AdamWGroup(Structure):
@@ -280,6 +281,14 @@ _SIGNATURES = {
     "tsod_conv3x3_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "tsod_conv3x3_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                        c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_bn_train_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "tsod_bn_stats_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_double, c_double,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_bn_apply_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                  c_int32, c_int32, c_void_p, c_void_p]),
+    "tsod_bn_train_grad_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]),
     "tsod_eval_match_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "tsod_eval_match_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,

@@ -1126,7 +1126,7 @@ class PlanOwner:
         shape = tuple(int(v) for v in shape)
 
         def build():
-            if self.training:
+            if self.training and not self._trains_in_plan():
                 raise TsodError("the HIP path implements the inference forward only: call .eval() first")
             return self.build_plan(shape[0], shape[2], shape[3], device, slot)
         # slot: independent buffer sets for forwards in flight concurrently (the packed weights are shared)
@@ -1135,6 +1135,10 @@ class PlanOwner:
     def _plan_variant(self) -> tuple:
         """Extra plan-cache key of an owner whose build_plan depends on a mode of the module (HarDNet's train_tail)."""
         return ()
+
+    def _trains_in_plan(self) -> bool:
+        """True where the plan about to be built is one for ``.train()`` (HarDNet's batch-statistics BatchNorm)."""
+        return False
 
     def _plan_for(self, x, slot: int = 0) -> "Plan":
         _ffi.require_cuda(x, type(self).__name__ + ".forward")

@@ -583,6 +583,82 @@ def conv3x3_bn_relu6_grad(x4, w, scale, y, dy, *, stride=2, cout=None, dy_off=0,
             None if dscale is None else dscale[:cout], None if dshift is None else dshift[:cout])
 
 
+def _bn_rows(t: torch.Tensor, what: str):
+    if t.dim() < 2 or not t.is_contiguous():
+        raise ValueError(f"{what}: contiguous [..., channels] tensors only, got {tuple(t.shape)}")
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def batch_norm_train(z, gamma, beta, eps, momentum, running_mean=None, running_var=None, *, act=ACT_NONE, off=0, out=None,
+                     out_off=0, C_real=None, num_batches_tracked=None, amax_out=None):
+    """Train-mode BatchNorm of NHWC rows (tsod_bn_stats_f32, tsod_bn_apply_f32) -> (y, mean, invstd).
+
+    z [..., ld] contiguous: the channels are [off, off + C_pad), C_pad = ``gamma``'s length rounded up to 4 (``C_real``: the real
+    channels, default ``gamma``'s length; the columns up to C_pad must exist in z).  gamma, beta [C_real].  mean [C_pad] and
+    invstd [C_pad] = 1 / sqrt(biased variance + eps) are the batch statistics over all rows, y = act(gamma * invstd * (z - mean)
+    + beta) in its folded form scale * z + shift, ``act`` ACT_NONE or ACT_RELU6.  ``out`` [..., ld_out] (default: a new
+    [..., C_pad] tensor) receives y at channels [out_off, out_off + C_pad), nothing else of it is touched; pad channels of y,
+    mean and invstd are exact zeros.  ``running_mean`` / ``running_var`` [C_real] (each optional) are updated in place like
+    torch's: (1 - momentum) * old + momentum * (mean | unbiased variance); ``num_batches_tracked`` (int64 scalar tensor) is
+    incremented; ``amax_out``: the range words of ``out``'s tensor.  ValueError for fewer than 2 rows (torch refuses one value
+    per channel in training mode).  Launches: two for the statistics (workgroup partials, their merge), one for y."""
+    require_cuda(z, "batch_norm_train")
+    M, ld = _bn_rows(z, "batch_norm_train")
+    if M < 2:
+        raise ValueError(f"batch_norm_train: more than one value per channel is needed in training mode, got {M} row(s)")
+    C_real = int(gamma.numel() if C_real is None else C_real)
+    cp = (C_real + 3) // 4 * 4
+    dev = z.device
+    if out is None:
+        out = torch.empty(z.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
+    Mo, ld_out = _bn_rows(out, "batch_norm_train")
+    if Mo != M:
+        raise ValueError(f"batch_norm_train: z has {M} rows, out {Mo}")
+    mean, invstd = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
+    scale, shift = (torch.empty((2, cp), dtype=torch.float32, device=dev) for _ in range(2))      # (value, f32 remainder)
+    L = lib()
+    ws_bytes = L.tsod_bn_train_workspace_bytes(M, cp)
+    ws = ARENA.get(dev, ws_bytes)
+    check(L.tsod_bn_stats_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(gamma), ptr(beta), float(eps), float(momentum),
+                              ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), ptr(mean), ptr(invstd), ptr(scale),
+                              ptr(shift), ptr(ws), ws_bytes, stream_ptr()), "bn_stats")
+    check(L.tsod_bn_apply_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(scale), ptr(shift), int(act), ptr(out), ld_out, int(out_off),
+                              _word_ptr(amax_out), stream_ptr()), "bn_apply")
+    return out, mean, invstd
+
+
+def batch_norm_train_grad(g, z, mean, invstd, gamma, *, g_off=0, z_off=0, dz=None, dz_off=0, C_real=None):
+    """The backward of ``batch_norm_train`` (tsod_bn_train_grad_f32) -> (dz, dgamma [C_pad], dbeta [C_pad]).
+
+    g [..., ld_g] contiguous (channels [g_off, g_off + C_pad)): the gradient of the BatchNorm's output - where a ReLU6
+    follows, already masked (what ``relu6_grad_mask`` / ``dwconv3x3_grad(act_dx=True)`` return).  z [..., ld_z] (channels
+    [z_off, z_off + C_pad)): the saved input.  mean, invstd [C_pad]: what the forward returned; gamma [C_real] (``C_real``
+    default: its length).  With xhat = (z - mean) * invstd: dgamma = sum g xhat, dbeta = sum g, dz = gamma * invstd * (g -
+    dbeta / M - xhat * dgamma / M), written to channels [dz_off, dz_off + C_pad) of ``dz`` (default: a new [..., C_pad] tensor);
+    pad channels of all three are exact zeros.  Launches: the workgroups' partial sums, their sum, the elementwise pass."""
+    require_cuda(g, "batch_norm_train_grad")
+    M, ld_g = _bn_rows(g, "batch_norm_train_grad")
+    Mz, ld_z = _bn_rows(z, "batch_norm_train_grad")
+    cp = mean.numel()
+    C_real = int(gamma.numel() if C_real is None else C_real)
+    if Mz != M or M < 2 or invstd.numel() != cp:
+        raise ValueError(f"batch_norm_train_grad: g has {M} rows, z {Mz} (at least 2), mean {cp} / invstd {invstd.numel()} channels")
+    dev = g.device
+    if dz is None:
+        dz = torch.empty(g.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
+    Md, ld_d = _bn_rows(dz, "batch_norm_train_grad")
+    if Md != M:
+        raise ValueError(f"batch_norm_train_grad: g has {M} rows, dz {Md}")
+    dgamma, dbeta = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
+    L = lib()
+    ws_bytes = L.tsod_bn_train_workspace_bytes(M, cp)
+    ws = ARENA.get(dev, ws_bytes)
+    check(L.tsod_bn_train_grad_f32(ptr(g), ld_g, int(g_off), ptr(z), ld_z, int(z_off), M, C_real, cp, ptr(mean), ptr(invstd),
+                                   ptr(gamma), ptr(dz), ld_d, int(dz_off), ptr(dgamma), ptr(dbeta), ptr(ws), ws_bytes, stream_ptr()),
+          "bn_train_grad")
+    return dz, dgamma, dbeta
+
+
 class _DWConv3x3(torch.autograd.Function):
     """``dwconv3x3_nhwc`` as an autograd node: forward tsod_dwconv3x3_f32, backward tsod_dwconv3x3_grad_f32 (one call gives
     all four gradients; d x is skipped when not asked for, the others are dropped)."""

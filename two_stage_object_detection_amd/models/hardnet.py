@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip_ops
-from .._ffi import ACT_RELU6, TsodError, lib, ptr, require_cuda
+from .._ffi import ACT_NONE, ACT_RELU6, TsodError, lib, ptr, require_cuda
 from ..engine import PackedConv, Plan, PlanOwner, fold_bn, stage_input
 from .hardnet_grads import _bn_stats, copy_pack, feature_map_with_grads, refresh_packs, rewrite_raw_conv
 
@@ -163,6 +163,22 @@ class _RawConv:
         return H, W
 
 
+class _IdentityEpilogue:
+    """A conv pack seen with scale 1, shift 0 and no activation - what runs in front of a batch-statistics BatchNorm (DESIGN.md
+    section 4.20).  Everything else (the weight and its bf16x3 / fp16x2 images, made on first use) is read from and written to the
+    pack itself, so the refresh after an optimizer step reaches both."""
+
+    def __init__(self, pack, device):
+        self.__dict__.update(pack=pack, scale=torch.ones(pack.cout, dtype=torch.float32, device=device),
+                             shift=torch.zeros(pack.cout, dtype=torch.float32, device=device), act=ACT_NONE)
+
+    def __getattr__(self, k):
+        return getattr(self.__dict__["pack"], k)
+
+    def __setattr__(self, k, v):
+        setattr(self.__dict__["pack"], k, v)
+
+
 def _pw_pack(layer, src_real, device):
     """The packed form of a 1x1 ConvLayer that gathers slices of ``src_real`` channels (a HarDBlock layer's ``layer1`` or a
     transition layer): the weight gathered to the padded slices it reads, BN folded, padded to 4 output channels."""
@@ -208,6 +224,7 @@ Unit = namedtuple("Unit", "name index module make write")
 class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     _train_mode = None           # set_train_mode(): a plain instance attribute once set - pickled and deep-copied, never in
                                  # the state_dict
+    _batch_stats = False         # set_train_mode(batch_stats=): likewise
 
     def __init__(self, depth_wise=True, arch=39):
         super().__init__()
@@ -312,7 +329,7 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
             return 0
         return self._tail_indices()[0] if mode in (None, "tail") else self._block_indices()[-mode]
 
-    def set_train_mode(self, mode):
+    def set_train_mode(self, mode, batch_stats=False):
         """How much of the backbone is differentiable: None (nothing, the default), "tail" (the last four modules of ``base``:
         the two depthwise 3x3 stride-2 convs, the ReLU between them, the grouped 1x1), ``n`` >= 1 (the tail and the last ``n``
         HarDBlocks: every ``CombConvLayer`` of those blocks, each block's transition ``ConvLayer``, any ``DWConvLayer`` between
@@ -343,12 +360,35 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         place in ``base``) and ``down`` (the ``DWConvLayer`` in front of the block: ``index``, ``dw``, ``dw_bn``, ``stride``; or
         None); in "full" mode ``stem``: ``x4`` (the image as the plan staged it, [N,H,W,4]), ``y0`` (``base.0``'s output), ``w0`` /
         ``scale0`` / ``bn0`` (its packed weight [c0,3,3,4], folded scale, BN statistics), ``base1`` (``base.1`` with the keys of a
-        block layer's 1x1, ``y`` its output) and ``dw`` / ``dw_bn`` (``base.2``'s)."""
+        block layer's 1x1, ``y`` its output) and ``dw`` / ``dw_bn`` (``base.2``'s).
+
+        ``batch_stats=True`` (modes ``n`` and "full"; "tail" has no BatchNorm and ignores it) adds the reference's contract,
+        ``.train()``: under ``.eval()`` nothing changes (same plan-cache key, same bits); under ``.train()`` with grad mode on the
+        forward takes a plan of its own variant in which every BatchNorm from the mode's first module on normalises with the
+        statistics of the current batch (over N, H, W), backpropagates through them and updates its ``running_mean``,
+        ``running_var`` (momentum, unbiased variance) and ``num_batches_tracked`` in the module's own storage - current when
+        ``forward`` returns; the section below stays folded on its running statistics (frozen BN) and its buffers do not change
+        by a bit.  Per such layer the conv runs with an identity epilogue into a raw buffer z, then tsod_bn_stats_f32 and
+        tsod_bn_apply_f32 write where the folded launch wrote; the backward runs tsod_bn_train_grad_f32
+        on the masked gradient and feeds dz to the conv backward with unit scale.  The records then carry ``bnt`` / ``dw_bnt`` /
+        ``bnt0`` (``z``, ``mean``, ``invstd``, ``gamma``, ``C``) where they carried ``bn`` / ``dw_bn`` / ``bn0`` (then None), and
+        ``scale`` is ones.  A difference from the reference: the ``nn.Dropout`` modules of ``base`` (HarDNet-85) stay the
+        identity, as on every other path.  Under ``.train()`` with grad mode off, or without ``batch_stats``, the forward raises
+        ``call .eval() first`` as before.  A BatchNorm of the section with ``momentum=None`` or ``track_running_stats=False``:
+        NotImplementedError here.  Memory on top of the mode's: the raw z of every BatchNorm of the section, N x h x w x C_pad
+        floats each, twice (plan and node) - for ``n = 1``, HarDNet-39, 600 x 600, batch 1: 150 x 150 pixels x (2 x 988 + 1 024)
+        channels x 4 B = 270 MB, twice."""
         if mode not in (None, "tail", "full"):
             mode = int(mode)
             if mode < 1 or mode > self.n_blocks:
                 raise ValueError(f"train_blocks: n must be 0..{self.n_blocks} (the HarDBlocks of this backbone), got {mode}")
-        self._train_mode = mode
+        batch_stats = bool(batch_stats) and mode not in (None, "tail")
+        if batch_stats:
+            for name, bn in self._section_norms(self._mode_start(mode)):
+                if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+                    raise NotImplementedError(f"batch_stats: {name} has momentum=None, track_running_stats=False or affine=False; "
+                                              "only the reference's BatchNorm2d (momentum, running statistics, affine) is built")
+        self._train_mode, self._batch_stats = mode, batch_stats
         if mode is not None:                                     # the widest mode ever set: where the refresh starts
             self.__dict__["_watch_from"] = min(self._mode_start(mode), self.__dict__.get("_watch_from", len(self.base)))
         return self
@@ -360,20 +400,20 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         the node is freed; the plan for grad mode off is a second plan of the same shape."""
         return self.set_train_mode((self._train_mode or "tail") if enabled else None)
 
-    def train_blocks(self, n: int):
-        """``set_train_mode(n)``; ``n = 0`` is "tail".  The stem is never reached (``train_full`` adds it).
+    def train_blocks(self, n: int, batch_stats=False):
+        """``set_train_mode(n, batch_stats)``; ``n = 0`` is "tail".  The stem is never reached (``train_full`` adds it).
         Memory: the plan keeps the section's block buffers, 1x1 outputs and transition outputs out of its pool and the node
         copies them, per block N x h x w x (P + sum of the layers' padded widths + the transition's width) floats: for
         ``n = 1``, HarDNet-39, 600 x 600, batch 1 that is 150 x 150 pixels x (1 628 + 988 + 1 024) channels x 4 B = 328 MB,
         twice (plan and node), plus one zeroed gradient buffer of the block buffer's size per block during the backward."""
-        return self.set_train_mode(int(n) or "tail")
+        return self.set_train_mode(int(n) or "tail", batch_stats)
 
-    def train_full(self):
-        """``set_train_mode("full")``: ``trainable_parameters()`` is then every parameter of the module in ``base`` order.
+    def train_full(self, batch_stats=False):
+        """``set_train_mode("full", batch_stats)``: ``trainable_parameters()`` is then every parameter of the module in ``base`` order.
         Memory on top of ``train_blocks(all)``: N x H x W x 4 floats of image and N x H/2 x W/2 x (c0 + c1) floats of stem
         outputs, twice (plan and node), plus one gradient buffer of ``base.0``'s output during the backward: HarDNet-39 at
         600 x 600, batch 1: 5.8 + 25.9 MB; at 800 x 1333, batch 8: 137 + 615 MB."""
-        return self.set_train_mode("full")
+        return self.set_train_mode("full", batch_stats)
 
     def trainable_parameters(self):
         """The parameters the feature map's autograd node reaches, in ``base`` order: everything from the first module of the
@@ -387,20 +427,40 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     def _active_mode(self):
         return self._train_mode if torch.is_grad_enabled() else None
 
+    def _section_norms(self, start):
+        """(name, BatchNorm2d) of every unit from ``base[start]`` on, in ``base`` order."""
+        return [(u.name + ".norm", u.module.norm) for u in self._units() if u.index >= start and hasattr(u.module, "norm")]
+
+    def _trains_in_plan(self) -> bool:
+        """The batch-statistics variant is on: ``batch_stats`` set, ``.train()``, grad mode on."""
+        return self._batch_stats and self.training and self._active_mode() not in (None, "tail")
+
     def _plan_variant(self):
         mode = self._active_mode()
         if mode is None:
             return ()
-        return ("train_" + mode,) if isinstance(mode, str) else ("train_blocks", mode)
+        key = ("train_" + mode,) if isinstance(mode, str) else ("train_blocks", mode)
+        return key + ("batch_stats",) if self._trains_in_plan() else key
 
     def _forward_train(self, x, slot, nchw):
-        if self.training:
+        batch_stats = self._trains_in_plan()
+        if self.training and not batch_stats:
             raise TsodError("the HIP path implements the inference forward only: call .eval() first")
         refresh_packs(self)
         plan = self._plan_for(x, slot)
+        if batch_stats and any(getattr(bn, k).data_ptr() != p for bn, k, p in plan.bn_bound):
+            # a parameter or buffer was rebound (load_state_dict(assign=True), ``bn.running_mean = ...``, ``p.data = ...``): the
+            # plan's launches hold the old storage (kept alive, never freed under them) - build the plan again
+            for key in [k for k, v in self._plans.items() if v is plan]:
+                del self._plans[key]
+            plan = self._plan_for(x, slot)
         stage_input(plan, x)
         plan.run()
         self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
+        if batch_stats:                                          # the launches wrote the section's buffers: torch must know
+            for _, bn in self._section_norms(self._mode_start(self._train_mode)):
+                for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+                    torch.autograd.graph.increment_version(b)
         return feature_map_with_grads(plan, nchw, self._trainable_named())
 
     def forward_nhwc(self, x, slot: int = 0):
@@ -422,21 +482,62 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         mode = self._active_mode()
         start = len(mods) if mode is None else self._mode_start(mode)
         plan.tail, plan.block_records, plan.stem_record, pending_down = [], [], None, None
+        # the batch-statistics variant (section 4.20): a BatchNorm at base[i], i >= start, runs as conv with identity epilogue ->
+        # raw z (kept for the node, outside the pool) -> tsod_bn_stats_f32 -> tsod_bn_apply_f32 into the folded launch's place
+        batch_stats = self._trains_in_plan()
+        bn_steps = []                                            # the statistics launches: they share one workspace
+        plan.bn_bound = []                                       # (module, attribute, pointer) of every tensor of the module a launch holds
 
-        def pack(name):
-            return plan.packed(name, lambda: units[name].make(device))
+        def pack(name, raw=False):
+            pc = plan.packed(name, lambda: units[name].make(device))
+            return _IdentityEpilogue(pc, device) if raw else pc
 
         def bn_pack(name, bn, cp):
-            return plan.packed(name + ".bn", lambda: _bn_stats(bn, cp, device))
+            return None if batch_stats else plan.packed(name + ".bn", lambda: _bn_stats(bn, cp, device))
 
-        def pw_record(name, index, rc, bn, cout, real, offs, slices, y, y_off=0, off=0):
+        def raw_like(dst_shape, cp):
+            return torch.empty(tuple(dst_shape[:3]) + (cp,), dtype=torch.float32, device=device)
+
+        def emit_bn(bn, z, C, act, dst, dst_off):
+            """batch statistics of z [N,h,w,C_pad] and y = act(BN(z)) into dst's slice -> what the node keeps of it"""
+            own = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
+            if any(getattr(bn, k).device != z.device for k in own):
+                raise TsodError("batch_stats: the module's BatchNorm parameters and buffers must live on the forward's device")
+            cp = z.shape[3]
+            M = z.numel() // cp
+            if M < 2:
+                raise ValueError("batch_stats: more than one value per channel is needed in training mode "
+                                 f"(a BatchNorm of the trainable section sees {M} pixel)")
+            mean, invstd, scale, shift = vec = [torch.empty(n * cp, dtype=torch.float32, device=device) for n in (1, 1, 2, 2)]
+            bn_steps.append(plan.call(L.tsod_bn_stats_f32, ptr(z), M, C, cp, cp, 0, ptr(bn.weight), ptr(bn.bias), float(bn.eps),
+                                      float(bn.momentum), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
+                                      ptr(mean), ptr(invstd), ptr(scale), ptr(shift), None, 0,
+                                      keep=[z] + vec + [getattr(bn, k) for k in own]))
+            plan.bn_bound.extend((bn, k, ptr(getattr(bn, k))) for k in own)     # (_forward_train: rebound storage = a new plan)
+            plan.call(L.tsod_bn_apply_f32, ptr(z), M, C, cp, cp, 0, ptr(scale), ptr(shift), act, ptr(dst), dst.shape[3], dst_off,
+                      plan.amax_ptr(dst) or None, keep=(dst,))
+            return dict(z=z, mean=mean, invstd=invstd, gamma=bn.weight, C=C)
+
+        def conv_bn(name, layer, rc, x, dst, dst_off, C, train, **kw):
+            """a ConvLayer's launch(es): folded, or (train) conv -> z, batch statistics, apply; -> the node's ``bnt`` or None"""
+            if not train:
+                plan.conv(rc, x, dst, out_off=dst_off, name=name, **kw)
+                return None
+            z = raw_like(dst.shape, rc.cout)
+            plan.conv(rc, x, z, name=name, **kw)
+            return emit_bn(layer.norm, z, C, ACT_RELU6, dst, dst_off)
+
+        def pw_record(name, index, rc, bn, cout, real, offs, slices, y, y_off=0, off=0, bnt=None):
             """a trainable 1x1 ConvLayer for the node (hardnet_grads.pw_copy)"""
             return dict(index=index, rc=rc, slices=list(slices), segs=[(offs[k], _pad4(real[k])) for k in slices],
-                        seg_real=[real[k] for k in slices], cout=cout, y=y, y_off=y_off, off=off, bn=bn_pack(name, bn, rc.cout))
+                        seg_real=[real[k] for k in slices], cout=cout, y=y, y_off=y_off, off=off, bn=bn_pack(name, bn, rc.cout),
+                        bnt=bnt)
 
         def dw_record(name, index, dw, bn, stride, C, x=None):
             """a trainable depthwise layer (or the pair conv) for the node (hardnet_grads.dw_copy)"""
-            return dict(index=index, dw=dw, stride=stride, C=C, x=x, dw_bn=None if bn is None else bn_pack(name, bn, dw[3]))
+            dw, bnt = (dw[:4], dw[4]) if len(dw) == 5 else (dw, None)
+            return dict(index=index, dw=dw, stride=stride, C=C, x=x, dw_bn=None if bn is None else bn_pack(name, bn, dw[3]),
+                        dw_bnt=bnt)
 
         def dest_for(next_idx, C, h, w):
             """Where the tensor feeding module ``next_idx`` must be written: slice 0 of the next
@@ -447,29 +548,41 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 return plan.pool.alloc((N, h, w, P)), 0
             return plan.pool.alloc((N, h, w, _pad4(C))), 0
 
-        def emit_dw(name, src, src_off, stride, relu, dst, dst_off):
+        def emit_dw(name, src, src_off, stride, relu, dst, dst_off, bn=None):
+            """``bn``: the layer's BatchNorm where it runs on batch statistics; the pack returned then has unit scale, zero shift
+            and the node's ``dw_bnt`` as a fifth entry (dw_record takes it off)"""
             w33, scale, shift, cp = dw = pack(name)
             n, h, w_, P = src.shape
+            out, out_off = dst, dst_off
+            if bn is not None:
+                scale, shift = plan.packed(("identity", cp), lambda: (torch.ones(cp, dtype=torch.float32, device=device),
+                                                                      torch.zeros(cp, dtype=torch.float32, device=device)))
+                out, out_off = raw_like(dst.shape, cp), 0
             plan.call(L.tsod_dwconv3x3_amax_f32, ptr(src), n, h, w_, cp, P, src_off, ptr(w33), ptr(scale), ptr(shift), stride,
-                      1 if relu else 0, ptr(dst), dst.shape[3], dst_off, plan.amax_ptr(dst) or None, keep=(src, dst, w33, scale, shift))
+                      1 if relu else 0, ptr(out), out.shape[3], out_off, plan.amax_ptr(out) or None, keep=(src, out, w33, scale, shift))
+            if bn is not None:
+                return (w33, scale, shift, cp, emit_bn(bn, out, bn.num_features, ACT_NONE, dst, dst_off))
             return dw
 
         # --- stem: 3x3 s2 conv (3 -> c0, input padded to 4 channels), 1x1 conv, dw3x3 s2
-        pc0 = pack("base.0")
+        stem_bn = batch_stats and start == 0
+        pc0 = pack("base.0", stem_bn)
         h, w = pc0.out_hw(H, W)
-        t0 = plan.conv(pc0, x4, plan.pool.alloc((N, h, w, pc0.cout)), name="base.0")
-        pc1 = pack("base.1")
-        t1 = plan.conv(pc1, t0, plan.pool.alloc((N, h, w, pc1.cout)), name="base.1")
+        t0 = plan.pool.alloc((N, h, w, pc0.cout))
+        bnt0 = conv_bn("base.0", mods[0], pc0, x4, t0, 0, mods[0].norm.num_features, stem_bn)
+        pc1 = pack("base.1", stem_bn)
+        t1 = plan.pool.alloc((N, h, w, pc1.cout))
+        bnt1 = conv_bn("base.1", mods[1], pc1, t0, t1, 0, mods[1].norm.num_features, stem_bn)
         if start > 0:
             plan.pool.release(t0)
         h2, w2 = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         cur, cur_off = dest_for(3, pc1.cout, h2, w2)
-        dw = emit_dw("base.2", t1, 0, 2, False, cur, cur_off)
+        dw = emit_dw("base.2", t1, 0, 2, False, cur, cur_off, mods[2].norm if stem_bn else None)
         if start > 0:
             plan.pool.release(t1)
         else:                                                    # "full": the stem's two outputs and the staged image stay
-            plan.stem_record = dict(y0=t0, pc0=pc0, bn0=bn_pack("base.0", mods[0].norm, pc0.cout),
-                                    base1=pw_record("base.1", 1, pc1, mods[1].norm, pc1.cout, [pc1.cin], [0], [0], t1),
+            plan.stem_record = dict(y0=t0, pc0=pc0, bn0=bn_pack("base.0", mods[0].norm, pc0.cout), bnt0=bnt0,
+                                    base1=pw_record("base.1", 1, pc1, mods[1].norm, pc1.cout, [pc1.cin], [0], [0], t1, bnt=bnt1),
                                     base2=dw_record("base.2", 2, dw, mods[2].norm, 2, pc1.cout))
         cur_C = pc1.cout
         h, w = h2, w2
@@ -489,13 +602,15 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 for li, comb in enumerate(m.layers, start=1):
                     link = m.links[li - 1]
                     name = f"base.{i}.layers.{li - 1}"
-                    rc = pack(name + ".layer1")
+                    bn_on = batch_stats and rec is not None
+                    rc = pack(name + ".layer1", bn_on)
                     tmp = plan.pool.alloc((N, h, w, rc.cout))
-                    plan.conv(rc, buf, tmp, segs=[(offs[k], _pad4(real[k])) for k in link], name=name + ".layer1")
-                    dw = emit_dw(name + ".layer2", tmp, 0, 1, False, buf, offs[li])
+                    bnt = conv_bn(name + ".layer1", comb.layer1, rc, buf, tmp, 0, real[li], bn_on,
+                                  segs=[(offs[k], _pad4(real[k])) for k in link])
+                    dw = emit_dw(name + ".layer2", tmp, 0, 1, False, buf, offs[li], comb.layer2.norm if bn_on else None)
                     if rec is not None:
                         rec["layers"].append((pw_record(name + ".layer1", i, rc, comb.layer1.norm, real[li], real, offs, link, tmp,
-                                                        0, offs[li]),
+                                                        0, offs[li], bnt=bnt),
                                               dw_record(name + ".layer2", i, dw, comb.layer2.norm, 1, real[li])))
                     else:
                         plan.pool.release(tmp)
@@ -504,24 +619,26 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 i += 1
                 if isinstance(mods[i], nn.Dropout):
                     i += 1
-                rc = pack(f"base.{i}")
+                rc = pack(f"base.{i}", batch_stats and rec is not None)
                 dst, dst_off = dest_for(i + 1, rc.cout, h, w)
                 if isinstance(mods[i + 1], DWConvLayer):          # "downsample" dw3x3 at stride 1 follows
                     plan.pool.release(dst)
                     dst, dst_off = plan.pool.alloc((N, h, w, rc.cout)), 0
-                plan.conv(rc, buf, dst, segs=[(offs[k], _pad4(real[k])) for k in outs], out_off=dst_off, name=f"base.{i}")
+                bnt = conv_bn(f"base.{i}", mods[i], rc, buf, dst, dst_off, rc.cout_real, batch_stats and rec is not None,
+                              segs=[(offs[k], _pad4(real[k])) for k in outs])
                 if rec is not None:
                     # (the last block's transition output is the tail's first input: its mask is taken there)
                     last = not any(isinstance(later, HarDBlock) for later in mods[i + 1:])
                     rec["transition"] = pw_record(f"base.{i}", i, rc, mods[i].norm, rc.cout_real, real, offs, outs,
-                                                  None if last else dst, dst_off)
+                                                  None if last else dst, dst_off, bnt=bnt)
                 else:
                     plan.pool.release(buf)
                 cur, cur_off, cur_C = dst, dst_off, rc.cout
                 i += 1
             elif isinstance(m, DWConvLayer):
                 dst, dst_off = dest_for(i + 1, cur_C, h, w)
-                dw = emit_dw(f"base.{i}", cur, cur_off, m.dwconv.stride[0], False, dst, dst_off)
+                dw = emit_dw(f"base.{i}", cur, cur_off, m.dwconv.stride[0], False, dst, dst_off,
+                             m.norm if batch_stats and i > start else None)
                 if i > start:                                    # between two trainable blocks: its input stays
                     pending_down = dw_record(f"base.{i}", i, dw, m.norm, m.dwconv.stride[0], cur_C)
                 else:
@@ -558,6 +675,11 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         plan.tail_inputs = [r["x"] for r in plan.tail]           # (tensor, channel offset) of the three tail layers
         plan.output_nhwc = cur
         plan.output_amax = plan.amax_ptr(cur)
+        if bn_steps:
+            need = max(L.tsod_bn_train_workspace_bytes(st[1][1], st[1][3]) for st in bn_steps)
+            plan.bn_workspace = torch.empty(need, dtype=torch.uint8, device=device)
+            for st in bn_steps:
+                st[1][17:19] = [ptr(plan.bn_workspace), need]
         return plan.finalize()
 
     def forward(self, x):

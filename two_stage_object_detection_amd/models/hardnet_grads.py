@@ -7,7 +7,10 @@ the copies the node keeps of what ``build_plan`` recorded, and the refresh of th
     where the consumer's record holds it), ``off`` (its slice of the block buffer), ``bn`` (BN statistics);
   * a depthwise layer (``layer2``, the DWConvLayer between blocks, ``base.2``, the tail's two convs - and the tail's pair conv,
     which needs the same facts): ``index``, ``dw`` (its pack), ``stride``, ``C``, ``dw_bn`` (BN statistics or None) and ``x``
-    = (input, channel offset) where no 1x1 record holds that input as its ``y`` (the tail), else None."""
+    = (input, channel offset) where no 1x1 record holds that input as its ``y`` (the tail), else None.
+Where the layer's BatchNorm ran on batch statistics the record carries ``bnt`` (1x1) / ``dw_bnt``
+(depthwise) = ``z`` (the conv's raw output [N,h,w,C_pad]), ``mean``, ``invstd``, ``gamma`` (the module's ``weight``), ``C``; its
+pack then has unit scale and ``bn`` / ``dw_bn`` are None."""
 from __future__ import annotations
 
 import torch
@@ -34,16 +37,32 @@ def _conv33_weight(d, C):                                     # [3][3][C_pad] ->
     return d[:, :, :C].reshape(9, C).t().reshape(C, 1, 3, 3)
 
 
+def bnt_copy(bnt):
+    """the node's own copy of what a batch-statistics BatchNorm's backward reads (None where the BatchNorm is folded)"""
+    if bnt is None:
+        return None
+    return dict(C=bnt["C"], **{k: bnt[k].detach().clone() for k in ("z", "mean", "invstd", "gamma")})
+
+
 def pw_copy(rec):
     rc, y = rec["rc"], rec["y"]
     return dict(index=rec["index"], off=rec["off"], cout=rec["cout"], segs=rec["segs"], seg_real=rec["seg_real"],
                 slices=rec["slices"], w=rc.w.view(rc.cout, -1).clone(), scale=rc.scale.clone(), bn=rec["bn"],
-                y=None if y is None else y[..., rec["y_off"]:rec["y_off"] + rc.cout].clone())
+                y=None if y is None else y[..., rec["y_off"]:rec["y_off"] + rc.cout].clone(), bnt=bnt_copy(rec.get("bnt")))
 
 
 def dw_copy(rec):
     return dict(rec, dw=tuple(t.clone() if isinstance(t, torch.Tensor) else t for t in rec["dw"]),
-                x=None if rec["x"] is None else (rec["x"][0].clone(), rec["x"][1]))
+                x=None if rec["x"] is None else (rec["x"][0].clone(), rec["x"][1]), dw_bnt=bnt_copy(rec.get("dw_bnt")))
+
+
+def _bn_train_back(out, prefix, bnt, g, g_off=0):
+    """A batch-statistics BatchNorm's backward from the (masked) gradient of its output: its ``weight`` / ``bias`` gradients go
+    to ``out`` straight from dgamma / dbeta, dz (the conv's output gradient) is returned."""
+    dz, dgamma, dbeta = hip_ops.batch_norm_train_grad(g, bnt["z"], bnt["mean"], bnt["invstd"], bnt["gamma"], g_off=g_off,
+                                                      C_real=bnt["C"])
+    out[prefix + ".weight"], out[prefix + ".bias"] = dgamma[:bnt["C"]], dbeta[:bnt["C"]]
+    return dz
 
 
 class _BackboneGrads(torch.autograd.Function):
@@ -74,17 +93,25 @@ class _BackboneGrads(torch.autograd.Function):
         def dw_layer(prefix, x, rec, dy, dy_off):
             """backward of a DWConvLayer whose input x is a ReLU6 output -> that layer's masked gradient"""
             w33, sc, sh = rec["dw"][:3]
-            want = need[prefix + ".dwconv.weight"] or any(wants(prefix + ".norm"))
+            bnt = rec.get("dw_bnt")
+            if bnt is not None:                                   # batch statistics: dz first, then the conv with unit scale
+                dy, dy_off = _bn_train_back(out, prefix + ".norm", bnt, dy, dy_off), 0
+                want = need[prefix + ".dwconv.weight"]
+            else:
+                want = need[prefix + ".dwconv.weight"] or any(wants(prefix + ".norm"))
             g, d_w, d_sc, d_sh = hip_ops.dwconv3x3_grad(x, w33, sc, sh, rec["stride"], False, dy, want_params=want, dy_off=dy_off,
                                                         act_dx=True)
             if want:
                 out[prefix + ".dwconv.weight"] = _conv33_weight(d_w, rec["C"])
-                out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = _bn_grads(d_sc, d_sh, rec["dw_bn"], rec["C"])
+                if bnt is None:
+                    out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = _bn_grads(d_sc, d_sh, rec["dw_bn"], rec["C"])
             return g
 
         def pw_layer(prefix, buf, lay, g, dbuf, want_seg):
             """backward of a 1x1 ConvLayer from its masked gradient g: parameter gradients, and dx added into dbuf"""
             want_w, (want_g, want_b) = need[prefix + ".conv.weight"], wants(prefix + ".norm")
+            if lay.get("bnt") is not None:                        # batch statistics: dz first, then the conv with unit scale
+                g, want_g, want_b = _bn_train_back(out, prefix + ".norm", lay["bnt"], g), False, False
             _, d_w, d_sc, d_sh = hip_ops.conv1x1_bn_relu6_grad(
                 buf, lay["segs"], lay["w"], lay["scale"], None, g, seg_real=lay["seg_real"], seg_want=want_seg, cout=lay["cout"],
                 dx=dbuf, accumulate=True, want_dx=any(want_seg), want_dw=want_w, want_dscale=want_g, want_dshift=want_g or want_b)
@@ -138,7 +165,14 @@ class _BackboneGrads(torch.autograd.Function):
             d0 = torch.zeros_like(stem["y0"])
             pw_layer("base.1", stem["y0"], lay1, g, d0, [True])
             want_w, (want_g, want_b) = need["base.0.conv.weight"], wants("base.0.norm")
-            if want_w or want_g or want_b:
+            if stem.get("bnt0") is not None:                      # batch statistics: the mask pass, dz, then the conv's dW with
+                y0 = stem["y0"]                                   # unit scale and a mask that is open everywhere
+                dz = _bn_train_back(out, "base.0.norm", stem["bnt0"], hip_ops.relu6_grad_mask(y0, d0))
+                if want_w:
+                    out["base.0.conv.weight"] = hip_ops.conv3x3_bn_relu6_grad(
+                        stem["x4"], stem["w0"], stem["scale0"], torch.ones_like(y0), dz, stride=2, cout=stem["bnt0"]["C"],
+                        want_dscale=False, want_dshift=False)[0]
+            elif want_w or want_g or want_b:
                 c0 = stem["y0"].shape[3]
                 d_w, d_sc, d_sh = hip_ops.conv3x3_bn_relu6_grad(stem["x4"], stem["w0"], stem["scale0"], stem["y0"], d0, stride=2,
                                                                 want_dw=want_w, want_dscale=want_g, want_dshift=True)
@@ -162,7 +196,7 @@ def feature_map_with_grads(plan, nchw, named):
         sr = plan.stem_record
         pc0 = sr["pc0"]
         saved["stem"] = dict(dw_copy(sr["base2"]), x4=plan.input_nhwc.clone(), y0=sr["y0"].clone(), w0=pc0.w.clone(),
-                             scale0=pc0.scale.clone(), bn0=sr["bn0"], base1=pw_copy(sr["base1"]))
+                             scale0=pc0.scale.clone(), bn0=sr["bn0"], bnt0=bnt_copy(sr.get("bnt0")), base1=pw_copy(sr["base1"]))
     return _BackboneGrads.apply(saved, *(p for _, p in named))
 
 
@@ -183,7 +217,8 @@ def rewrite_raw_conv(owner, old, new):
             e = hip_ops.fp16x2_weight_scale_exp(old.w)
             for plan in owner._plans.values():
                 for st in plan.conv_steps:
-                    if st.pc is old and int(st.desc.precision) == _ffi.PREC_FP16X2:
+                    # (a batch-statistics plan holds the pack behind hardnet._IdentityEpilogue)
+                    if getattr(st.pc, "pack", st.pc) is old and int(st.desc.precision) == _ffi.PREC_FP16X2:
                         st.desc.w_scale_exp = int(e)
                         plan.graph = None
             owner._bump_version()
@@ -200,7 +235,8 @@ def copy_pack(owner, old, new):
 
 def refresh_packs(owner):
     """Rewrite in place the packed images of every unit (``owner._units()``), from the first unit of the widest training mode
-    ever set on, whose parameters changed (``_version``) since they were last known to match: plans and graphs keep their
+    ever set on, whose parameters or BatchNorm buffers (the running statistics move under ``batch_stats``) changed (``_version``)
+    since they were last known to match: plans and graphs keep their
     pointers; an autograd node of an earlier forward holds copies.  Nothing while no mode was ever set: today's contract for
     in-place edits (``invalidate_packed``)."""
     start = owner.__dict__.get("_watch_from")
@@ -210,7 +246,7 @@ def refresh_packs(owner):
     stale = {}
     for u in owner._units():
         if u.index >= start:
-            v = tuple(p._version for p in u.module.parameters())
+            v = tuple(t._version for t in list(u.module.parameters()) + list(u.module.buffers()))
             if seen.get(u.name) != v:
                 seen[u.name] = v
                 stale[u.name] = u

@@ -213,14 +213,21 @@ class FasterRCNNTrainer(nn.Module):
     ``backbone_grads="full"``: the same with ``feat_extra.train_full()`` - every parameter of the backbone, the stem
     (``base.0`` - ``base.2``) included; the frozen-backbone check has nothing left to refuse.
 
-    Not provided: train-mode BatchNorm and the ResNet backbones' backward (``head_grads`` fine-tunes the heads
+    ``bn_batch_stats=True`` (keyword-only, with ``backbone_grads`` an int or "full"): the reference's ``model.train()``
+    contract for the trainable section - ``forward`` is then allowed under ``.train()``, the mode is set with
+    ``batch_stats=True`` and every BatchNorm the mode reaches normalises with the statistics of the batch, backpropagates
+    through them and moves its running statistics (``HarDNetFeatureExtraction.set_train_mode``); the
+    frozen section below stays folded, dropout stays the identity.  Under ``.eval()`` nothing changes.
+
+    Not provided: the ResNet backbones' backward (``head_grads`` fine-tunes the heads
     on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks, ``"full"`` the whole
     HarDNet; ``features=`` trains a
     backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
     and tuning (the forward runs whatever plan the backbone holds).  ``eval_fn`` / ``calculate_metrics``: see there."""
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
-                 backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False, backbone_grads=None):
+                 backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False, backbone_grads=None,
+                 bn_batch_stats=False):
         super().__init__()
         if head_img_size not in ("chw", "hw"):
             raise ValueError(f"head_img_size must be 'chw' (the reference's) or 'hw', got {head_img_size!r}")
@@ -249,6 +256,10 @@ class FasterRCNNTrainer(nn.Module):
         self.head_img_size = head_img_size
         self.head_grads = bool(head_grads)
         self.backbone_grads = backbone_grads
+        if bn_batch_stats and backbone_grads in (None, "tail"):
+            raise ValueError("bn_batch_stats=True needs backbone_grads = a number of HarDBlocks or 'full' (the tail has no "
+                             f"BatchNorm), got backbone_grads={backbone_grads!r}")
+        self.bn_batch_stats = bool(bn_batch_stats)
         self.__dict__["_uid"] = next(_UID)          # scratch ownership, as FasterRCNN's
         self.__dict__["_head_versions"] = None
 
@@ -287,7 +298,7 @@ class FasterRCNNTrainer(nn.Module):
                              f"{tuple(features.shape)}")
 
     def forward(self, imgs, bboxes, labels, scale=1, *, features=None):
-        if self.training:
+        if self.training and not self.bn_batch_stats:
             raise TsodError("the HIP path implements the inference forward only: call .eval() first")
         if features is None:
             x = torch.stack(list(imgs)) if isinstance(imgs, (list, tuple)) else imgs
@@ -306,7 +317,7 @@ class FasterRCNNTrainer(nn.Module):
         grads = self.head_grads and torch.is_grad_enabled()
         tail = self.backbone_grads is not None and features is None and torch.is_grad_enabled()
         if tail or (grads and features is None):                         # what the mode does not reach must be frozen
-            ours = {id(p) for p in self.feat_extra.set_train_mode(self.backbone_grads).trainable_parameters()} if tail else ()
+            ours = {id(p) for p in self.feat_extra.set_train_mode(self.backbone_grads, self.bn_batch_stats).trainable_parameters()} if tail else ()
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
             if frozen:
                 why = ("(head_grads=True) computes the head parameters' gradients on a frozen backbone, but" if not tail else
