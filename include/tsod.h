@@ -671,6 +671,31 @@ int tsod_pw_wgrad_f32(const float *g, int64_t M, int32_t N, int32_t g_pitch, con
 int tsod_pw_dgrad_f32(const float *g, int64_t M, int32_t N, int32_t g_pitch, const float *w, const float *scale,
                       const tsod_pw_segs *segs, float *dx, int32_t dx_pitch, int32_t accumulate, tsod_stream_t stream);
 
+/* ---- what a ResNet Bottleneck's backward adds to the 1x1 kernels above -----------------------------
+ * y = prelu(z) with ONE slope a, finite and > 0 (the caller checks), so that the saved output y has z's sign.
+ * No float atomics; bit-identical from run to run.
+ * tsod_prelu_grad_f32: g [rows][g_pitch] = dy [rows][dy_pitch] (columns [dy_off, dy_off + C)) * (y > 0 ? 1 : slope), y
+ *   [rows][y_pitch] the forward's output; *dslope_num = sum dy * y * [y < 0] (the slope's gradient times the slope), a two-stage
+ *   sum: per-workgroup partials in the workspace, then one finishing workgroup.  dslope_num NULL: no sum, the workspace is not
+ *   read.  An exact y == 0 takes the slope branch and adds nothing to the sum.  16-byte aligned, C / pitches / dy_off multiples
+ *   of 4.  workspace: tsod_prelu_grad_workspace_bytes(rows, C) (0 for a shape that is refused).
+ * tsod_conv3x3_dense_wgrad_f32: the parameter gradients of z = scale[o] * conv3x3(x, w, pad 1, stride 1) + shift[o] from the
+ *   masked gradient g [N][H][W][g_pitch] (Cout columns), x [N][H][W][x_pitch] (C channels), w [Cout][3][3][C] unscaled (the
+ *   forward's f32 pack), scale [Cout]: dWraw = g^T patches(x) on v_mfma_f32_32x32x2_f32 with K = 9 C gathered columns, N H W cut
+ *   into slices by tsod_pw_wgrad_f32's rule; dw [Cout][3][3][C] = scale[o] * dWraw, dscale [Cout] = sum_k w[o][k] dWraw[o][k],
+ *   dshift [Cout] = sum g; each of the three may be NULL (not all).  C, Cout, pitches multiples of 4; x, g, workspace 16-byte
+ *   aligned.  stride: only 1 is built, anything else is TSOD_ERR_UNSUPPORTED.
+ *   workspace: tsod_conv3x3_dense_wgrad_workspace_bytes(N, H, W, C, Cout) (0 for a shape that is refused).
+ * The 3x3 conv's dx is tsod_conv2d_f32 on g with the weights w_rot[c][kh][kw][o] = scale[o] * w[o][2 - kh][2 - kw][c]. */
+size_t tsod_prelu_grad_workspace_bytes(int64_t rows, int32_t C);
+int tsod_prelu_grad_f32(const float *y, int64_t rows, int32_t C, int32_t y_pitch, const float *dy, int32_t dy_pitch,
+                        int32_t dy_off, float slope, float *g, int32_t g_pitch, float *dslope_num, void *workspace,
+                        size_t workspace_bytes, tsod_stream_t stream);
+size_t tsod_conv3x3_dense_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cout);
+int tsod_conv3x3_dense_wgrad_f32(const float *g, int32_t N, int32_t H, int32_t W, int32_t Cout, int32_t g_pitch, const float *x,
+                                 int32_t C, int32_t x_pitch, const float *w, const float *scale, int32_t stride, float *dw,
+                                 float *dscale, float *dshift, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- the parameter gradients of HarDNet's first layer ----------------------------------------------
  * y[n][oh][ow][o] = relu6(scale[o] * sum_{kh,kw,c} w[o][kh][kw][c] x4[n][oh s - 1 + kh][ow s - 1 + kw][c] + shift[o]), s = stride
  * (1 or 2), pad 1, OH = (H - 1) / s + 1, OW = (W - 1) / s + 1.  x4 [N][H][W][4] (channel 3 is padding and is never read), y

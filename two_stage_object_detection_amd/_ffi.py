@@ -278,6 +278,13 @@ _SIGNATURES = {
                                   c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_pw_dgrad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, POINTER(PwSegs), c_void_p, c_int32,
                                   c_int32, c_void_p]),
+    "tsod_prelu_grad_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "tsod_prelu_grad_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_conv3x3_dense_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "tsod_conv3x3_dense_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                             c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]),
     "tsod_conv3x3_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "tsod_conv3x3_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                        c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -1,4 +1,4 @@
-// grad_reduce.h -- what the backward files (head_grads.hip, pw_grads.hip, conv3x3_grads.hip, dw_grads.hip) share, once: the
+// grad_reduce.h -- what the backward files (head_grads.hip, pw_grads.hip, conv_grads.hip, conv3x3_grads.hip, dw_grads.hip) share, once: the
 // f32 MFMA weight-gradient tile with its slice plan, the fixed-order sum of a workgroup's waves through LDS, the sum of the
 // slices' partials in slice order, and the strict ReLU6 window.  The results of those files are bit-identical from run to run
 // because every order below depends on the shape only; it is stated here and nowhere else:
@@ -6,6 +6,12 @@
 //   tsod_wgrad_tile           a wave adds its m-pairs ascending (the MFMA adds row 2p before 2p + 1), then the wave tree; the
 //                             bias adds the two lane halves, then the waves as (w0 + w1) + (w2 + w3)
 //   tsod_sum_in_slice_order   0 + p[0] + p[1] + ..., one add after the other, whatever number of loads is in flight
+//   tsod_tree_sum_256         256 threads' values through LDS: t += t + 128, then + 64, ... + 1 (a binary tree, thread 0 has the sum)
+//   tsod_wgrad_finish_row     dWraw[o][k] = the slabs in slice order; dscale[o]: thread t adds w[o][k] dWraw[o][k] over k = t,
+//                             t + 256, ... ascending, then tsod_tree_sum_256; dshift[o] = the slices' column sums in slice order
+//   tsod_strided_sum_256      a grid-stride loop's lane sum (elements t, t + G, ... ascending, a quad as x, y, z, w), then
+//                             tsod_tree_sum_256 per workgroup; the finish: thread t adds partials t, t + 256, ... ascending, then
+//                             tsod_tree_sum_256 (conv_grads.hip's PReLU slope sum; G and the partial count depend on the shape only)
 #pragma once
 #include "tsod_internal.h"
 
@@ -36,6 +42,18 @@ __device__ inline float tsod_sum_in_slice_order(const float *__restrict__ src, l
     }
     for (; z < count; ++z) sum += src[z * stride];
     return sum;
+}
+
+// ---------------------------------------------------------------------------------------------------------- 256-thread tree
+// every thread of a 256-thread workgroup calls it; `lds`: 256 floats; the sum is the return value of thread 0 (others: partial)
+__device__ __forceinline__ float tsod_tree_sum_256(float v, float *lds, int tid) {
+    lds[tid] = v;
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) lds[tid] += lds[tid + st];
+        __syncthreads();
+    }
+    return lds[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------- wave tree
@@ -118,12 +136,20 @@ inline size_t tsod_wgrad_plan_bytes(const tsod_wgrad_plan &s) {
 }
 inline float *tsod_wgrad_plan_bias(const tsod_wgrad_plan &s, float *part) { return part + (size_t)s.splits * s.n_pad * s.k_pad; }
 
+// xrow of a GEMM whose X rows are dY's rows (the 1x1 layers, the head): row m of X, always there
+struct tsod_wgrad_same_row {
+    __device__ __forceinline__ bool operator()(long m, int, long &mx) const { mx = m; return true; }
+};
+
 // The body of a kWgThreads kernel on grid (n_tiles * k_tiles, splits).  xcol(k): the column of X that holds gathered column k
-// (k % 4 == 0; the quad k .. k + 3 lies there, 16-byte aligned), or -1 when k is past K.  `lds`: kWgLdsFloats.
-template <class XCol>
+// (k % 4 == 0; the quad k .. k + 3 lies there, 16-byte aligned), or -1 when k is past K.  xrow(m, k, mx): false where gathered
+// column k of dY's row m (m < M) is a zero (a conv's padding), else true with mx = the row of X that holds it; k is the lane's
+// first column, the same for every m it asks about.  `lds`: kWgLdsFloats.
+template <class XCol, class XRow = tsod_wgrad_same_row>
 __device__ __forceinline__ void tsod_wgrad_tile(const float *__restrict__ dy, long M, int N, int dy_pitch,
                                                 const float *__restrict__ x, int x_pitch, XCol xcol, const tsod_wgrad_plan &sh,
-                                                float *__restrict__ part, float *__restrict__ part_b, float *lds) {
+                                                float *__restrict__ part, float *__restrict__ part_b, float *lds,
+                                                XRow xrow = XRow()) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tile = blockIdx.x, split = blockIdx.y;
     const int nt = tile / sh.k_tiles, kt = tile - nt * sh.k_tiles;
@@ -155,7 +181,10 @@ __device__ __forceinline__ void tsod_wgrad_tile(const float *__restrict__ dy, lo
             xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             a0[u] = a1[u] = 0.f;
             if (p < p_end && m < M) {
-                if (xc >= 0) xv[u] = *reinterpret_cast<const float4 *>(x + m * x_pitch + xc);
+                if (xc >= 0) {
+                    long mx;
+                    if (xrow(m, k0 + 4 * c, mx)) xv[u] = *reinterpret_cast<const float4 *>(x + mx * x_pitch + xc);
+                }
                 const float *yr = dy + m * dy_pitch + n0;
                 if (n_ok0) a0[u] = yr[c];
                 if (n_ok1) a1[u] = yr[32 + c];
@@ -196,6 +225,38 @@ __device__ __forceinline__ void tsod_wgrad_tile(const float *__restrict__ dy, lo
         const float v = ((bl[lane] + bl[64 + lane]) + (bl[128 + lane] + bl[192 + lane]));
         part_b[(long)split * sh.n_pad + n0 + lane] = v;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------- wgrad finish
+// The body of a 256-thread kernel, one workgroup per real output row o, after tsod_wgrad_tile: dWraw[o][k] = the slabs in slice
+// order, dW = scale[o] * dWraw at the real columns (real(k): the column of dw [.][k_real], or -1 for a pad column), and
+// w[o][k] * dWraw[o][k] summed per thread in ascending k, then over the threads by tsod_tree_sum_256: dscale[o].
+// dshift[o] = the slices' column sums in slice order.  w [.][K].  `lds`: 256 floats.
+template <class RealCol>
+__device__ __forceinline__ void tsod_wgrad_finish_row(const float *__restrict__ part, const float *__restrict__ part_b,
+                                                      const tsod_wgrad_plan &sh, int K, int k_real, RealCol real,
+                                                      const float *__restrict__ w, const float *__restrict__ scale,
+                                                      float *__restrict__ dw, float *__restrict__ dscale,
+                                                      float *__restrict__ dshift, float *lds) {
+    const int o = blockIdx.x, tid = threadIdx.x;
+    const long stride = sh.n_pad * sh.k_pad;
+    const float s = scale[o];
+    float dot = 0.f;
+    if (dw || dscale) {
+        for (int k = tid; k < K; k += 256) {
+            const float raw = tsod_sum_in_slice_order(part + (long)o * sh.k_pad + k, stride, sh.splits);
+            if (dw) {
+                const int kr = real(k);
+                if (kr >= 0) dw[(long)o * k_real + kr] = s * raw;
+            }
+            dot += w[(long)o * K + k] * raw;
+        }
+    }
+    if (dscale) {
+        const float sum = tsod_tree_sum_256(dot, lds, tid);
+        if (tid == 0) dscale[o] = sum;
+    }
+    if (dshift && tid == 0) dshift[o] = tsod_sum_in_slice_order(part_b + o, sh.n_pad, sh.splits);
 }
 
 }  // namespace

@@ -59,38 +59,14 @@ pw_wgrad_partial_kernel(const float *__restrict__ g, long M, int N, int g_pitch,
                     lds);
 }
 
-// One workgroup per real output row o.  Thread t walks k = t, t + 256, ...: dWraw[o][k] = the slabs in slice order,
-// dW = scale[o] * dWraw at the real columns, and w[o][k] * dWraw[o][k] summed per thread in ascending k, then over the threads
-// by a binary tree (t += 128, 64, ... 1): dscale[o].  dshift[o] = the slices' column sums in slice order.
+// One workgroup per real output row o: grad_reduce.h's finish with the segments' pad columns dropped.
 __global__ void __launch_bounds__(256)
 pw_wgrad_finish_kernel(const float *__restrict__ part, const float *__restrict__ part_b, tsod_wgrad_plan sh, int K, int k_real,
                        tsod_pw_segs sg, const float *__restrict__ w, const float *__restrict__ scale, float *__restrict__ dw,
                        float *__restrict__ dscale, float *__restrict__ dshift) {
     __shared__ float lds[256];
-    const int o = blockIdx.x, tid = threadIdx.x;
-    const long stride = sh.n_pad * sh.k_pad;
-    const float s = scale[o];
-    float dot = 0.f;
-    if (dw || dscale) {
-        for (int k = tid; k < K; k += 256) {
-            const float raw = tsod_sum_in_slice_order(part + (long)o * sh.k_pad + k, stride, sh.splits);
-            if (dw) {
-                const int kr = pw_real_column(sg, k);
-                if (kr >= 0) dw[(long)o * k_real + kr] = s * raw;
-            }
-            dot += w[(long)o * K + k] * raw;
-        }
-    }
-    if (dscale) {
-        lds[tid] = dot;
-        __syncthreads();
-        for (int st = 128; st >= 1; st >>= 1) {
-            if (tid < st) lds[tid] += lds[tid + st];
-            __syncthreads();
-        }
-        if (tid == 0) dscale[o] = lds[0];
-    }
-    if (dshift && tid == 0) dshift[o] = tsod_sum_in_slice_order(part_b + o, sh.n_pad, sh.splits);
+    tsod_wgrad_finish_row(part, part_b, sh, K, k_real, [&](int k) { return pw_real_column(sg, k); }, w, scale, dw, dscale, dshift,
+                          lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- dgrad

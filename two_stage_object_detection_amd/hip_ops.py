@@ -583,6 +583,63 @@ def conv3x3_bn_relu6_grad(x4, w, scale, y, dy, *, stride=2, cout=None, dy_off=0,
             None if dscale is None else dscale[:cout], None if dshift is None else dshift[:cout])
 
 
+def prelu_grad(y: torch.Tensor, dy: torch.Tensor, slope: float, dy_off: int = 0, want_dslope: bool = True, g=None):
+    """The backward of y = prelu(z) with one slope > 0, from the saved OUTPUT (tsod_prelu_grad_f32) ->
+    (g, dslope_num): g = dy[..., dy_off:dy_off + C] * (y > 0 ? 1 : slope), dslope_num [1] = sum dy * y * [y < 0] (the slope's
+    gradient is dslope_num / slope) or None without ``want_dslope``.  y [..., C] and dy [..., P] contiguous; ``g``: where to
+    write ([..., Pg], columns [0, C); default a fresh [..., C])."""
+    require_cuda(y, "prelu_grad")
+    if not (y.is_contiguous() and dy.is_contiguous() and (g is None or g.is_contiguous())):
+        raise ValueError("prelu_grad: y, dy and g must be contiguous")
+    C = y.shape[-1]
+    rows = y.numel() // C
+    if g is None:
+        g = torch.empty_like(y)
+    for what, t, first in (("dy", dy, int(dy_off)), ("g", g, 0)):
+        if t.dim() < 1 or first < 0 or first + C > t.shape[-1] or t.numel() != rows * t.shape[-1] or t.device != y.device \
+                or t.dtype != torch.float32:
+            raise ValueError(f"prelu_grad: {what} {tuple(t.shape)} does not hold columns [{first}, {first + C}) of y's {rows} rows "
+                             f"(y {tuple(y.shape)}) as float32 on {y.device}")
+    num = torch.empty(1, dtype=torch.float32, device=y.device) if want_dslope else None
+    L = lib()
+    ws_bytes = L.tsod_prelu_grad_workspace_bytes(rows, C) if want_dslope else 0
+    ws = ARENA.get(y.device, ws_bytes) if ws_bytes else None
+    check(L.tsod_prelu_grad_f32(ptr(y), rows, C, C, ptr(dy), dy.shape[-1], int(dy_off), float(slope), ptr(g), g.shape[-1], ptr(num),
+                                ptr(ws), ws_bytes, stream_ptr()), "prelu_grad")
+    return g, num
+
+
+def conv3x3_dense_wgrad(g, x, w, scale, *, stride=1, want_dw=True, want_dscale=True, want_dshift=True):
+    """The parameter gradients of z = scale * conv3x3(x, w, pad 1) + shift from the masked gradient g (DESIGN.md section 4.21;
+    tsod_conv3x3_dense_wgrad_f32) -> (dW [Cout,3,3,C] in the pack's layout or None, dscale [Cout] or None, dshift [Cout] or None).
+    g [N,H,W,Cout], x [N,H,W,C], w [Cout,3,3,C] (the forward's f32 pack, unscaled), scale [Cout]; all contiguous."""
+    require_cuda(x, "conv3x3_dense_wgrad")
+    if not (g.is_contiguous() and x.is_contiguous() and w.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("conv3x3_dense_wgrad: g, x, w and scale must be contiguous")
+    N, H, W, C = x.shape
+    Cout = w.shape[0]
+    if tuple(w.shape) != (Cout, 3, 3, C) or tuple(g.shape) != (N, H, W, Cout) or scale.numel() != Cout:
+        raise ValueError(f"conv3x3_dense_wgrad: g {tuple(g.shape)}, x {tuple(x.shape)}, w {tuple(w.shape)} do not belong together")
+    if not (want_dw or want_dscale or want_dshift):
+        raise ValueError("conv3x3_dense_wgrad: nothing is wanted")
+    dev = x.device
+    dw = torch.empty_like(w) if want_dw else None
+    dscale = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dscale else None
+    dshift = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dshift else None
+    L = lib()
+    ws_bytes = L.tsod_conv3x3_dense_wgrad_workspace_bytes(N, H, W, C, Cout)
+    ws = ARENA.get(dev, ws_bytes) if ws_bytes else None
+    check(L.tsod_conv3x3_dense_wgrad_f32(ptr(g), N, H, W, Cout, Cout, ptr(x), C, C, ptr(w), ptr(scale), int(stride), ptr(dw),
+                                         ptr(dscale), ptr(dshift), ptr(ws), ws_bytes, stream_ptr()), "conv3x3_dense_wgrad")
+    return dw, dscale, dshift
+
+
+def rotate_conv3x3_weight(w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """w [Cout,3,3,C] (a 3x3 conv's f32 pack), scale [Cout] -> w_rot [C,3,3,Cout] = scale[o] * w[o][2 - kh][2 - kw][c]: the pack
+    with which ``conv2d_nhwc(g, w_rot, pad=1)`` is that conv's dx (stride 1, pad 1)."""
+    return (w * scale.view(-1, 1, 1, 1)).flip(1, 2).permute(3, 1, 2, 0).contiguous()
+
+
 def _bn_rows(t: torch.Tensor, what: str):
     if t.dim() < 2 or not t.is_contiguous():
         raise ValueError(f"{what}: contiguous [..., channels] tensors only, got {tuple(t.shape)}")

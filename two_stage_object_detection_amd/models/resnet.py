@@ -18,7 +18,9 @@ import torch.nn as nn
 
 from .. import hip_ops
 from .._ffi import ACT_NONE, ACT_PRELU, TsodError, lib, ptr, require_cuda, stem_out_hw
-from ..engine import FusedBottleneckWeights, FusedShortcutConv, FusedStemWeights, PackedConv, Plan, PlanOwner, prelu_slope
+from ..engine import (FusedBottleneckWeights, FusedShortcutConv, FusedStemWeights, PackedConv, Plan, PlanOwner, prelu_slope,
+                      stage_input)
+from . import resnet_grads
 
 
 def _conv(cin, cout, k, stride=1, pad=0, groups=1):
@@ -30,7 +32,9 @@ class _ResidualBlock(nn.Module):
     expansion = 1
     _stage_names: tuple = ()
 
-    def _emit(self, plan: Plan, x: torch.Tensor, name: str) -> torch.Tensor:
+    def _emit(self, plan: Plan, x: torch.Tensor, name: str, record: bool = False) -> torch.Tensor:
+        """``record`` (a trained block, ``resnet_grads.eligible``): the same launches, but the stage outputs stay out of the
+        buffer pool and go, with the packs, to ``plan.block_records`` for the autograd node."""
         dev = plan.device
         slope = prelu_slope(self.relu)
         identity = x
@@ -61,6 +65,7 @@ class _ResidualBlock(nn.Module):
             identity = plan.conv(pc, x, plan.pool.alloc((x.shape[0], oh, ow, pc.cout)), name=f"{name}.downsample")
         cur = x
         last = len(self._stage_names) - 1
+        ys, pcs = [], []
         for i, (cname, bname) in enumerate(self._stage_names):
             conv, bn = getattr(self, cname), getattr(self, bname)
             if conv.groups != 1:                      # ResNeXt's grouped 3x3 (models/resnet.py:46-47): direct kernel, no MFMA
@@ -81,11 +86,15 @@ class _ResidualBlock(nn.Module):
             oh, ow = pc.out_hw(cur.shape[1], cur.shape[2])
             out = plan.pool.alloc((cur.shape[0], oh, ow, pc.cout))
             plan.conv(pc, cur, out, residual=identity if i == last else None, name=f"{name}.{cname}")
-            if cur is not x:
+            ys.append(out)
+            pcs.append(pc)
+            if cur is not x and not record:
                 plan.pool.release(cur)
             cur = out
         if identity is not x:
             plan.pool.release(identity)
+        if record:
+            plan.block_records.append(resnet_grads.block_record(plan, self, name, x, ys, pcs))
         return cur
 
     def _emit_grouped(self, plan: Plan, conv, bn, cur, x, slope, name):
@@ -141,6 +150,9 @@ class Bottleneck(_ResidualBlock):
 
 
 class ResNet(PlanOwner, nn.Module):
+    _train_mode = None           # set_train_mode(): a plain instance attribute once set - pickled and deep-copied, never in
+                                 # the state_dict
+
     def __init__(self, block, blocks_num, num_classes=25, include_top=True, groups=1, width_per_group=64):
         super().__init__()
         self.include_top = include_top
@@ -174,6 +186,108 @@ class ResNet(PlanOwner, nn.Module):
                    for _ in range(1, block_num)]
         return nn.Sequential(*blocks)
 
+    # -- training mode -------------------------------------------------
+    @property
+    def n_blocks(self) -> int:
+        """The largest ``n`` of ``train_blocks(n)``: the length of the run of eligible blocks at the end of ``layer4`` (identity
+        Bottlenecks with a dense 3x3 at stride 1: 2 for resnet50 / resnet101, 0 for resnet34 and resnext50_32x4d)."""
+        n = 0
+        for blk in reversed(list(self.layer4)):
+            if not resnet_grads.eligible(blk):
+                break
+            n += 1
+        return n
+
+    @property
+    def train_mode(self):
+        """None | n (int >= 1): what ``set_train_mode`` was given last."""
+        return self._train_mode
+
+    def set_train_mode(self, mode):
+        """How much of the backbone is differentiable: None (nothing, the default) or ``n`` in 1..``n_blocks`` (the last ``n``
+        blocks of ``layer4``, ten tensors each: ``conv{1,2,3}.weight``, ``bn{1,2,3}.weight`` / ``.bias``, ``relu.weight``;
+        ValueError outside that range).  Returns self.
+
+        The contract is ``HarDNetFeatureExtraction.set_train_mode``'s: eval() only; BatchNorm stays folded - its ``weight`` /
+        ``bias`` get gradients through the folded scale / shift, its running statistics are constants.  While a mode is on, grad
+        mode enabled and a parameter of the section requires grad, the map that ``forward`` / ``forward_nhwc`` return carries ONE
+        autograd node (``resnet_grads._ResNetGrads``; HIP kernels of csrc/conv_grads.hip and pw_grads.hip, the 3x3's dx through
+        the forward conv library) that gives the gradients of ``trainable_parameters()`` and nothing for the image.  The forward
+        runs the same launches on a plan of its own (another plan-cache key) and returns the same bits; that plan keeps, per
+        trained block, the block input and the three stage outputs out of its buffer pool, and the node copies them.  The
+        PReLU slope of every trained block must be finite and > 0 (TsodError otherwise): the masks are taken from the saved
+        outputs.  With no mode ever set nothing of the inference path changes.
+
+        In-place updates of the parameters (an optimizer step) are noticed through their ``_version`` before the next forward of
+        ANY kind for the blocks of the widest mode ever set: a changed block's packs are dropped and packed again, every plan
+        of the module is dropped and ``weights_version`` moves (``refresh_packs()``).  The comparison runs in a forward of this
+        module, not in ``optimizer.step()``: a graph captured around the module (``FasterRCNN.make_graphed``) that is replayed
+        right after a step, with no eager forward in between, still passes its ``weights_version`` check and runs the old
+        weights - call ``refresh_packs()`` after ``step()`` where graphs are replayed.
+
+        ``f.grad_fn.saved`` is the dict the backward reads: ``names`` (the parameter names in ``trainable_parameters()`` order),
+        ``nchw``, and ``blocks``: per trained block in forward order ``name``, ``x``, ``y1``, ``y2``, ``y3`` (NHWC copies), ``w`` / ``scale``
+        (the three f32 packs [Cout,KH,KW,Cin] and folded scales), ``rot`` (the 3x3 dgrad's image [C,3,3,Cout]), ``slope``, ``bn``
+        (per stage: running mean, 1 / sqrt(var + eps))."""
+        if mode is not None:
+            mode = int(mode)
+            if mode < 1 or mode > self.n_blocks:
+                raise ValueError(f"train_blocks: n must be 1..n_blocks = {self.n_blocks} (the identity Bottlenecks at the end of "
+                                 f"layer4 of this backbone), got {mode}")
+            watched = self.__dict__.setdefault("_watched", {})
+            for name, blk in self._section(mode):                # the widest mode ever set: what the refresh watches
+                watched.setdefault(name, resnet_grads.versions_of(blk))
+        self._train_mode = mode
+        return self
+
+    def refresh_packs(self):
+        """Notice in-place changes of the watched blocks now (``resnet_grads.refresh_packs``: packs and plans dropped,
+        ``weights_version`` moved) instead of at the next forward: the call a training loop makes after ``optimizer.step()``
+        when it replays captured graphs of this module, which go stale through ``weights_version`` only.  Returns self."""
+        resnet_grads.refresh_packs(self)
+        return self
+
+    def train_blocks(self, n: int):
+        """``set_train_mode(n)``.  Memory: per trained block N x h x w x 10 width floats (x, y1, y2, y3), twice (plan and node),
+        and one rotated 3x3 image per trained block and device."""
+        return self.set_train_mode(int(n))
+
+    def _section(self, n):
+        blocks = list(self.layer4)
+        return [(f"layer4.{i}", blocks[i]) for i in range(len(blocks) - n, len(blocks))]
+
+    def _trainable_named(self):
+        return [(f"{name}.{k}", p) for name, blk in self._section(self._train_mode or 0) for k, p in blk.named_parameters()]
+
+    def trainable_parameters(self):
+        """The parameters the feature map's autograd node reaches, in module order; empty with no mode on."""
+        return [p for _, p in self._trainable_named()]
+
+    def _active_mode(self):
+        if self._train_mode is None or self.include_top or not torch.is_grad_enabled():      # (include_top: forward raises)
+            return None
+        return self._train_mode if any(p.requires_grad for p in self.trainable_parameters()) else None
+
+    def _plan_variant(self):
+        mode = self._active_mode()
+        return () if mode is None else ("train_blocks", mode)
+
+    def _forward_train(self, x, slot, nchw):
+        if self.training:
+            raise TsodError("the HIP path implements the inference forward only: call .eval() first")
+        resnet_grads.refresh_packs(self)
+        plan = self._plan_for(x, slot)
+        stage_input(plan, x)
+        plan.run()
+        self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
+        return resnet_grads.feature_map_with_grads(plan, nchw, self._trainable_named())
+
+    def forward_nhwc(self, x, slot: int = 0):
+        if self._active_mode() is not None:
+            return self._forward_train(x, slot, nchw=False)
+        resnet_grads.refresh_packs(self)
+        return super().forward_nhwc(x, slot)
+
     # -- plan (cache, invalidation, lookup: engine.PlanOwner) -----------------------------------
     def build_plan(self, N, H, W, device, slot=0) -> Plan:
         """Launch plan for a [N,3,H,W] input: NCHW->NHWC4, 7x7 stem as a 7x8x4 implicit GEMM with
@@ -199,16 +313,25 @@ class ResNet(PlanOwner, nn.Module):
             plan.call(lib().tsod_maxpool3x3s2_f32, ptr(s_out), N, oh, ow, 64, 64, ptr(cur), 64, keep=(s_out, cur))
             plan.alias_amax(cur, s_out)          # range words: max |pooled| <= max |stem output|
             plan.pool.release(s_out)
+        # a training mode (with grad mode on): the last ``mode`` blocks of layer4 run the same launches, but what the autograd
+        # node needs of them stays out of the pool (the node copies it after the run) and is recorded for it
+        mode = self._active_mode()
+        trained = {name for name, _ in self._section(mode)} if mode else set()
+        plan.block_records = []
         for li in range(1, 5):
             for bi, blk in enumerate(getattr(self, f"layer{li}")):
-                nxt = blk._emit(plan, cur, f"layer{li}.{bi}")
-                plan.pool.release(cur)
+                record = f"layer{li}.{bi}" in trained
+                nxt = blk._emit(plan, cur, f"layer{li}.{bi}", record)
+                if not record:
+                    plan.pool.release(cur)
                 cur = nxt
         plan.output_nhwc = cur
         plan.output_amax = plan.amax_ptr(cur)
         return plan.finalize()
 
     def forward(self, x):
+        if self._active_mode() is not None:
+            return self._forward_train(x, 0, nchw=True)
         feat = self.forward_nhwc(x)
         if self.include_top:
             raise TsodError("include_top=True (avgpool + fc classifier) is outside the detector forward path; "

@@ -219,7 +219,17 @@ class FasterRCNNTrainer(nn.Module):
     through them and moves its running statistics (``HarDNetFeatureExtraction.set_train_mode``); the
     frozen section below stays folded, dropout stays the identity.  Under ``.eval()`` nothing changes.
 
-    Not provided: the ResNet backbones' backward (``head_grads`` fine-tunes the heads
+    ResNet backbones: ``backbone_grads`` keeps raising ValueError for them; the identity Bottlenecks at the end of ``layer4``
+    (resnet50 / resnet101: ``layer4.1``, ``layer4.2``) train through the ``features=`` path, whose map may carry any autograd
+    history - here the backbone's own node (``ResNet.train_blocks``):
+
+        tr = FasterRCNNTrainer("train", nc, backbone="resnet50", head_grads=True).eval()
+        tr.feat_extra.requires_grad_(False); tr.feat_extra.train_blocks(2)
+        for p in tr.feat_extra.trainable_parameters(): p.requires_grad_(True)
+        losses = tr(x, bboxes, labels, features=tr.feat_extra(x))[0]; (losses[-1] / 32).backward()
+
+    Not provided: the rest of the ResNet backbones' backward - projection blocks, the earlier stages, the stem, BasicBlock,
+    ResNeXt's grouped 3x3, batch-statistics BatchNorm (``head_grads`` fine-tunes the heads
     on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks, ``"full"`` the whole
     HarDNet; ``features=`` trains a
     backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
