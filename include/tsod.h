@@ -696,6 +696,37 @@ int tsod_conv3x3_dense_wgrad_f32(const float *g, int32_t N, int32_t H, int32_t W
                                  int32_t C, int32_t x_pitch, const float *w, const float *scale, int32_t stride, float *dw,
                                  float *dscale, float *dshift, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
 
+/* ---- what a projection Bottleneck's backward adds to those -----------------------------------------
+ * A 3x3 at stride s (1 or 2), pad 1: x [N][H][W], outputs [N][OH][OW] with OH = (H - 1) / s + 1, OW = (W - 1) / s + 1.
+ * No float atomics; bit-identical from run to run.
+ * tsod_conv3x3_strided_wgrad_f32: tsod_conv3x3_dense_wgrad_f32's contract with g [N][OH][OW][g_pitch] over the output grid
+ *   and x [N][H][W][x_pitch]; the slices cut N OH OW.  stride 1 or 2, anything else is TSOD_ERR_UNSUPPORTED; with stride 1 the
+ *   bits of tsod_conv3x3_dense_wgrad_f32.  workspace: tsod_conv3x3_strided_wgrad_workspace_bytes(N, H, W, C, Cout, stride) (0 for
+ *   a shape that is refused).
+ * tsod_prelu_grad_d2s_f32: tsod_prelu_grad_f32 for y [N][H][W][y_pitch] (C channels) whose dy is never written out: it is read
+ *   from p [N][(H - 1) / 2 + 2][(W - 1) / 2 + 2][p_pitch] (4 C columns), the stride-1, pad-1 conv of the stride-2 3x3's masked
+ *   output gradient with the 2x2 phase pack [4 C][2][2][Cout] (rows ((ih & 1) 2 + (iw & 1)) C + c), as
+ *   dy[n][ih][iw][c] = p[n][(ih >> 1) + 1][(iw >> 1) + 1][((ih & 1) 2 + (iw & 1)) C + c].  The grid, the sum and its order are
+ *   tsod_prelu_grad_f32's for rows = N H W.  dslope_num may be NULL.  16-byte aligned, C and pitches multiples of 4.
+ *   workspace: tsod_prelu_grad_d2s_workspace_bytes(N, H, W, C) (0 for a shape that is refused).
+ * tsod_pixel_subsample_f32: xs [N][OH][OW][xs_pitch] (C columns) = x [N][H][W][x_pitch] at pixels (s oh, s ow), any s >= 1: the
+ *   rows a strided 1x1 conv reads, so that tsod_pw_wgrad_f32 serves it.
+ * tsod_pixel_upsample_add_f32: dx[n][s oh][s ow][c] = dx[n][s oh][s ow][c] + d[n][oh][ow][c] (dx the first operand, one add per
+ *   touched element; every other element of dx is left as it is): that conv's input gradient added into the block's.
+ *   Both: C and pitches multiples of 4, 16-byte aligned, N H W below 2^31. */
+size_t tsod_conv3x3_strided_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t stride);
+int tsod_conv3x3_strided_wgrad_f32(const float *g, int32_t N, int32_t H, int32_t W, int32_t Cout, int32_t g_pitch, const float *x,
+                                   int32_t C, int32_t x_pitch, const float *w, const float *scale, int32_t stride, float *dw,
+                                   float *dscale, float *dshift, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+size_t tsod_prelu_grad_d2s_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C);
+int tsod_prelu_grad_d2s_f32(const float *y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t y_pitch, const float *p,
+                            int32_t p_pitch, float slope, float *g, int32_t g_pitch, float *dslope_num, void *workspace,
+                            size_t workspace_bytes, tsod_stream_t stream);
+int tsod_pixel_subsample_f32(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t x_pitch, int32_t stride,
+                             float *xs, int32_t xs_pitch, tsod_stream_t stream);
+int tsod_pixel_upsample_add_f32(float *dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t dx_pitch, int32_t stride,
+                                const float *d, int32_t d_pitch, tsod_stream_t stream);
+
 /* ---- the parameter gradients of HarDNet's first layer ----------------------------------------------
  * y[n][oh][ow][o] = relu6(scale[o] * sum_{kh,kw,c} w[o][kh][kw][c] x4[n][oh s - 1 + kh][ow s - 1 + kw][c] + shift[o]), s = stride
  * (1 or 2), pad 1, OH = (H - 1) / s + 1, OW = (W - 1) / s + 1.  x4 [N][H][W][4] (channel 3 is padding and is never read), y

@@ -285,6 +285,17 @@ _SIGNATURES = {
     "tsod_conv3x3_dense_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
                                              c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                              c_void_p]),
+    "tsod_conv3x3_strided_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "tsod_conv3x3_strided_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                               c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                               c_void_p]),
+    "tsod_prelu_grad_d2s_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "tsod_prelu_grad_d2s_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float,
+                                        c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_pixel_subsample_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                         c_void_p]),
+    "tsod_pixel_upsample_add_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                            c_void_p]),
     "tsod_conv3x3_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "tsod_conv3x3_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                        c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -1,4 +1,5 @@
-// grad_reduce.h -- what the backward files (head_grads.hip, pw_grads.hip, conv_grads.hip, conv3x3_grads.hip, dw_grads.hip) share, once: the
+// grad_reduce.h -- what the backward files (head_grads.hip, pw_grads.hip, conv_grads.hip, conv_strided_grads.hip, conv3x3_grads.hip,
+// dw_grads.hip) share, once: the
 // f32 MFMA weight-gradient tile with its slice plan, the fixed-order sum of a workgroup's waves through LDS, the sum of the
 // slices' partials in slice order, and the strict ReLU6 window.  The results of those files are bit-identical from run to run
 // because every order below depends on the shape only; it is stated here and nowhere else:
@@ -12,6 +13,10 @@
 //   tsod_strided_sum_256      a grid-stride loop's lane sum (elements t, t + G, ... ascending, a quad as x, y, z, w), then
 //                             tsod_tree_sum_256 per workgroup; the finish: thread t adds partials t, t + 256, ... ascending, then
 //                             tsod_tree_sum_256 (conv_grads.hip's PReLU slope sum; G and the partial count depend on the shape only)
+//   conv_strided_grads.hip    tsod_conv3x3_strided_wgrad_f32 is tsod_wgrad_tile and tsod_wgrad_finish_row over the rows of the
+//                             OUTPUT grid (m = (n, oh, ow) ascending): at stride 1 the dense kernel's orders, add for add
+//   conv_grads.hip, strided   tsod_prelu_grad_d2s_f32 is tsod_strided_sum_256 over y's N H W rows (where dy is read from does
+//                             not enter the order); tsod_pixel_upsample_add_f32 makes one add per element, dx + d
 #pragma once
 #include "tsod_internal.h"
 

@@ -640,6 +640,102 @@ def rotate_conv3x3_weight(w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return (w * scale.view(-1, 1, 1, 1)).flip(1, 2).permute(3, 1, 2, 0).contiguous()
 
 
+def s2d_conv3x3_weight(w: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """w [Cout,3,3,C] (a 3x3 conv's f32 pack), scale [Cout] -> w_s2d [4 C,2,2,Cout], the 2x2 phase pack of that conv's dx at
+    stride 2, pad 1: row ((ih & 1) 2 + (iw & 1)) C + c holds, per axis, for an even phase tap offset
+    d = 0 <-> k = 1, for an odd phase d = 0 <-> k = 2 and d = 1 <-> k = 0; an entry is scale[o] * w[o][kh][kw][c] or zero.
+    With P = ``conv2d_nhwc(g, w_s2d, pad=1)`` [N,OH+1,OW+1,4 C]: dx[n,ih,iw,c] = P[n, (ih >> 1) + 1, (iw >> 1) + 1,
+    ((ih & 1) 2 + (iw & 1)) C + c]."""
+    Cout, _, _, C = w.shape
+    ws = w * scale.view(-1, 1, 1, 1)
+    out = torch.zeros((2, 2, C, 2, 2, Cout), dtype=w.dtype, device=w.device)
+    taps = (((0, 1),), ((0, 2), (1, 0)))                          # per phase parity: (tap offset d, filter index k)
+    for ph in (0, 1):
+        for pw in (0, 1):
+            for dh, kh in taps[ph]:
+                for dw, kw in taps[pw]:
+                    out[ph, pw, :, dh, dw, :] = ws[:, kh, kw, :].t()
+    return out.view(4 * C, 2, 2, Cout)
+
+
+def conv3x3_strided_wgrad(g, x, w, scale, *, stride, want_dw=True, want_dscale=True, want_dshift=True):
+    """``conv3x3_dense_wgrad`` for a 3x3 at stride 1 or 2, pad 1 (tsod_conv3x3_strided_wgrad_f32): g
+    [N,OH,OW,>= Cout] over the output grid, OH = (H - 1) // stride + 1; x [N,H,W,>= C]; the channels are the first Cout / C of
+    each pixel.  With stride 1 the bits of ``conv3x3_dense_wgrad``."""
+    require_cuda(x, "conv3x3_strided_wgrad")
+    if not (g.is_contiguous() and x.is_contiguous() and w.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("conv3x3_strided_wgrad: g, x, w and scale must be contiguous")
+    N, H, W, Px = x.shape
+    Cout, C, stride = w.shape[0], w.shape[3], int(stride)
+    if stride not in (1, 2):
+        raise ValueError(f"conv3x3_strided_wgrad: stride 1 or 2, got {stride}")
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if tuple(w.shape) != (Cout, 3, 3, C) or tuple(g.shape[:3]) != (N, OH, OW) or g.shape[3] < Cout or Px < C or scale.numel() != Cout:
+        raise ValueError(f"conv3x3_strided_wgrad: g {tuple(g.shape)}, x {tuple(x.shape)}, w {tuple(w.shape)} do not belong together "
+                         f"at stride {stride}")
+    if not (want_dw or want_dscale or want_dshift):
+        raise ValueError("conv3x3_strided_wgrad: nothing is wanted")
+    dev = x.device
+    dw = torch.empty_like(w) if want_dw else None
+    dscale = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dscale else None
+    dshift = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dshift else None
+    L = lib()
+    ws_bytes = L.tsod_conv3x3_strided_wgrad_workspace_bytes(N, H, W, C, Cout, stride)
+    ws = ARENA.get(dev, ws_bytes) if ws_bytes else None
+    check(L.tsod_conv3x3_strided_wgrad_f32(ptr(g), N, H, W, Cout, g.shape[3], ptr(x), C, Px, ptr(w), ptr(scale), stride, ptr(dw),
+                                           ptr(dscale), ptr(dshift), ptr(ws), ws_bytes, stream_ptr()), "conv3x3_strided_wgrad")
+    return dw, dscale, dshift
+
+
+def prelu_grad_d2s(y: torch.Tensor, p: torch.Tensor, slope: float, want_dslope: bool = True):
+    """``prelu_grad`` for the input y [N,H,W,C] of a stride-2 3x3 whose dy is read from the phase-stacked image p
+    [N,(H-1)//2+2,(W-1)//2+2,4 C] of ``s2d_conv3x3_weight`` (DESIGN.md section 4.22; tsod_prelu_grad_d2s_f32) -> (g, dslope_num)."""
+    require_cuda(y, "prelu_grad_d2s")
+    if not (y.is_contiguous() and p.is_contiguous()) or y.dim() != 4:
+        raise ValueError("prelu_grad_d2s: y [N,H,W,C] and p must be contiguous")
+    N, H, W, C = y.shape
+    if tuple(p.shape) != (N, (H - 1) // 2 + 2, (W - 1) // 2 + 2, 4 * C) or p.dtype != torch.float32 or p.device != y.device:
+        raise ValueError(f"prelu_grad_d2s: p {tuple(p.shape)} is not the phase-stacked image of y {tuple(y.shape)}")
+    g = torch.empty_like(y)
+    num = torch.empty(1, dtype=torch.float32, device=y.device) if want_dslope else None
+    L = lib()
+    ws_bytes = L.tsod_prelu_grad_d2s_workspace_bytes(N, H, W, C) if want_dslope else 0
+    ws = ARENA.get(y.device, ws_bytes) if ws_bytes else None
+    check(L.tsod_prelu_grad_d2s_f32(ptr(y), N, H, W, C, C, ptr(p), 4 * C, float(slope), ptr(g), C, ptr(num), ptr(ws), ws_bytes,
+                                    stream_ptr()), "prelu_grad_d2s")
+    return g, num
+
+
+def pixel_subsample(x: torch.Tensor, stride: int, C: int | None = None) -> torch.Tensor:
+    """xs [N,OH,OW,C] = x[n, stride oh, stride ow, :C] (tsod_pixel_subsample_f32); x [N,H,W,P] contiguous, C default P."""
+    require_cuda(x, "pixel_subsample")
+    if not x.is_contiguous() or x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("pixel_subsample: x [N,H,W,P] must be contiguous float32")
+    N, H, W, P = x.shape
+    C, stride = P if C is None else int(C), int(stride)
+    if stride < 1:
+        raise ValueError(f"pixel_subsample: stride must be >= 1, got {stride}")
+    xs = torch.empty((N, (H - 1) // stride + 1, (W - 1) // stride + 1, C), dtype=torch.float32, device=x.device)
+    check(lib().tsod_pixel_subsample_f32(ptr(x), N, H, W, C, P, stride, ptr(xs), C, stream_ptr()), "pixel_subsample")
+    return xs
+
+
+def pixel_upsample_add(dx: torch.Tensor, d: torch.Tensor, stride: int, C: int | None = None) -> torch.Tensor:
+    """dx[n, stride oh, stride ow, :C] += d[n, oh, ow, :C] in place (tsod_pixel_upsample_add_f32; dx the first operand); dx
+    [N,H,W,P], d [N,OH,OW,Pd] contiguous, C default d's Pd.  Returns dx."""
+    require_cuda(dx, "pixel_upsample_add")
+    if not (dx.is_contiguous() and d.is_contiguous()) or dx.dim() != 4 or d.dim() != 4 or dx.dtype != torch.float32:
+        raise ValueError("pixel_upsample_add: dx [N,H,W,P] and d [N,OH,OW,Pd] must be contiguous float32")
+    N, H, W, P = dx.shape
+    C, stride = d.shape[3] if C is None else int(C), int(stride)
+    if stride < 1:
+        raise ValueError(f"pixel_upsample_add: stride must be >= 1, got {stride}")
+    if tuple(d.shape[:3]) != (N, (H - 1) // stride + 1, (W - 1) // stride + 1) or d.device != dx.device or d.dtype != torch.float32:
+        raise ValueError(f"pixel_upsample_add: d {tuple(d.shape)} is not dx {tuple(dx.shape)} at stride {stride}")
+    check(lib().tsod_pixel_upsample_add_f32(ptr(dx), N, H, W, C, P, stride, ptr(d), d.shape[3], stream_ptr()), "pixel_upsample_add")
+    return dx
+
+
 def _bn_rows(t: torch.Tensor, what: str):
     if t.dim() < 2 or not t.is_contiguous():
         raise ValueError(f"{what}: contiguous [..., channels] tensors only, got {tuple(t.shape)}")

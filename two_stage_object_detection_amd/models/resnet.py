@@ -33,15 +33,15 @@ class _ResidualBlock(nn.Module):
     _stage_names: tuple = ()
 
     def _emit(self, plan: Plan, x: torch.Tensor, name: str, record: bool = False) -> torch.Tensor:
-        """``record`` (a trained block, ``resnet_grads.eligible``): the same launches, but the stage outputs stay out of the
-        buffer pool and go, with the packs, to ``plan.block_records`` for the autograd node."""
+        """``record`` (a trained block, ``resnet_grads.eligible`` / ``eligible_stage``): the same launches, but the stage
+        outputs stay out of the buffer pool and go, with the packs, to ``plan.block_records`` for the autograd node."""
         dev = plan.device
         slope = prelu_slope(self.relu)
         identity = x
         # the whole block as ONE launch (tsod_bottleneck_fp16x2): 64 mid channels, stride 1 - layer1, the HBM-bound stage of the trunk
         # (the 64-channel intermediates stay in LDS): the identity blocks layer1.1 / layer1.2 and (round 5) the block in front of
         # them, whose shortcut is a 1x1 projection at stride 1 (layer1.0): conv3 + shortcut as one stacked-K GEMM inside the launch
-        if getattr(plan, "fuse_bottleneck", False) and len(self._stage_names) == 3:
+        if getattr(plan, "fuse_bottleneck", False) and len(self._stage_names) == 3 and not record:
             ident = self.downsample is None and self.conv1.in_channels == self.conv3.out_channels
             proj = (getattr(plan, "fuse_projection", False) and self.downsample is not None and len(self.downsample) == 2 and isinstance(self.downsample[0], nn.Conv2d)
                     and self.downsample[0].kernel_size == (1, 1) and self.downsample[0].stride == (1, 1) and self.downsample[0].groups == 1)
@@ -77,7 +77,8 @@ class _ResidualBlock(nn.Module):
                     conv.weight, bn, ds_conv.weight, ds_bn, ds_conv.stride[0], dev, ACT_PRELU, slope))
                 out = plan.pool.alloc((cur.shape[0], cur.shape[1], cur.shape[2], pc.cout))
                 plan.conv(pc, cur, out, segs=[(0, pc.cin)], name=f"{name}.{cname}+downsample", x2=x, stride2=pc.stride2)
-                if cur is not x:
+                ys.append(out)                        # (no pack joins pcs: a trained block's record makes plain ones)
+                if cur is not x and not record:
                     plan.pool.release(cur)
                 cur = out
                 continue
@@ -149,6 +150,9 @@ class Bottleneck(_ResidualBlock):
         self.downsample = downsample
 
 
+_STAGES = ("layer4", "layer3", "layer2")       # what ``train_from`` may be given, narrowest section first
+
+
 class ResNet(PlanOwner, nn.Module):
     _train_mode = None           # set_train_mode(): a plain instance attribute once set - pickled and deep-copied, never in
                                  # the state_dict
@@ -199,8 +203,20 @@ class ResNet(PlanOwner, nn.Module):
         return n
 
     @property
+    def trainable_stages(self) -> tuple:
+        """The stage names ``train_from`` accepts, widest last: a stage is offered when every block from its first to the end of
+        ``layer4`` is ``resnet_grads.eligible_stage`` (resnet50 / resnet101: ("layer4", "layer3", "layer2"); resnet34 and
+        resnext50_32x4d: ()).  ``layer1`` is never offered: its blocks run as one launch each and keep no stage outputs."""
+        stages = []
+        for stage in _STAGES:
+            if not all(resnet_grads.eligible_stage(blk) for blk in getattr(self, stage)):
+                break
+            stages.append(stage)
+        return tuple(stages)
+
+    @property
     def train_mode(self):
-        """None | n (int >= 1): what ``set_train_mode`` was given last."""
+        """None | n (int >= 1) | a stage name: what ``set_train_mode`` was given last."""
         return self._train_mode
 
     def set_train_mode(self, mode):
@@ -228,12 +244,27 @@ class ResNet(PlanOwner, nn.Module):
         ``f.grad_fn.saved`` is the dict the backward reads: ``names`` (the parameter names in ``trainable_parameters()`` order),
         ``nchw``, and ``blocks``: per trained block in forward order ``name``, ``x``, ``y1``, ``y2``, ``y3`` (NHWC copies), ``w`` / ``scale``
         (the three f32 packs [Cout,KH,KW,Cin] and folded scales), ``rot`` (the 3x3 dgrad's image [C,3,3,Cout]), ``slope``, ``bn``
-        (per stage: running mean, 1 / sqrt(var + eps))."""
-        if mode is not None:
+        (per stage: running mean, 1 / sqrt(var + eps)).
+
+        ``mode`` a stage name of ``trainable_stages`` ("layer4", "layer3", "layer2"; ValueError for
+        anything else): every block from the first block of that stage to the end of ``layer4`` under the same contract, on the
+        plan key ("train_from", stage).  An identity block has the ten tensors above, a projection block thirteen: the ten, then
+        ``downsample.0.weight``, ``downsample.1.weight``, ``downsample.1.bias``.  Its entry of ``blocks`` also carries ``wd`` /
+        ``scaled`` (the shortcut's f32 pack and folded scale; ``w[2]`` / ``scale[2]`` are conv3's, made for the backward: the forward
+        runs both as one folded GEMM), ``stride``, ``s2d`` (conv2's 2x2 phase pack [4 C,2,2,Cout] where the stride is 2, and ``rot``
+        is None then) and ``bn_d``."""
+        if isinstance(mode, str):
+            if mode == "layer1":
+                raise ValueError("train_from: layer1 cannot be trained: each of its blocks runs as one launch and keeps no stage "
+                                 f"outputs for a backward; trainable_stages = {self.trainable_stages}")
+            if mode not in self.trainable_stages:
+                raise ValueError(f"train_from: stage must be one of trainable_stages = {self.trainable_stages}, got {mode!r}")
+        elif mode is not None:
             mode = int(mode)
             if mode < 1 or mode > self.n_blocks:
                 raise ValueError(f"train_blocks: n must be 1..n_blocks = {self.n_blocks} (the identity Bottlenecks at the end of "
                                  f"layer4 of this backbone), got {mode}")
+        if mode is not None:
             watched = self.__dict__.setdefault("_watched", {})
             for name, blk in self._section(mode):                # the widest mode ever set: what the refresh watches
                 watched.setdefault(name, resnet_grads.versions_of(blk))
@@ -252,7 +283,16 @@ class ResNet(PlanOwner, nn.Module):
         and one rotated 3x3 image per trained block and device."""
         return self.set_train_mode(int(n))
 
+    def train_from(self, stage: str):
+        """``set_train_mode(stage)``: every block from the first of ``stage`` (one of ``trainable_stages``) to the end of
+        ``layer4``.  Memory: what ``train_blocks`` keeps, per trained block, and per trained stride-2 3x3 and device the 2x2 phase
+        pack, 16 / 9 of the weight, in place of the rotated image."""
+        return self.set_train_mode(str(stage))
+
     def _section(self, n):
+        if isinstance(n, str):
+            return [(f"{stage}.{i}", blk) for stage in reversed(_STAGES[:_STAGES.index(n) + 1])
+                    for i, blk in enumerate(getattr(self, stage))]
         blocks = list(self.layer4)
         return [(f"layer4.{i}", blocks[i]) for i in range(len(blocks) - n, len(blocks))]
 
@@ -270,7 +310,7 @@ class ResNet(PlanOwner, nn.Module):
 
     def _plan_variant(self):
         mode = self._active_mode()
-        return () if mode is None else ("train_blocks", mode)
+        return () if mode is None else ("train_from" if isinstance(mode, str) else "train_blocks", mode)
 
     def _forward_train(self, x, slot, nchw):
         if self.training:
@@ -313,7 +353,8 @@ class ResNet(PlanOwner, nn.Module):
             plan.call(lib().tsod_maxpool3x3s2_f32, ptr(s_out), N, oh, ow, 64, 64, ptr(cur), 64, keep=(s_out, cur))
             plan.alias_amax(cur, s_out)          # range words: max |pooled| <= max |stem output|
             plan.pool.release(s_out)
-        # a training mode (with grad mode on): the last ``mode`` blocks of layer4 run the same launches, but what the autograd
+        # a training mode (with grad mode on): the section's blocks (the last ``mode`` of layer4, or a stage onward) run the same
+        # launches, but what the autograd
         # node needs of them stays out of the pool (the node copies it after the run) and is recorded for it
         mode = self._active_mode()
         trained = {name for name, _ in self._section(mode)} if mode else set()

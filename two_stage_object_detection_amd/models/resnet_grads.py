@@ -1,11 +1,15 @@
-"""The training side of ``ResNet``: the ONE autograd node of its feature map over the identity
-Bottlenecks at the end of ``layer4``, the copies the node keeps of what ``build_plan`` recorded, and what happens to the packed
-weights after an optimizer step.
+"""The training side of ``ResNet`` (DESIGN.md sections 4.21 and 4.22): the ONE autograd node of its feature map over the
+trained Bottlenecks (``train_blocks``: the identity blocks at the end of ``layer4``; ``train_from``: every block from the first
+of a stage on, projection blocks included), the copies the node keeps of what ``build_plan`` recorded, and what happens to the
+packed weights after an optimizer step.
 
 ``build_plan`` records every trained block as a dict: ``name`` ("layer4.2"), ``x`` (the block's input [N,h,w,4 width]), ``ys``
 (the three stage outputs y1, y2 [N,h,w,width] and y3 [N,h,w,4 width], each after BN and PReLU, y3 after the residual add too),
 ``pcs`` (the three ``PackedConv``), ``rot`` (conv2's rotated, scaled image: the 3x3 dgrad's weights), ``slope`` (the PReLU
-slope the launches carry by value) and ``bn`` (the three BatchNorms' running mean and 1 / sqrt(var + eps))."""
+slope the launches carry by value) and ``bn`` (the three BatchNorms' running mean and 1 / sqrt(var + eps)).  A projection block
+(``downsample``; its forward runs conv3 and the shortcut as one stacked GEMM on folded weights) carries ``pcs[2]`` as a plain
+pack of conv3 made for the backward, and ``pcd`` (the same of ``downsample.0``), ``stride``, ``s2d`` (conv2's 2x2 phase pack where the
+stride is 2; ``rot`` is None then) and ``bn_d``."""
 from __future__ import annotations
 
 import math
@@ -16,6 +20,7 @@ from torch.autograd.function import once_differentiable
 
 from .. import _ffi, hip_ops
 from .._ffi import TsodError
+from ..engine import PackedConv
 from .hardnet_grads import _bn_grads, _bn_stats
 
 
@@ -24,26 +29,53 @@ def eligible(blk) -> bool:
     return (len(blk._stage_names) == 3 and blk.conv2.groups == 1 and blk.conv2.stride == (1, 1) and blk.downsample is None)
 
 
+def eligible_stage(blk) -> bool:
+    """A block ``train_from`` can reach: a Bottleneck with a dense 3x3 at stride 1 or 2 whose shortcut is the identity or
+    Sequential(1x1 conv with groups 1 and conv2's stride, BatchNorm2d)."""
+    if len(blk._stage_names) != 3 or blk.conv2.groups != 1 or blk.conv2.stride not in ((1, 1), (2, 2)):
+        return False
+    ds = blk.downsample
+    if ds is None:
+        return blk.conv2.stride == (1, 1)
+    return (isinstance(ds, torch.nn.Sequential) and len(ds) == 2 and isinstance(ds[0], torch.nn.Conv2d)
+            and isinstance(ds[1], torch.nn.BatchNorm2d) and ds[0].kernel_size == (1, 1) and ds[0].groups == 1
+            and ds[0].stride == blk.conv2.stride and ds[0].bias is None)
+
+
 def block_record(plan, blk, name, x, ys, pcs):
     """What the node needs of one trained block of the plan being built (``_ResidualBlock._emit``)."""
     slope = pcs[0].slope
     if not (math.isfinite(slope) and slope > 0.0):
         raise TsodError(f"{name}: the PReLU slope is {slope}; a trained block needs a finite slope > 0 (its backward takes the "
                         "mask from the saved outputs, and sign(prelu(z)) = sign(z) only then)")
-    pc2 = pcs[1]
-    rot = plan.packed(f"{name}.conv2.rot", lambda: hip_ops.rotate_conv3x3_weight(pc2.w, pc2.scale))
+    pc2, pcs = pcs[1], list(pcs)
+    ds, rec = blk.downsample, {}
+    if ds is not None:
+        # the forward's stacked GEMM holds conv3 and the shortcut folded and side by side: the backward reads plain packs and
+        # folded scales of its own, made once per (block, device) under the block's name (refresh_packs drops them with the rest)
+        if len(pcs) == 2:
+            pcs.append(plan.packed(f"{name}.conv3.grad", lambda: PackedConv(blk.conv3.weight, plan.device, bn=blk.bn3)))
+        pcd = plan.packed(f"{name}.downsample.grad", lambda: PackedConv(ds[0].weight, plan.device, bn=ds[1]))
+        rec = dict(pcd=pcd, stride=pc2.stride, bn_d=_bn_stats(ds[1], pcd.cout, plan.device),
+                   s2d=plan.packed(f"{name}.conv2.s2d", lambda: hip_ops.s2d_conv3x3_weight(pc2.w, pc2.scale)) if pc2.stride == 2
+                   else None)
+    rot = None if pc2.stride == 2 else plan.packed(f"{name}.conv2.rot", lambda: hip_ops.rotate_conv3x3_weight(pc2.w, pc2.scale))
     bn = [_bn_stats(getattr(blk, b), pc.cout, plan.device) for (_, b), pc in zip(blk._stage_names, pcs)]
-    return dict(name=name, x=x, ys=list(ys), pcs=list(pcs), rot=rot, slope=slope, bn=bn)
+    return dict(name=name, x=x, ys=list(ys), pcs=pcs, rot=rot, slope=slope, bn=bn, **rec)
 
 
-def block_copy(rec):
+def block_copy(rec, x=None):
     """The node's own view of a block record: forwards and backwards may interleave in any order.  The activations are copied
-    (the plan's buffers are written by the next forward).  The packs, scales and the rotated image are held by reference:
-    nothing writes them in place - a changed block's packs are dropped and made anew (``refresh_packs``), so the objects the
-    forward saw stay as they were for as long as the node holds them."""
+    (the plan's buffers are written by the next forward); ``x``: the copy that already exists of the block's input (the previous
+    trained block's y3 is the same buffer: one copy serves both, the backward writes into neither).  The packs, scales and the
+    rotated image are held by reference: nothing writes them in place - a changed block's packs are dropped and made anew
+    (``refresh_packs``), so the objects the forward saw stay as they were for as long as the node holds them."""
     y1, y2, y3 = (t.clone() for t in rec["ys"])
-    return dict(name=rec["name"], x=rec["x"].clone(), y1=y1, y2=y2, y3=y3, w=[pc.w for pc in rec["pcs"]],
-                scale=[pc.scale for pc in rec["pcs"]], rot=rec["rot"], slope=rec["slope"], bn=rec["bn"])
+    out = dict(name=rec["name"], x=rec["x"].clone() if x is None else x, y1=y1, y2=y2, y3=y3, w=[pc.w for pc in rec["pcs"]],
+               scale=[pc.scale for pc in rec["pcs"]], rot=rec["rot"], slope=rec["slope"], bn=rec["bn"])
+    if "pcd" in rec:                                              # a projection block
+        out.update(wd=rec["pcd"].w, scaled=rec["pcd"].scale, stride=rec["stride"], s2d=rec["s2d"], bn_d=rec["bn_d"])
+    return out
 
 
 class _ResNetGrads(torch.autograd.Function):
@@ -51,7 +83,11 @@ class _ResNetGrads(torch.autograd.Function):
     hands out the map the plan computed; backward runs, on the node's OWN copies (``ctx.saved``), per trained block from the
     last one down: tsod_prelu_grad_f32 on y3, conv3's tsod_pw_wgrad_f32 / tsod_pw_dgrad_f32, the mask on y2, conv2's
     tsod_conv3x3_dense_wgrad_f32 and its dx through the forward conv library on the rotated image, the mask on y1, conv1's wgrad,
-    and dx = g3 + conv1's dgrad (skipped for the earliest block).  It returns the gradients in torch's parameter layouts."""
+    and dx = g3 + conv1's dgrad (skipped for the earliest block).  A projection block (DESIGN.md section 4.22): the shortcut's
+    tsod_pw_wgrad_f32 / tsod_pw_dgrad_f32 from g3 on the rows tsod_pixel_subsample_f32 takes of x; conv2 through
+    tsod_conv3x3_strided_wgrad_f32; at stride 2 its dx is the forward conv library on the 2x2 phase pack, read by
+    tsod_prelu_grad_d2s_f32; dx = conv1's dgrad, then the shortcut's added by tsod_pixel_upsample_add_f32.  It returns the
+    gradients in torch's parameter layouts."""
 
     @staticmethod
     def forward(ctx, saved, *params):
@@ -86,22 +122,54 @@ class _ResNetGrads(torch.autograd.Function):
             params_of(prefix, i, d_w, d_sc, d_sh, b["bn"][i - 1], lambda d: d.view(d.shape[0], d.shape[1], 1, 1))
             return dx
 
+        def shortcut(prefix, b, g3, want_dx):
+            """downsample.0 / downsample.1 from g3 -> the shortcut's dx over the subsampled grid (None unless wanted)."""
+            w, g, bb = (need[f"{prefix}.downsample.{k}"] for k in ("0.weight", "1.weight", "1.bias"))
+            if not (w or g or bb or want_dx):
+                return None
+            wd = b["wd"]
+            xs = b["x"] if b["stride"] == 1 else hip_ops.pixel_subsample(b["x"], b["stride"])
+            dxs, d_w, d_sc, d_sh = hip_ops.conv1x1_bn_relu6_grad(xs, [(0, wd.shape[3])], wd, b["scaled"], None, g3,
+                                                                 dx=torch.empty_like(xs) if want_dx else None, want_dx=want_dx,
+                                                                 want_dw=w, want_dscale=g, want_dshift=g or bb)
+            if d_w is not None:
+                out[f"{prefix}.downsample.0.weight"] = d_w.view(d_w.shape[0], d_w.shape[1], 1, 1)
+            if d_sc is not None:
+                out[f"{prefix}.downsample.1.weight"], out[f"{prefix}.downsample.1.bias"] = _bn_grads(d_sc, d_sh, b["bn_d"], d_sh.numel())
+            elif d_sh is not None:
+                out[f"{prefix}.downsample.1.bias"] = d_sh
+            return dxs
+
         blocks = sv["blocks"]
         for bi in range(len(blocks) - 1, -1, -1):
             b = blocks[bi]
             prefix, a = b["name"], b["slope"]
             want_a = need[prefix + ".relu.weight"]
+            first = bi == 0                                       # the earliest trained block: nobody wants its dx
+            proj = "wd" in b
             g3, s3 = hip_ops.prelu_grad(b["y3"], d3, a, want_dslope=want_a)
             d2 = pointwise(prefix, 3, b["y2"], b, g3, torch.empty_like(b["y2"]), False, True)
+            dxs = shortcut(prefix, b, g3, not first) if proj else None
             g2, s2 = hip_ops.prelu_grad(b["y2"], d2, a, want_dslope=want_a)
             w2 = wants(prefix, 2)
             if any(w2.values()):
-                d_w, d_sc, d_sh = hip_ops.conv3x3_dense_wgrad(g2, b["y1"], b["w"][1], b["scale"][1], **w2)
+                if proj:
+                    d_w, d_sc, d_sh = hip_ops.conv3x3_strided_wgrad(g2, b["y1"], b["w"][1], b["scale"][1], stride=b["stride"], **w2)
+                else:
+                    d_w, d_sc, d_sh = hip_ops.conv3x3_dense_wgrad(g2, b["y1"], b["w"][1], b["scale"][1], **w2)
                 params_of(prefix, 2, d_w, d_sc, d_sh, b["bn"][1], lambda d: d.permute(0, 3, 1, 2).contiguous())
-            d1 = hip_ops.conv2d_nhwc(g2, b["rot"], pad=1, precision=_ffi.PREC_F32)
-            g1, s1 = hip_ops.prelu_grad(b["y1"], d1, a, want_dslope=want_a)
-            first = bi == 0                                       # the earliest trained block: nobody wants its dx
-            d3 = pointwise(prefix, 1, b["x"], b, g1, None if first else g3.clone(), True, not first)
+            if b["rot"] is None:                                  # stride 2: the phase-stacked image, read through the mask pass
+                p = hip_ops.conv2d_nhwc(g2, b["s2d"], pad=1, precision=_ffi.PREC_F32)
+                g1, s1 = hip_ops.prelu_grad_d2s(b["y1"], p, a, want_dslope=want_a)
+            else:
+                d1 = hip_ops.conv2d_nhwc(g2, b["rot"], pad=1, precision=_ffi.PREC_F32)
+                g1, s1 = hip_ops.prelu_grad(b["y1"], d1, a, want_dslope=want_a)
+            if not proj:
+                d3 = pointwise(prefix, 1, b["x"], b, g1, None if first else g3.clone(), True, not first)
+            else:
+                d3 = pointwise(prefix, 1, b["x"], b, g1, None if first else torch.empty_like(b["x"]), False, not first)
+                if not first:
+                    hip_ops.pixel_upsample_add(d3, dxs, b["stride"])
             if want_a:
                 out[prefix + ".relu.weight"] = ((s3 + s2) + s1) / a
         return (None,) + tuple(out.get(k) if n else None for k, n in need.items())
@@ -110,8 +178,12 @@ class _ResNetGrads(torch.autograd.Function):
 def feature_map_with_grads(plan, nchw, named):
     """The output of the training-mode ``plan`` that just ran, carrying the node over ``named`` (``_trainable_named()``)."""
     out = plan.output_nhwc
-    saved = dict(out=hip_ops.nhwc_to_nchw(out) if nchw else out.clone(), nchw=nchw, names=[k for k, _ in named],
-                 blocks=[block_copy(r) for r in plan.block_records])
+    blocks, prev = [], None
+    for rec in plan.block_records:
+        shared = prev is not None and prev["ys"][2] is rec["x"]
+        blocks.append(block_copy(rec, blocks[-1]["y3"] if shared else None))
+        prev = rec
+    saved = dict(out=hip_ops.nhwc_to_nchw(out) if nchw else out.clone(), nchw=nchw, names=[k for k, _ in named], blocks=blocks)
     return _ResNetGrads.apply(saved, *(p for _, p in named))
 
 

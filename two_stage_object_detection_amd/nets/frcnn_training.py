@@ -219,16 +219,20 @@ class FasterRCNNTrainer(nn.Module):
     through them and moves its running statistics (``HarDNetFeatureExtraction.set_train_mode``); the
     frozen section below stays folded, dropout stays the identity.  Under ``.eval()`` nothing changes.
 
-    ResNet backbones: ``backbone_grads`` keeps raising ValueError for them; the identity Bottlenecks at the end of ``layer4``
-    (resnet50 / resnet101: ``layer4.1``, ``layer4.2``) train through the ``features=`` path, whose map may carry any autograd
-    history - here the backbone's own node (``ResNet.train_blocks``):
+    ``backbone_grads="layer4" | "layer3" | "layer2"`` (ResNet backbones that offer the stage: ``feat_extra.trainable_stages``,
+    resnet50 / resnet101): the same with ``feat_extra.train_from(stage)`` - every Bottleneck from the first block of that stage to
+    the end of ``layer4``, projection blocks included (33 / 96 / 139 tensors for resnet50).  BatchNorm
+    stays folded: ``bn_batch_stats=True`` raises ValueError with them, and ints, "tail" and "full" keep raising for ResNet
+    backbones.  The identity Bottlenecks at the end of ``layer4`` alone (``layer4.1``, ``layer4.2``) train through the
+    ``features=`` path, whose map may carry any autograd history - here the backbone's own node (``ResNet.train_blocks``,
+    DESIGN.md section 4.21):
 
         tr = FasterRCNNTrainer("train", nc, backbone="resnet50", head_grads=True).eval()
         tr.feat_extra.requires_grad_(False); tr.feat_extra.train_blocks(2)
         for p in tr.feat_extra.trainable_parameters(): p.requires_grad_(True)
         losses = tr(x, bboxes, labels, features=tr.feat_extra(x))[0]; (losses[-1] / 32).backward()
 
-    Not provided: the rest of the ResNet backbones' backward - projection blocks, the earlier stages, the stem, BasicBlock,
+    Not provided: the rest of the ResNet backbones' backward - ``layer1`` and the stem, BasicBlock,
     ResNeXt's grouped 3x3, batch-statistics BatchNorm (``head_grads`` fine-tunes the heads
     on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks, ``"full"`` the whole
     HarDNet; ``features=`` trains a
@@ -242,12 +246,21 @@ class FasterRCNNTrainer(nn.Module):
         if head_img_size not in ("chw", "hw"):
             raise ValueError(f"head_img_size must be 'chw' (the reference's) or 'hw', got {head_img_size!r}")
         n_blocks = backbone_grads if isinstance(backbone_grads, int) and not isinstance(backbone_grads, bool) else None
-        if backbone_grads not in (None, "tail", "full") and (n_blocks is None or n_blocks < 1):
+        hardnet = str(backbone).startswith("hardnet")
+        # a ResNet stage name ("layer4" ...): checked against the backbone's trainable_stages once it is built
+        stage = backbone_grads if isinstance(backbone_grads, str) and backbone_grads not in ("tail", "full") and not hardnet else None
+        if stage is None and backbone_grads not in (None, "tail", "full") and (n_blocks is None or n_blocks < 1):
             raise ValueError(f"backbone_grads must be None, 'tail', 'full' or a number of HarDBlocks >= 1, got {backbone_grads!r}")
-        if backbone_grads is not None and not str(backbone).startswith("hardnet"):
+        if stage is None and backbone_grads is not None and not hardnet:
             raise ValueError(f"backbone_grads={backbone_grads!r} trains the HarDNet tail (the last four modules of "
-                             f"feat_extra.base) and the HarDBlocks before it; backbone {backbone!r} has none")
+                             f"feat_extra.base) and the HarDBlocks before it; backbone {backbone!r} has none (a ResNet backbone "
+                             "takes a stage name of feat_extra.trainable_stages)")
+        if stage is not None and bn_batch_stats:
+            raise ValueError(f"bn_batch_stats=True: backbone {backbone!r} trains with BatchNorm folded only (backbone_grads={stage!r})")
         self.feat_extra, feat_ch, native_stride = _make_extractor(backbone)
+        if stage is not None and stage not in getattr(self.feat_extra, "trainable_stages", ()):
+            raise ValueError(f"backbone_grads={stage!r}: backbone {backbone!r} offers the stages "
+                             f"{getattr(self.feat_extra, 'trainable_stages', ())} (feat_extra.trainable_stages)")
         if n_blocks is not None and n_blocks > self.feat_extra.n_blocks:
             raise ValueError(f"backbone_grads={n_blocks}: backbone {backbone!r} has {self.feat_extra.n_blocks} HarDBlocks")
         self.feat_stride = native_stride if (feat_stride == 16 and native_stride != 16) else feat_stride
@@ -327,12 +340,17 @@ class FasterRCNNTrainer(nn.Module):
         grads = self.head_grads and torch.is_grad_enabled()
         tail = self.backbone_grads is not None and features is None and torch.is_grad_enabled()
         if tail or (grads and features is None):                         # what the mode does not reach must be frozen
-            ours = {id(p) for p in self.feat_extra.set_train_mode(self.backbone_grads, self.bn_batch_stats).trainable_parameters()} if tail else ()
+            stage = isinstance(self.backbone_grads, str) and self.backbone_grads not in ("tail", "full")       # a ResNet stage
+            mode_args = (self.backbone_grads,) if stage else (self.backbone_grads, self.bn_batch_stats)
+            ours = {id(p) for p in self.feat_extra.set_train_mode(*mode_args).trainable_parameters()} if tail else ()
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
             if frozen:
                 why = ("(head_grads=True) computes the head parameters' gradients on a frozen backbone, but" if not tail else
                        "(backbone_grads='tail') reaches the six tail tensors of the backbone only (feat_extra.tail_parameters()); "
                        "every other backbone parameter must be frozen, but" if self.backbone_grads == "tail" else
+                       f"(backbone_grads={self.backbone_grads!r}) reaches the backbone's blocks from {self.backbone_grads}.0 to the end "
+                       "of layer4 only (feat_extra.trainable_parameters()); every other backbone parameter must be frozen, but"
+                       if stage else
                        f"(backbone_grads={self.backbone_grads}) reaches the backbone's tail and last {self.backbone_grads} HarDBlocks "
                        "only (feat_extra.trainable_parameters()); every other backbone parameter must be frozen, but")
                 raise TsodError(f"FasterRCNNTrainer{why} feat_extra.{frozen[0]} (and {len(frozen) - 1} more) requires grad"
