@@ -727,6 +727,39 @@ int tsod_pixel_subsample_f32(const float *x, int32_t N, int32_t H, int32_t W, in
 int tsod_pixel_upsample_add_f32(float *dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t dx_pitch, int32_t stride,
                                 const float *d, int32_t d_pitch, tsod_stream_t stream);
 
+/* ---- the backward of ResNet's stem ------------------------------------------------------------------
+ * z = scale[o] * conv7x7(x4, w, stride 2, pad 3)[o] + shift[o], y = prelu(z) [N][OH][OW] with OH = (H - 1) / 2 + 1, then
+ * MaxPool2d(3, 2, 1) to [N][PH][PW] with PH = (OH - 1) / 2 + 1, PW = (OW - 1) / 2 + 1.  No float atomics; bit-identical from run
+ * to run.
+ * tsod_prelu_grad_pool_f32: tsod_prelu_grad_f32 for y [N][OH][OW][y_pitch] (C channels) whose dy is never written out: it is
+ *   gathered from dp [N][PH][PW][dp_pitch], the gradient of the pooled map, as dy[n][oh][ow][c] = the sum, over the windows
+ *   (ph, pw) that contain (oh, ow) in ascending (ph, pw), of dp[n][ph][pw][c] where the window's maximum is first met at
+ *   (oh, ow).  Window ph covers rows 2 ph - 1 .. 2 ph + 1; "first": an ascending (kh, kw) scan of the window's taps inside the
+ *   image with a strict > to replace (torch's max_pool2d backward); the winner is recomputed from y, no index tensor exists.
+ *   Then g = dy * (y > 0 ? 1 : slope) and *dslope_num = sum dy * y * [y < 0]; the grid, the sum and its order are
+ *   tsod_prelu_grad_f32's for rows = N OH OW, an exact y == 0 behaves as there.  dslope_num may be NULL.  Inputs are finite (the
+ *   place of a NaN among the taps is not specified).  16-byte aligned, C and pitches multiples of 4; N OH OW C / 4 below 2^31
+ *   (TSOD_ERR_UNSUPPORTED).  workspace: tsod_prelu_grad_pool_workspace_bytes(N, OH, OW, C) (0 for a shape that is refused).
+ * tsod_conv7x7s2_wgrad_f32: the parameter gradients of z from the masked gradient g [N][OH][OW][g_pitch] (Cout columns), the
+ *   staged image x4 [N][H][W][4], w [Cout][7][8][4] unscaled (the forward's f32 pack: kw = 7 and c = 3 are zero padding), scale
+ *   [Cout].  dWraw[o][kh][kw][c] = sum_{n,oh,ow} g[n][oh][ow][o] x4[n][2 oh - 3 + kh][2 ow - 3 + kw][c] (taps outside the image
+ *   are zeros) on v_mfma_f32_32x32x2_f32, one kernel row (8 x 4 floats, contiguous in x4) per column tile, over slices of pixel
+ *   pairs numbered (n, oh, ow / 2) ascending: ceil(pairs / 256) pairs per slice, at least 64; the shape alone fixes them.  A
+ *   finishing launch adds the slices in slice order and writes dw [Cout][7][8][4] = scale[o] * dWraw with exact zeros in the
+ *   padding, dscale [Cout] = the sum over the 147 real taps of w * dWraw in ascending (kh, kw, c), dshift [Cout] = sum g.
+ *   Each of the three may be NULL (not all).  Channel 3 of x4 and the pixels a kw = 7 tap would read reach no result, whatever
+ *   they hold (a NaN included).  Cout must be 64 and N H W at most (2^31 - 1) / 4 (TSOD_ERR_UNSUPPORTED otherwise).  16-byte
+ *   aligned pointers, g_pitch a multiple of 4.
+ *   workspace: tsod_conv7x7s2_wgrad_workspace_bytes(N, H, W, Cout) = slices * 64 * 225 floats; 0 for a shape that is refused. */
+size_t tsod_prelu_grad_pool_workspace_bytes(int32_t N, int32_t OH, int32_t OW, int32_t C);
+int tsod_prelu_grad_pool_f32(const float *y, int32_t N, int32_t OH, int32_t OW, int32_t C, int32_t y_pitch, const float *dp,
+                             int32_t dp_pitch, float slope, float *g, int32_t g_pitch, float *dslope_num, void *workspace,
+                             size_t workspace_bytes, tsod_stream_t stream);
+size_t tsod_conv7x7s2_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t Cout);
+int tsod_conv7x7s2_wgrad_f32(const float *g, int32_t N, int32_t H, int32_t W, int32_t Cout, int32_t g_pitch, const float *x4,
+                             const float *w, const float *scale, float *dw, float *dscale, float *dshift, void *workspace,
+                             size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- the parameter gradients of HarDNet's first layer ----------------------------------------------
  * y[n][oh][ow][o] = relu6(scale[o] * sum_{kh,kw,c} w[o][kh][kw][c] x4[n][oh s - 1 + kh][ow s - 1 + kw][c] + shift[o]), s = stride
  * (1 or 2), pad 1, OH = (H - 1) / s + 1, OW = (W - 1) / s + 1.  x4 [N][H][W][4] (channel 3 is padding and is never read), y

@@ -296,6 +296,12 @@ _SIGNATURES = {
                                          c_void_p]),
     "tsod_pixel_upsample_add_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
                                             c_void_p]),
+    "tsod_prelu_grad_pool_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "tsod_prelu_grad_pool_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float,
+                                         c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_conv7x7s2_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "tsod_conv7x7s2_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_conv3x3_wgrad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "tsod_conv3x3_wgrad_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                        c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

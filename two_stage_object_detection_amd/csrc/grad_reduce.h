@@ -1,5 +1,5 @@
 // grad_reduce.h -- what the backward files (head_grads.hip, pw_grads.hip, conv_grads.hip, conv_strided_grads.hip, conv3x3_grads.hip,
-// dw_grads.hip) share, once: the
+// stem_grads.hip, dw_grads.hip) share, once: the
 // f32 MFMA weight-gradient tile with its slice plan, the fixed-order sum of a workgroup's waves through LDS, the sum of the
 // slices' partials in slice order, and the strict ReLU6 window.  The results of those files are bit-identical from run to run
 // because every order below depends on the shape only; it is stated here and nowhere else:
@@ -17,6 +17,10 @@
 //                             OUTPUT grid (m = (n, oh, ow) ascending): at stride 1 the dense kernel's orders, add for add
 //   conv_grads.hip, strided   tsod_prelu_grad_d2s_f32 is tsod_strided_sum_256 over y's N H W rows (where dy is read from does
 //                             not enter the order); tsod_pixel_upsample_add_f32 makes one add per element, dx + d
+//   stem_grads.hip            tsod_prelu_grad_pool_f32 adds the won windows' dp in ascending (ph, pw), then tsod_strided_sum_256
+//                             over y's N OH OW rows; tsod_conv7x7s2_wgrad_f32: a wave adds its pixel pairs ascending, the wave tree
+//                             per tile of 32 channels, dshift's two pixel halves last, the slices by tsod_sum_in_slice_order, dscale
+//                             one thread's sum over the 147 real taps in ascending (kh, kw, c)
 #pragma once
 #include "tsod_internal.h"
 

@@ -706,6 +706,64 @@ def prelu_grad_d2s(y: torch.Tensor, p: torch.Tensor, slope: float, want_dslope: 
     return g, num
 
 
+def prelu_grad_pool(y: torch.Tensor, dp: torch.Tensor, slope: float, want_dslope: bool = True, C: int | None = None, g=None):
+    """``prelu_grad`` for the input y [N,OH,OW,>= C] of ``MaxPool2d(3, 2, 1)`` whose dy is gathered from dp [N,PH,PW,>= C], the
+    gradient of the pooled map (PH = (OH-1)//2+1; DESIGN.md section 4.23; tsod_prelu_grad_pool_f32) -> (g, dslope_num): every
+    element takes the dp of the windows whose first maximum it is.  The channels are the first ``C`` of each pixel (default
+    y's last dimension); ``g``: where to write ([N,OH,OW,>= C]; default a fresh [N,OH,OW,C])."""
+    require_cuda(y, "prelu_grad_pool")
+    if y.dim() != 4 or dp.dim() != 4 or not (y.is_contiguous() and dp.is_contiguous() and (g is None or g.is_contiguous())):
+        raise ValueError("prelu_grad_pool: y [N,OH,OW,P], dp [N,PH,PW,P] and g must be contiguous")
+    N, OH, OW, Py = y.shape
+    C = Py if C is None else int(C)
+    if g is None:
+        g = torch.empty((N, OH, OW, C), dtype=torch.float32, device=y.device)
+    if (tuple(dp.shape[:3]) != (N, (OH - 1) // 2 + 1, (OW - 1) // 2 + 1) or dp.shape[3] < C or Py < C or g.dim() != 4
+            or tuple(g.shape[:3]) != (N, OH, OW) or g.shape[3] < C
+            or any(t.dtype != torch.float32 or t.device != y.device for t in (y, dp, g))):
+        raise ValueError(f"prelu_grad_pool: dp {tuple(dp.shape)} / g {tuple(g.shape)} do not belong to {C} channels of y "
+                         f"{tuple(y.shape)} as float32 on {y.device}")
+    num = torch.empty(1, dtype=torch.float32, device=y.device) if want_dslope else None
+    L = lib()
+    ws_bytes = L.tsod_prelu_grad_pool_workspace_bytes(N, OH, OW, C) if want_dslope else 0
+    ws = ARENA.get(y.device, ws_bytes) if ws_bytes else None
+    check(L.tsod_prelu_grad_pool_f32(ptr(y), N, OH, OW, C, Py, ptr(dp), dp.shape[3], float(slope), ptr(g), g.shape[3], ptr(num),
+                                     ptr(ws), ws_bytes, stream_ptr()), "prelu_grad_pool")
+    return g, num
+
+
+def conv7x7s2_wgrad(g, x4, w, scale, want_dw=True, want_dscale=True, want_dshift=True, raw=False):
+    """The parameter gradients of ResNet's conv1, z = scale * conv7x7(x4, w, stride 2, pad 3) + shift, from the masked gradient
+    g (tsod_conv7x7s2_wgrad_f32) -> (dW [64,3,7,7] in torch's layout or None, dscale [64] or None,
+    dshift [64] or None).  g [N,OH,OW,>= 64] (the first 64 columns), x4 [N,H,W,4] the staged image (channel 3 reaches nothing),
+    w [64,7,8,4] the forward's f32 pack, scale [64]; all contiguous.  ``raw``: dW as the kernel writes it, [64,7,8,4] with exact
+    zeros in the padding."""
+    require_cuda(x4, "conv7x7s2_wgrad")
+    if not (g.is_contiguous() and x4.is_contiguous() and w.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("conv7x7s2_wgrad: g, x4, w and scale must be contiguous")
+    if x4.dim() != 4 or x4.shape[3] != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (7, 8, 4):
+        raise ValueError(f"conv7x7s2_wgrad: x4 must be [N,H,W,4] and w [Cout,7,8,4], got {tuple(x4.shape)}, {tuple(w.shape)}")
+    N, H, W, _ = x4.shape
+    Cout = w.shape[0]
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if g.dim() != 4 or tuple(g.shape[:3]) != (N, OH, OW) or g.shape[3] < Cout or scale.numel() != Cout:
+        raise ValueError(f"conv7x7s2_wgrad: g {tuple(g.shape)}, x4 {tuple(x4.shape)}, w {tuple(w.shape)} do not belong together")
+    if not (want_dw or want_dscale or want_dshift):
+        raise ValueError("conv7x7s2_wgrad: nothing is wanted")
+    dev = x4.device
+    dw = torch.empty_like(w) if want_dw else None
+    dscale = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dscale else None
+    dshift = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dshift else None
+    L = lib()
+    ws_bytes = L.tsod_conv7x7s2_wgrad_workspace_bytes(N, H, W, Cout)
+    ws = ARENA.get(dev, ws_bytes) if ws_bytes else None
+    check(L.tsod_conv7x7s2_wgrad_f32(ptr(g), N, H, W, Cout, g.shape[3], ptr(x4), ptr(w), ptr(scale), ptr(dw), ptr(dscale),
+                                     ptr(dshift), ptr(ws), ws_bytes, stream_ptr()), "conv7x7s2_wgrad")
+    if dw is not None and not raw:
+        dw = dw[:, :, :7, :3].permute(0, 3, 1, 2).contiguous()
+    return dw, dscale, dshift
+
+
 def pixel_subsample(x: torch.Tensor, stride: int, C: int | None = None) -> torch.Tensor:
     """xs [N,OH,OW,C] = x[n, stride oh, stride ow, :C] (tsod_pixel_subsample_f32); x [N,H,W,P] contiguous, C default P."""
     require_cuda(x, "pixel_subsample")

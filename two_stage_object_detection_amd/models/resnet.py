@@ -151,6 +151,7 @@ class Bottleneck(_ResidualBlock):
 
 
 _STAGES = ("layer4", "layer3", "layer2")       # what ``train_from`` may be given, narrowest section first
+_STEM = "stem"                                 # ... and the widest: conv1 / bn1 / relu and every block
 
 
 class ResNet(PlanOwner, nn.Module):
@@ -215,8 +216,25 @@ class ResNet(PlanOwner, nn.Module):
         return tuple(stages)
 
     @property
+    def trainable_sections(self) -> tuple:
+        """Everything ``train_from`` accepts, widest last: ``trainable_stages``, then "stem" (the whole backbone: ``conv1``,
+        ``bn1``, ``relu`` and every block of ``layer1`` ... ``layer4``) where all three stages are offered, every block of
+        ``layer1`` is ``resnet_grads.eligible_stage``, ``conv1`` is Conv2d(3, 64, 7, 2, 3, bias=False) and ``maxpool`` is
+        MaxPool2d(3, 2, 1) (resnet50 / resnet101; resnet34 and resnext50_32x4d: ())."""
+        stages = self.trainable_stages
+        c, mp = self.conv1, self.maxpool
+        pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        stem_ok = (isinstance(c, nn.Conv2d) and (c.in_channels, c.out_channels) == (3, 64) and c.kernel_size == (7, 7)
+                   and c.stride == (2, 2) and c.padding == (3, 3) and c.dilation == (1, 1) and c.groups == 1 and c.bias is None
+                   and isinstance(mp, nn.MaxPool2d) and pair(mp.kernel_size) == (3, 3) and pair(mp.stride) == (2, 2)
+                   and pair(mp.padding) == (1, 1) and pair(mp.dilation) == (1, 1) and not mp.ceil_mode)
+        if stages == _STAGES and stem_ok and all(resnet_grads.eligible_stage(blk) for blk in self.layer1):
+            return stages + (_STEM,)
+        return stages
+
+    @property
     def train_mode(self):
-        """None | n (int >= 1) | a stage name: what ``set_train_mode`` was given last."""
+        """None | n (int >= 1) | a name of ``trainable_sections``: what ``set_train_mode`` was given last."""
         return self._train_mode
 
     def set_train_mode(self, mode):
@@ -252,13 +270,28 @@ class ResNet(PlanOwner, nn.Module):
         ``downsample.0.weight``, ``downsample.1.weight``, ``downsample.1.bias``.  Its entry of ``blocks`` also carries ``wd`` /
         ``scaled`` (the shortcut's f32 pack and folded scale; ``w[2]`` / ``scale[2]`` are conv3's, made for the backward: the forward
         runs both as one folded GEMM), ``stride``, ``s2d`` (conv2's 2x2 phase pack [4 C,2,2,Cout] where the stride is 2, and ``rot``
-        is None then) and ``bn_d``."""
+        is None then) and ``bn_d``.
+
+        ``mode`` "stem" (where ``trainable_sections`` offers it; ``train_full()``): the whole backbone,
+        on the plan key ("train_from", "stem").  ``trainable_parameters()`` is then every parameter of an ``include_top=False``
+        module in module order: ``conv1.weight``, ``bn1.weight``, ``bn1.bias``, ``relu.weight``, then the blocks of ``layer1`` ...
+        ``layer4`` as above.  The contract is the same but for the launches: this plan always runs the stem and ``layer1`` as
+        per-layer launches (conv1 as a ``PackedConv``, tsod_maxpool3x3s2_f32, three convs per block), whatever ``fuse_stem``,
+        ``fuse_bottleneck`` and ``fuse_projection`` say - the one-launch kernels keep nothing for a backward - so its map has the
+        bits of the inference forward with those three switches off (the default); inference keeps its one-launch kernels.
+        The stem's slope must be finite and > 0 too.  ``saved`` gains ``stem``: ``x4`` (the staged image [N,H,W,4]), ``y``
+        (conv1's output after BN and PReLU), ``w`` / ``scale`` (conv1's f32 pack [64,7,8,4] and folded scale), ``slope``, ``bn``;
+        the pooled map is ``blocks[0]["x"]``.  With the four stem tensors frozen (``requires_grad_(False)``) no stem launch runs
+        in the backward and ``layer1.0`` is the earliest block: "from layer1 on"."""
         if isinstance(mode, str):
             if mode == "layer1":
                 raise ValueError("train_from: layer1 cannot be trained: each of its blocks runs as one launch and keeps no stage "
-                                 f"outputs for a backward; trainable_stages = {self.trainable_stages}")
-            if mode not in self.trainable_stages:
-                raise ValueError(f"train_from: stage must be one of trainable_stages = {self.trainable_stages}, got {mode!r}")
+                                 f"outputs for a backward; trainable_stages = {self.trainable_stages}.  Where trainable_sections "
+                                 'offers "stem", train_from("stem") with conv1 / bn1 / relu frozen by requires_grad_(False) '
+                                 "trains from layer1 on: that plan runs layer1 as per-layer launches")
+            if mode not in self.trainable_sections:
+                raise ValueError(f"train_from: stage must be one of trainable_stages = {self.trainable_stages} (trainable_sections "
+                                 f"= {self.trainable_sections}), got {mode!r}")
         elif mode is not None:
             mode = int(mode)
             if mode < 1 or mode > self.n_blocks:
@@ -266,7 +299,7 @@ class ResNet(PlanOwner, nn.Module):
                                  f"layer4 of this backbone), got {mode}")
         if mode is not None:
             watched = self.__dict__.setdefault("_watched", {})
-            for name, blk in self._section(mode):                # the widest mode ever set: what the refresh watches
+            for name, blk in self._stem_modules(mode) + self._section(mode):     # the widest mode ever set: what the refresh watches
                 watched.setdefault(name, resnet_grads.versions_of(blk))
         self._train_mode = mode
         return self
@@ -289,7 +322,17 @@ class ResNet(PlanOwner, nn.Module):
         pack, 16 / 9 of the weight, in place of the rotated image."""
         return self.set_train_mode(str(stage))
 
+    def train_full(self):
+        """``set_train_mode("stem")``: every parameter of the backbone (named after HarDNet's).  Memory: what ``train_from``
+        keeps for every block, and the stem's output N x OH x OW x 64 floats and the staged image N x H x W x 4, each twice."""
+        return self.set_train_mode(_STEM)
+
+    def _stem_modules(self, mode):
+        return [(k, getattr(self, k)) for k in resnet_grads.STEM_MODULES] if mode == _STEM else []
+
     def _section(self, n):
+        if n == _STEM:
+            return [(f"layer{li}.{i}", blk) for li in range(1, 5) for i, blk in enumerate(getattr(self, f"layer{li}"))]
         if isinstance(n, str):
             return [(f"{stage}.{i}", blk) for stage in reversed(_STAGES[:_STAGES.index(n) + 1])
                     for i, blk in enumerate(getattr(self, stage))]
@@ -297,7 +340,8 @@ class ResNet(PlanOwner, nn.Module):
         return [(f"layer4.{i}", blocks[i]) for i in range(len(blocks) - n, len(blocks))]
 
     def _trainable_named(self):
-        return [(f"{name}.{k}", p) for name, blk in self._section(self._train_mode or 0) for k, p in blk.named_parameters()]
+        mode = self._train_mode or 0
+        return [(f"{name}.{k}", p) for name, blk in self._stem_modules(mode) + self._section(mode) for k, p in blk.named_parameters()]
 
     def trainable_parameters(self):
         """The parameters the feature map's autograd node reaches, in module order; empty with no mode on."""
@@ -339,7 +383,9 @@ class ResNet(PlanOwner, nn.Module):
         x4 = plan.pool.alloc((N, H, W, 4))
         plan.input_nhwc = x4
         oh, ow, ph, pw = stem_out_hw(H, W)
-        if self.fuse_stem and tuple(self.conv1.weight.shape) == (64, 3, 7, 7):
+        mode = self._active_mode()
+        plan.stem_record = None
+        if mode != _STEM and self.fuse_stem and tuple(self.conv1.weight.shape) == (64, 3, 7, 7):
             # conv1 + bn1 + PReLU + max pool as ONE launch that reads the images where stage_input finds them (NCHW or NHWC4):
             # no layout pass, the 64-channel conv output never leaves the CU (tsod_stem_fp16x2)
             fs = plan.packed("conv1.fused", lambda: FusedStemWeights(self.conv1, self.bn1, self.relu, device))
@@ -352,11 +398,13 @@ class ResNet(PlanOwner, nn.Module):
             cur = plan.pool.alloc((N, ph, pw, 64))
             plan.call(lib().tsod_maxpool3x3s2_f32, ptr(s_out), N, oh, ow, 64, 64, ptr(cur), 64, keep=(s_out, cur))
             plan.alias_amax(cur, s_out)          # range words: max |pooled| <= max |stem output|
-            plan.pool.release(s_out)
+            if mode == _STEM:                    # the trained stem: the image and conv1's output stay out of the pool (x4 is never
+                plan.stem_record = resnet_grads.stem_record(plan, self, x4, s_out, stem)      # released), the node copies them
+            else:
+                plan.pool.release(s_out)
         # a training mode (with grad mode on): the section's blocks (the last ``mode`` of layer4, or a stage onward) run the same
         # launches, but what the autograd
         # node needs of them stays out of the pool (the node copies it after the run) and is recorded for it
-        mode = self._active_mode()
         trained = {name for name, _ in self._section(mode)} if mode else set()
         plan.block_records = []
         for li in range(1, 5):

@@ -9,7 +9,11 @@ packed weights after an optimizer step.
 slope the launches carry by value) and ``bn`` (the three BatchNorms' running mean and 1 / sqrt(var + eps)).  A projection block
 (``downsample``; its forward runs conv3 and the shortcut as one stacked GEMM on folded weights) carries ``pcs[2]`` as a plain
 pack of conv3 made for the backward, and ``pcd`` (the same of ``downsample.0``), ``stride``, ``s2d`` (conv2's 2x2 phase pack where the
-stride is 2; ``rot`` is None then) and ``bn_d``."""
+stride is 2; ``rot`` is None then) and ``bn_d``.
+
+The "stem" mode (section 4.23) also records the stem, ``plan.stem_record``: ``x4`` (the staged image [N,H,W,4]), ``y`` (conv1's
+output after BN and PReLU [N,OH,OW,64]), ``pc`` (conv1's ``PackedConv``), ``slope`` and ``bn``; the pooled map is the first block's
+``x``."""
 from __future__ import annotations
 
 import math
@@ -64,6 +68,25 @@ def block_record(plan, blk, name, x, ys, pcs):
     return dict(name=name, x=x, ys=list(ys), pcs=pcs, rot=rot, slope=slope, bn=bn, **rec)
 
 
+def stem_record(plan, owner, x4, y, pc):
+    """What the node needs of the stem of the plan being built (``ResNet.build_plan`` in the "stem" mode)."""
+    slope = pc.slope
+    if not (math.isfinite(slope) and slope > 0.0):
+        raise TsodError(f"relu: the stem's PReLU slope is {slope}; a trained stem needs a finite slope > 0 (its backward takes the "
+                        "mask from the saved output, and sign(prelu(z)) = sign(z) only then)")
+    return dict(x4=x4, y=y, pc=pc, slope=slope, bn=_bn_stats(owner.bn1, pc.cout, plan.device))
+
+
+def stem_copy(rec):
+    """The node's own view of the stem record: the activations copied, the pack and scale by reference (``block_copy``)."""
+    return dict(x4=rec["x4"].clone(), y=rec["y"].clone(), w=rec["pc"].w, scale=rec["pc"].scale, slope=rec["slope"], bn=rec["bn"])
+
+
+STEM_NAMES = ("conv1.weight", "bn1.weight", "bn1.bias", "relu.weight")
+STEM_MODULES = ("conv1", "bn1", "relu")                          # what ``refresh_packs`` watches of the stem
+STEM_PACK_KEYS = ("conv1", "conv1.fused")                        # ... and the ``_packed_cache`` names their change drops
+
+
 def block_copy(rec, x=None):
     """The node's own view of a block record: forwards and backwards may interleave in any order.  The activations are copied
     (the plan's buffers are written by the next forward); ``x``: the copy that already exists of the block's input (the previous
@@ -86,8 +109,10 @@ class _ResNetGrads(torch.autograd.Function):
     and dx = g3 + conv1's dgrad (skipped for the earliest block).  A projection block (DESIGN.md section 4.22): the shortcut's
     tsod_pw_wgrad_f32 / tsod_pw_dgrad_f32 from g3 on the rows tsod_pixel_subsample_f32 takes of x; conv2 through
     tsod_conv3x3_strided_wgrad_f32; at stride 2 its dx is the forward conv library on the 2x2 phase pack, read by
-    tsod_prelu_grad_d2s_f32; dx = conv1's dgrad, then the shortcut's added by tsod_pixel_upsample_add_f32.  It returns the
-    gradients in torch's parameter layouts."""
+    tsod_prelu_grad_d2s_f32; dx = conv1's dgrad, then the shortcut's added by tsod_pixel_upsample_add_f32.  The stem (section
+    4.23, where one of its four tensors needs a gradient): the earliest block's dx is the gradient of the pooled map, read by
+    tsod_prelu_grad_pool_f32 on the stem's y, then tsod_conv7x7s2_wgrad_f32 on the staged image.  It returns the gradients in
+    torch's parameter layouts."""
 
     @staticmethod
     def forward(ctx, saved, *params):
@@ -141,11 +166,13 @@ class _ResNetGrads(torch.autograd.Function):
             return dxs
 
         blocks = sv["blocks"]
+        stem = sv.get("stem")
+        want_stem = stem is not None and any(need[k] for k in STEM_NAMES)
         for bi in range(len(blocks) - 1, -1, -1):
             b = blocks[bi]
             prefix, a = b["name"], b["slope"]
             want_a = need[prefix + ".relu.weight"]
-            first = bi == 0                                       # the earliest trained block: nobody wants its dx
+            first = bi == 0 and not want_stem                     # the earliest trained block: nobody wants its dx
             proj = "wd" in b
             g3, s3 = hip_ops.prelu_grad(b["y3"], d3, a, want_dslope=want_a)
             d2 = pointwise(prefix, 3, b["y2"], b, g3, torch.empty_like(b["y2"]), False, True)
@@ -172,6 +199,21 @@ class _ResNetGrads(torch.autograd.Function):
                     hip_ops.pixel_upsample_add(d3, dxs, b["stride"])
             if want_a:
                 out[prefix + ".relu.weight"] = ((s3 + s2) + s1) / a
+        if want_stem:                                             # d3: layer1.0's dx, the gradient of the pooled map
+            a, want_a = stem["slope"], need["relu.weight"]
+            g, s = hip_ops.prelu_grad_pool(stem["y"], d3, a, want_dslope=want_a)
+            w, gm, bt = need["conv1.weight"], need["bn1.weight"], need["bn1.bias"]
+            if w or gm or bt:
+                d_w, d_sc, d_sh = hip_ops.conv7x7s2_wgrad(g, stem["x4"], stem["w"], stem["scale"], want_dw=w, want_dscale=gm,
+                                                          want_dshift=gm or bt)
+                if d_w is not None:
+                    out["conv1.weight"] = d_w
+                if d_sc is not None:
+                    out["bn1.weight"], out["bn1.bias"] = _bn_grads(d_sc, d_sh, stem["bn"], d_sh.numel())
+                elif d_sh is not None:
+                    out["bn1.bias"] = d_sh
+            if want_a:
+                out["relu.weight"] = s / a
         return (None,) + tuple(out.get(k) if n else None for k, n in need.items())
 
 
@@ -184,6 +226,8 @@ def feature_map_with_grads(plan, nchw, named):
         blocks.append(block_copy(rec, blocks[-1]["y3"] if shared else None))
         prev = rec
     saved = dict(out=hip_ops.nhwc_to_nchw(out) if nchw else out.clone(), nchw=nchw, names=[k for k, _ in named], blocks=blocks)
+    if getattr(plan, "stem_record", None) is not None:
+        saved["stem"] = stem_copy(plan.stem_record)
     return _ResNetGrads.apply(saved, *(p for _, p in named))
 
 
@@ -193,7 +237,8 @@ def versions_of(module) -> tuple:
 
 
 def refresh_packs(owner):
-    """Drop what was packed from every watched block (``owner._watched``: the blocks of the widest ``train_blocks`` ever set) whose
+    """Drop what was packed from every watched block (``owner._watched``: the blocks of the widest mode ever set, and in the
+    "stem" mode ``conv1`` / ``bn1`` / ``relu``, whose packs are "conv1" and "conv1.fused") whose
     parameters or BatchNorm buffers changed (``_version``) since they were last known to match: the block's entries of
     ``_packed_cache`` (its three packs with their bf16x3 / fp16x2 images, the rotated image), every plan of the owner (a launch
     descriptor carries the slope by value, so no plan survives a step), and ``weights_version`` moves so that a captured graph
@@ -204,14 +249,17 @@ def refresh_packs(owner):
     watched = owner.__dict__.get("_watched")
     if not watched:
         return
-    stale = []
+    prefixes, names = [], set()
     for name, seen in watched.items():
         v = versions_of(owner.get_submodule(name))
         if v != seen:
             watched[name] = v
-            stale.append(name + ".")
-    if stale:
-        for key in [k for k in owner._packed_cache if isinstance(k[0], str) and k[0].startswith(tuple(stale))]:
+            if name in STEM_MODULES:                              # conv1 / bn1 / relu share the stem's two packs, kept under
+                names.update(STEM_PACK_KEYS)                      # names of their own: no "<block>." prefix matches them
+            else:
+                prefixes.append(name + ".")
+    if prefixes or names:
+        for key in [k for k in owner._packed_cache if isinstance(k[0], str) and (k[0] in names or k[0].startswith(tuple(prefixes)))]:
             del owner._packed_cache[key]
         owner.__dict__["_plans"] = OrderedDict()
         owner._bump_version()

@@ -29,9 +29,9 @@ _UID = itertools.count(1)
 
 
 def _make_extractor(backbone):
-    if backbone == "resnet50":
-        from ..models.resnet import resnet50
-        return resnet50(include_top=False), 2048, 32
+    if backbone in ("resnet50", "resnet101"):
+        from ..models import resnet
+        return getattr(resnet, backbone)(include_top=False), 2048, 32
     if backbone in ("hardnet39", "hardnet68", "hardnet85"):
         return HarDNetFeatureExtraction(depth_wise=True, arch=int(backbone[-2:])), 512, 16
     raise ValueError(f"unknown backbone {backbone!r}")

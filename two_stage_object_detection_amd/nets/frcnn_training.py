@@ -223,7 +223,9 @@ class FasterRCNNTrainer(nn.Module):
     resnet50 / resnet101): the same with ``feat_extra.train_from(stage)`` - every Bottleneck from the first block of that stage to
     the end of ``layer4``, projection blocks included (33 / 96 / 139 tensors for resnet50).  BatchNorm
     stays folded: ``bn_batch_stats=True`` raises ValueError with them, and ints, "tail" and "full" keep raising for ResNet
-    backbones.  The identity Bottlenecks at the end of ``layer4`` alone (``layer4.1``, ``layer4.2``) train through the
+    backbones.  ``backbone_grads="stem"`` (where ``feat_extra.trainable_sections`` offers it: resnet50 / resnet101): the same with
+    ``feat_extra.train_from("stem")`` - the whole backbone, ``conv1`` / ``bn1`` / ``relu`` and ``layer1`` included (DESIGN.md section
+    4.23; 176 tensors for resnet50); that forward runs the stem and ``layer1`` as per-layer launches.  The identity Bottlenecks at the end of ``layer4`` alone (``layer4.1``, ``layer4.2``) train through the
     ``features=`` path, whose map may carry any autograd history - here the backbone's own node (``ResNet.train_blocks``,
     DESIGN.md section 4.21):
 
@@ -232,7 +234,7 @@ class FasterRCNNTrainer(nn.Module):
         for p in tr.feat_extra.trainable_parameters(): p.requires_grad_(True)
         losses = tr(x, bboxes, labels, features=tr.feat_extra(x))[0]; (losses[-1] / 32).backward()
 
-    Not provided: the rest of the ResNet backbones' backward - ``layer1`` and the stem, BasicBlock,
+    Not provided: the rest of the ResNet backbones' backward - BasicBlock,
     ResNeXt's grouped 3x3, batch-statistics BatchNorm (``head_grads`` fine-tunes the heads
     on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks, ``"full"`` the whole
     HarDNet; ``features=`` trains a
@@ -258,9 +260,10 @@ class FasterRCNNTrainer(nn.Module):
         if stage is not None and bn_batch_stats:
             raise ValueError(f"bn_batch_stats=True: backbone {backbone!r} trains with BatchNorm folded only (backbone_grads={stage!r})")
         self.feat_extra, feat_ch, native_stride = _make_extractor(backbone)
-        if stage is not None and stage not in getattr(self.feat_extra, "trainable_stages", ()):
+        if stage is not None and stage not in getattr(self.feat_extra, "trainable_sections", ()):
             raise ValueError(f"backbone_grads={stage!r}: backbone {backbone!r} offers the stages "
-                             f"{getattr(self.feat_extra, 'trainable_stages', ())} (feat_extra.trainable_stages)")
+                             f"{getattr(self.feat_extra, 'trainable_stages', ())} (feat_extra.trainable_stages; with \"stem\": "
+                             f"{getattr(self.feat_extra, 'trainable_sections', ())}, feat_extra.trainable_sections)")
         if n_blocks is not None and n_blocks > self.feat_extra.n_blocks:
             raise ValueError(f"backbone_grads={n_blocks}: backbone {backbone!r} has {self.feat_extra.n_blocks} HarDBlocks")
         self.feat_stride = native_stride if (feat_stride == 16 and native_stride != 16) else feat_stride
@@ -348,6 +351,9 @@ class FasterRCNNTrainer(nn.Module):
                 why = ("(head_grads=True) computes the head parameters' gradients on a frozen backbone, but" if not tail else
                        "(backbone_grads='tail') reaches the six tail tensors of the backbone only (feat_extra.tail_parameters()); "
                        "every other backbone parameter must be frozen, but" if self.backbone_grads == "tail" else
+                       "(backbone_grads='stem') reaches the backbone's section \"stem\" only: conv1, bn1, relu and the blocks of layer1 "
+                       "to layer4 (feat_extra.trainable_parameters()); every other backbone parameter must be frozen, but"
+                       if self.backbone_grads == "stem" else
                        f"(backbone_grads={self.backbone_grads!r}) reaches the backbone's blocks from {self.backbone_grads}.0 to the end "
                        "of layer4 only (feat_extra.trainable_parameters()); every other backbone parameter must be frozen, but"
                        if stage else
