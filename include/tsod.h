@@ -814,6 +814,35 @@ int tsod_bn_train_grad_f32(const float *g, int32_t g_ld, int32_t g_off, const fl
                            int32_t dz_ld, int32_t dz_off, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
                            tsod_stream_t stream);
 
+/* ---- what ResNet puts behind a train-mode BatchNorm -------------------------------------------------
+ * The conventions, the grid, the summation rules and the error codes of the section above; every tensor has its own pitch and
+ * offset.  PReLU with ONE slope by value; neither entry point checks it (the caller keeps it finite and > 0, so that the saved
+ * output has the pre-activation's sign).
+ * tsod_bn_apply_prelu_f32: y = prelu(scale * z + shift + R, slope).  scale, shift [2][C_pad]: tsod_bn_stats_f32's value +
+ *   remainder pairs.  R is nothing (r == z2 == NULL), the residual tensor r [M][r_ld] (channels [r_off, r_off + C_pad)), or the
+ *   second normalised operand scale2 * z2 + shift2 (z2 [M][z2_ld], channels [z2_off, z2_off + C_pad); scale2, shift2 [2][C_pad]
+ *   pairs, both required with z2); r and z2 together: TSOD_ERR_INVALID_ARG.  (scale * z + shift) + R is added in f64 and
+ *   rounded to f32 once, then o > 0 ? o : slope * o in f32.  amax_out: the range words of y's tensor (NULL: none).  M >= 1.
+ * tsod_bn_prelu_train_grad_f32: tsod_prelu_grad_f32 and tsod_bn_train_grad_f32 in three launches (partials, their sum, the
+ *   elementwise pass).  y the saved output of the PReLU, dy its gradient, z / mean / invstd / gamma as in
+ *   tsod_bn_train_grad_f32.  g = y > 0 ? dy : slope * dy in f32 (an exact y == 0 takes the slope branch); dgamma, dbeta, dz:
+ *   tsod_bn_train_grad_f32's on that g.  *dslope_num (NULL: none) = sum dy * y * [y < 0] in f64 (an exact 0 adds nothing): per
+ *   real channel by the rule of the other two sums, then over the channels ascending - 64 contiguous runs of ceil(C_pad / 64)
+ *   channels, each ascending, merged ascending - and rounded to f32 once.  g_out (NULL: none; channels [g_off, g_off + C_pad) of
+ *   rows of g_ld floats): g written out, pad channels exact zeros.  M >= 2.
+ *   workspace: tsod_bn_prelu_train_grad_workspace_bytes(M, C_pad) = three partials per workgroup and channel plus the totals;
+ *   0 for a shape that is refused. */
+int tsod_bn_apply_prelu_f32(const float *z, int64_t M, int32_t C_real, int32_t C_pad, int32_t z_ld, int32_t z_off,
+                            const float *scale, const float *shift, const float *r, int32_t r_ld, int32_t r_off, const float *z2,
+                            int32_t z2_ld, int32_t z2_off, const float *scale2, const float *shift2, float slope, float *y,
+                            int32_t y_ld, int32_t y_off, uint32_t *amax_out, tsod_stream_t stream);
+size_t tsod_bn_prelu_train_grad_workspace_bytes(int64_t M, int32_t C_pad);
+int tsod_bn_prelu_train_grad_f32(const float *y, int32_t y_ld, int32_t y_off, const float *dy, int32_t dy_ld, int32_t dy_off,
+                                 const float *z, int32_t z_ld, int32_t z_off, int64_t M, int32_t C_real, int32_t C_pad,
+                                 const float *mean, const float *invstd, const float *gamma, float slope, float *dz,
+                                 int32_t dz_ld, int32_t dz_off, float *dgamma, float *dbeta, float *dslope_num, float *g_out,
+                                 int32_t g_ld, int32_t g_off, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- detection mAP: COCOeval's evaluateImg + accumulate, area range "all", no crowd / ignore flags ------
  * The reference's calculate_metrics (nets/frcnn_training.py:372-565) defines no usable metric; this is the project's own.
  * IoU is tsod_bbox_iou_f32's expression (eps 1e-8, no +1), compared as IoU >= t in f32.  Three steps:

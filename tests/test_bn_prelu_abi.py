@@ -1,0 +1,129 @@
+"""The C ABI of train-mode BatchNorm with ResNet's epilogue (csrc/bn_prelu_train.hip) and the float64
+restatement of tests/bn_prelu_restated.py: everything here runs without a GPU."""
+import ctypes
+import os
+import re
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bn_prelu_restated as R  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _lib():
+    from two_stage_object_detection_amd import _ffi
+    if not os.path.exists(_ffi.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return _ffi, _ffi.lib()
+
+
+def _status(L, rc):
+    return L.tsod_status_str(rc).decode().upper()
+
+
+def test_exports_exist_in_header_binding_and_library():
+    _ffi, L = _lib()
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tsod.h")).read(), flags=re.S)
+    raw = ctypes.CDLL(_ffi.LIB_PATH)
+    for name, n_args in (("tsod_bn_apply_prelu_f32", 22), ("tsod_bn_prelu_train_grad_workspace_bytes", 2),
+                         ("tsod_bn_prelu_train_grad_f32", 28)):
+        decl = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", text, flags=re.S)
+        assert decl is not None, name
+        assert len(decl.group(1).split(",")) == n_args == len(_ffi._SIGNATURES[name][1]), name
+        assert hasattr(raw, name), name
+    assert _ffi._SIGNATURES["tsod_bn_apply_prelu_f32"][1][16] is ctypes.c_float                  # the slope, by value
+    assert _ffi._SIGNATURES["tsod_bn_prelu_train_grad_f32"][1][15] is ctypes.c_float
+    from two_stage_object_detection_amd import hip_ops
+    for fn in (hip_ops.batch_norm_stats, hip_ops.batch_norm_prelu_train, hip_ops.batch_norm_prelu_train_grad):
+        assert fn.__doc__ and "4.2" in fn.__doc__, fn.__name__
+
+
+def test_argument_errors():
+    """Every argument check returns its code on the host, before any launch (the pointers are never dereferenced); the codes are
+    tsod_bn_apply_f32's and tsod_bn_train_grad_f32's for the same mistakes."""
+    _, L = _lib()
+    A, odd = 0x10000, 0x10004
+    ws = L.tsod_bn_prelu_train_grad_workspace_bytes(70, 12)
+    assert ws > 0 and L.tsod_bn_prelu_train_grad_workspace_bytes(1, 12) == 0 and L.tsod_bn_prelu_train_grad_workspace_bytes(70, 10) == 0
+
+    def apply(z=A, M=70, C_real=10, C_pad=12, z_ld=32, z_off=8, scale=A, shift=A, r=None, r_ld=16, r_off=4, z2=None, z2_ld=20,
+              z2_off=8, scale2=A, shift2=A, y=A, y_ld=12, y_off=0, amax=None):
+        return L.tsod_bn_apply_prelu_f32(z, M, C_real, C_pad, z_ld, z_off, scale, shift, r, r_ld, r_off, z2, z2_ld, z2_off, scale2,
+                                         shift2, 0.25, y, y_ld, y_off, amax, None)
+
+    def grad(y=A, y_ld=12, y_off=0, dy=A, dy_ld=12, dy_off=0, z=A, z_ld=32, z_off=8, M=70, C_real=10, C_pad=12, mean=A, invstd=A,
+             gamma=A, dz=A, dz_ld=16, dz_off=4, dgamma=A, dbeta=A, num=A, g=None, g_ld=12, g_off=0, w=A, wb=ws):
+        return L.tsod_bn_prelu_train_grad_f32(y, y_ld, y_off, dy, dy_ld, dy_off, z, z_ld, z_off, M, C_real, C_pad, mean, invstd, gamma,
+                                              0.25, dz, dz_ld, dz_off, dgamma, dbeta, num, g, g_ld, g_off, w, wb, None)
+    # a null required pointer
+    for fn, names in ((apply, ("z", "scale", "shift", "y")), (grad, ("y", "dy", "z", "mean", "invstd", "gamma", "dz", "dgamma", "dbeta"))):
+        for k in names:
+            assert "INVALID" in _status(L, fn(**{k: None})), (fn.__name__, k)
+        # C_pad % 4, a misaligned pointer, more real channels than padded ones
+        assert "ALIGN" in _status(L, fn(C_pad=10)), fn.__name__
+        assert "ALIGN" in _status(L, fn(z=odd)), fn.__name__
+        assert "INVALID" in _status(L, fn(C_real=13)) and "INVALID" in _status(L, fn(C_real=0)), fn.__name__
+    # the three forms of R: a residual and a second operand together, a second operand without its pairs
+    assert "INVALID" in _status(L, apply(r=A, z2=A))
+    assert "INVALID" in _status(L, apply(z2=A, scale2=None)) and "INVALID" in _status(L, apply(z2=A, shift2=None))
+    # the optional operands' slices are checked only when they are there
+    assert "INVALID" in _status(L, apply(r=A, r_off=8)) and "INVALID" in _status(L, apply(z2=A, z2_off=12))
+    assert "ALIGN" in _status(L, apply(r=odd)) and "ALIGN" in _status(L, apply(r=A, r_ld=18)) and "ALIGN" in _status(L, apply(z2=A, z2_off=6))
+    assert "ALIGN" in _status(L, apply(z2=A, scale2=odd)) and "ALIGN" in _status(L, apply(z2=A, shift2=odd))
+    assert "INVALID" in _status(L, grad(g=A, g_off=4)) and "ALIGN" in _status(L, grad(g=odd)) and "ALIGN" in _status(L, grad(g=A, g_ld=14))
+    # rows: the grad needs two, the elementwise apply one
+    assert "INVALID" in _status(L, grad(M=1)) and "INVALID" in _status(L, apply(M=0))
+    # offsets beyond ld, pitches and offsets that are no multiples of 4
+    assert "INVALID" in _status(L, apply(z_off=24)) and "INVALID" in _status(L, apply(y_off=4)) and "INVALID" in _status(L, apply(z_off=-4))
+    assert "INVALID" in _status(L, grad(y_off=4)) and "INVALID" in _status(L, grad(dy_off=4)) and "INVALID" in _status(L, grad(z_off=24))
+    assert "INVALID" in _status(L, grad(dz_off=8))
+    assert "ALIGN" in _status(L, apply(y_ld=14)) and "ALIGN" in _status(L, apply(scale=odd)) and "ALIGN" in _status(L, apply(amax=A + 16))
+    assert "ALIGN" in _status(L, grad(dz_ld=18)) and "ALIGN" in _status(L, grad(mean=odd)) and "ALIGN" in _status(L, grad(dy=odd))
+    assert "ALIGN" in _status(L, grad(y=odd)) and "ALIGN" in _status(L, grad(dy_off=2, dy_ld=16))
+    # workspace
+    assert "WORKSPACE" in _status(L, grad(w=None)) and "WORKSPACE" in _status(L, grad(wb=ws - 8)) and "WORKSPACE" in _status(L, grad(w=odd))
+
+
+def test_workspace_is_three_partials_per_workgroup_plus_the_totals():
+    _ffi, L = _lib()
+    Rw = _ffi.BN_ROWS_PER_WORKGROUP
+    q = L.tsod_bn_prelu_train_grad_workspace_bytes
+    for M in (2, Rw, Rw + 1, 3 * Rw + 5, 90000):
+        for cp in (4, 68, 260, 2048):
+            assert q(M, cp) == (-(-M // Rw) + 1) * 3 * cp * 8
+
+
+def test_restatement_is_the_definition():
+    """The float64 reference is the entry points' formulas, the mask comes from the saved output, and the yardstick covers every
+    cell with a positive figure for every quantity."""
+    _ffi, _ = _lib()
+    M, C, cp, kind, form, slope = 5, 10, 12, "unit", "second", 0.25
+    c, ref, ys = R.case(M, C, cp, kind), R.reference(M, C, cp, kind, form, slope), R.saved_output(M, C, cp, kind, form, slope)
+    z, z2 = c["z"][:, R.sl("z", C)].double(), c["z2"][:, R.sl("z2", C)].double()
+
+    def norm(t, gamma, beta):
+        xhat = (t - t.mean(0)) / torch.sqrt(t.var(0, unbiased=False) + R.EPS)
+        return xhat, xhat * gamma.double() + beta.double()
+    xhat, bn = norm(z, c["gamma"], c["beta"])
+    pre = bn + norm(z2, c["gamma2"], c["beta2"])[1]
+    assert torch.allclose(ref["y"], torch.where(pre > 0, pre, slope * pre), rtol=1e-12, atol=1e-12)
+    assert torch.equal(ys, ref["y"].float())
+    dy = c["dy"][:, R.sl("dy", C)].double()
+    g = dy * torch.where(ys > 0, 1.0, slope).double()
+    assert torch.equal(ref["g"].double(), g)                              # (0.25: the product is exact)
+    assert torch.allclose(ref["dgamma"], (g * xhat).sum(0), rtol=1e-10) and torch.allclose(ref["dbeta"], g.sum(0), rtol=1e-12)
+    k = c["gamma"].double() / torch.sqrt(z.var(0, unbiased=False) + R.EPS)
+    want = k * (g - g.mean(0) - xhat * (g * xhat).mean(0))
+    assert float((ref["dz"] - want).abs().max()) <= 1e-9 * float(k.max())
+    # sum dy y [y < 0] is the slope's gradient times the slope, up to the rounding of the saved y
+    auto = R.backward(c, form, slope, ys, torch.float64)["dslope"]
+    assert abs(float(ref["dslope"] - auto)) <= 1e-6 * float((dy * ys.double()).abs().sum())
+    for kind in R.KINDS:
+        for label in R.row_counts(_ffi.BN_ROWS_PER_WORKGROUP):
+            for form in R.FORMS:
+                cell = R.yardstick(_ffi.BN_ROWS_PER_WORKGROUP, kind, label, form)
+                assert set(cell) == set(R.QUANTITIES) and all(v > 0 for v in cell.values()), (kind, label, form, cell)

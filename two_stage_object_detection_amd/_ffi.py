@@ -313,6 +313,14 @@ _SIGNATURES = {
     "tsod_bn_train_grad_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
                                        c_void_p]),
+    "tsod_bn_apply_prelu_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                        c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32,
+                                        c_void_p, c_void_p]),
+    "tsod_bn_prelu_train_grad_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "tsod_bn_prelu_train_grad_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                             c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32,
+                                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t,
+                                             c_void_p]),
     "tsod_eval_match_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "tsod_eval_match_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,

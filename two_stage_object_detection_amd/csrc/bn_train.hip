@@ -16,57 +16,9 @@
 //                    come from L2 the second time), the workgroups' (n, mean, M2) are merged by Chan's rule
 //   across them      partial b of channel c lies at part[b][.][c]; 16 lanes per channel take contiguous runs of ceil(B / 16)
 //                    partials ascending, lane 0 then merges the 16 runs ascending
-#include "tsod_internal.h"
+#include "bn_rows.h"
 
 namespace {
-
-constexpr int kBnThreads = 256;
-constexpr int kBnRows = TSOD_BN_ROWS_PER_WORKGROUP;
-constexpr int kBnFinishChannels = 16, kBnFinishRuns = kBnThreads / kBnFinishChannels;
-
-// channel quads across a workgroup: the power of two that covers C4, at most 64 (then blockIdx.y walks chunks of 64 quads)
-__host__ __device__ inline int bn_quads_across(int C4) {
-    int q = 1;
-    while (q < C4 && q < 64) q <<= 1;
-    return q;
-}
-inline long bn_row_blocks(long M) { return (M + kBnRows - 1) / kBnRows; }
-
-// v summed over the threads that share a channel quad (tid, tid + qx, tid + 2 qx, ...): a binary tree in LDS, every thread gets
-// the total.  `lds`: NV * 256 doubles; the leading barrier frees them from an earlier call.
-template <int NV>
-__device__ __forceinline__ void bn_block_sum(double (&v)[NV], double *lds, int tid, int qx) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < NV; ++e) lds[e * kBnThreads + tid] = v[e];
-    __syncthreads();
-    for (int s = kBnThreads / 2; s >= qx; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int e = 0; e < NV; ++e) lds[e * kBnThreads + tid] += lds[e * kBnThreads + tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int e = 0; e < NV; ++e) v[e] = lds[e * kBnThreads + (tid & (qx - 1))];
-}
-
-struct bn_lane {
-    int q, ry, rows_step;                                               // channel quad, first row of the thread, row step
-    long m0, m1;                                                        // the workgroup's rows
-    bool live;
-};
-__device__ __forceinline__ bn_lane bn_lane_of(long M, int C4, int qx) {
-    bn_lane t;
-    const int tid = threadIdx.x;
-    t.q = blockIdx.y * qx + (tid & (qx - 1));
-    t.ry = tid / qx;
-    t.rows_step = kBnThreads / qx;
-    t.m0 = (long)blockIdx.x * kBnRows;
-    t.m1 = t.m0 + kBnRows < M ? t.m0 + kBnRows : M;
-    t.live = t.q < C4;
-    return t;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- stats
 // part [B][2][C_pad] doubles: the workgroup's mean and the centred sum of squares about it, per channel
@@ -296,10 +248,6 @@ bn_grad_dz_kernel(const float *__restrict__ g, int g_ld, int g_off, const float 
         *reinterpret_cast<float4 *>(dc + m * dz_ld) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
-
-inline bool bn_slice_ok(int32_t C_pad, int32_t ld, int32_t off) { return off >= 0 && ld > 0 && (long)off + C_pad <= ld; }
-inline bool bn_slice_aligned(const void *p, int32_t ld, int32_t off) { return tsod_aligned16(p) && (ld & 3) == 0 && (off & 3) == 0; }
-inline dim3 bn_grid(long M, int C4) { return dim3((unsigned)bn_row_blocks(M), (unsigned)tsod_cdiv(C4, bn_quads_across(C4))); }
 
 }  // namespace
 

@@ -825,16 +825,10 @@ def batch_norm_train(z, gamma, beta, eps, momentum, running_mean=None, running_v
     Mo, ld_out = _bn_rows(out, "batch_norm_train")
     if Mo != M:
         raise ValueError(f"batch_norm_train: z has {M} rows, out {Mo}")
-    mean, invstd = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
-    scale, shift = (torch.empty((2, cp), dtype=torch.float32, device=dev) for _ in range(2))      # (value, f32 remainder)
-    L = lib()
-    ws_bytes = L.tsod_bn_train_workspace_bytes(M, cp)
-    ws = ARENA.get(dev, ws_bytes)
-    check(L.tsod_bn_stats_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(gamma), ptr(beta), float(eps), float(momentum),
-                              ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), ptr(mean), ptr(invstd), ptr(scale),
-                              ptr(shift), ptr(ws), ws_bytes, stream_ptr()), "bn_stats")
-    check(L.tsod_bn_apply_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(scale), ptr(shift), int(act), ptr(out), ld_out, int(out_off),
-                              _word_ptr(amax_out), stream_ptr()), "bn_apply")
+    mean, invstd, scale, shift = batch_norm_stats(z, gamma, beta, eps, momentum, running_mean, running_var, off=off, C_real=C_real,
+                                                  num_batches_tracked=num_batches_tracked)
+    check(lib().tsod_bn_apply_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(scale), ptr(shift), int(act), ptr(out), ld_out,
+                                  int(out_off), _word_ptr(amax_out), stream_ptr()), "bn_apply")
     return out, mean, invstd
 
 
@@ -868,6 +862,125 @@ def batch_norm_train_grad(g, z, mean, invstd, gamma, *, g_off=0, z_off=0, dz=Non
                                    ptr(gamma), ptr(dz), ld_d, int(dz_off), ptr(dgamma), ptr(dbeta), ptr(ws), ws_bytes, stream_ptr()),
           "bn_train_grad")
     return dz, dgamma, dbeta
+
+
+def batch_norm_stats(z, gamma, beta, eps, momentum, running_mean=None, running_var=None, *, off=0, C_real=None,
+                     num_batches_tracked=None):
+    """The statistics half of a train-mode BatchNorm (tsod_bn_stats_f32) -> (mean, invstd, scale, shift).
+
+    z, gamma, beta, the running statistics and ``num_batches_tracked`` as in ``batch_norm_train``.  mean, invstd [C_pad]; scale =
+    gamma * invstd and shift = beta - mean * scale as [2, C_pad]: the float32 value and the float32 remainder of the float64 one
+    (what ``batch_norm_prelu_train`` takes for its second operand).  ValueError for fewer than 2 rows.  Two launches."""
+    require_cuda(z, "batch_norm_stats")
+    M, ld = _bn_rows(z, "batch_norm_stats")
+    if M < 2:
+        raise ValueError(f"batch_norm_stats: more than one value per channel is needed in training mode, got {M} row(s)")
+    C_real = int(gamma.numel() if C_real is None else C_real)
+    cp = (C_real + 3) // 4 * 4
+    dev = z.device
+    mean, invstd = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
+    scale, shift = (torch.empty((2, cp), dtype=torch.float32, device=dev) for _ in range(2))      # (value, f32 remainder)
+    L = lib()
+    ws_bytes = L.tsod_bn_train_workspace_bytes(M, cp)
+    ws = ARENA.get(dev, ws_bytes)
+    check(L.tsod_bn_stats_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(gamma), ptr(beta), float(eps), float(momentum),
+                              ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), ptr(mean), ptr(invstd), ptr(scale),
+                              ptr(shift), ptr(ws), ws_bytes, stream_ptr()), "bn_stats")
+    return mean, invstd, scale, shift
+
+
+def batch_norm_prelu_train(z, gamma, beta, eps, momentum, slope, running_mean=None, running_var=None, *, off=0, residual=None,
+                           residual_off=0, second=None, out=None, out_off=0, C_real=None, num_batches_tracked=None, amax_out=None):
+    """Train-mode BatchNorm with ResNet's epilogue (tsod_bn_stats_f32, tsod_bn_apply_prelu_f32)
+    -> (y, mean, invstd).
+
+    y = prelu(gamma * invstd * (z - mean) + beta + R, slope) on the batch statistics of z, everything else as in
+    ``batch_norm_train``: z [..., ld] contiguous with the channels at [off, off + C_pad), gamma, beta [C_real], the running
+    statistics and ``num_batches_tracked`` updated in place, ``out`` [..., ld_out] receiving y at [out_off, out_off + C_pad)
+    (default: a new [..., C_pad] tensor), pad channels exact zeros, ``amax_out`` the range words of ``out``'s tensor, ValueError
+    for fewer than 2 rows.  R is at most one of
+      ``residual``  a tensor [..., ld_r] with as many rows (channels [residual_off, residual_off + C_pad)): an identity block's x;
+      ``second``    (z2, scale2, shift2, z2_off): another BatchNorm's input [..., ld_2] (channels [z2_off, z2_off + C_pad)) with
+                    the scale / shift ``batch_norm_stats`` gave for it: a projection block's downsample.1.
+    The BatchNorm's terms and R are added in float64 and rounded to float32 once; the PReLU (one ``slope``, by value, not
+    checked here: the module keeps it finite and > 0) runs on that.  Launches: two for the statistics, one for y."""
+    require_cuda(z, "batch_norm_prelu_train")
+    M, ld = _bn_rows(z, "batch_norm_prelu_train")
+    if residual is not None and second is not None:
+        raise ValueError("batch_norm_prelu_train: a residual tensor or a second normalised operand, not both")
+    C_real = int(gamma.numel() if C_real is None else C_real)
+    cp = (C_real + 3) // 4 * 4
+    dev = z.device
+    if out is None:
+        out = torch.empty(z.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
+    rows = [("out", out)]
+    if residual is not None:
+        rows.append(("residual", residual))
+    z2 = scale2 = shift2 = None
+    z2_off = 0
+    if second is not None:
+        z2, scale2, shift2, z2_off = second
+        rows.append(("second", z2))
+        if tuple(scale2.shape) != (2, cp) or tuple(shift2.shape) != (2, cp):
+            raise ValueError(f"batch_norm_prelu_train: the second operand's scale / shift must be [2, {cp}]")
+    lds = {}
+    for what, t in rows:
+        Mt, lds[what] = _bn_rows(t, "batch_norm_prelu_train")
+        if Mt != M or t.device != dev or t.dtype != torch.float32:
+            raise ValueError(f"batch_norm_prelu_train: z has {M} float32 rows on {dev}, {what} is {tuple(t.shape)} {t.dtype} on {t.device}")
+    mean, invstd, scale, shift = batch_norm_stats(z, gamma, beta, eps, momentum, running_mean, running_var, off=off, C_real=C_real,
+                                                  num_batches_tracked=num_batches_tracked)
+    check(lib().tsod_bn_apply_prelu_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(scale), ptr(shift), ptr(residual),
+                                        lds.get("residual", 0), int(residual_off), ptr(z2), lds.get("second", 0), int(z2_off),
+                                        ptr(scale2), ptr(shift2), float(slope), ptr(out), lds["out"], int(out_off),
+                                        _word_ptr(amax_out), stream_ptr()), "bn_apply_prelu")
+    return out, mean, invstd
+
+
+def batch_norm_prelu_train_grad(y, dy, z, mean, invstd, gamma, slope, *, y_off=0, dy_off=0, z_off=0, dz=None, dz_off=0, C_real=None,
+                                want_dslope=True, want_g=False, g=None, g_off=0):
+    """The backward of ``batch_norm_prelu_train`` from its saved output (tsod_bn_prelu_train_grad_f32)
+    -> (dz, dgamma [C_pad], dbeta [C_pad], dslope_num [1] or None, g or None).
+
+    ``prelu_grad`` followed by ``batch_norm_train_grad`` as one group of three launches.  y [..., ld_y] (channels [y_off, y_off +
+    C_pad)): the saved OUTPUT of the PReLU; dy [..., ld_dy] (channels [dy_off, ...)): its gradient; z [..., ld_z] (channels
+    [z_off, ...)): the BatchNorm's saved input; mean, invstd [C_pad]: what the forward returned; gamma [C_real] (``C_real``
+    default: its length); ``slope`` the forward's, finite and > 0.  g = dy * (y > 0 ? 1 : slope), an exact y == 0 taking the
+    slope branch; with xhat = (z - mean) * invstd: dgamma = sum g xhat, dbeta = sum g, dz = gamma * invstd * (g - dbeta / M -
+    xhat * dgamma / M), written to channels [dz_off, dz_off + C_pad) of ``dz`` (default: a new [..., C_pad] tensor).
+    dslope_num = sum dy * y * [y < 0] over the real channels (the slope's gradient times the slope), None without
+    ``want_dslope``.  ``want_g`` (or a ``g`` [..., ld_g] to write at channels [g_off, ...)): g itself - what the residual branch
+    of a block's last stage reads.  Whatever R the forward added needs no term here: d(z_bn + R) = g for both.  Pad channels
+    of every output are exact zeros.  All tensors contiguous float32 with as many rows, at least 2."""
+    require_cuda(y, "batch_norm_prelu_train_grad")
+    M, ld_y = _bn_rows(y, "batch_norm_prelu_train_grad")
+    cp = mean.numel()
+    C_real = int(gamma.numel() if C_real is None else C_real)
+    if M < 2 or invstd.numel() != cp:
+        raise ValueError(f"batch_norm_prelu_train_grad: y has {M} rows (at least 2), mean {cp} / invstd {invstd.numel()} channels")
+    dev = y.device
+    if dz is None:
+        dz = torch.empty(y.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
+    if g is None and want_g:
+        g = torch.empty(y.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
+    lds = {}
+    for what, t in (("dy", dy), ("z", z), ("dz", dz), ("g", g)):
+        if t is None:
+            continue
+        Mt, lds[what] = _bn_rows(t, "batch_norm_prelu_train_grad")
+        if Mt != M or t.device != dev or t.dtype != torch.float32:
+            raise ValueError(f"batch_norm_prelu_train_grad: y has {M} float32 rows on {dev}, {what} is {tuple(t.shape)} {t.dtype} on "
+                             f"{t.device}")
+    dgamma, dbeta = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
+    num = torch.empty(1, dtype=torch.float32, device=dev) if want_dslope else None
+    L = lib()
+    ws_bytes = L.tsod_bn_prelu_train_grad_workspace_bytes(M, cp)
+    ws = ARENA.get(dev, ws_bytes)
+    check(L.tsod_bn_prelu_train_grad_f32(ptr(y), ld_y, int(y_off), ptr(dy), lds["dy"], int(dy_off), ptr(z), lds["z"], int(z_off), M,
+                                         C_real, cp, ptr(mean), ptr(invstd), ptr(gamma), float(slope), ptr(dz), lds["dz"],
+                                         int(dz_off), ptr(dgamma), ptr(dbeta), ptr(num), ptr(g), lds.get("g", 0), int(g_off), ptr(ws),
+                                         ws_bytes, stream_ptr()), "bn_prelu_train_grad")
+    return dz, dgamma, dbeta, num, g
 
 
 class _DWConv3x3(torch.autograd.Function):

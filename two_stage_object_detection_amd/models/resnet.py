@@ -21,6 +21,39 @@ from .._ffi import ACT_NONE, ACT_PRELU, TsodError, lib, ptr, require_cuda, stem_
 from ..engine import (FusedBottleneckWeights, FusedShortcutConv, FusedStemWeights, PackedConv, Plan, PlanOwner, prelu_slope,
                       stage_input)
 from . import resnet_grads
+from .hardnet import _IdentityEpilogue
+
+_BN_OWN = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
+
+
+def _bn_stats_step(plan: Plan, bn, name: str, z: torch.Tensor):
+    """tsod_bn_stats_f32 of the raw conv output z [N,h,w,C] on the module's own gamma / beta / running buffers (DESIGN.md section
+    4.24) -> (what the node keeps of this BatchNorm, scale, shift); scale and shift are the [2, C] value + remainder pairs."""
+    if any(getattr(bn, k).device != z.device for k in _BN_OWN):
+        raise TsodError("batch_stats: the module's BatchNorm parameters and buffers must live on the forward's device")
+    C = z.shape[3]
+    M = z.numel() // C
+    if M < 2:
+        raise ValueError(f"batch_stats: more than one value per channel is needed in training mode ({name} sees {M} pixel)")
+    if C != bn.num_features or C % 4:
+        raise TsodError(f"batch_stats: {name} has {bn.num_features} channels, its conv output {C}; a multiple of 4 is needed")
+    mean, invstd, scale, shift = vec = [torch.empty(n * C, dtype=torch.float32, device=z.device) for n in (1, 1, 2, 2)]
+    plan.bn_steps.append(plan.call(lib().tsod_bn_stats_f32, ptr(z), M, C, C, C, 0, ptr(bn.weight), ptr(bn.bias), float(bn.eps),
+                                   float(bn.momentum), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
+                                   ptr(mean), ptr(invstd), ptr(scale), ptr(shift), None, 0,
+                                   keep=[z] + vec + [getattr(bn, k) for k in _BN_OWN]))
+    plan.bn_bound.extend((bn, k, ptr(getattr(bn, k))) for k in _BN_OWN)   # (_forward_train: rebound storage = a new plan)
+    return dict(z=z, mean=mean, invstd=invstd, gamma=bn.weight, C=C), scale, shift
+
+
+def _bn_apply_prelu_step(plan: Plan, z, scale, shift, slope, dst, residual=None, second=None):
+    """tsod_bn_apply_prelu_f32: dst = prelu(scale * z + shift + R, slope) with R nothing, ``residual`` or ``second`` = (z2, scale2,
+    shift2), and dst's range words."""
+    C = z.shape[3]
+    z2, scale2, shift2 = second if second is not None else (None, None, None)
+    plan.call(lib().tsod_bn_apply_prelu_f32, ptr(z), z.numel() // C, C, C, C, 0, ptr(scale), ptr(shift), ptr(residual),
+              0 if residual is None else residual.shape[3], 0, ptr(z2), 0 if z2 is None else z2.shape[3], 0, ptr(scale2),
+              ptr(shift2), float(slope), ptr(dst), dst.shape[3], 0, plan.amax_ptr(dst) or None, keep=(z, dst, residual, z2))
 
 
 def _conv(cin, cout, k, stride=1, pad=0, groups=1):
@@ -98,6 +131,45 @@ class _ResidualBlock(nn.Module):
             plan.block_records.append(resnet_grads.block_record(plan, self, name, x, ys, pcs))
         return cur
 
+    def _emit_batch_stats(self, plan: Plan, x: torch.Tensor, name: str) -> torch.Tensor:
+        """A trained Bottleneck of the batch-statistics plan: per BatchNorm the conv with an identity
+        epilogue into a raw z outside the pool (one pack per conv, shared with the folded plans), tsod_bn_stats_f32 on the
+        module's own tensors, tsod_bn_apply_prelu_f32; conv3's apply adds x or the shortcut's BatchNorm as its second operand,
+        so a projection block runs conv3 and downsample.0 as two convs.  Everything goes to ``plan.block_records``."""
+        dev = plan.device
+        slope = prelu_slope(self.relu)
+        N = x.shape[0]
+
+        def raw_conv(key, conv, bn, act, src):
+            pc = plan.packed(key, lambda: PackedConv(conv.weight, dev, bn=bn, stride=conv.stride[0], pad=conv.padding[0], act=act,
+                                                     slope=slope if act == ACT_PRELU else 0.0))
+            oh, ow = pc.out_hw(src.shape[1], src.shape[2])
+            z = torch.empty((N, oh, ow, pc.cout), dtype=torch.float32, device=dev)
+            plan.conv(_IdentityEpilogue(pc, dev), src, z, name=key)
+            return pc, z
+
+        cur, ys, pcs, bnts = x, [], [], []
+        pcd = bnt_d = None
+        for i, (cname, bname) in enumerate(self._stage_names):
+            conv, bn = getattr(self, cname), getattr(self, bname)
+            pc, z = raw_conv(f"{name}.{cname}", conv, bn, ACT_PRELU, cur)
+            bnt, scale, shift = _bn_stats_step(plan, bn, f"{name}.{bname}", z)
+            out = plan.pool.alloc(tuple(z.shape))
+            if i < 2:
+                _bn_apply_prelu_step(plan, z, scale, shift, slope, out)
+            elif self.downsample is None:
+                _bn_apply_prelu_step(plan, z, scale, shift, slope, out, residual=x)
+            else:
+                pcd, zd = raw_conv(f"{name}.downsample", self.downsample[0], self.downsample[1], ACT_NONE, x)
+                bnt_d, scale_d, shift_d = _bn_stats_step(plan, self.downsample[1], f"{name}.downsample.1", zd)
+                _bn_apply_prelu_step(plan, z, scale, shift, slope, out, second=(zd, scale_d, shift_d))
+            ys.append(out)
+            pcs.append(pc)
+            bnts.append(bnt)
+            cur = out
+        plan.block_records.append(resnet_grads.block_record_batch_stats(plan, self, name, x, ys, pcs, bnts, pcd, bnt_d))
+        return cur
+
     def _emit_grouped(self, plan: Plan, conv, bn, cur, x, slope, name):
         from ..engine import fold_bn
         C, groups, stride = conv.out_channels, conv.groups, conv.stride[0]
@@ -157,6 +229,7 @@ _STEM = "stem"                                 # ... and the widest: conv1 / bn1
 class ResNet(PlanOwner, nn.Module):
     _train_mode = None           # set_train_mode(): a plain instance attribute once set - pickled and deep-copied, never in
                                  # the state_dict
+    _batch_stats = False         # set_train_mode(batch_stats=): likewise
 
     def __init__(self, block, blocks_num, num_classes=25, include_top=True, groups=1, width_per_group=64):
         super().__init__()
@@ -237,7 +310,7 @@ class ResNet(PlanOwner, nn.Module):
         """None | n (int >= 1) | a name of ``trainable_sections``: what ``set_train_mode`` was given last."""
         return self._train_mode
 
-    def set_train_mode(self, mode):
+    def set_train_mode(self, mode, batch_stats=False):
         """How much of the backbone is differentiable: None (nothing, the default) or ``n`` in 1..``n_blocks`` (the last ``n``
         blocks of ``layer4``, ten tensors each: ``conv{1,2,3}.weight``, ``bn{1,2,3}.weight`` / ``.bias``, ``relu.weight``;
         ValueError outside that range).  Returns self.
@@ -282,7 +355,28 @@ class ResNet(PlanOwner, nn.Module):
         The stem's slope must be finite and > 0 too.  ``saved`` gains ``stem``: ``x4`` (the staged image [N,H,W,4]), ``y``
         (conv1's output after BN and PReLU), ``w`` / ``scale`` (conv1's f32 pack [64,7,8,4] and folded scale), ``slope``, ``bn``;
         the pooled map is ``blocks[0]["x"]``.  With the four stem tensors frozen (``requires_grad_(False)``) no stem launch runs
-        in the backward and ``layer1.0`` is the earliest block: "from layer1 on"."""
+        in the backward and ``layer1.0`` is the earliest block: "from layer1 on".
+
+        ``batch_stats=True`` (every mode) adds the reference's contract, ``.train()``: under ``.eval()``
+        nothing changes (same plan-cache key, same bits); under ``.train()`` with grad mode on the forward takes a plan of its
+        own variant (the key gains "batch_stats") in which every BatchNorm from the mode's first module on normalises with the
+        statistics of the current batch (over N, H, W), backpropagates through them and updates its ``running_mean``,
+        ``running_var`` (momentum, unbiased variance) and ``num_batches_tracked`` in the module's own storage - current when
+        ``forward`` returns; the blocks below stay folded on their running statistics (frozen BN) and their buffers do not change
+        by a bit.  Per such BatchNorm the conv runs with an identity epilogue into a raw buffer z, then tsod_bn_stats_f32 and
+        tsod_bn_apply_prelu_f32 (conv3's adds the block input, or ``downsample.1`` on its own z as a second operand: a projection
+        block then runs conv3 and ``downsample.0`` as two convs); the stem is conv1, statistics, apply, tsod_maxpool3x3s2_f32.
+        The backward runs tsod_bn_prelu_train_grad_f32 on (y, d, z) per stage - behind a stride-2 3x3 and behind the stem the
+        gathering mask kernels followed by tsod_bn_train_grad_f32, which also serves ``downsample.1`` - and feeds dz to the
+        conv backward with unit scale; ``bn*.weight`` / ``.bias`` gradients are dgamma / dbeta.  ``saved`` then carries
+        ``batch_stats`` = True and, per block, ``bnt`` (per stage: ``z``, ``mean``, ``invstd``, ``gamma``, ``C`` - the node's own
+        copies) in place of ``bn``, ``scale`` as ones, ``rot`` / ``s2d`` made from the unscaled weight, and for a projection block
+        ``bnt_d`` in place of ``bn_d``; ``stem`` carries ``bnt`` likewise.  The slopes must still be finite and > 0.  Under
+        ``.train()`` with grad mode off, without ``batch_stats`` or with nothing of the section requiring grad, the forward raises
+        ``call .eval() first`` as before.  A BatchNorm of the section with ``momentum=None``, ``track_running_stats=False`` or
+        ``affine=False``: NotImplementedError here; BatchNorm tensors off the forward's device: TsodError, and fewer than two
+        pixels per channel in any BatchNorm of the section: ValueError, both in the forward.  Memory on top of the mode's: the raw
+        z of every BatchNorm of the section, twice (plan and node)."""
         if isinstance(mode, str):
             if mode == "layer1":
                 raise ValueError("train_from: layer1 cannot be trained: each of its blocks runs as one launch and keeps no stage "
@@ -297,6 +391,13 @@ class ResNet(PlanOwner, nn.Module):
             if mode < 1 or mode > self.n_blocks:
                 raise ValueError(f"train_blocks: n must be 1..n_blocks = {self.n_blocks} (the identity Bottlenecks at the end of "
                                  f"layer4 of this backbone), got {mode}")
+        batch_stats = bool(batch_stats) and mode is not None
+        if batch_stats:
+            for name, bn in self._section_norms(mode):
+                if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+                    raise NotImplementedError(f"batch_stats: {name} has momentum=None, track_running_stats=False or affine=False; "
+                                              "only the reference's BatchNorm2d (momentum, running statistics, affine) is built")
+        self._batch_stats = batch_stats
         if mode is not None:
             watched = self.__dict__.setdefault("_watched", {})
             for name, blk in self._stem_modules(mode) + self._section(mode):     # the widest mode ever set: what the refresh watches
@@ -311,21 +412,21 @@ class ResNet(PlanOwner, nn.Module):
         resnet_grads.refresh_packs(self)
         return self
 
-    def train_blocks(self, n: int):
+    def train_blocks(self, n: int, batch_stats=False):
         """``set_train_mode(n)``.  Memory: per trained block N x h x w x 10 width floats (x, y1, y2, y3), twice (plan and node),
         and one rotated 3x3 image per trained block and device."""
-        return self.set_train_mode(int(n))
+        return self.set_train_mode(int(n), batch_stats)
 
-    def train_from(self, stage: str):
+    def train_from(self, stage: str, batch_stats=False):
         """``set_train_mode(stage)``: every block from the first of ``stage`` (one of ``trainable_stages``) to the end of
         ``layer4``.  Memory: what ``train_blocks`` keeps, per trained block, and per trained stride-2 3x3 and device the 2x2 phase
         pack, 16 / 9 of the weight, in place of the rotated image."""
-        return self.set_train_mode(str(stage))
+        return self.set_train_mode(str(stage), batch_stats)
 
-    def train_full(self):
+    def train_full(self, batch_stats=False):
         """``set_train_mode("stem")``: every parameter of the backbone (named after HarDNet's).  Memory: what ``train_from``
         keeps for every block, and the stem's output N x OH x OW x 64 floats and the staged image N x H x W x 4, each twice."""
-        return self.set_train_mode(_STEM)
+        return self.set_train_mode(_STEM, batch_stats)
 
     def _stem_modules(self, mode):
         return [(k, getattr(self, k)) for k in resnet_grads.STEM_MODULES] if mode == _STEM else []
@@ -338,6 +439,15 @@ class ResNet(PlanOwner, nn.Module):
                     for i, blk in enumerate(getattr(self, stage))]
         blocks = list(self.layer4)
         return [(f"layer4.{i}", blocks[i]) for i in range(len(blocks) - n, len(blocks))]
+
+    def _section_norms(self, mode):
+        """(name, BatchNorm2d) of every BatchNorm of the mode's section, in module order."""
+        norms = [("bn1", self.bn1)] if mode == _STEM else []
+        for name, blk in self._section(mode):
+            norms += [(f"{name}.{b}", getattr(blk, b)) for _, b in blk._stage_names]
+            if blk.downsample is not None:
+                norms.append((f"{name}.downsample.1", blk.downsample[1]))
+        return norms
 
     def _trainable_named(self):
         mode = self._train_mode or 0
@@ -352,18 +462,36 @@ class ResNet(PlanOwner, nn.Module):
             return None
         return self._train_mode if any(p.requires_grad for p in self.trainable_parameters()) else None
 
+    def _trains_in_plan(self) -> bool:
+        """The batch-statistics variant is on: ``batch_stats`` set, ``.train()``, grad mode on, a parameter requiring grad."""
+        return self._batch_stats and self.training and self._active_mode() is not None
+
     def _plan_variant(self):
         mode = self._active_mode()
-        return () if mode is None else ("train_from" if isinstance(mode, str) else "train_blocks", mode)
+        if mode is None:
+            return ()
+        key = ("train_from" if isinstance(mode, str) else "train_blocks", mode)
+        return key + ("batch_stats",) if self._trains_in_plan() else key
 
     def _forward_train(self, x, slot, nchw):
-        if self.training:
+        batch_stats = self._trains_in_plan()
+        if self.training and not batch_stats:
             raise TsodError("the HIP path implements the inference forward only: call .eval() first")
         resnet_grads.refresh_packs(self)
         plan = self._plan_for(x, slot)
+        if batch_stats and any(getattr(bn, k).data_ptr() != p for bn, k, p in plan.bn_bound):
+            # a parameter or buffer was rebound (load_state_dict(assign=True), ``bn.running_mean = ...``, ``p.data = ...``): the
+            # plan's launches hold the old storage (kept alive, never freed under them) - build the plan again
+            for key in [k for k, v in self._plans.items() if v is plan]:
+                del self._plans[key]
+            plan = self._plan_for(x, slot)
         stage_input(plan, x)
         plan.run()
         self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
+        if batch_stats:                                          # the launches wrote the section's buffers: torch must know
+            for _, bn in self._section_norms(self._train_mode):
+                for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+                    torch.autograd.graph.increment_version(b)
         return resnet_grads.feature_map_with_grads(plan, nchw, self._trainable_named())
 
     def forward_nhwc(self, x, slot: int = 0):
@@ -385,6 +513,9 @@ class ResNet(PlanOwner, nn.Module):
         oh, ow, ph, pw = stem_out_hw(H, W)
         mode = self._active_mode()
         plan.stem_record = None
+        # the batch-statistics variant (section 4.24): the statistics launches share one workspace
+        batch_stats = self._trains_in_plan()
+        plan.bn_steps, plan.bn_bound = [], []
         if mode != _STEM and self.fuse_stem and tuple(self.conv1.weight.shape) == (64, 3, 7, 7):
             # conv1 + bn1 + PReLU + max pool as ONE launch that reads the images where stage_input finds them (NCHW or NHWC4):
             # no layout pass, the 64-channel conv output never leaves the CU (tsod_stem_fp16x2)
@@ -394,12 +525,20 @@ class ResNet(PlanOwner, nn.Module):
             stem = plan.packed("conv1", lambda: PackedConv(self.conv1.weight, device, bn=self.bn1, stride=2, pad=3, act=ACT_PRELU,
                                                            slope=prelu_slope(self.relu), cin_pad=4, kw_pad=8))
             assert (oh, ow) == tuple(stem.out_hw(H, W))
-            s_out = plan.conv(stem, x4, plan.pool.alloc((N, oh, ow, 64)), name="conv1")
+            bnt0 = None
+            if batch_stats and mode == _STEM:    # conv1 -> z, statistics, apply; the pool below is the folded plan's
+                z0 = torch.empty((N, oh, ow, 64), dtype=torch.float32, device=device)
+                plan.conv(_IdentityEpilogue(stem, device), x4, z0, name="conv1")
+                bnt0, scale0, shift0 = _bn_stats_step(plan, self.bn1, "bn1", z0)
+                s_out = plan.pool.alloc((N, oh, ow, 64))
+                _bn_apply_prelu_step(plan, z0, scale0, shift0, stem.slope, s_out)
+            else:
+                s_out = plan.conv(stem, x4, plan.pool.alloc((N, oh, ow, 64)), name="conv1")
             cur = plan.pool.alloc((N, ph, pw, 64))
             plan.call(lib().tsod_maxpool3x3s2_f32, ptr(s_out), N, oh, ow, 64, 64, ptr(cur), 64, keep=(s_out, cur))
             plan.alias_amax(cur, s_out)          # range words: max |pooled| <= max |stem output|
             if mode == _STEM:                    # the trained stem: the image and conv1's output stay out of the pool (x4 is never
-                plan.stem_record = resnet_grads.stem_record(plan, self, x4, s_out, stem)      # released), the node copies them
+                plan.stem_record = resnet_grads.stem_record(plan, self, x4, s_out, stem, bnt0)    # released), the node copies them
             else:
                 plan.pool.release(s_out)
         # a training mode (with grad mode on): the section's blocks (the last ``mode`` of layer4, or a stage onward) run the same
@@ -410,12 +549,18 @@ class ResNet(PlanOwner, nn.Module):
         for li in range(1, 5):
             for bi, blk in enumerate(getattr(self, f"layer{li}")):
                 record = f"layer{li}.{bi}" in trained
-                nxt = blk._emit(plan, cur, f"layer{li}.{bi}", record)
+                name = f"layer{li}.{bi}"
+                nxt = blk._emit_batch_stats(plan, cur, name) if record and batch_stats else blk._emit(plan, cur, name, record)
                 if not record:
                     plan.pool.release(cur)
                 cur = nxt
         plan.output_nhwc = cur
         plan.output_amax = plan.amax_ptr(cur)
+        if plan.bn_steps:
+            need = max(lib().tsod_bn_train_workspace_bytes(st[1][1], st[1][3]) for st in plan.bn_steps)
+            plan.bn_workspace = torch.empty(need, dtype=torch.uint8, device=device)
+            for st in plan.bn_steps:
+                st[1][17:19] = [ptr(plan.bn_workspace), need]
         return plan.finalize()
 
     def forward(self, x):

@@ -13,7 +13,12 @@ stride is 2; ``rot`` is None then) and ``bn_d``.
 
 The "stem" mode (section 4.23) also records the stem, ``plan.stem_record``: ``x4`` (the staged image [N,H,W,4]), ``y`` (conv1's
 output after BN and PReLU [N,OH,OW,64]), ``pc`` (conv1's ``PackedConv``), ``slope`` and ``bn``; the pooled map is the first block's
-``x``."""
+``x``.
+
+The batch-statistics plan (section 4.24; ``block_record_batch_stats``) records per block ``bnt`` in place of ``bn`` - per stage
+what the BatchNorm's backward reads: the raw conv output ``z``, ``mean``, ``invstd``, ``gamma`` (the module's parameter) and ``C`` -
+``one`` (the unit scales the conv backward takes), ``rot`` / ``s2d`` made from the unscaled weights, and for a projection block
+``pcd``, ``stride`` and ``bnt_d``; the stem record carries ``bnt`` too."""
 from __future__ import annotations
 
 import math
@@ -25,7 +30,7 @@ from torch.autograd.function import once_differentiable
 from .. import _ffi, hip_ops
 from .._ffi import TsodError
 from ..engine import PackedConv
-from .hardnet_grads import _bn_grads, _bn_stats
+from .hardnet_grads import _bn_grads, _bn_stats, bnt_copy
 
 
 def eligible(blk) -> bool:
@@ -68,17 +73,62 @@ def block_record(plan, blk, name, x, ys, pcs):
     return dict(name=name, x=x, ys=list(ys), pcs=pcs, rot=rot, slope=slope, bn=bn, **rec)
 
 
-def stem_record(plan, owner, x4, y, pc):
-    """What the node needs of the stem of the plan being built (``ResNet.build_plan`` in the "stem" mode)."""
+def _check_slope(name, slope):
+    if not (math.isfinite(slope) and slope > 0.0):
+        raise TsodError(f"{name}: the PReLU slope is {slope}; a trained block needs a finite slope > 0 (its backward takes the "
+                        "mask from the saved outputs, and sign(prelu(z)) = sign(z) only then)")
+
+
+def block_record_batch_stats(plan, blk, name, x, ys, pcs, bnts, pcd, bnt_d):
+    """``block_record`` for a block of the batch-statistics plan (``_ResidualBlock._emit_batch_stats``): the BatchNorms are not
+    folded, so the conv backward runs with unit scale and conv2's dx images are made from the unscaled weight, under cache
+    names of their own (dropped with the block's packs by ``refresh_packs``)."""
+    slope = pcs[0].slope
+    _check_slope(name, slope)
+    pc2 = pcs[1]
+    one = [plan.packed(f"{name}.one.{pc.cout}", lambda pc=pc: torch.ones(pc.cout, dtype=torch.float32, device=plan.device))
+           for pc in pcs]
+    rot = s2d = None
+    if pc2.stride == 2:
+        s2d = plan.packed(f"{name}.conv2.s2d.raw", lambda: hip_ops.s2d_conv3x3_weight(pc2.w, one[1]))
+    else:
+        rot = plan.packed(f"{name}.conv2.rot.raw", lambda: hip_ops.rotate_conv3x3_weight(pc2.w, one[1]))
+    rec = dict(name=name, x=x, ys=list(ys), pcs=list(pcs), rot=rot, s2d=s2d, slope=slope, stride=pc2.stride, bnt=list(bnts),
+               one=one)
+    if pcd is not None:
+        rec.update(pcd=pcd, bnt_d=bnt_d)
+    return rec
+
+
+def block_copy_batch_stats(rec, x=None):
+    """``block_copy`` for a record of the batch-statistics plan: every BatchNorm's z, mean, invstd and gamma are copied too (the
+    next forward overwrites the first three, an optimizer step the last)."""
+    y1, y2, y3 = (t.clone() for t in rec["ys"])
+    out = dict(name=rec["name"], x=rec["x"].clone() if x is None else x, y1=y1, y2=y2, y3=y3, w=[pc.w for pc in rec["pcs"]],
+               scale=rec["one"], rot=rec["rot"], s2d=rec["s2d"], slope=rec["slope"], stride=rec["stride"],
+               bnt=[bnt_copy(b) for b in rec["bnt"]])
+    if "pcd" in rec:
+        out.update(wd=rec["pcd"].w, bnt_d=bnt_copy(rec["bnt_d"]))
+    return out
+
+
+def stem_record(plan, owner, x4, y, pc, bnt=None):
+    """What the node needs of the stem of the plan being built (``ResNet.build_plan`` in the "stem" mode); ``bnt``: the stem's
+    BatchNorm ran on batch statistics (section 4.24) - what its backward reads, in place of ``bn``."""
     slope = pc.slope
     if not (math.isfinite(slope) and slope > 0.0):
         raise TsodError(f"relu: the stem's PReLU slope is {slope}; a trained stem needs a finite slope > 0 (its backward takes the "
                         "mask from the saved output, and sign(prelu(z)) = sign(z) only then)")
+    if bnt is not None:
+        return dict(x4=x4, y=y, pc=pc, slope=slope, bnt=bnt)
     return dict(x4=x4, y=y, pc=pc, slope=slope, bn=_bn_stats(owner.bn1, pc.cout, plan.device))
 
 
 def stem_copy(rec):
     """The node's own view of the stem record: the activations copied, the pack and scale by reference (``block_copy``)."""
+    if "bnt" in rec:
+        return dict(x4=rec["x4"].clone(), y=rec["y"].clone(), w=rec["pc"].w, scale=torch.ones_like(rec["pc"].scale),
+                    slope=rec["slope"], bnt=bnt_copy(rec["bnt"]))
     return dict(x4=rec["x4"].clone(), y=rec["y"].clone(), w=rec["pc"].w, scale=rec["pc"].scale, slope=rec["slope"], bn=rec["bn"])
 
 
@@ -126,6 +176,9 @@ class _ResNetGrads(torch.autograd.Function):
         need = dict(zip(sv["names"], ctx.needs_input_grad[1:]))
         out = {}
         d3 = hip_ops.nchw_to_nhwc(gy) if sv["nchw"] else gy.contiguous()
+        if sv.get("batch_stats"):
+            _backward_batch_stats(sv, need, out, d3)
+            return (None,) + tuple(out.get(k) if n else None for k, n in need.items())
 
         def params_of(prefix, i, d_w, d_sc, d_sh, stats, to_torch):
             if d_w is not None:
@@ -217,15 +270,95 @@ class _ResNetGrads(torch.autograd.Function):
         return (None,) + tuple(out.get(k) if n else None for k, n in need.items())
 
 
+def _backward_batch_stats(sv, need, out, d3):
+    """The backward of the batch-statistics plan into ``out``: today's order per block, with every
+    mask + BatchNorm pair as one tsod_bn_prelu_train_grad_f32 where the stage's output gradient exists as a tensor (behind a
+    stride-2 3x3 and behind the stem the gathering mask kernel, then tsod_bn_train_grad_f32, which also serves downsample.1 on
+    g3), and the conv backward from dz with unit scale."""
+    def bn_params(prefix, dgamma, dbeta, C):
+        out[prefix + ".weight"], out[prefix + ".bias"] = dgamma[:C], dbeta[:C]
+
+    def stage(prefix, i, b, y, d, want_a, want_g=False):
+        """mask and BatchNorm of stage i from (y, d, z) -> (dz, the slope's sum, g or None)"""
+        t = b["bnt"][i - 1]
+        dz, dgamma, dbeta, s, g = hip_ops.batch_norm_prelu_train_grad(y, d, t["z"], t["mean"], t["invstd"], t["gamma"], b["slope"],
+                                                                      C_real=t["C"], want_dslope=want_a, want_g=want_g)
+        bn_params(f"{prefix}.bn{i}", dgamma, dbeta, t["C"])
+        return dz, s, g
+
+    def plain_bn(prefix, t, g):
+        dz, dgamma, dbeta = hip_ops.batch_norm_train_grad(g, t["z"], t["mean"], t["invstd"], t["gamma"], C_real=t["C"])
+        bn_params(prefix, dgamma, dbeta, t["C"])
+        return dz
+
+    def pointwise(name, x, w, one, dz, dx, accumulate, want_dx):
+        dx, d_w, _, _ = hip_ops.conv1x1_bn_relu6_grad(x, [(0, w.shape[3])], w, one, None, dz, dx=dx, accumulate=accumulate,
+                                                      want_dx=want_dx, want_dw=need[name], want_dscale=False, want_dshift=False)
+        if d_w is not None:
+            out[name] = d_w.view(d_w.shape[0], d_w.shape[1], 1, 1)
+        return dx
+
+    blocks = sv["blocks"]
+    stem = sv.get("stem")
+    want_stem = stem is not None and any(need[k] for k in STEM_NAMES)
+    for bi in range(len(blocks) - 1, -1, -1):
+        b = blocks[bi]
+        prefix, a = b["name"], b["slope"]
+        want_a = need[prefix + ".relu.weight"]
+        first = bi == 0 and not want_stem                         # the earliest trained block: nobody wants its dx
+        proj = "wd" in b
+        dz3, s3, g3 = stage(prefix, 3, b, b["y3"], d3, want_a, want_g=True)
+        dxs = None
+        if proj:                                                  # downsample.1 has no activation: the plain grad on g3
+            dzd = plain_bn(f"{prefix}.downsample.1", b["bnt_d"], g3)
+            xs = b["x"] if b["stride"] == 1 else hip_ops.pixel_subsample(b["x"], b["stride"])
+            dxs = pointwise(f"{prefix}.downsample.0.weight", xs, b["wd"], b["scale"][2], dzd,
+                            None if first else torch.empty_like(xs), False, not first)
+        d2 = pointwise(f"{prefix}.conv3.weight", b["y2"], b["w"][2], b["scale"][2], dz3, torch.empty_like(b["y2"]), False, True)
+        dz2, s2, _ = stage(prefix, 2, b, b["y2"], d2, want_a)
+        if need[f"{prefix}.conv2.weight"]:
+            d_w, _, _ = hip_ops.conv3x3_strided_wgrad(dz2, b["y1"], b["w"][1], b["scale"][1], stride=b["stride"], want_dw=True,
+                                                      want_dscale=False, want_dshift=False)
+            out[f"{prefix}.conv2.weight"] = d_w.permute(0, 3, 1, 2).contiguous()
+        if b["rot"] is None:                                      # stride 2: the phase-stacked image, read through the mask pass
+            p = hip_ops.conv2d_nhwc(dz2, b["s2d"], pad=1, precision=_ffi.PREC_F32)
+            g1, s1 = hip_ops.prelu_grad_d2s(b["y1"], p, a, want_dslope=want_a)
+            dz1 = plain_bn(f"{prefix}.bn1", b["bnt"][0], g1)
+        else:
+            d1 = hip_ops.conv2d_nhwc(dz2, b["rot"], pad=1, precision=_ffi.PREC_F32)
+            dz1, s1, _ = stage(prefix, 1, b, b["y1"], d1, want_a)
+        if not proj:
+            d3 = pointwise(f"{prefix}.conv1.weight", b["x"], b["w"][0], b["scale"][0], dz1, None if first else g3, True, not first)
+        else:
+            d3 = pointwise(f"{prefix}.conv1.weight", b["x"], b["w"][0], b["scale"][0], dz1,
+                           None if first else torch.empty_like(b["x"]), False, not first)
+            if not first:
+                hip_ops.pixel_upsample_add(d3, dxs, b["stride"])
+        if want_a:
+            out[prefix + ".relu.weight"] = ((s3 + s2) + s1) / a
+    if want_stem:                                                 # d3: layer1.0's dx, the gradient of the pooled map
+        a, want_a = stem["slope"], need["relu.weight"]
+        g, s = hip_ops.prelu_grad_pool(stem["y"], d3, a, want_dslope=want_a)
+        dz = plain_bn("bn1", stem["bnt"], g)
+        if need["conv1.weight"]:
+            out["conv1.weight"] = hip_ops.conv7x7s2_wgrad(dz, stem["x4"], stem["w"], stem["scale"], want_dw=True, want_dscale=False,
+                                                          want_dshift=False)[0]
+        if want_a:
+            out["relu.weight"] = s / a
+
+
 def feature_map_with_grads(plan, nchw, named):
     """The output of the training-mode ``plan`` that just ran, carrying the node over ``named`` (``_trainable_named()``)."""
     out = plan.output_nhwc
     blocks, prev = [], None
     for rec in plan.block_records:
         shared = prev is not None and prev["ys"][2] is rec["x"]
-        blocks.append(block_copy(rec, blocks[-1]["y3"] if shared else None))
+        copy = block_copy_batch_stats if "bnt" in rec else block_copy
+        blocks.append(copy(rec, blocks[-1]["y3"] if shared else None))
         prev = rec
     saved = dict(out=hip_ops.nhwc_to_nchw(out) if nchw else out.clone(), nchw=nchw, names=[k for k, _ in named], blocks=blocks)
+    if plan.bn_steps:
+        saved["batch_stats"] = True
     if getattr(plan, "stem_record", None) is not None:
         saved["stem"] = stem_copy(plan.stem_record)
     return _ResNetGrads.apply(saved, *(p for _, p in named))

@@ -234,8 +234,17 @@ class FasterRCNNTrainer(nn.Module):
         for p in tr.feat_extra.trainable_parameters(): p.requires_grad_(True)
         losses = tr(x, bboxes, labels, features=tr.feat_extra(x))[0]; (losses[-1] / 32).backward()
 
+    Train-mode BatchNorm for a ResNet section reaches the trainer through the same path - the keyword
+    ``bn_batch_stats`` keeps its refusal for ResNet backbones; the trainer stays in ``.eval()``, the backbone alone goes to
+    ``.train()``:
+
+        tr = FasterRCNNTrainer("train", nc, backbone="resnet50", head_grads=True).eval()
+        tr.feat_extra.requires_grad_(False); tr.feat_extra.train_from("layer4", batch_stats=True).train()
+        for p in tr.feat_extra.trainable_parameters(): p.requires_grad_(True)
+        losses = tr(x, bboxes, labels, features=tr.feat_extra(x))[0]; (losses[-1] / 32).backward()
+
     Not provided: the rest of the ResNet backbones' backward - BasicBlock,
-    ResNeXt's grouped 3x3, batch-statistics BatchNorm (``head_grads`` fine-tunes the heads
+    ResNeXt's grouped 3x3 (``head_grads`` fine-tunes the heads
     on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks, ``"full"`` the whole
     HarDNet; ``features=`` trains a
     backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
