@@ -890,6 +890,51 @@ int tsod_eval_accumulate_f64(const tsod_eval_record *records, int64_t capacity, 
                              int32_t num_classes, int32_t T, double *ap, int64_t *tp, int64_t *fp, int64_t *fn, double *recall,
                              void *workspace, size_t workspace_bytes, tsod_stream_t stream);
 
+/* ---- COCO detection evaluation: the section-4.14 metric with COCOeval's area ranges, crowd regions,
+ * ignore rules and detection caps, in one pass.  tsod_eval_match_f32 / tsod_eval_accumulate_f64 above are unchanged.
+ *
+ * tsod_eval_match_coco_f32: one update.  det, counts / keep / n_kept, gt_boxes, gt_labels, gt_counts, iou_thr [T],
+ *   num_classes, ignore_class, the drop rules, the per-(image, class) order and the limits are tsod_eval_match_f32's.
+ *   gt_crowd [B][G] uint8 (NULL: none is crowd), gt_area [B][G] f32 (NULL: the box's own area), area_lo / area_hi [A]
+ *   (device, f32, 1 <= A <= 4), max_dets = the largest cap.  A box's area is (x2-x1)*(y2-y1) as an f32 product.  For every
+ *   range a on its own, COCOeval's evaluateImg: a ground truth is ignored when it is crowd or area < lo[a] || area > hi[a]
+ *   (f32, both bounds inclusive); the class's ground truth is walked not-ignored first, then ignored, each ascending; the
+ *   first max_dets detections of the (image, class) are walked in order, every threshold t on its own: a ground truth
+ *   already matched at t is skipped unless it is crowd; the walk stops where it reaches the ignored part holding a
+ *   not-ignored best; a candidate needs IoU >= max(t, best so far), equal IoUs go to the later position.  IoU against a crowd
+ *   ground truth is inter / (area_det + 1e-8), otherwise tsod_bbox_iou_f32's expression.  A detection matched to an ignored
+ *   ground truth is ignored (neither TP nor FP), and so is an unmatched detection whose own area lies outside the range.
+ *   Appends one tsod_eval_record_coco per surviving detection exactly as tsod_eval_match_f32 appends its records, and adds
+ *   the not-ignored ground truth to npig [num_classes][A] (device int64, integer atomics).
+ *   workspace: tsod_eval_match_coco_workspace_bytes(B, R) (0 for a refused B or R).  Dynamic LDS at the limits G = 1024,
+ *   R = 8192: 143360 bytes.
+ * tsod_eval_accumulate_coco_f64: every record so far, sorted as tsod_eval_accumulate_f64 sorts.  max_dets_list [M] (HOST,
+ *   ascending from >= 1, 1 <= M <= 4, last entry <= max_dets, the value the match ran with; TSOD_ERR_INVALID_ARG otherwise).
+ *   Matching is greedy in score order, so the result under cap m is the records with rank < max_dets_list[m].  Per (class c,
+ *   range a, cap m, threshold t): ignored records add to neither count, integer cumulative TP / FP, precision tp / (tp + fp)
+ *   in f64 made monotone from the right, sampled by the rule 100 tp >= k npig[c][a], k = 0..100.  Outputs
+ *   [num_classes][A][M][T]: ap and recall = tp / npig (f64, -1 when npig[c][a] == 0), tp / fp / fn (int64).  Fixed-order sums:
+ *   run to run bit-identical.  workspace: tsod_eval_accumulate_coco_workspace_bytes(capacity, num_classes). */
+typedef struct tsod_eval_record_coco {
+    float score;
+    int32_t cls;
+    int32_t rank;        /* 0-based place in the (image, class) order */
+    uint32_t tp_mask[4]; /* [a] bit t: matched to a not-ignored ground truth of range a at iou_thr[t] */
+    uint32_t ig_mask[4]; /* [a] bit t: ignored in range a at iou_thr[t] */
+} tsod_eval_record_coco;
+size_t tsod_eval_match_coco_workspace_bytes(int32_t B, int32_t R);
+int tsod_eval_match_coco_f32(const float *det, int32_t B, int32_t R, const int32_t *counts, const int32_t *keep,
+                             const int32_t *n_kept, const float *gt_boxes, const int64_t *gt_labels, const int32_t *gt_counts,
+                             const uint8_t *gt_crowd, const float *gt_area, int32_t G, const float *iou_thr, int32_t T,
+                             const float *area_lo, const float *area_hi, int32_t A, int32_t num_classes, int32_t max_dets,
+                             int32_t ignore_class, tsod_eval_record_coco *records, int64_t capacity, int64_t *n_records,
+                             int64_t *npig, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+size_t tsod_eval_accumulate_coco_workspace_bytes(int64_t capacity, int32_t num_classes);
+int tsod_eval_accumulate_coco_f64(const tsod_eval_record_coco *records, int64_t capacity, const int64_t *n_records,
+                                  const int64_t *npig, int32_t num_classes, int32_t A, int32_t T, const int32_t *max_dets_list,
+                                  int32_t M, int32_t max_dets, double *ap, int64_t *tp, int64_t *fp, int64_t *fn, double *recall,
+                                  void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- input step (the step before the path) ----------------------------------------------
  * dataset/dataloader.py:35-44 + dataset/transform.py:14-17: a decoded RGB image becomes an f32 CHW tensor with
  * values 0..255 and is resized to the detector's fixed size by torchvision v2 Resize, i.e. ATen's antialiased

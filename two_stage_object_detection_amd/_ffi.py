@@ -331,6 +331,14 @@ _SIGNATURES = {
     "tsod_eval_accumulate_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "tsod_eval_accumulate_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_eval_match_coco_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "tsod_eval_match_coco_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                                         c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_eval_accumulate_coco_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "tsod_eval_accumulate_coco_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                              c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

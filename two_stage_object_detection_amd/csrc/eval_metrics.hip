@@ -15,6 +15,11 @@
 //                          workgroup per (class, threshold) scans TP over its segment in order, bins each position's f64 precision
 //                          by floor(100 tp / npig) (LDS integer max), and the suffix max over the 101 bins is the envelope sampled
 //                          at the 101 recall points.
+//   eval_match_coco_kernel, eval_ap_coco_kernel
+//                          the same two steps with COCOeval's area ranges, crowd regions, ignore rules and detection caps
+//                          (DESIGN.md section 4.25): the match walks each class chain once per area range, not-ignored ground
+//                          truth first; the AP scan runs per (class, range, cap, threshold) over the records the range does not
+//                          ignore and the cap admits.  Ordering, offsets, compaction, sort and segments are shared.
 // Every count is an integer; every f64 value comes from one division or a fixed-order sum: two runs give identical bits.
 #include "tsod_internal.h"
 
@@ -29,6 +34,12 @@ constexpr int kRadixItems = 16;       // keys per thread per radix tile
 constexpr int kRadixTile = kThreads * kRadixItems;
 constexpr int kApItems = 16;          // positions per thread per chunk of the AP scan
 constexpr float kIouEps = 1e-8f;
+constexpr int kMaxA = 4;              // area ranges: the words of a COCO record's masks
+constexpr int kMaxM = 4;              // detection caps of one COCO accumulate
+constexpr unsigned kCrowdFlag = 1u << kMaxA;   // gflag: bit a = ignored in area range a, bit kMaxA = crowd
+static_assert(sizeof(tsod_eval_record_coco) == 44, "hip_ops.EVAL_COCO_RECORD_INTS rows of int32");
+
+struct DetCaps { int v[kMaxM]; };
 
 __device__ __forceinline__ unsigned desc_score_bits(float s) {
     unsigned u = __float_as_uint(s);
@@ -74,30 +85,11 @@ __device__ __forceinline__ long det_row(const int *__restrict__ keep, int b, int
 }
 
 // ------------------------------------------------------------------------------------------------------ matching
-__global__ void __launch_bounds__(kThreads)
-eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ counts, const int *__restrict__ keep,
-                  const int *__restrict__ n_kept, const float *__restrict__ gt_boxes, const long long *__restrict__ gt_labels,
-                  const int *__restrict__ gt_counts, int G, const float *__restrict__ thr_in, int T, int C, int max_dets,
-                  int ignore_class, int NP, tsod_eval_record *__restrict__ stage, int *__restrict__ stage_counts,
-                  unsigned long long *__restrict__ npig) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);          // [NP]
-    float4 *gbox = reinterpret_cast<float4 *>(keys + NP);                              // [G]
-    int *gcls = reinterpret_cast<int *>(gbox + G);                                     // [G]
-    unsigned *matched = reinterpret_cast<unsigned *>(gcls + G);                          // [G]: bit t = matched at threshold t
-    int *gmatch_list = reinterpret_cast<int *>(matched + G);                           // [4][G]: a wave's class GT list
-    float *gmatch_iou = reinterpret_cast<float *>(gmatch_list + 4 * G);                // [4][G]: and their IoUs
-    unsigned short *comp = reinterpret_cast<unsigned short *>(gmatch_iou + 4 * G);     // [NP]
-    __shared__ float thr[kMaxT];
-    __shared__ int scr[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// keys[p] of image b's candidate p < n: class << 45 | order-inverted score bits << 13 | p; all ones for dropped rows and padding
+__device__ __forceinline__ void fill_detection_keys(const float *__restrict__ det, int R, const int *__restrict__ keep, int b, int n,
+                                                    int C, int ignore_class, int NP, unsigned long long *keys) {
     const long drow0 = (long)b * R;
-
-    int n = keep != nullptr ? n_kept[b] : counts[b];
-    n = min(max(n, 0), R);
-    const int gn = G > 0 ? min(max(gt_counts[b], 0), G) : 0;
-    if (tid < T) thr[tid] = thr_in[tid];
-    for (int p = tid; p < NP; p += kThreads) {
+    for (int p = threadIdx.x; p < NP; p += kThreads) {
         unsigned long long key = ~0ull;
         if (p < n) {
             const long r = det_row(keep, b, R, p);
@@ -113,21 +105,13 @@ eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ 
         }
         keys[p] = key;
     }
-    for (int g = tid; g < G; g += kThreads) {
-        int cls = -1;
-        if (g < gn) {
-            gbox[g] = reinterpret_cast<const float4 *>(gt_boxes)[(long)b * G + g];
-            const long long l = gt_labels[(long)b * G + g];
-            if (l >= 0 && l < C && l != ignore_class) {
-                cls = (int)l;
-                atomicAdd(npig + cls, 1ull);
-            }
-        }
-        gcls[g] = cls;
-        matched[g] = 0u;
-    }
-    __syncthreads();
+}
 
+// Orders the filled keys (call after a barrier) and caps every class segment at max_dets: comp[p] = the survivor's place in the
+// image's record list.  Returns the number of survivors; ends on a barrier.
+__device__ __forceinline__ int sort_and_cap_detections(unsigned long long *keys, unsigned short *comp, int NP, int max_dets,
+                                                       int *scr) {
+    const int tid = threadIdx.x;
     // ascending bitonic sort of the NP keys: (class, descending score, row); padding (all ones) last
     for (int k = 2; k <= NP; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -164,8 +148,51 @@ eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ 
         while (a < z) { const int m = (a + z) >> 1; if (keys[m] < lo) a = m + 1; else z = m; }
         if (p - a < max_dets) comp[p] = (unsigned short)at++;
     }
-    if (tid == 0) stage_counts[b] = total;
     __syncthreads();
+    return total;
+}
+
+__global__ void __launch_bounds__(kThreads)
+eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ counts, const int *__restrict__ keep,
+                  const int *__restrict__ n_kept, const float *__restrict__ gt_boxes, const long long *__restrict__ gt_labels,
+                  const int *__restrict__ gt_counts, int G, const float *__restrict__ thr_in, int T, int C, int max_dets,
+                  int ignore_class, int NP, tsod_eval_record *__restrict__ stage, int *__restrict__ stage_counts,
+                  unsigned long long *__restrict__ npig) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);          // [NP]
+    float4 *gbox = reinterpret_cast<float4 *>(keys + NP);                              // [G]
+    int *gcls = reinterpret_cast<int *>(gbox + G);                                     // [G]
+    unsigned *matched = reinterpret_cast<unsigned *>(gcls + G);                          // [G]: bit t = matched at threshold t
+    int *gmatch_list = reinterpret_cast<int *>(matched + G);                           // [4][G]: a wave's class GT list
+    float *gmatch_iou = reinterpret_cast<float *>(gmatch_list + 4 * G);                // [4][G]: and their IoUs
+    unsigned short *comp = reinterpret_cast<unsigned short *>(gmatch_iou + 4 * G);     // [NP]
+    __shared__ float thr[kMaxT];
+    __shared__ int scr[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long drow0 = (long)b * R;
+
+    int n = keep != nullptr ? n_kept[b] : counts[b];
+    n = min(max(n, 0), R);
+    const int gn = G > 0 ? min(max(gt_counts[b], 0), G) : 0;
+    if (tid < T) thr[tid] = thr_in[tid];
+    fill_detection_keys(det, R, keep, b, n, C, ignore_class, NP, keys);
+    for (int g = tid; g < G; g += kThreads) {
+        int cls = -1;
+        if (g < gn) {
+            gbox[g] = reinterpret_cast<const float4 *>(gt_boxes)[(long)b * G + g];
+            const long long l = gt_labels[(long)b * G + g];
+            if (l >= 0 && l < C && l != ignore_class) {
+                cls = (int)l;
+                atomicAdd(npig + cls, 1ull);
+            }
+        }
+        gcls[g] = cls;
+        matched[g] = 0u;
+    }
+    __syncthreads();
+
+    const int total = sort_and_cap_detections(keys, comp, NP, max_dets, scr);
+    if (tid == 0) stage_counts[b] = total;
 
     // greedy matching: class segments dealt round-robin to the four waves; a wave walks its chain in order.  Per detection the
     // lanes first compute its IoU with the class's ground truth (the class's GT list, ascending, built once per segment), then
@@ -239,6 +266,171 @@ eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ 
     }
 }
 
+// IoU of detection A against a crowd region: the intersection of tsod_bbox_iou over the detection's own area
+__device__ __forceinline__ float crowd_iou(const float4 A, const float4 Bx, float area_a, float eps) {
+    const float tlx = fmaxf(A.x, Bx.x), tly = fmaxf(A.y, Bx.y);
+    const float brx = fminf(A.z, Bx.z), bry = fminf(A.w, Bx.w);
+    const float w = fmaxf(brx - tlx, 0.f), h = fmaxf(bry - tly, 0.f);
+    return (w * h) / (area_a + eps);
+}
+
+// eval_match_kernel with COCOeval's ignore rules: the same ordering and cap, then per class chain the
+// area ranges one after the other over the same matched[] words.  For range a the class's GT list is the not-ignored ones
+// (ascending), then the ignored ones (ascending); lane t < T walks the first part for its arg-max as eval_match_kernel does and,
+// only when that found nothing, the second part, where a crowd region may be taken again.
+__global__ void __launch_bounds__(kThreads)
+eval_match_coco_kernel(const float *__restrict__ det, int R, const int *__restrict__ counts, const int *__restrict__ keep,
+                       const int *__restrict__ n_kept, const float *__restrict__ gt_boxes, const long long *__restrict__ gt_labels,
+                       const int *__restrict__ gt_counts, const unsigned char *__restrict__ gt_crowd,
+                       const float *__restrict__ gt_area, int G, const float *__restrict__ thr_in, int T,
+                       const float *__restrict__ area_lo, const float *__restrict__ area_hi, int A, int C, int max_dets,
+                       int ignore_class, int NP, tsod_eval_record_coco *__restrict__ stage, int *__restrict__ stage_counts,
+                       unsigned long long *__restrict__ npig) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);          // [NP]
+    float4 *gbox = reinterpret_cast<float4 *>(keys + NP);                              // [G]
+    int *gcls = reinterpret_cast<int *>(gbox + G);                                     // [G]
+    unsigned *gflag = reinterpret_cast<unsigned *>(gcls + G);                          // [G]: ignore bits per range, crowd
+    unsigned *matched = gflag + G;                                                     // [G]: bit t, for the range being walked
+    int *gmatch_list = reinterpret_cast<int *>(matched + G);                           // [4][G]: a wave's class GT list
+    float *gmatch_iou = reinterpret_cast<float *>(gmatch_list + 4 * G);                // [4][G]: and their IoUs
+    unsigned short *comp = reinterpret_cast<unsigned short *>(gmatch_iou + 4 * G);     // [NP]
+    __shared__ float thr[kMaxT];
+    __shared__ float alo[kMaxA], ahi[kMaxA];
+    __shared__ int scr[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long drow0 = (long)b * R;
+
+    int n = keep != nullptr ? n_kept[b] : counts[b];
+    n = min(max(n, 0), R);
+    const int gn = G > 0 ? min(max(gt_counts[b], 0), G) : 0;
+    if (tid < T) thr[tid] = thr_in[tid];
+    if (tid < A) { alo[tid] = area_lo[tid]; ahi[tid] = area_hi[tid]; }
+    fill_detection_keys(det, R, keep, b, n, C, ignore_class, NP, keys);
+    __syncthreads();
+    for (int g = tid; g < G; g += kThreads) {
+        int cls = -1;
+        unsigned flag = 0u;
+        if (g < gn) {
+            const float4 box = reinterpret_cast<const float4 *>(gt_boxes)[(long)b * G + g];
+            gbox[g] = box;
+            const long long l = gt_labels[(long)b * G + g];
+            if (l >= 0 && l < C && l != ignore_class) {
+                cls = (int)l;
+                const bool crowd = gt_crowd != nullptr && gt_crowd[(long)b * G + g] != 0;
+                const float area = gt_area != nullptr ? gt_area[(long)b * G + g] : (box.z - box.x) * (box.w - box.y);
+                if (crowd) flag = kCrowdFlag;
+                for (int a = 0; a < A; ++a) {
+                    if (crowd || area < alo[a] || area > ahi[a]) flag |= 1u << a;
+                    else atomicAdd(npig + (long)cls * A + a, 1ull);
+                }
+            }
+        }
+        gcls[g] = cls;
+        gflag[g] = flag;
+    }
+    __syncthreads();
+
+    const int total = sort_and_cap_detections(keys, comp, NP, max_dets, scr);
+    if (tid == 0) stage_counts[b] = total;
+
+    int *glist = gmatch_list + wave * G;
+    float *giou = gmatch_iou + wave * G;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const float th = lane < T ? thr[lane] : 0.f;
+    int seg = 0;
+    for (int base = 0; base < NP; base += 64) {
+        const int p = base + lane;
+        const unsigned long long key = p < NP ? keys[p] : ~0ull;
+        const bool valid = key != ~0ull;
+        const bool start = valid && (p == 0 || (keys[p - 1] >> 45) != (key >> 45));
+        unsigned long long starts = __ballot(start);
+        if (__ballot(valid) == 0ull) break;
+        while (starts) {
+            const int sl = __builtin_ctzll(starts);
+            starts &= starts - 1;
+            const int s = base + sl;
+            if ((seg++ & 3) != wave) continue;
+            const unsigned long long cls_hi = keys[s] >> 45;
+            const int cls = (int)cls_hi;
+            for (int a = 0; a < A; ++a) {
+                const float lo = alo[a], hi = ahi[a];
+                int nn = 0, nc = 0;                                      // not-ignored GT of the class, all of them
+                for (unsigned part = 0; part < 2u; ++part) {
+                    for (int g0 = 0; g0 < gn; g0 += 64) {
+                        const int g = g0 + lane;
+                        const bool in = g < gn && gcls[g] == cls && ((gflag[g] >> a) & 1u) == part;
+                        const unsigned long long bal = __ballot(in);
+                        if (in) glist[nc + __popcll(bal & lt)] = g;
+                        nc += __popcll(bal);
+                    }
+                    if (part == 0u) nn = nc;
+                }
+                wave_sync();
+                for (int i = lane; i < nc; i += 64) matched[glist[i]] = 0u;
+                for (int q0 = 0; q0 < max_dets; q0 += 64) {
+                    const int qi = q0 + lane, pq = s + qi;
+                    const unsigned long long kq = (qi < max_dets && pq < NP) ? keys[pq] : ~0ull;
+                    const bool mine = kq != ~0ull && (kq >> 45) == cls_hi;  // a prefix of the lanes: the keys are sorted
+                    const int nv = __popcll(__ballot(mine));
+                    float bx = 0.f, by = 0.f, bz = 0.f, bw = 0.f, sc = 0.f;
+                    if (mine) {
+                        const float *dq = det + (drow0 + det_row(keep, b, R, (int)(kq & 0x1FFFu))) * 6;
+                        bx = dq[0]; by = dq[1]; bz = dq[2]; bw = dq[3]; sc = dq[4];
+                    }
+                    for (int qq = 0; qq < nv; ++qq) {
+                        const float4 dbox = make_float4(lane_value(bx, qq), lane_value(by, qq), lane_value(bz, qq), lane_value(bw, qq));
+                        const float darea = (dbox.z - dbox.x) * (dbox.w - dbox.y);
+                        for (int i = lane; i < nc; i += 64) {
+                            const int g = glist[i];
+                            giou[i] = (gflag[g] & kCrowdFlag) ? crowd_iou(dbox, gbox[g], darea, kIouEps)
+                                                              : tsod_bbox_iou(dbox, gbox[g], kIouEps);
+                        }
+                        wave_sync();                                     // (also orders the reset of matched[] above)
+                        float best = -__builtin_inff();
+                        int bg = -1;
+                        bool ignored = false;
+                        if (lane < T) {
+                            for (int i = 0; i < nn; ++i) {
+                                const float v = giou[i];
+                                const int g = glist[i];
+                                if (v >= th && v >= best && !((matched[g] >> lane) & 1u)) { best = v; bg = g; }
+                            }
+                            if (bg < 0) {                                // nothing not-ignored: the ignored part, crowd re-matchable
+                                for (int i = nn; i < nc; ++i) {
+                                    const float v = giou[i];
+                                    const int g = glist[i];
+                                    if (v >= th && v >= best && (!((matched[g] >> lane) & 1u) || (gflag[g] & kCrowdFlag))) {
+                                        best = v;
+                                        bg = g;
+                                    }
+                                }
+                                ignored = bg >= 0 || darea < lo || darea > hi;
+                            }
+                            if (bg >= 0) atomicOr(&matched[bg], 1u << lane);
+                        }
+                        const unsigned tp = (unsigned)__ballot(bg >= 0 && !ignored);   // lanes >= T: neither
+                        const unsigned ig = (unsigned)__ballot(ignored);
+                        if (lane == qq) {
+                            tsod_eval_record_coco *rec = stage + drow0 + comp[s + qi];
+                            if (a == 0) {
+                                rec->score = sc;
+                                rec->cls = cls;
+                                rec->rank = qi;
+                                for (int k = 1; k < kMaxA; ++k) { rec->tp_mask[k] = 0u; rec->ig_mask[k] = 0u; }
+                            }
+                            rec->tp_mask[a] = tp;
+                            rec->ig_mask[a] = ig;
+                        }
+                        wave_sync();
+                    }
+                    if (nv < 64) break;
+                }
+            }
+        }
+    }
+}
+
 // running total += counts, offsets[b] = running total before image b (update order, then image order)
 __global__ void __launch_bounds__(kThreads)
 eval_offsets_kernel(const int *__restrict__ counts, int B, long long *__restrict__ offsets, long long *__restrict__ n_records) {
@@ -256,9 +448,10 @@ eval_offsets_kernel(const int *__restrict__ counts, int B, long long *__restrict
     if (threadIdx.x == 0) *n_records = carry;
 }
 
+template <typename Rec>
 __global__ void __launch_bounds__(kThreads)
-eval_compact_kernel(const tsod_eval_record *__restrict__ stage, const int *__restrict__ counts, const long long *__restrict__ offsets,
-                    int R, tsod_eval_record *__restrict__ records, long long capacity) {
+eval_compact_kernel(const Rec *__restrict__ stage, const int *__restrict__ counts, const long long *__restrict__ offsets, int R,
+                    Rec *__restrict__ records, long long capacity) {
     const int b = blockIdx.y;
     const int j = blockIdx.x * kThreads + threadIdx.x;
     if (j >= counts[b]) return;
@@ -396,28 +589,44 @@ int launch_sort(const unsigned long long *keys_in, const int *vals_in, long long
 }
 
 // ------------------------------------------------------------------------------------------------------ accumulate
+template <typename Rec>
 __global__ void __launch_bounds__(kThreads)
-eval_keys_kernel(const tsod_eval_record *__restrict__ records, long long n_max, const long long *__restrict__ n_dev,
+eval_keys_kernel(const Rec *__restrict__ records, long long n_max, const long long *__restrict__ n_dev,
                  unsigned long long *__restrict__ keys) {
     const long long n = live_count(n_max, n_dev);
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
-    const tsod_eval_record r = records[i];
+    const Rec r = records[i];
     keys[i] = ((unsigned long long)(unsigned)r.cls << 32) | desc_score_bits(r.score);
 }
 
+// what the AP scan reads of a record, at its sorted position i: the TP mask, or for a COCO record planes of `plane` words each,
+// (rank, tp_mask[0..4), ig_mask[0..4))
+__device__ __forceinline__ void store_sorted(unsigned *masks, long long, long long i, const tsod_eval_record &r) {
+    masks[i] = r.tp_mask;
+}
+__device__ __forceinline__ void store_sorted(unsigned *masks, long long plane, long long i, const tsod_eval_record_coco &r) {
+    masks[i] = (unsigned)r.rank;
+#pragma unroll
+    for (int a = 0; a < kMaxA; ++a) {
+        masks[(1 + a) * plane + i] = r.tp_mask[a];
+        masks[(1 + kMaxA + a) * plane + i] = r.ig_mask[a];
+    }
+}
+
 // per-class [begin, end) of the sorted keys, and the TP masks in sorted order
+template <typename Rec>
 __global__ void __launch_bounds__(kThreads)
-eval_segments_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ perm,
-                     const tsod_eval_record *__restrict__ records, long long n_max, const long long *__restrict__ n_dev,
-                     int *__restrict__ seg_begin, int *__restrict__ seg_end, unsigned *__restrict__ masks) {
+eval_segments_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ perm, const Rec *__restrict__ records,
+                     long long n_max, const long long *__restrict__ n_dev, int *__restrict__ seg_begin,
+                     int *__restrict__ seg_end, unsigned *__restrict__ masks) {
     const long long n = live_count(n_max, n_dev);
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(keys[i] >> 32);
     if (i == 0 || (int)(keys[i - 1] >> 32) != c) seg_begin[c] = (int)i;
     if (i == n - 1 || (int)(keys[i + 1] >> 32) != c) seg_end[c] = (int)(i + 1);
-    masks[i] = records[perm[i]].tp_mask;
+    store_sorted(masks, n_max, i, records[perm[i]]);
 }
 
 // workgroup (c, t): TP / FP along the class's sorted segment, the precision envelope and its 101-point sample
@@ -483,6 +692,80 @@ eval_ap_kernel(const unsigned *__restrict__ masks, const int *__restrict__ seg_b
     }
 }
 
+// workgroup (c, a, m, t) of the COCO accumulate: eval_ap_kernel over the class's records with rank < cap[m] that range a does
+// not ignore at threshold t; `sorted` holds store_sorted's planes.
+__global__ void __launch_bounds__(kThreads)
+eval_ap_coco_kernel(const unsigned *__restrict__ sorted, long long plane, const int *__restrict__ seg_begin,
+                    const int *__restrict__ seg_end, const long long *__restrict__ npig, int A, int M, int T, DetCaps caps,
+                    double *__restrict__ ap, long long *__restrict__ tp_out, long long *__restrict__ fp_out,
+                    long long *__restrict__ fn_out, double *__restrict__ recall) {
+    __shared__ unsigned long long bins[101];
+    __shared__ int scr[4];
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x % T, m = (blockIdx.x / T) % M, a = (blockIdx.x / (T * M)) % A, c = blockIdx.x / (T * M * A);
+    const unsigned cap = (unsigned)(m == 0 ? caps.v[0] : m == 1 ? caps.v[1] : m == 2 ? caps.v[2] : caps.v[3]);
+    const unsigned *rank = sorted, *tpw = sorted + (1 + a) * plane, *igw = sorted + (1 + kMaxA + a) * plane;
+    const int s = seg_begin[c], e = seg_end[c];
+    const long long np = npig[(long)c * A + a];
+    if (tid < 101) bins[tid] = 0ull;
+    long long carry_tp = 0, carry_n = 0;
+    for (int c0 = s; c0 < e; c0 += kThreads * kApItems) {
+        const int j0 = c0 + tid * kApItems, j1 = min(j0 + kApItems, e);
+        unsigned live = 0u, hit = 0u;                                 // bit j - j0: counted at all, counted as a TP
+        for (int j = j0; j < j1; ++j) {
+            const unsigned l = (rank[j] < cap && !((igw[j] >> t) & 1u)) ? 1u : 0u;
+            live |= l << (j - j0);
+            hit |= (l & (tpw[j] >> t)) << (j - j0);
+        }
+        int total = 0;                                                // TP in the low half, counted records in the high half
+        const int ex = block_exclusive_scan(__popc(hit) | (__popc(live) << 16), scr, &total);
+        if (np > 0) {
+            long long tp = carry_tp + (ex & 0xFFFF), n = carry_n + (ex >> 16);
+            int cur = -1;
+            unsigned long long best = 0ull;
+            for (int j = j0; j < j1; ++j) {
+                if (!((live >> (j - j0)) & 1u)) continue;
+                tp += (hit >> (j - j0)) & 1u;
+                ++n;
+                const double prec = (double)tp / (double)n;
+                const long long q = (100 * tp) / np;
+                const int bin = q < 100 ? (int)q : 100;
+                if (bin != cur) {
+                    if (cur >= 0) atomicMax(&bins[cur], best);
+                    cur = bin;
+                    best = 0ull;
+                }
+                const unsigned long long pb = (unsigned long long)__double_as_longlong(prec);
+                best = pb > best ? pb : best;
+            }
+            if (cur >= 0) atomicMax(&bins[cur], best);
+        }
+        carry_tp += total & 0xFFFF;
+        carry_n += total >> 16;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const long k = blockIdx.x;
+        tp_out[k] = carry_tp;
+        fp_out[k] = carry_n - carry_tp;
+        fn_out[k] = np - carry_tp;
+        if (np > 0) {
+            unsigned long long env = 0ull;
+            for (int i = 100; i >= 0; --i) {
+                env = bins[i] > env ? bins[i] : env;
+                bins[i] = env;
+            }
+            double sum = 0.0;
+            for (int i = 0; i <= 100; ++i) sum += __longlong_as_double((long long)bins[i]);
+            ap[k] = sum / 101.0;
+            recall[k] = (double)carry_tp / (double)np;
+        } else {
+            ap[k] = -1.0;
+            recall[k] = -1.0;
+        }
+    }
+}
+
 int class_bits(int C) {
     int bits = 1;
     while (bits < 31 && (1ll << bits) < (long long)C) ++bits;
@@ -498,14 +781,14 @@ struct AccWs {
     size_t sort_bytes, bytes;
 };
 
-AccWs acc_ws_layout(void *ws, long long capacity, int C) {
+AccWs acc_ws_layout(void *ws, long long capacity, int C, int mask_planes = 1) {
     AccWs w;
     char *p = static_cast<char *>(ws);
     size_t off = 0;
     w.keys = reinterpret_cast<unsigned long long *>(p + off);        off += tsod_align_up((size_t)capacity * 8, 256);
     w.sorted_keys = reinterpret_cast<unsigned long long *>(p + off); off += tsod_align_up((size_t)capacity * 8, 256);
     w.perm = reinterpret_cast<int *>(p + off);                       off += tsod_align_up((size_t)capacity * 4, 256);
-    w.masks = reinterpret_cast<unsigned *>(p + off);                 off += tsod_align_up((size_t)capacity * 4, 256);
+    w.masks = reinterpret_cast<unsigned *>(p + off);                 off += tsod_align_up((size_t)capacity * 4 * mask_planes, 256);
     w.seg_begin = reinterpret_cast<int *>(p + off);                  off += tsod_align_up((size_t)C * 4, 256);
     w.seg_end = reinterpret_cast<int *>(p + off);                    off += tsod_align_up((size_t)C * 4, 256);
     w.sort_ws = p + off;
@@ -516,6 +799,8 @@ AccWs acc_ws_layout(void *ws, long long capacity, int C) {
 }
 
 size_t match_lds_bytes(int NP, int G) { return (size_t)NP * 8 + (size_t)G * (16 + 4 + 4 + 4 * 8) + (size_t)NP * 2; }
+size_t match_coco_lds_bytes(int NP, int G) { return match_lds_bytes(NP, G) + (size_t)G * 4; }   // + gflag
+constexpr int kCocoPlanes = 1 + 2 * kMaxA;
 
 }  // namespace
 
@@ -557,7 +842,7 @@ extern "C" int tsod_eval_match_f32(const float *det, int32_t B, int32_t R, const
                        ignore_class, NP, stage, stage_counts, reinterpret_cast<unsigned long long *>(npig));
     hipLaunchKernelGGL(eval_offsets_kernel, dim3(1), dim3(kThreads), 0, st, stage_counts, B, offsets,
                        reinterpret_cast<long long *>(n_records));
-    hipLaunchKernelGGL(eval_compact_kernel, dim3((unsigned)tsod_cdiv(R, kThreads), B), dim3(kThreads), 0, st, stage, stage_counts,
+    hipLaunchKernelGGL(eval_compact_kernel<tsod_eval_record>, dim3((unsigned)tsod_cdiv(R, kThreads), B), dim3(kThreads), 0, st, stage, stage_counts,
                        offsets, R, records, (long long)capacity);
     return tsod_launch_status();
 }
@@ -603,14 +888,105 @@ extern "C" int tsod_eval_accumulate_f64(const tsod_eval_record *records, int64_t
     if (hipMemsetAsync(w.seg_begin, 0, (size_t)num_classes * 4, st) != hipSuccess ||
         hipMemsetAsync(w.seg_end, 0, (size_t)num_classes * 4, st) != hipSuccess)
         return TSOD_ERR_LAUNCH;
-    hipLaunchKernelGGL(eval_keys_kernel, dim3(grid), dim3(kThreads), 0, st, records, (long long)capacity, nd, w.keys);
+    hipLaunchKernelGGL(eval_keys_kernel<tsod_eval_record>, dim3(grid), dim3(kThreads), 0, st, records, (long long)capacity, nd, w.keys);
     const int rc = launch_sort(w.keys, nullptr, capacity, nd, 0, 32 + class_bits(num_classes), w.sorted_keys, w.perm,
                                sort_ws_layout(w.sort_ws, capacity), st);
     if (rc != TSOD_OK) return rc;
-    hipLaunchKernelGGL(eval_segments_kernel, dim3(grid), dim3(kThreads), 0, st, w.sorted_keys, w.perm, records,
+    hipLaunchKernelGGL(eval_segments_kernel<tsod_eval_record>, dim3(grid), dim3(kThreads), 0, st, w.sorted_keys, w.perm, records,
                        (long long)capacity, nd, w.seg_begin, w.seg_end, w.masks);
     hipLaunchKernelGGL(eval_ap_kernel, dim3((unsigned)num_classes * (unsigned)T), dim3(kThreads), 0, st, w.masks, w.seg_begin,
                        w.seg_end, reinterpret_cast<const long long *>(npig), T, ap, reinterpret_cast<long long *>(tp),
                        reinterpret_cast<long long *>(fp), reinterpret_cast<long long *>(fn), recall);
+    return tsod_launch_status();
+}
+
+extern "C" size_t tsod_eval_match_coco_workspace_bytes(int32_t B, int32_t R) {
+    if (B <= 0 || R <= 0 || R > kMaxR || B > 65535) return 0;
+    return tsod_align_up((size_t)B * R * sizeof(tsod_eval_record_coco), 256) + tsod_align_up((size_t)B * 4, 256) +
+           tsod_align_up((size_t)B * 8, 256);
+}
+
+extern "C" int tsod_eval_match_coco_f32(const float *det, int32_t B, int32_t R, const int32_t *counts, const int32_t *keep,
+                                        const int32_t *n_kept, const float *gt_boxes, const int64_t *gt_labels,
+                                        const int32_t *gt_counts, const uint8_t *gt_crowd, const float *gt_area, int32_t G,
+                                        const float *iou_thr, int32_t T, const float *area_lo, const float *area_hi, int32_t A,
+                                        int32_t num_classes, int32_t max_dets, int32_t ignore_class,
+                                        tsod_eval_record_coco *records, int64_t capacity, int64_t *n_records, int64_t *npig,
+                                        void *workspace, size_t workspace_bytes, tsod_stream_t stream) {
+    TSOD_REQUIRE(det && iou_thr && area_lo && area_hi && records && n_records && npig, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE((keep != nullptr) == (n_kept != nullptr) && (counts != nullptr) != (keep != nullptr), TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(B > 0 && R > 0 && G >= 0 && T > 0 && A > 0 && num_classes > 0 && max_dets > 0 && capacity >= 0,
+                 TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(G == 0 || (gt_boxes && gt_labels && gt_counts), TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(R <= kMaxR && G <= kMaxG && T <= kMaxT && A <= kMaxA && num_classes <= kMaxClasses && B <= 65535,
+                 TSOD_ERR_UNSUPPORTED);
+    TSOD_REQUIRE(G == 0 || tsod_aligned16(gt_boxes), TSOD_ERR_ALIGNMENT);
+    TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_match_coco_workspace_bytes(B, R), TSOD_ERR_WORKSPACE);
+    char *p = static_cast<char *>(workspace);
+    const size_t stage_bytes = tsod_align_up((size_t)B * R * sizeof(tsod_eval_record_coco), 256);
+    tsod_eval_record_coco *stage = reinterpret_cast<tsod_eval_record_coco *>(p);
+    int *stage_counts = reinterpret_cast<int *>(p + stage_bytes);
+    long long *offsets = reinterpret_cast<long long *>(p + stage_bytes + tsod_align_up((size_t)B * 4, 256));
+    int NP = 64;
+    while (NP < R) NP <<= 1;
+    const size_t lds = match_coco_lds_bytes(NP, G);
+    hipStream_t st = tsod_stream(stream);
+    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(eval_match_coco_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return TSOD_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(eval_match_coco_kernel, dim3(B), dim3(kThreads), lds, st, det, R, counts, keep, n_kept, gt_boxes,
+                       reinterpret_cast<const long long *>(gt_labels), gt_counts, gt_crowd, gt_area, G, iou_thr, T, area_lo,
+                       area_hi, A, num_classes, max_dets, ignore_class, NP, stage, stage_counts,
+                       reinterpret_cast<unsigned long long *>(npig));
+    hipLaunchKernelGGL(eval_offsets_kernel, dim3(1), dim3(kThreads), 0, st, stage_counts, B, offsets,
+                       reinterpret_cast<long long *>(n_records));
+    hipLaunchKernelGGL(eval_compact_kernel<tsod_eval_record_coco>, dim3((unsigned)tsod_cdiv(R, kThreads), B), dim3(kThreads), 0,
+                       st, stage, stage_counts, offsets, R, records, (long long)capacity);
+    return tsod_launch_status();
+}
+
+extern "C" size_t tsod_eval_accumulate_coco_workspace_bytes(int64_t capacity, int32_t num_classes) {
+    if (capacity <= 0 || num_classes <= 0 || num_classes > kMaxClasses || capacity > (int64_t)INT32_MAX - kRadixTile) return 0;
+    return acc_ws_layout(nullptr, capacity, num_classes, kCocoPlanes).bytes;
+}
+
+extern "C" int tsod_eval_accumulate_coco_f64(const tsod_eval_record_coco *records, int64_t capacity, const int64_t *n_records,
+                                             const int64_t *npig, int32_t num_classes, int32_t A, int32_t T,
+                                             const int32_t *max_dets_list, int32_t M, int32_t max_dets, double *ap, int64_t *tp,
+                                             int64_t *fp, int64_t *fn, double *recall, void *workspace, size_t workspace_bytes,
+                                             tsod_stream_t stream) {
+    TSOD_REQUIRE(records && n_records && npig && max_dets_list && ap && tp && fp && fn && recall, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(capacity > 0 && num_classes > 0 && T > 0 && A > 0 && M > 0 && max_dets > 0, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(T <= kMaxT && A <= kMaxA && M <= kMaxM && num_classes <= kMaxClasses &&
+                     capacity <= (int64_t)INT32_MAX - kRadixTile,
+                 TSOD_ERR_UNSUPPORTED);
+    DetCaps caps = {{0, 0, 0, 0}};
+    for (int m = 0; m < M; ++m) {
+        TSOD_REQUIRE(max_dets_list[m] > (m ? max_dets_list[m - 1] : 0), TSOD_ERR_INVALID_ARG);   // ascending, from 1
+        caps.v[m] = max_dets_list[m];
+    }
+    TSOD_REQUIRE(caps.v[M - 1] <= max_dets, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_accumulate_coco_workspace_bytes(capacity, num_classes),
+                 TSOD_ERR_WORKSPACE);
+    const AccWs w = acc_ws_layout(workspace, capacity, num_classes, kCocoPlanes);
+    hipStream_t st = tsod_stream(stream);
+    const long long *nd = reinterpret_cast<const long long *>(n_records);
+    const unsigned grid = (unsigned)tsod_cdiv(capacity, kThreads);
+    if (hipMemsetAsync(w.seg_begin, 0, (size_t)num_classes * 4, st) != hipSuccess ||
+        hipMemsetAsync(w.seg_end, 0, (size_t)num_classes * 4, st) != hipSuccess)
+        return TSOD_ERR_LAUNCH;
+    hipLaunchKernelGGL(eval_keys_kernel<tsod_eval_record_coco>, dim3(grid), dim3(kThreads), 0, st, records, (long long)capacity,
+                       nd, w.keys);
+    const int rc = launch_sort(w.keys, nullptr, capacity, nd, 0, 32 + class_bits(num_classes), w.sorted_keys, w.perm,
+                               sort_ws_layout(w.sort_ws, capacity), st);
+    if (rc != TSOD_OK) return rc;
+    hipLaunchKernelGGL(eval_segments_kernel<tsod_eval_record_coco>, dim3(grid), dim3(kThreads), 0, st, w.sorted_keys, w.perm,
+                       records, (long long)capacity, nd, w.seg_begin, w.seg_end, w.masks);
+    hipLaunchKernelGGL(eval_ap_coco_kernel, dim3((unsigned)num_classes * (unsigned)(A * M * T)), dim3(kThreads), 0, st, w.masks,
+                       (long long)capacity, w.seg_begin, w.seg_end, reinterpret_cast<const long long *>(npig), A, M, T, caps, ap,
+                       reinterpret_cast<long long *>(tp), reinterpret_cast<long long *>(fp), reinterpret_cast<long long *>(fn),
+                       recall);
     return tsod_launch_status();
 }

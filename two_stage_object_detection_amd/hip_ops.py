@@ -1413,6 +1413,58 @@ def eval_accumulate(records: torch.Tensor, n_records: torch.Tensor, npig: torch.
     return out
 
 
+EVAL_COCO_RECORD_INTS = 11           # tsod_eval_record_coco = (score f32, class, rank, tp_mask[4], ig_mask[4]), int32 rows
+EVAL_COCO_MAX_AREAS = 4              # area ranges of one match / words of a record's masks
+EVAL_COCO_MAX_CAPS = 4               # detection caps of one accumulate
+
+
+def eval_match_coco(det: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_counts: torch.Tensor,
+                    iou_thr: torch.Tensor, area_lo: torch.Tensor, area_hi: torch.Tensor, num_classes: int, max_dets: int,
+                    ignore_class: int, records: torch.Tensor, n_records: torch.Tensor, npig: torch.Tensor, *, gt_crowd=None,
+                    gt_area=None, counts=None, keep=None, n_kept=None) -> None:
+    """One update of the COCO evaluator's device state (tsod_eval_match_coco_f32): eval_match's inputs plus gt_crowd [B,G]
+    uint8 and gt_area [B,G] f32 (either may be None) and the area ranges area_lo / area_hi [A] f32 on the device.  Appends to
+    records [capacity,11] int32 at n_records [1] int64 and adds to npig [num_classes,A] int64, in place."""
+    require_cuda(det, "eval_match_coco")
+    B, R, six = det.shape
+    if six != 6:
+        raise ValueError(f"eval_match_coco: detection records are [B,R,6], got {tuple(det.shape)}")
+    G = gt_boxes.shape[1]
+    for name, x, dtype in (("gt_crowd", gt_crowd, torch.uint8), ("gt_area", gt_area, torch.float32)):
+        if x is not None:
+            _require_cuda_any(x, f"eval_match_coco: {name}", dtype)
+            if tuple(x.shape) != (B, G) or not x.is_contiguous():
+                raise ValueError(f"eval_match_coco: {name} must be a contiguous [{B},{G}] tensor, got {tuple(x.shape)}")
+    L = lib()
+    ws_bytes = L.tsod_eval_match_coco_workspace_bytes(B, R)
+    ws = EVAL_ARENA.get(det.device, ws_bytes)
+    check(L.tsod_eval_match_coco_f32(ptr(det), B, R, ptr(counts), ptr(keep), ptr(n_kept), ptr(gt_boxes) if G else None,
+                                     ptr(gt_labels) if G else None, ptr(gt_counts) if G else None,
+                                     ptr(gt_crowd) if G else None, ptr(gt_area) if G else None, G, ptr(iou_thr),
+                                     iou_thr.shape[0], ptr(area_lo), ptr(area_hi), area_lo.shape[0], int(num_classes),
+                                     int(max_dets), int(ignore_class), ptr(records), records.shape[0], ptr(n_records), ptr(npig),
+                                     ptr(ws), ws_bytes, stream_ptr()), "eval_match_coco")
+
+
+def eval_accumulate_coco(records: torch.Tensor, n_records: torch.Tensor, npig: torch.Tensor, T: int, max_dets_list,
+                         max_dets: int) -> torch.Tensor:
+    """tsod_eval_accumulate_coco_f64 over every record so far -> one int64 tensor [5, C, A, M, T] on the device: the bits of
+    AP (f64), TP, FP, FN, the bits of recall (f64), in that order.  npig [C,A]; max_dets_list: the M ascending caps (host
+    ints), the last at most ``max_dets``, the cap the records were matched with."""
+    C, A = npig.shape
+    caps = (c_int32 * len(max_dets_list))(*[int(m) for m in max_dets_list])
+    M = len(caps)
+    out = torch.empty((5, C, A, M, int(T)), dtype=torch.int64, device=records.device)
+    L = lib()
+    ws_bytes = L.tsod_eval_accumulate_coco_workspace_bytes(records.shape[0], C)
+    ws = EVAL_ARENA.get(records.device, ws_bytes)
+    check(L.tsod_eval_accumulate_coco_f64(ptr(records), records.shape[0], ptr(n_records), ptr(npig), C, A, int(T),
+                                          caps, M, int(max_dets), ptr(out[0]), ptr(out[1]),
+                                          ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(ws), ws_bytes, stream_ptr()),
+          "eval_accumulate_coco")
+    return out
+
+
 # ----------------------------------------------------------------------------- training-side box ops
 def anchor_targets(bbox: torch.Tensor, anchor: torch.Tensor, n_pos: int, n_sample: int, pos_iou_thresh: float,
                    neg_iou_thresh: float):

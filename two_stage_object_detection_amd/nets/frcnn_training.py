@@ -26,7 +26,7 @@ from ..models.hardnet import HarNetClassifier
 from .classify import HarNetRoIHead
 from .frcnn import _UID, _make_extractor
 from .rpn import RegionProposalNetwork
-from ..utils.metrics import DetectionEvaluator
+from ..utils.metrics import COCOEvaluator, DetectionEvaluator
 
 
 class AnchorTargetCreator:
@@ -465,23 +465,53 @@ class FasterRCNNTrainer(nn.Module):
         of per-batch values; every image is scored against its own ground truth, not ``bboxes[0]``.  The predictions come
         from the ground-truth-conditioned samples of ``forward`` (the reference's design), so the score sees the ground truth
         it is measured against: ``FasterRCNN.predict`` + ``DetectionEvaluator`` is the honest score of a detector."""
-        self.eval()
         ev = DetectionEvaluator(self.n_classes + 1, iou_thresholds=(map_iou_threshold,), ignore_class=0)
+        loss = self._evaluate(ev, eval_dataloader, scale, nms_iou_threshold)
+        if loss is None:
+            return 0, 0
+        return loss, ev.compute()["mAP"]
+
+    def _evaluate(self, ev, eval_dataloader, scale, nms_iou_threshold, per_gt=False):
+        """The evaluation loop of ``eval_fn`` / ``eval_coco``: every batch through ``forward`` and ``_records`` into ``ev`` ->
+        the mean over batches of ``losses[-1]`` (summed on the device, read once), None for an empty loader.  ``per_gt``: a
+        batch may carry per-image crowd flags and areas as a fourth and fifth element, passed to ``ev.update``."""
+        self.eval()
         dev = next(self.parameters()).device
         loss_total, batches = None, 0
-        for imgs, bboxes, labels in eval_dataloader:
+        for imgs, bboxes, labels, *extra in eval_dataloader:
+            if len(extra) > (2 if per_gt else 0):
+                raise ValueError(f"a batch of {3 + len(extra)} elements: (imgs, bboxes, labels"
+                                 + ("[, crowd[, area]])" if per_gt else ")") + " expected")
             imgs = [im.to(dev) for im in imgs] if isinstance(imgs, (list, tuple)) else imgs.to(dev)
             bboxes = [bb.to(dev, torch.float32) for bb in bboxes]
             labels = [lb.to(dev) for lb in labels]
+            kw = {}
+            if len(extra) > 0 and extra[0] is not None:
+                kw["gt_crowd"] = [c.to(dev) for c in extra[0]]
+            if len(extra) > 1 and extra[1] is not None:
+                kw["gt_area"] = [a.to(dev, torch.float32) for a in extra[1]]
             losses, anchors_pred, classes_pred, classes_score_pred = self.forward(imgs, bboxes, labels, scale)[:4]
             loss = losses[-1].detach()
             loss_total = loss if loss_total is None else loss_total + loss
             det_sorted, keep, n_kept = self._records(anchors_pred, classes_pred, classes_score_pred, nms_iou_threshold)
-            ev.update(det_sorted, bboxes, [lb.to(torch.int64) + 1 for lb in labels], keep=keep, n_kept=n_kept)
+            ev.update(det_sorted, bboxes, [lb.to(torch.int64) + 1 for lb in labels], keep=keep, n_kept=n_kept, **kw)
             batches += 1
-        if batches == 0:
-            return 0, 0
-        return float(loss_total) / batches, ev.compute()["mAP"]
+        return float(loss_total) / batches if batches else None
+
+    def eval_coco(self, eval_dataloader, scale=1, nms_iou_threshold=0.7):
+        """``eval_fn``'s loop run once for the whole COCO table -> (avg_eval_loss, stats).
+
+        Every batch runs through ``forward`` and the reference's per-class NMS exactly as in ``eval_fn``; the rows go into one
+        ``COCOEvaluator(n_classes + 1, ignore_class=0)``: COCO's ten thresholds, four area ranges and
+        caps (1, 10, 100) at once, where the reference's training loop calls ``eval_fn`` once per threshold.  A batch is
+        ``(imgs, bboxes, labels)``, or carries per-image ``crowd`` flags as a fourth and ``area`` values as a fifth element
+        (lists of [G_i] tensors).  ``stats`` is ``COCOEvaluator.compute()``'s dict; (0, {}) for an empty loader.  What
+        ``eval_fn`` says about predictions conditioned on the ground truth holds here too."""
+        ev = COCOEvaluator(self.n_classes + 1, ignore_class=0)
+        loss = self._evaluate(ev, eval_dataloader, scale, nms_iou_threshold, per_gt=True)
+        if loss is None:
+            return 0, {}
+        return loss, ev.compute()
 
     def calculate_metrics(self, anchors_pred, classes_pred, classes_score_pred, anchors_gt, classes_gt,
                           nms_iou_threshold: float = 0.7, map_iou_threshold: float = 0.7):

@@ -20,6 +20,9 @@ Deliberate deviations from the reference's evident intent: one-to-one matching (
 when any GT of its class has IoU > t); classes without ground truth are excluded (the reference appends 0); the mAP is one
 dataset-level number (the reference averages per-batch values); every image is scored against its own ground truth (the
 reference uses ``bboxes[0]`` only).
+
+``COCOEvaluator`` is the same metric with COCO's area ranges, crowd regions, ignore rules and
+detection caps: the whole COCO table (AP, AP50, AP75, APs / APm / APl, AR1 / AR10 / AR100, ARs / ARm / ARl) from one pass.
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ from .. import hip_ops
 from .._ffi import TsodError, require_cuda
 
 COCO_IOU_THRESHOLDS = tuple(float(np.float32(v)) for v in np.linspace(0.5, 0.95, 10))
+COCO_AREA_RANGES = (("all", 0, 1e10), ("small", 0, 32 ** 2), ("medium", 32 ** 2, 96 ** 2), ("large", 96 ** 2, 1e10))
 MAX_THRESHOLDS = 32
 
 
@@ -46,6 +50,12 @@ def _as_list(x, what):
 def _aligned(t: torch.Tensor) -> torch.Tensor:
     t = t.contiguous()
     return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _require_gpu(t, what):
+    """require_cuda without its float32 rule (flags and labels)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        require_cuda(t, what)
 
 
 class DetectionEvaluator:
@@ -64,6 +74,8 @@ class DetectionEvaluator:
     (``mAP``, ``AP50`` / ``AP75`` when those thresholds are evaluated, ``AP`` [C,T] f64 with -1 for classes without ground
     truth, ``recall`` (likewise), ``TP`` / ``FP`` / ``FN`` [C,T] int64, ``npig`` [C] int64, ``iou_thresholds``).  ``reset()``
     clears the state."""
+
+    _RECORD_INTS = hip_ops.EVAL_RECORD_INTS       # int32 words of one record row
 
     def __init__(self, num_classes: int, iou_thresholds=COCO_IOU_THRESHOLDS, max_dets: int = 100, ignore_class=None):
         thr = [float(np.float32(v)) for v in iou_thresholds]
@@ -89,7 +101,7 @@ class DetectionEvaluator:
     def _state(self, dev):
         if self._device is None:
             self._device = dev
-            self._records = torch.empty((0, hip_ops.EVAL_RECORD_INTS), dtype=torch.int32, device=dev)
+            self._records = torch.empty((0, self._RECORD_INTS), dtype=torch.int32, device=dev)
             self._n = torch.zeros((1,), dtype=torch.int64, device=dev)
             self._npig = torch.zeros((self.num_classes,), dtype=torch.int64, device=dev)
             self._thr = torch.tensor(self.iou_thresholds, dtype=torch.float32, device=dev)
@@ -100,7 +112,7 @@ class DetectionEvaluator:
         need = self._bound + extra
         cap = self._records.shape[0]
         if need > cap:
-            grown = torch.empty((max(need, 2 * cap), hip_ops.EVAL_RECORD_INTS), dtype=torch.int32, device=self._device)
+            grown = torch.empty((max(need, 2 * cap), self._RECORD_INTS), dtype=torch.int32, device=self._device)
             if self._bound:
                 grown[:self._bound].copy_(self._records[:self._bound])
             self._records = grown
@@ -227,6 +239,140 @@ class DetectionEvaluator:
                 if thr == float(np.float32(v)):
                     res[name] = _mean(ap[has_gt, t])
         return res
+
+
+class COCOEvaluator(DetectionEvaluator):
+    """COCOeval's detection table in one pass on the GPU: ``DetectionEvaluator``'s metric with area
+    ranges, crowd regions, COCO's ignore rules and several detection caps.
+
+    ``COCOEvaluator(num_classes, iou_thresholds=0.50:0.95:0.05, max_dets=(1, 10, 100), area_ranges=COCO_AREA_RANGES,
+    ignore_class=None)``: ``max_dets`` are ascending caps per (image, class), at most 4; ``area_ranges`` are at most 4
+    ``(name, lo, hi)`` triples with both bounds inclusive (f32).
+
+    ``update(det, gt_boxes, gt_labels, *, gt_crowd=None, gt_area=None, counts=None, keep=None, n_kept=None, gt_counts=None)``
+    takes every input form of ``DetectionEvaluator.update``; ``gt_crowd`` (nonzero = a crowd region) and ``gt_area`` (replaces
+    the box's own area (x2-x1)*(y2-y1)) are lists of [G_i] tensors or padded [B,G] tensors.  No host synchronisation.
+    ``compute()`` reads the results back once and returns COCO's numbers - ``AP`` / ``AP50`` / ``AP75`` (area "all", the last
+    cap), ``APs`` / ``APm`` / ``APl``, ``AR<cap>`` for every cap (area "all"), ``ARs`` / ``ARm`` / ``ARl`` (the last cap), each
+    the mean over the entries that are not -1 and present only when its threshold, range ("all" / "small" / "medium" / "large"
+    by name) and cap are configured - with the arrays ``precision`` and ``recall`` [C,A,M,T] f64 (-1 where the class has no
+    not-ignored ground truth in the range), ``TP`` / ``FP`` / ``FN`` [C,A,M,T] int64, ``npig`` [C,A] int64 and
+    ``iou_thresholds``, ``area_ranges``, ``max_dets``."""
+
+    _RECORD_INTS = hip_ops.EVAL_COCO_RECORD_INTS
+
+    def __init__(self, num_classes: int, iou_thresholds=COCO_IOU_THRESHOLDS, max_dets=(1, 10, 100),
+                 area_ranges=COCO_AREA_RANGES, ignore_class=None):
+        caps = tuple(int(m) for m in max_dets)
+        if not 0 < len(caps) <= hip_ops.EVAL_COCO_MAX_CAPS or caps[0] <= 0 or any(a >= b for a, b in zip(caps, caps[1:])):
+            raise ValueError(f"COCOEvaluator: 1 to {hip_ops.EVAL_COCO_MAX_CAPS} ascending positive caps, got {max_dets}")
+        ranges = tuple((str(name), float(np.float32(lo)), float(np.float32(hi))) for name, lo, hi in area_ranges)
+        if not 0 < len(ranges) <= hip_ops.EVAL_COCO_MAX_AREAS:
+            raise ValueError(f"COCOEvaluator: 1 to {hip_ops.EVAL_COCO_MAX_AREAS} area ranges, got {len(ranges)}")
+        super().__init__(num_classes, iou_thresholds, caps[-1], ignore_class)
+        self.caps = caps
+        self.area_ranges = ranges
+
+    def _state(self, dev):
+        fresh = self._device is None
+        super()._state(dev)
+        if fresh:
+            self._npig = torch.zeros((self.num_classes, len(self.area_ranges)), dtype=torch.int64, device=dev)
+            self._lo = torch.tensor([r[1] for r in self.area_ranges], dtype=torch.float32, device=dev)
+            self._hi = torch.tensor([r[2] for r in self.area_ranges], dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def _per_gt(x, what, like, dtype):
+        """gt_crowd / gt_area as a padded [B,G] tensor of ``dtype`` beside the padded labels ``like`` (None stays None)."""
+        if x is None:
+            return None
+        B, G = like.shape
+        rows = _as_list(x, what)
+        if rows is None:
+            _require_gpu(x, "COCOEvaluator.update")
+            if tuple(x.shape) != (B, G):
+                raise ValueError(f"COCOEvaluator.update: {what} {tuple(x.shape)} beside ground truth [{B},{G}]")
+            return (x != 0).to(dtype).contiguous() if dtype == torch.uint8 else x.to(dtype).contiguous()
+        if len(rows) != B:
+            raise ValueError(f"COCOEvaluator.update: {B} images, {len(rows)} {what} sets")
+        out = torch.zeros((B, G), dtype=dtype, device=like.device)
+        for b, r in enumerate(rows):
+            _require_gpu(r, "COCOEvaluator.update")
+            if r.dim() != 1 or r.shape[0] > G:
+                raise ValueError(f"COCOEvaluator.update: {what} [G] per image, got {tuple(r.shape)}")
+            out[b, :r.shape[0]].copy_((r != 0) if dtype == torch.uint8 else r)
+        return out
+
+    def update(self, det, gt_boxes, gt_labels, *, gt_crowd=None, gt_area=None, counts=None, keep=None, n_kept=None,
+               gt_counts=None):
+        det, counts, keep, n_kept = self._detections(det, counts, keep, n_kept)
+        B, R = det.shape[:2]
+        dev = det.device
+        gb, gl, gc = self._ground_truth(gt_boxes, gt_labels, B, dev, gt_counts)
+        crowd = self._per_gt(gt_crowd, "gt_crowd", gl, torch.uint8)
+        area = self._per_gt(gt_area, "gt_area", gl, torch.float32)
+        self._state(dev)
+        self._reserve(B * R)
+        hip_ops.eval_match_coco(det, gb, gl, gc, self._thr, self._lo, self._hi, self.num_classes, self.max_dets,
+                                self.ignore_class, self._records, self._n, self._npig, gt_crowd=crowd, gt_area=area,
+                                counts=counts, keep=keep, n_kept=n_kept)
+        self._bound += B * R
+
+    def records(self):
+        """The records so far, in record order, read back to the host (a test / debugging accessor): (score [N] f32,
+        class [N] int32, rank [N] int32, TP masks [N,4] uint32, ignore masks [N,4] uint32) numpy arrays."""
+        n = 0 if self._device is None else int(self._n.item())
+        r = self._records[:n].cpu().numpy() if n else np.zeros((0, self._RECORD_INTS), np.int32)
+        return (r[:, 0].view(np.float32).copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3:7].view(np.uint32).copy(),
+                r[:, 7:11].view(np.uint32).copy())
+
+    def compute(self) -> dict:
+        if self._device is None:
+            raise RuntimeError("COCOEvaluator.compute: nothing was passed to update()")
+        C, A, M, T = self.num_classes, len(self.area_ranges), len(self.caps), len(self.iou_thresholds)
+        self._reserve(1)                                                  # capacity > 0 even when every batch was empty
+        out = hip_ops.eval_accumulate_coco(self._records, self._n, self._npig, T, self.caps, self.max_dets)
+        host = torch.cat([out.view(-1), self._npig.view(-1)]).cpu().numpy()   # the one host read
+        body = host[:5 * C * A * M * T].reshape(5, C, A, M, T)
+        ap, recall = body[0].view(np.float64), body[4].view(np.float64)
+        res = {
+            "precision": torch.from_numpy(ap.copy()),
+            "recall": torch.from_numpy(recall.copy()),
+            "TP": torch.from_numpy(body[1].copy()),
+            "FP": torch.from_numpy(body[2].copy()),
+            "FN": torch.from_numpy(body[3].copy()),
+            "npig": torch.from_numpy(host[5 * C * A * M * T:].reshape(C, A).copy()),
+            "iou_thresholds": self.iou_thresholds,
+            "area_ranges": self.area_ranges,
+            "max_dets": self.caps,
+        }
+        res.update(coco_summary(ap, recall, self.iou_thresholds, [r[0] for r in self.area_ranges], self.caps))
+        return res
+
+
+def coco_summary(precision, recall, iou_thresholds, area_names, caps) -> dict:
+    """COCO's summary numbers from the [C,A,M,T] arrays: each the ``_mean`` of the entries that are not -1 (NaN when there is
+    none); a key is present only when its threshold, area range (by name) and cap are configured."""
+    area = {name: a for a, name in reversed(list(enumerate(area_names)))}
+
+    def valid(x):
+        return x[x > -1]
+
+    res = {}
+    last = len(caps) - 1
+    if "all" in area:
+        res["AP"] = _mean(valid(precision[:, area["all"], last, :]))
+        for name, v in (("AP50", 0.5), ("AP75", 0.75)):
+            for t, thr in enumerate(iou_thresholds):
+                if thr == float(np.float32(v)):
+                    res[name] = _mean(valid(precision[:, area["all"], last, t]))
+        for m, cap in enumerate(caps):
+            res[f"AR{cap}"] = _mean(valid(recall[:, area["all"], m, :]))
+    for key, name in (("s", "small"), ("m", "medium"), ("l", "large")):
+        if name in area:
+            res["AP" + key] = _mean(valid(precision[:, area[name], last, :]))
+            res["AR" + key] = _mean(valid(recall[:, area[name], last, :]))
+    return res
 
 
 def _mean(values) -> float:
