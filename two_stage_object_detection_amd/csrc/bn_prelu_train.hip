@@ -8,10 +8,7 @@
 //                                  ? 1 : slope) is made from the saved output y where it is used and written out only on request
 //                                  (g_out), the slope's sum dy * y * [y < 0] rides along with the BatchNorm's two sums
 //
-// The sums are f64 with no float atomics, in an order the shape alone fixes:
-//   in a workgroup   as in bn_train.hip (a thread's rows ascending, then bn_block_sum's tree)
-//   across them      partial b of channel c lies at part[b][.][c]; 16 lanes per channel take contiguous runs of ceil(B / 16)
-//                    partials ascending, lane 0 then merges the 16 runs ascending
+// The sums are f64 with no float atomics, in an order the shape alone fixes (bn_rows.h: in a workgroup, across them), and
 //   the slope        the channels' f64 totals (real channels only) are added in ascending channel order by the first wave of the
 //                    elementwise launch's workgroup (0, 0): 64 lanes take contiguous runs of ceil(C_pad / 64) channels ascending,
 //                    lane 0 then merges the 64 runs ascending
@@ -115,39 +112,6 @@ bn_prelu_grad_partial_kernel(const float *__restrict__ y, int y_ld, int y_off, c
     }
 }
 
-// total [3][C_pad] doubles (what the elementwise pass reads) and the f32 dgamma / dbeta [C_pad]; pad channels: exact zeros
-__global__ void __launch_bounds__(kBnThreads)
-bn_prelu_grad_finish_kernel(const double *__restrict__ part, long B, int C_real, int C_pad, double *__restrict__ total,
-                            float *__restrict__ dgamma, float *__restrict__ dbeta) {
-    __shared__ double lds[3 * kBnThreads];
-    const int tid = threadIdx.x;
-    const int cl = tid % kBnFinishChannels, run = tid / kBnFinishChannels;
-    const int c = blockIdx.x * kBnFinishChannels + cl;
-    const long per = (B + kBnFinishRuns - 1) / kBnFinishRuns;
-    const long b0 = run * per, b1 = b0 + per < B ? b0 + per : B;
-    double sx = 0., sg = 0., ss = 0.;
-    if (c < C_real) {
-        for (long b = b0; b < b1; ++b) {
-            sx += part[(3 * b) * C_pad + c];
-            sg += part[(3 * b + 1) * C_pad + c];
-            ss += part[(3 * b + 2) * C_pad + c];
-        }
-    }
-    lds[tid] = sx; lds[kBnThreads + tid] = sg; lds[2 * kBnThreads + tid] = ss;
-    __syncthreads();
-    if (run != 0 || c >= C_pad) return;
-    for (int r = 1; r < kBnFinishRuns; ++r) {
-        sx += lds[r * kBnFinishChannels + cl];
-        sg += lds[kBnThreads + r * kBnFinishChannels + cl];
-        ss += lds[2 * kBnThreads + r * kBnFinishChannels + cl];
-    }
-    total[c] = sx;
-    total[C_pad + c] = sg;
-    total[2 * C_pad + c] = ss;
-    dgamma[c] = (float)sx;
-    dbeta[c] = (float)sg;
-}
-
 template <bool kGOut>
 __global__ void __launch_bounds__(kBnThreads)
 bn_prelu_grad_dz_kernel(const float *__restrict__ y, int y_ld, int y_off, const float *__restrict__ dy, int dy_ld, int dy_off,
@@ -175,16 +139,7 @@ bn_prelu_grad_dz_kernel(const float *__restrict__ y, int y_ld, int y_off, const 
     const bn_lane t = bn_lane_of(M, C4, qx);
     if (!t.live) return;
     const int c = 4 * t.q;
-    double mu[4], iv[4], k[4], a[4], b[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const bool real = c + e < C_real;
-        mu[e] = (double)mean[c + e];
-        iv[e] = (double)invstd[c + e];
-        k[e] = real ? (double)gamma[c + e] * iv[e] : 0.;
-        b[e] = total[c + e] / (double)M;
-        a[e] = total[C_pad + c + e] / (double)M;
-    }
+    const bn_dz_quad q = bn_dz_quad_of(mean, invstd, gamma, total, M, C_real, C_pad, c);
     const float *yc = y + y_off + c, *dc = dy + dy_off + c, *zc = z + z_off + c;
     float *oc = dz + dz_off + c;
     float *gc = kGOut ? g_out + g_off + c : nullptr;
@@ -199,8 +154,7 @@ bn_prelu_grad_dz_kernel(const float *__restrict__ y, int y_ld, int y_off, const 
         for (int e = 0; e < 4; ++e) {
             const bool real = c + e < C_real;
             const float g = yq[e] > 0.f ? dq[e] : slope * dq[e];
-            const double xh = ((double)zq[e] - mu[e]) * iv[e];
-            o[e] = real ? (float)(k[e] * ((double)g - a[e] - xh * b[e])) : 0.f;
+            o[e] = real ? bn_dz_of(q, e, g, zq[e]) : 0.f;
             gq[e] = real ? g : 0.f;
         }
         *reinterpret_cast<float4 *>(oc + m * dz_ld) = make_float4(o[0], o[1], o[2], o[3]);
@@ -269,7 +223,7 @@ extern "C" int tsod_bn_prelu_train_grad_f32(const float *y, int32_t y_ld, int32_
     const dim3 grid = bn_grid(M, C_pad / 4);
     hipLaunchKernelGGL(bn_prelu_grad_partial_kernel, grid, dim3(kBnThreads), 0, st, y, y_ld, y_off, dy, dy_ld, dy_off, z, z_ld, z_off,
                        (long)M, C_pad / 4, mean, invstd, slope, part);
-    hipLaunchKernelGGL(bn_prelu_grad_finish_kernel, dim3((unsigned)tsod_cdiv(C_pad, kBnFinishChannels)), dim3(kBnThreads), 0, st,
+    hipLaunchKernelGGL(bn_sum_finish_kernel<3>, dim3((unsigned)tsod_cdiv(C_pad, kBnFinishChannels)), dim3(kBnThreads), 0, st,
                        (const double *)part, B, C_real, C_pad, total, dgamma, dbeta);
     auto dz_kernel = g_out != nullptr ? &bn_prelu_grad_dz_kernel<true> : &bn_prelu_grad_dz_kernel<false>;
     hipLaunchKernelGGL(dz_kernel, grid, dim3(kBnThreads), 0, st, y, y_ld, y_off, dy, dy_ld, dy_off, z, z_ld, z_off, (long)M, C_pad / 4,

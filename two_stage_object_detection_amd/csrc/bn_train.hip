@@ -9,13 +9,10 @@
 // All memory-bound: a workgroup owns kBnRows rows x (up to) 256 channels, a thread one channel quad (16-byte loads) and every
 // RY-th row of the workgroup's rows.  The sums are kept in f64 (what that costs beside a copy of the same bytes is measured in
 // DESIGN.md section 4.20, "Cost"): the statistics are then the correctly rounded f32 of the exact ones, which is what torch's CPU kernels give
-// (their accumulation type for float is double); grad_reduce.h's f32 helpers are therefore not used here, its rule is:
-// no float atomics, and every order below depends on the shape only, so results are bit-identical from run to run:
-//   in a workgroup   a thread adds its rows ascending, then a binary tree over the row lanes (t += 128, 64, ... QX)
+// (their accumulation type for float is double); grad_reduce.h's f32 helpers are therefore not used here, its rule is: no float
+// atomics, and every order depends on the shape only (bn_rows.h: in a workgroup, across them).  On top of that:
 //   variance         never E[x^2] - E[x]^2: a workgroup takes its own mean first and then the centred squares about it (its rows
 //                    come from L2 the second time), the workgroups' (n, mean, M2) are merged by Chan's rule
-//   across them      partial b of channel c lies at part[b][.][c]; 16 lanes per channel take contiguous runs of ceil(B / 16)
-//                    partials ascending, lane 0 then merges the 16 runs ascending
 #include "bn_rows.h"
 
 namespace {
@@ -183,36 +180,6 @@ bn_grad_partial_kernel(const float *__restrict__ g, int g_ld, int g_off, const f
     }
 }
 
-// total [2][C_pad] doubles (what the elementwise pass reads) and the f32 dgamma / dbeta [C_pad]; pad channels: exact zeros
-__global__ void __launch_bounds__(kBnThreads)
-bn_grad_finish_kernel(const double *__restrict__ part, long B, int C_real, int C_pad, double *__restrict__ total,
-                      float *__restrict__ dgamma, float *__restrict__ dbeta) {
-    __shared__ double lds[2 * kBnThreads];
-    const int tid = threadIdx.x;
-    const int cl = tid % kBnFinishChannels, run = tid / kBnFinishChannels;
-    const int c = blockIdx.x * kBnFinishChannels + cl;
-    const long per = (B + kBnFinishRuns - 1) / kBnFinishRuns;
-    const long b0 = run * per, b1 = b0 + per < B ? b0 + per : B;
-    double sx = 0., sg = 0.;
-    if (c < C_real) {
-        for (long b = b0; b < b1; ++b) {
-            sx += part[(2 * b) * C_pad + c];
-            sg += part[(2 * b + 1) * C_pad + c];
-        }
-    }
-    lds[tid] = sx; lds[kBnThreads + tid] = sg;
-    __syncthreads();
-    if (run != 0 || c >= C_pad) return;
-    for (int r = 1; r < kBnFinishRuns; ++r) {
-        sx += lds[r * kBnFinishChannels + cl];
-        sg += lds[kBnThreads + r * kBnFinishChannels + cl];
-    }
-    total[c] = sx;
-    total[C_pad + c] = sg;
-    dgamma[c] = (float)sx;
-    dbeta[c] = (float)sg;
-}
-
 __global__ void __launch_bounds__(kBnThreads)
 bn_grad_dz_kernel(const float *__restrict__ g, int g_ld, int g_off, const float *__restrict__ z, int z_ld, int z_off, long M, int C4,
                   int C_real, const float *__restrict__ mean, const float *__restrict__ invstd, const float *__restrict__ gamma,
@@ -221,17 +188,7 @@ bn_grad_dz_kernel(const float *__restrict__ g, int g_ld, int g_off, const float 
     const bn_lane t = bn_lane_of(M, C4, qx);
     if (!t.live) return;
     const int c = 4 * t.q;
-    const int C_pad = 4 * C4;
-    double mu[4], iv[4], k[4], a[4], b[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const bool real = c + e < C_real;
-        mu[e] = (double)mean[c + e];
-        iv[e] = (double)invstd[c + e];
-        k[e] = real ? (double)gamma[c + e] * iv[e] : 0.;
-        b[e] = total[c + e] / (double)M;
-        a[e] = total[C_pad + c + e] / (double)M;
-    }
+    const bn_dz_quad q = bn_dz_quad_of(mean, invstd, gamma, total, M, C_real, 4 * C4, c);
     const float *gc = g + g_off + c, *zc = z + z_off + c;
     float *dc = dz + dz_off + c;
 #pragma unroll 4
@@ -241,10 +198,7 @@ bn_grad_dz_kernel(const float *__restrict__ g, int g_ld, int g_off, const float 
         const float gq[4] = {gv.x, gv.y, gv.z, gv.w}, zq[4] = {zv.x, zv.y, zv.z, zv.w};
         float o[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double xh = ((double)zq[e] - mu[e]) * iv[e];
-            o[e] = c + e < C_real ? (float)(k[e] * ((double)gq[e] - a[e] - xh * b[e])) : 0.f;
-        }
+        for (int e = 0; e < 4; ++e) o[e] = c + e < C_real ? bn_dz_of(q, e, gq[e], zq[e]) : 0.f;
         *reinterpret_cast<float4 *>(dc + m * dz_ld) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
@@ -311,7 +265,7 @@ extern "C" int tsod_bn_train_grad_f32(const float *g, int32_t g_ld, int32_t g_of
     const dim3 grid = bn_grid(M, C_pad / 4);
     hipLaunchKernelGGL(bn_grad_partial_kernel, grid, dim3(kBnThreads), 0, st, g, g_ld, g_off, z, z_ld, z_off, (long)M, C_pad / 4, mean,
                        invstd, part);
-    hipLaunchKernelGGL(bn_grad_finish_kernel, dim3((unsigned)tsod_cdiv(C_pad, kBnFinishChannels)), dim3(kBnThreads), 0, st,
+    hipLaunchKernelGGL(bn_sum_finish_kernel<2>, dim3((unsigned)tsod_cdiv(C_pad, kBnFinishChannels)), dim3(kBnThreads), 0, st,
                        (const double *)part, B, C_real, C_pad, total, dgamma, dbeta);
     hipLaunchKernelGGL(bn_grad_dz_kernel, grid, dim3(kBnThreads), 0, st, g, g_ld, g_off, z, z_ld, z_off, (long)M, C_pad / 4, C_real,
                        mean, invstd, gamma, (const double *)total, dz, dz_ld, dz_off);

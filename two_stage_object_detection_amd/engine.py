@@ -57,6 +57,44 @@ class PackedConv:
         return ((H + 2 * self.pad - self.kh) // self.stride + 1, (W + 2 * self.pad - self.kw_logical) // self.stride + 1)
 
 
+class _IdentityEpilogue:
+    """A conv pack seen with scale 1, shift 0 and no activation - what runs in front of a batch-statistics BatchNorm (DESIGN.md
+    section 4.20).  Everything else (the weight and its bf16x3 / fp16x2 images, made on first use) is read from and written to the
+    pack itself, so the refresh after an optimizer step reaches both."""
+
+    def __init__(self, pack, device):
+        self.__dict__.update(pack=pack, scale=torch.ones(pack.cout, dtype=torch.float32, device=device),
+                             shift=torch.zeros(pack.cout, dtype=torch.float32, device=device), act=ACT_NONE)
+
+    def __getattr__(self, k):
+        return getattr(self.__dict__["pack"], k)
+
+    def __setattr__(self, k, v):
+        setattr(self.__dict__["pack"], k, v)
+
+
+# -- what the backbones' autograd nodes share of a BatchNorm (models/hardnet_grads.py, models/resnet_grads.py)
+def bn_fold_stats(bn, C_pad, device):
+    """(running mean, 1 / sqrt(running var + eps)) of an eval-mode BatchNorm, padded to ``C_pad`` with zeros: what turns
+    (dscale, dshift) into the gradients of ``weight`` / ``bias`` (scale = weight * inv, shift = bias - mean * scale)."""
+    inv = 1.0 / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    pad = (0, C_pad - bn.num_features)
+    return tuple(torch.nn.functional.pad(v.float().cpu(), pad).to(device) for v in (bn.running_mean.detach(), inv))
+
+
+def bn_fold_grads(dscale, dshift, stats, C):
+    """d weight = (dscale - mean * dshift) * inv, d bias = dshift (DESIGN.md section 4.17's folding rule), on [C] vectors."""
+    mean, inv = stats
+    return (dscale[:C] - mean[:C] * dshift[:C]) * inv[:C], dshift[:C]
+
+
+def bnt_copy(bnt):
+    """the node's own copy of what a batch-statistics BatchNorm's backward reads (None where the BatchNorm is folded)"""
+    if bnt is None:
+        return None
+    return dict(C=bnt["C"], **{k: bnt[k].detach().clone() for k in ("z", "mean", "invstd", "gamma")})
+
+
 class FusedShortcutConv:
     """The last 1x1 conv of a residual block and its projection shortcut as ONE stacked-K GEMM (tsod_conv2d_dual_f32):
         out = act( [y | x(strided)] . [W3 * s3 | Wd * sd]^T + (b3 + bd) )
@@ -277,6 +315,11 @@ class Plan:
         self._bound_input = None
         self.keep: list = []                 # keeps descriptors / tensors alive
         self.workspace: torch.Tensor | None = None
+        # the batch-statistics variant of a backbone's plan (DESIGN.md sections 4.20 and 4.24; ``bn_stats``)
+        self.batch_stats = False             # the builder's flag: the plan's trainable section runs BatchNorm on batch statistics
+        self.bn_steps: list = []             # (launch, where its two workspace arguments are, M, C_pad) per statistics launch
+        self.bn_bound: list = []             # (module, attribute, pointer) of every tensor of a BatchNorm module a launch holds
+        self.bn_workspace: torch.Tensor | None = None
         self.graph = None
         # fp16x2 layers OR 1 into this word when a launch ends with non-finite accumulators (include/tsod.h: range_flag);
         # a PlanOwner hands its plans one word per (device, in-flight slot) out of a tensor of its own (PlanOwner._new_plan): the
@@ -355,6 +398,26 @@ class Plan:
         self.steps.append([fn, list(args)])
         self.keep.extend(keep)
         return self.steps[-1]
+
+    BN_OWN = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
+
+    def bn_stats(self, bn, z, C_real, where):
+        """tsod_bn_stats_f32 of the raw conv output z [N,h,w,C_pad] on the module's own gamma / beta / running buffers (DESIGN.md
+        sections 4.20 and 4.24) -> (what the node keeps of this BatchNorm, scale, shift); scale and shift are the [2, C_pad] value
+        + remainder pairs.  ``where`` names the BatchNorm in the refusal; the launch's workspace is bound by ``finalize``."""
+        own = [getattr(bn, k) for k in self.BN_OWN]
+        if any(t.device != z.device for t in own):
+            raise TsodError("batch_stats: the module's BatchNorm parameters and buffers must live on the forward's device")
+        cp = z.shape[3]
+        M = z.numel() // cp
+        if M < 2:
+            raise ValueError(f"batch_stats: more than one value per channel is needed in training mode ({where} sees {M} pixel)")
+        mean, invstd, scale, shift = vec = [torch.empty(n * cp, dtype=torch.float32, device=z.device) for n in (1, 1, 2, 2)]
+        args = [ptr(z), M, C_real, cp, cp, 0, ptr(bn.weight), ptr(bn.bias), float(bn.eps), float(bn.momentum), ptr(bn.running_mean),
+                ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(mean), ptr(invstd), ptr(scale), ptr(shift)]
+        self.bn_steps.append((self.call(lib().tsod_bn_stats_f32, *args, None, 0, keep=[z] + vec + own), len(args), M, cp))
+        self.bn_bound.extend((bn, k, ptr(t)) for k, t in zip(self.BN_OWN, own))     # (_forward_train: rebound storage = a new plan)
+        return dict(z=z, mean=mean, invstd=invstd, gamma=bn.weight, C=C_real), scale, shift
 
     # the conv kernel addresses every tensor through 32-bit byte offsets (buffer descriptors): one launch may
     # touch at most this many bytes of any single tensor; larger batches are cut into image groups
@@ -461,7 +524,8 @@ class Plan:
 
     def finalize(self):
         """Size the shared K-slice workspace (stream order makes sharing safe) and bind it.  Its head holds the arrival
-        tickets of the K-sliced tiles, which every launch expects to find zero and leaves zero: zero-filled once here."""
+        tickets of the K-sliced tiles, which every launch expects to find zero and leaves zero: zero-filled once here.  The
+        statistics launches ``bn_stats`` recorded get one workspace of their own, once; a plan without any allocates nothing."""
         need = 256
         for st in self.conv_steps:
             st.ws_bytes = lib().tsod_conv2d_workspace_bytes(byref(st.desc))
@@ -473,6 +537,11 @@ class Plan:
             self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
         for st in self.conv_steps:
             st.args[:] = st.args_on(self.workspace)              # (in place: self.steps launches this very list)
+        if self.bn_steps and self.bn_workspace is None:          # the statistics launches share one workspace of their own
+            need = max(lib().tsod_bn_train_workspace_bytes(M, cp) for _, _, M, cp in self.bn_steps)
+            self.bn_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            for (_, args), at, _, _ in self.bn_steps:
+                args[at:at + 2] = [ptr(self.bn_workspace), need]
         self.graph = None
         return self
 
@@ -1145,6 +1214,30 @@ class PlanOwner:
         if x.dim() != 4 or x.shape[1] != 3:
             raise TsodError(f"expected [N,3,H,W], got {tuple(x.shape)}")
         return self._plan_for_shape(x.shape, x.device, slot)
+
+    def _forward_train(self, x, slot, nchw):
+        """A backbone's forward while a training mode is active -> the feature map carrying its autograd node.  The backbone
+        supplies ``_grads`` (its module with ``refresh_packs`` and ``feature_map_with_grads``), ``_mode_norms()`` (the
+        BatchNorms of the current mode's section) and ``_trainable_named()``."""
+        batch_stats = self._trains_in_plan()
+        if self.training and not batch_stats:
+            raise TsodError("the HIP path implements the inference forward only: call .eval() first")
+        self._grads.refresh_packs(self)
+        plan = self._plan_for(x, slot)
+        if batch_stats and any(getattr(bn, k).data_ptr() != p for bn, k, p in plan.bn_bound):
+            # a parameter or buffer was rebound (load_state_dict(assign=True), ``bn.running_mean = ...``, ``p.data = ...``): the
+            # plan's launches hold the old storage (kept alive, never freed under them) - build the plan again
+            for key in [k for k, v in self._plans.items() if v is plan]:
+                del self._plans[key]
+            plan = self._plan_for(x, slot)
+        stage_input(plan, x)
+        plan.run()
+        self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
+        if batch_stats:                                          # the launches wrote the section's buffers: torch must know
+            for _, bn in self._mode_norms():
+                for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+                    torch.autograd.graph.increment_version(b)
+        return self._grads.feature_map_with_grads(plan, nchw, self._trainable_named())
 
     def forward_nhwc(self, x, slot: int = 0) -> torch.Tensor:
         """[N,3,H,W] (or NHWC4Images) -> NHWC feature map (plan-owned buffer, valid until the next forward)."""

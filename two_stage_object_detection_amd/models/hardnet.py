@@ -25,8 +25,9 @@ import torch.nn as nn
 
 from .. import hip_ops
 from .._ffi import ACT_NONE, ACT_RELU6, TsodError, lib, ptr, require_cuda
-from ..engine import PackedConv, Plan, PlanOwner, fold_bn, stage_input
-from .hardnet_grads import _bn_stats, copy_pack, feature_map_with_grads, refresh_packs, rewrite_raw_conv
+from ..engine import PackedConv, Plan, PlanOwner, _IdentityEpilogue, bn_fold_stats, fold_bn
+from . import hardnet_grads
+from .hardnet_grads import copy_pack, refresh_packs, rewrite_raw_conv
 
 
 def _pad4(c: int) -> int:
@@ -163,22 +164,6 @@ class _RawConv:
         return H, W
 
 
-class _IdentityEpilogue:
-    """A conv pack seen with scale 1, shift 0 and no activation - what runs in front of a batch-statistics BatchNorm (DESIGN.md
-    section 4.20).  Everything else (the weight and its bf16x3 / fp16x2 images, made on first use) is read from and written to the
-    pack itself, so the refresh after an optimizer step reaches both."""
-
-    def __init__(self, pack, device):
-        self.__dict__.update(pack=pack, scale=torch.ones(pack.cout, dtype=torch.float32, device=device),
-                             shift=torch.zeros(pack.cout, dtype=torch.float32, device=device), act=ACT_NONE)
-
-    def __getattr__(self, k):
-        return getattr(self.__dict__["pack"], k)
-
-    def __setattr__(self, k, v):
-        setattr(self.__dict__["pack"], k, v)
-
-
 def _pw_pack(layer, src_real, device):
     """The packed form of a 1x1 ConvLayer that gathers slices of ``src_real`` channels (a HarDBlock layer's ``layer1`` or a
     transition layer): the weight gathered to the padded slices it reads, BN folded, padded to 4 output channels."""
@@ -225,6 +210,7 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     _train_mode = None           # set_train_mode(): a plain instance attribute once set - pickled and deep-copied, never in
                                  # the state_dict
     _batch_stats = False         # set_train_mode(batch_stats=): likewise
+    _grads = hardnet_grads       # (PlanOwner._forward_train: its refresh_packs and feature_map_with_grads)
 
     def __init__(self, depth_wise=True, arch=39):
         super().__init__()
@@ -442,26 +428,8 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         key = ("train_" + mode,) if isinstance(mode, str) else ("train_blocks", mode)
         return key + ("batch_stats",) if self._trains_in_plan() else key
 
-    def _forward_train(self, x, slot, nchw):
-        batch_stats = self._trains_in_plan()
-        if self.training and not batch_stats:
-            raise TsodError("the HIP path implements the inference forward only: call .eval() first")
-        refresh_packs(self)
-        plan = self._plan_for(x, slot)
-        if batch_stats and any(getattr(bn, k).data_ptr() != p for bn, k, p in plan.bn_bound):
-            # a parameter or buffer was rebound (load_state_dict(assign=True), ``bn.running_mean = ...``, ``p.data = ...``): the
-            # plan's launches hold the old storage (kept alive, never freed under them) - build the plan again
-            for key in [k for k, v in self._plans.items() if v is plan]:
-                del self._plans[key]
-            plan = self._plan_for(x, slot)
-        stage_input(plan, x)
-        plan.run()
-        self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
-        if batch_stats:                                          # the launches wrote the section's buffers: torch must know
-            for _, bn in self._section_norms(self._mode_start(self._train_mode)):
-                for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
-                    torch.autograd.graph.increment_version(b)
-        return feature_map_with_grads(plan, nchw, self._trainable_named())
+    def _mode_norms(self):
+        return self._section_norms(self._mode_start(self._train_mode))
 
     def forward_nhwc(self, x, slot: int = 0):
         if self._active_mode() is not None:
@@ -484,39 +452,26 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         plan.tail, plan.block_records, plan.stem_record, pending_down = [], [], None, None
         # the batch-statistics variant (section 4.20): a BatchNorm at base[i], i >= start, runs as conv with identity epilogue ->
         # raw z (kept for the node, outside the pool) -> tsod_bn_stats_f32 -> tsod_bn_apply_f32 into the folded launch's place
-        batch_stats = self._trains_in_plan()
-        bn_steps = []                                            # the statistics launches: they share one workspace
-        plan.bn_bound = []                                       # (module, attribute, pointer) of every tensor of the module a launch holds
+        batch_stats = plan.batch_stats = self._trains_in_plan()
 
         def pack(name, raw=False):
             pc = plan.packed(name, lambda: units[name].make(device))
             return _IdentityEpilogue(pc, device) if raw else pc
 
         def bn_pack(name, bn, cp):
-            return None if batch_stats else plan.packed(name + ".bn", lambda: _bn_stats(bn, cp, device))
+            return None if batch_stats else plan.packed(name + ".bn", lambda: bn_fold_stats(bn, cp, device))
 
         def raw_like(dst_shape, cp):
             return torch.empty(tuple(dst_shape[:3]) + (cp,), dtype=torch.float32, device=device)
 
         def emit_bn(bn, z, C, act, dst, dst_off):
             """batch statistics of z [N,h,w,C_pad] and y = act(BN(z)) into dst's slice -> what the node keeps of it"""
-            own = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
-            if any(getattr(bn, k).device != z.device for k in own):
-                raise TsodError("batch_stats: the module's BatchNorm parameters and buffers must live on the forward's device")
             cp = z.shape[3]
+            bnt, scale, shift = plan.bn_stats(bn, z, C, "a BatchNorm of the trainable section")
             M = z.numel() // cp
-            if M < 2:
-                raise ValueError("batch_stats: more than one value per channel is needed in training mode "
-                                 f"(a BatchNorm of the trainable section sees {M} pixel)")
-            mean, invstd, scale, shift = vec = [torch.empty(n * cp, dtype=torch.float32, device=device) for n in (1, 1, 2, 2)]
-            bn_steps.append(plan.call(L.tsod_bn_stats_f32, ptr(z), M, C, cp, cp, 0, ptr(bn.weight), ptr(bn.bias), float(bn.eps),
-                                      float(bn.momentum), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                                      ptr(mean), ptr(invstd), ptr(scale), ptr(shift), None, 0,
-                                      keep=[z] + vec + [getattr(bn, k) for k in own]))
-            plan.bn_bound.extend((bn, k, ptr(getattr(bn, k))) for k in own)     # (_forward_train: rebound storage = a new plan)
             plan.call(L.tsod_bn_apply_f32, ptr(z), M, C, cp, cp, 0, ptr(scale), ptr(shift), act, ptr(dst), dst.shape[3], dst_off,
                       plan.amax_ptr(dst) or None, keep=(dst,))
-            return dict(z=z, mean=mean, invstd=invstd, gamma=bn.weight, C=C)
+            return bnt
 
         def conv_bn(name, layer, rc, x, dst, dst_off, C, train, **kw):
             """a ConvLayer's launch(es): folded, or (train) conv -> z, batch statistics, apply; -> the node's ``bnt`` or None"""
@@ -675,11 +630,6 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         plan.tail_inputs = [r["x"] for r in plan.tail]           # (tensor, channel offset) of the three tail layers
         plan.output_nhwc = cur
         plan.output_amax = plan.amax_ptr(cur)
-        if bn_steps:
-            need = max(L.tsod_bn_train_workspace_bytes(st[1][1], st[1][3]) for st in bn_steps)
-            plan.bn_workspace = torch.empty(need, dtype=torch.uint8, device=device)
-            for st in bn_steps:
-                st[1][17:19] = [ptr(plan.bn_workspace), need]
         return plan.finalize()
 
     def forward(self, x):

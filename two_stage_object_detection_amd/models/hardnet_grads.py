@@ -17,31 +17,11 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _ffi, hip_ops
-
-
-def _bn_stats(bn, C_pad, device):
-    """(running mean, 1 / sqrt(running var + eps)) of an eval-mode BatchNorm, padded to ``C_pad`` with zeros: what turns
-    (dscale, dshift) into the gradients of ``weight`` / ``bias`` (scale = weight * inv, shift = bias - mean * scale)."""
-    inv = 1.0 / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    pad = (0, C_pad - bn.num_features)
-    return tuple(torch.nn.functional.pad(v.float().cpu(), pad).to(device) for v in (bn.running_mean.detach(), inv))
-
-
-def _bn_grads(dscale, dshift, stats, C):
-    """d weight = (dscale - mean * dshift) * inv, d bias = dshift (DESIGN.md section 4.17's folding rule), on [C] vectors."""
-    mean, inv = stats
-    return (dscale[:C] - mean[:C] * dshift[:C]) * inv[:C], dshift[:C]
+from ..engine import bn_fold_grads, bnt_copy
 
 
 def _conv33_weight(d, C):                                     # [3][3][C_pad] -> torch's [C,1,3,3]
     return d[:, :, :C].reshape(9, C).t().reshape(C, 1, 3, 3)
-
-
-def bnt_copy(bnt):
-    """the node's own copy of what a batch-statistics BatchNorm's backward reads (None where the BatchNorm is folded)"""
-    if bnt is None:
-        return None
-    return dict(C=bnt["C"], **{k: bnt[k].detach().clone() for k in ("z", "mean", "invstd", "gamma")})
 
 
 def pw_copy(rec):
@@ -104,7 +84,7 @@ class _BackboneGrads(torch.autograd.Function):
             if want:
                 out[prefix + ".dwconv.weight"] = _conv33_weight(d_w, rec["C"])
                 if bnt is None:
-                    out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = _bn_grads(d_sc, d_sh, rec["dw_bn"], rec["C"])
+                    out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = bn_fold_grads(d_sc, d_sh, rec["dw_bn"], rec["C"])
             return g
 
         def pw_layer(prefix, buf, lay, g, dbuf, want_seg):
@@ -119,7 +99,7 @@ class _BackboneGrads(torch.autograd.Function):
                 out[prefix + ".conv.weight"] = d_w.view(d_w.shape[0], d_w.shape[1], 1, 1)
             if want_g or want_b:
                 zero = d_sh if d_sc is None else d_sc
-                out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = _bn_grads(zero, d_sh, lay["bn"], lay["cout"])
+                out[prefix + ".norm.weight"], out[prefix + ".norm.bias"] = bn_fold_grads(zero, d_sh, lay["bn"], lay["cout"])
 
         # ---- the tail (section 4.17); with trainable blocks the last transition's mask is fused into its first layer's dx gather
         blocks, stem = sv["blocks"], sv.get("stem")
@@ -177,8 +157,8 @@ class _BackboneGrads(torch.autograd.Function):
                 d_w, d_sc, d_sh = hip_ops.conv3x3_bn_relu6_grad(stem["x4"], stem["w0"], stem["scale0"], stem["y0"], d0, stride=2,
                                                                 want_dw=want_w, want_dscale=want_g, want_dshift=True)
                 out["base.0.conv.weight"] = d_w
-                out["base.0.norm.weight"], out["base.0.norm.bias"] = _bn_grads(d_sh if d_sc is None else d_sc, d_sh,
-                                                                               stem["bn0"], c0)
+                out["base.0.norm.weight"], out["base.0.norm.bias"] = bn_fold_grads(d_sh if d_sc is None else d_sc, d_sh,
+                                                                                   stem["bn0"], c0)
         return (None,) + tuple(out.get(k) if n else None for k, n in need.items())
 
 
@@ -217,7 +197,7 @@ def rewrite_raw_conv(owner, old, new):
             e = hip_ops.fp16x2_weight_scale_exp(old.w)
             for plan in owner._plans.values():
                 for st in plan.conv_steps:
-                    # (a batch-statistics plan holds the pack behind hardnet._IdentityEpilogue)
+                    # (a batch-statistics plan holds the pack behind engine._IdentityEpilogue)
                     if getattr(st.pc, "pack", st.pc) is old and int(st.desc.precision) == _ffi.PREC_FP16X2:
                         st.desc.w_scale_exp = int(e)
                         plan.graph = None

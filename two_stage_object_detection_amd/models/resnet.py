@@ -18,32 +18,18 @@ import torch.nn as nn
 
 from .. import hip_ops
 from .._ffi import ACT_NONE, ACT_PRELU, TsodError, lib, ptr, require_cuda, stem_out_hw
-from ..engine import (FusedBottleneckWeights, FusedShortcutConv, FusedStemWeights, PackedConv, Plan, PlanOwner, prelu_slope,
-                      stage_input)
+from ..engine import (FusedBottleneckWeights, FusedShortcutConv, FusedStemWeights, PackedConv, Plan, PlanOwner, _IdentityEpilogue,
+                      prelu_slope)
 from . import resnet_grads
-from .hardnet import _IdentityEpilogue
-
-_BN_OWN = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
 
 
 def _bn_stats_step(plan: Plan, bn, name: str, z: torch.Tensor):
-    """tsod_bn_stats_f32 of the raw conv output z [N,h,w,C] on the module's own gamma / beta / running buffers (DESIGN.md section
-    4.24) -> (what the node keeps of this BatchNorm, scale, shift); scale and shift are the [2, C] value + remainder pairs."""
-    if any(getattr(bn, k).device != z.device for k in _BN_OWN):
-        raise TsodError("batch_stats: the module's BatchNorm parameters and buffers must live on the forward's device")
+    """``plan.bn_stats`` of the raw conv output z [N,h,w,C] for the BatchNorm ``name``."""
     C = z.shape[3]
-    M = z.numel() // C
-    if M < 2:
-        raise ValueError(f"batch_stats: more than one value per channel is needed in training mode ({name} sees {M} pixel)")
+    out = plan.bn_stats(bn, z, C, name)
     if C != bn.num_features or C % 4:
         raise TsodError(f"batch_stats: {name} has {bn.num_features} channels, its conv output {C}; a multiple of 4 is needed")
-    mean, invstd, scale, shift = vec = [torch.empty(n * C, dtype=torch.float32, device=z.device) for n in (1, 1, 2, 2)]
-    plan.bn_steps.append(plan.call(lib().tsod_bn_stats_f32, ptr(z), M, C, C, C, 0, ptr(bn.weight), ptr(bn.bias), float(bn.eps),
-                                   float(bn.momentum), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                                   ptr(mean), ptr(invstd), ptr(scale), ptr(shift), None, 0,
-                                   keep=[z] + vec + [getattr(bn, k) for k in _BN_OWN]))
-    plan.bn_bound.extend((bn, k, ptr(getattr(bn, k))) for k in _BN_OWN)   # (_forward_train: rebound storage = a new plan)
-    return dict(z=z, mean=mean, invstd=invstd, gamma=bn.weight, C=C), scale, shift
+    return out
 
 
 def _bn_apply_prelu_step(plan: Plan, z, scale, shift, slope, dst, residual=None, second=None):
@@ -167,7 +153,7 @@ class _ResidualBlock(nn.Module):
             pcs.append(pc)
             bnts.append(bnt)
             cur = out
-        plan.block_records.append(resnet_grads.block_record_batch_stats(plan, self, name, x, ys, pcs, bnts, pcd, bnt_d))
+        plan.block_records.append(resnet_grads.block_record(plan, self, name, x, ys, pcs, bnts, pcd, bnt_d))
         return cur
 
     def _emit_grouped(self, plan: Plan, conv, bn, cur, x, slope, name):
@@ -230,6 +216,7 @@ class ResNet(PlanOwner, nn.Module):
     _train_mode = None           # set_train_mode(): a plain instance attribute once set - pickled and deep-copied, never in
                                  # the state_dict
     _batch_stats = False         # set_train_mode(batch_stats=): likewise
+    _grads = resnet_grads        # (PlanOwner._forward_train: its refresh_packs and feature_map_with_grads)
 
     def __init__(self, block, blocks_num, num_classes=25, include_top=True, groups=1, width_per_group=64):
         super().__init__()
@@ -335,7 +322,8 @@ class ResNet(PlanOwner, nn.Module):
         ``f.grad_fn.saved`` is the dict the backward reads: ``names`` (the parameter names in ``trainable_parameters()`` order),
         ``nchw``, and ``blocks``: per trained block in forward order ``name``, ``x``, ``y1``, ``y2``, ``y3`` (NHWC copies), ``w`` / ``scale``
         (the three f32 packs [Cout,KH,KW,Cin] and folded scales), ``rot`` (the 3x3 dgrad's image [C,3,3,Cout]), ``slope``, ``bn``
-        (per stage: running mean, 1 / sqrt(var + eps)).
+        (per stage: running mean, 1 / sqrt(var + eps)).  One record (``resnet_grads.block_record``), one copy (``block_copy``) and
+        one backward walk serve this layout and ``batch_stats``' below; the variant alone decides which keys an entry carries.
 
         ``mode`` a stage name of ``trainable_stages`` ("layer4", "layer3", "layer2"; ValueError for
         anything else): every block from the first block of that stage to the end of ``layer4`` under the same contract, on the
@@ -473,26 +461,8 @@ class ResNet(PlanOwner, nn.Module):
         key = ("train_from" if isinstance(mode, str) else "train_blocks", mode)
         return key + ("batch_stats",) if self._trains_in_plan() else key
 
-    def _forward_train(self, x, slot, nchw):
-        batch_stats = self._trains_in_plan()
-        if self.training and not batch_stats:
-            raise TsodError("the HIP path implements the inference forward only: call .eval() first")
-        resnet_grads.refresh_packs(self)
-        plan = self._plan_for(x, slot)
-        if batch_stats and any(getattr(bn, k).data_ptr() != p for bn, k, p in plan.bn_bound):
-            # a parameter or buffer was rebound (load_state_dict(assign=True), ``bn.running_mean = ...``, ``p.data = ...``): the
-            # plan's launches hold the old storage (kept alive, never freed under them) - build the plan again
-            for key in [k for k, v in self._plans.items() if v is plan]:
-                del self._plans[key]
-            plan = self._plan_for(x, slot)
-        stage_input(plan, x)
-        plan.run()
-        self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
-        if batch_stats:                                          # the launches wrote the section's buffers: torch must know
-            for _, bn in self._section_norms(self._train_mode):
-                for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
-                    torch.autograd.graph.increment_version(b)
-        return resnet_grads.feature_map_with_grads(plan, nchw, self._trainable_named())
+    def _mode_norms(self):
+        return self._section_norms(self._train_mode)
 
     def forward_nhwc(self, x, slot: int = 0):
         if self._active_mode() is not None:
@@ -514,8 +484,7 @@ class ResNet(PlanOwner, nn.Module):
         mode = self._active_mode()
         plan.stem_record = None
         # the batch-statistics variant (section 4.24): the statistics launches share one workspace
-        batch_stats = self._trains_in_plan()
-        plan.bn_steps, plan.bn_bound = [], []
+        batch_stats = plan.batch_stats = self._trains_in_plan()
         if mode != _STEM and self.fuse_stem and tuple(self.conv1.weight.shape) == (64, 3, 7, 7):
             # conv1 + bn1 + PReLU + max pool as ONE launch that reads the images where stage_input finds them (NCHW or NHWC4):
             # no layout pass, the 64-channel conv output never leaves the CU (tsod_stem_fp16x2)
@@ -556,11 +525,6 @@ class ResNet(PlanOwner, nn.Module):
                 cur = nxt
         plan.output_nhwc = cur
         plan.output_amax = plan.amax_ptr(cur)
-        if plan.bn_steps:
-            need = max(lib().tsod_bn_train_workspace_bytes(st[1][1], st[1][3]) for st in plan.bn_steps)
-            plan.bn_workspace = torch.empty(need, dtype=torch.uint8, device=device)
-            for st in plan.bn_steps:
-                st[1][17:19] = [ptr(plan.bn_workspace), need]
         return plan.finalize()
 
     def forward(self, x):
