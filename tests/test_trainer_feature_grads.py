@@ -19,7 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_trainer_grads import (A, N_CLASS, PARAMS, anchors, chain_losses, close, fixture_inputs, image,  # noqa: E402
                                 reference_state_dict, t, trunk, z, zg)  # noqa: F401  (fixtures)
 
-FLT_MAX = float(np.finfo(np.float32).max)
+from feature_grads_restated import (FLT_MAX, _f32, _roundf, align_avg_grad_f64, pool_argmax, pool_avg_by_gather,  # noqa: E402,F401
+                                    pool_avg_grad_f64, pool_bins, pool_bar, pool_grad_ref, roi_to_map)
 
 
 @pytest.fixture(scope="module")
@@ -46,126 +47,6 @@ def match_fixture(g, zf, variant, frac, what="", detached=False):
 
 
 # ------------------------------------------------------------------------------------------------------ the restatement
-def _f32(v):
-    return np.float32(v)
-
-
-def _roundf(v):
-    v = float(np.float32(v))
-    return int(np.floor(abs(v) + 0.5)) * (1 if v >= 0 else -1)
-
-
-def roi_to_map(r, img_h, img_w, Hf, Wf):
-    """nets/classify.py:35-36 in f32: (x1, y1, x2, y2) image -> map coordinates."""
-    x1, y1, x2, y2 = (np.float32(v) for v in r)
-    return (_f32(x1 / _f32(img_w)) * _f32(Wf), _f32(y1 / _f32(img_h)) * _f32(Hf), _f32(x2 / _f32(img_w)) * _f32(Wf),
-            _f32(y2 / _f32(img_h)) * _f32(Hf))
-
-
-def pool_bins(fm, Hf, Wf, PH=7, PW=7, scale=1.0):
-    """torchvision RoIPool's bins of one map-coordinate RoI: [(ph, pw, hs, he, ws, we)]."""
-    s = _f32(scale)
-    sw, sh, ew, eh = (_roundf(_f32(v) * s) for v in fm)
-    rw, rh = max(ew - sw + 1, 1), max(eh - sh + 1, 1)
-    bh, bw = _f32(rh) / _f32(PH), _f32(rw) / _f32(PW)
-    out = []
-    for ph in range(PH):
-        hs = min(max(int(np.floor(_f32(ph) * bh)) + sh, 0), Hf)
-        he = min(max(int(np.ceil(_f32(ph + 1) * bh)) + sh, 0), Hf)
-        for pw in range(PW):
-            ws = min(max(int(np.floor(_f32(pw) * bw)) + sw, 0), Wf)
-            we = min(max(int(np.ceil(_f32(pw + 1) * bw)) + sw, 0), Wf)
-            out.append((ph, pw, hs, he, ws, we))
-    return out
-
-
-def pool_argmax(feat, rois, roi_indices, img_h, img_w, PH=7, PW=7):
-    """feat [B,C,Hf,Wf] f32, rois [B,R,4] image coords -> [(k, b, idx [PH*PW, C] long map index or -1)] by torchvision's rule
-    (first maximum, h outer, w inner, above -FLT_MAX only; -1 for empty bins)."""
-    B, C, Hf, Wf = feat.shape
-    R = rois.shape[1]
-    out = []
-    for k, r in enumerate(rois.reshape(-1, 4).tolist()):
-        b = int(roi_indices[k // R])
-        idx = torch.full((PH * PW, C), -1, dtype=torch.long)
-        for ph, pw, hs, he, ws, we in pool_bins(roi_to_map(r, img_h, img_w, Hf, Wf), Hf, Wf, PH, PW):
-            if he <= hs or we <= ws:
-                continue
-            win = feat[b, :, hs:he, ws:we].reshape(C, -1)
-            j = torch.argmax(win, dim=1)
-            ok = win.gather(1, j[:, None])[:, 0] > -FLT_MAX
-            idx[ph * PW + pw] = torch.where(ok, (hs + j // (we - ws)) * Wf + ws + j % (we - ws), -1)
-        out.append((k, b, idx))
-    return out
-
-
-def pool_avg_by_gather(X, argmax):
-    """Differentiable RoIPool + mean: X [B,C,Hf,Wf] (any dtype) -> [K, C] gathering X at the f32 arg-max."""
-    B, C = X.shape[:2]
-    flat = X.reshape(B, C, -1)
-    rows = []
-    for k, b, idx in argmax:
-        ok = idx >= 0
-        v = flat[b].gather(1, idx.clamp(min=0).T).T * ok                   # [bins, C]
-        rows.append(v.sum(0) / idx.shape[0])
-    return torch.stack(rows)
-
-
-def pool_avg_grad_f64(feat, rois, roi_indices, img_h, img_w, d_out, PH=7, PW=7):
-    """float64 d feat [B,C,Hf,Wf] of the fused RoIPool + mean (autograd through pool_avg_by_gather)."""
-    X = feat.double().clone().requires_grad_(True)
-    y = pool_avg_by_gather(X, pool_argmax(feat, rois, roi_indices, img_h, img_w, PH, PW))
-    (y * d_out.double()).sum().backward()
-    return X.grad
-
-
-def align_avg_grad_f64(shape, rois, roi_indices, img_h, img_w, d_out, PH=7, PW=7, sampling_ratio=2, aligned=False):
-    """float64 d feat [B,C,Hf,Wf] of the fused RoIAlign + mean: torchvision's roi_align backward (positions, skips, clamps in
-    f32 as the kernels compute them; the weights and sums in float64)."""
-    B, C, Hf, Wf = shape
-    R = rois.shape[1]
-    d = torch.zeros((B, C, Hf, Wf), dtype=torch.float64)
-    dout = d_out.double()
-    for k, r in enumerate(rois.reshape(-1, 4).tolist()):
-        b = int(roi_indices[k // R])
-        x1, y1, x2, y2 = roi_to_map(r, img_h, img_w, Hf, Wf)
-        off = _f32(0.5 if aligned else 0.0)
-        sw_, sh_ = x1 - off, y1 - off
-        rw, rh = (x2 - off) - sw_, (y2 - off) - sh_
-        if not aligned:
-            rw, rh = max(rw, _f32(1)), max(rh, _f32(1))
-        bh, bw = rh / _f32(PH), rw / _f32(PW)
-        gh = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rh / _f32(PH)))
-        gw = sampling_ratio if sampling_ratio > 0 else int(np.ceil(rw / _f32(PW)))
-        count = max(gh * gw, 1)
-        g = dout[k] / (PH * PW) / count
-        for ph in range(PH):
-            for pw in range(PW):
-                for iy in range(gh):
-                    y = sh_ + _f32(ph) * bh + (_f32(iy) + _f32(.5)) * bh / _f32(gh)
-                    for ix in range(gw):
-                        x = sw_ + _f32(pw) * bw + (_f32(ix) + _f32(.5)) * bw / _f32(gw)
-                        if y < -1 or y > Hf or x < -1 or x > Wf:
-                            continue
-                        yy, xx = max(y, _f32(0)), max(x, _f32(0))
-                        yl, xl = int(yy), int(xx)
-                        if yl >= Hf - 1:
-                            yh = yl = Hf - 1
-                            yy = _f32(yl)
-                        else:
-                            yh = yl + 1
-                        if xl >= Wf - 1:
-                            xh = xl = Wf - 1
-                            xx = _f32(xl)
-                        else:
-                            xh = xl + 1
-                        ly, lx = float(yy) - yl, float(xx) - xl
-                        hy, hx = 1 - ly, 1 - lx
-                        for (cy, cx, w) in ((yl, xl, hy * hx), (yl, xh, hy * lx), (yh, xl, ly * hx), (yh, xh, ly * lx)):
-                            d[b, :, cy, cx] += w * g
-    return d
-
-
 def restated_feature_grad(X, W, rois, img_hw, gt_rpn_loc, gt_rpn_label, gt_roi_label, anchor, roi_anchor, sample_src,
                           sample_gt, bbox, img_size, weights=(0, 0, 0, 0, 1), detach_rois=False):
     """float64 d (sum_k weights[k] loss_k) / d X for one image: X [1,C,h,w] the f32 feature map, W the reference parameters,
@@ -362,6 +243,10 @@ def test_pool_grad_accumulates_and_pitches(dev):
     hip_ops.roi_pool_avg_grad_nhwc(fpitched, rois.to(dev), ri, 96, 112, dpitched[:, :64], d_feat=acc, accumulate=True)
     plain = gpu_pool_grad(dev, feat, rois, [1, 0], (96, 112), d_out)
     assert torch.equal(acc, base + plain)
+    # Wf = 14 is no multiple of the 4-pixel strip: the ragged row end against the float64 restatement under its derived bar
+    want, T, N = pool_grad_ref(feat, rois, [1, 0], 96, 112, d_out)
+    got = hip_ops.nhwc_to_nchw(plain).cpu().double()
+    assert bool(((got - want).abs() <= pool_bar(T, N)).all()) and bool((got[N == 0] == 0).all())
     acc = base.clone()
     hip_ops.roi_align_avg_grad_nhwc((2, 12, 14, 64), rois.to(dev), ri, 96, 112, dpitched[:, :64], d_feat=acc, accumulate=True)
     assert torch.equal(acc, base + gpu_pool_grad(dev, feat, rois, [1, 0], (96, 112), d_out, op="align"))
