@@ -468,7 +468,7 @@ __device__ __forceinline__ long long live_count(long long n_max, const long long
 
 __global__ void __launch_bounds__(kThreads)
 radix_hist_kernel(const unsigned long long *__restrict__ keys, long long n_max, const long long *__restrict__ n_dev, int shift,
-                  int nblk, unsigned *__restrict__ hist) {
+                  unsigned digit_mask, int nblk, unsigned *__restrict__ hist) {
     __shared__ unsigned h[256];
     const long long n = live_count(n_max, n_dev);
     h[threadIdx.x] = 0u;
@@ -477,7 +477,7 @@ radix_hist_kernel(const unsigned long long *__restrict__ keys, long long n_max, 
 #pragma unroll 4
     for (int it = 0; it < kRadixItems; ++it) {
         const long long i = tile + it * kThreads + threadIdx.x;
-        if (i < n) atomicAdd(&h[(unsigned)(keys[i] >> shift) & 255u], 1u);
+        if (i < n) atomicAdd(&h[(unsigned)(keys[i] >> shift) & digit_mask], 1u);
     }
     __syncthreads();
     hist[(long)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
@@ -502,8 +502,9 @@ radix_rowscan_kernel(unsigned *__restrict__ hist, int nblk, unsigned *__restrict
 
 __global__ void __launch_bounds__(kThreads)
 radix_scatter_kernel(const unsigned long long *__restrict__ keys_in, const int *__restrict__ vals_in, long long n_max,
-                     const long long *__restrict__ n_dev, int shift, int nblk, const unsigned *__restrict__ hist,
-                     const unsigned *__restrict__ totals, unsigned long long *__restrict__ keys_out, int *__restrict__ vals_out) {
+                     const long long *__restrict__ n_dev, int shift, unsigned digit_mask, int nblk,
+                     const unsigned *__restrict__ hist, const unsigned *__restrict__ totals,
+                     unsigned long long *__restrict__ keys_out, int *__restrict__ vals_out) {
     __shared__ unsigned base[256];
     __shared__ unsigned running[256];
     __shared__ unsigned wcnt[4][256];
@@ -522,7 +523,7 @@ radix_scatter_kernel(const unsigned long long *__restrict__ keys_in, const int *
         const bool valid = i < n;
         const unsigned long long key = valid ? keys_in[i] : 0ull;
         const int val = valid ? (vals_in != nullptr ? vals_in[i] : (int)i) : 0;
-        const unsigned d = (unsigned)(key >> shift) & 255u;
+        const unsigned d = (unsigned)(key >> shift) & digit_mask;
         unsigned long long peers = __ballot(valid);
 #pragma unroll
         for (int bit = 0; bit < 8; ++bit) {
@@ -578,10 +579,12 @@ int launch_sort(const unsigned long long *keys_in, const int *vals_in, long long
         unsigned long long *dk = to_out ? keys_out : w.alt_keys;
         int *dv = to_out ? vals_out : w.alt_vals;
         const int shift = begin_bit + 8 * i;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(nblk), dim3(kThreads), 0, st, src_k, n, n_dev, shift, nblk, w.hist);
+        const unsigned digit_mask = (1u << (end_bit - shift < 8 ? end_bit - shift : 8)) - 1u;   // the last pass stops at end_bit
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nblk), dim3(kThreads), 0, st, src_k, n, n_dev, shift, digit_mask, nblk,
+                           w.hist);
         hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(kThreads), 0, st, w.hist, nblk, w.totals);
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(kThreads), 0, st, src_k, src_v, n, n_dev, shift, nblk,
-                           w.hist, w.totals, dk, dv);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(kThreads), 0, st, src_k, src_v, n, n_dev, shift, digit_mask,
+                           nblk, w.hist, w.totals, dk, dv);
         src_k = dk;
         src_v = dv;
     }
