@@ -491,7 +491,9 @@ int tsod_detection_nms_f32(const float *det_sorted, const int32_t *counts, int32
  *   roi [R][4], bbox [G][4], gt_label [G] int64 -> the first counts[0] = S <= n_sample rows of
  *   sample_roi [n_sample][4], gt_roi_loc [n_sample][4], gt_roi_label [n_sample] int64;
  *   counts [4] int32 = (S, kept positives, kept negatives, status): status 1 = the reference raises IndexError here
- *   (quirk T2: a sampled negative's original index lies beyond the kept list). */
+ *   (quirk T2: a sampled negative's original index lies beyond the kept list).
+ * Both need 0 <= n_pos (pos_per_image) <= n_sample, i.e. pos_ratio in [0, 1]: beyond it the reference's negative slices take a
+ * negative bound (they drop only the last negatives), which is not restated - TSOD_ERR_INVALID_ARG. */
 size_t tsod_anchor_targets_workspace_bytes(int32_t A, int32_t G);
 int tsod_anchor_targets_f32(const float *anchor, int32_t A, const float *bbox, int32_t G, float pos_iou_thresh,
                             float neg_iou_thresh, int32_t n_pos, int32_t n_sample, float *loc, int64_t *label,

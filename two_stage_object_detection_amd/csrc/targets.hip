@@ -246,6 +246,9 @@ extern "C" int tsod_anchor_targets_f32(const float *anchor, int32_t A, const flo
                                        int32_t *argmax, void *workspace, size_t workspace_bytes, tsod_stream_t stream) {
     TSOD_REQUIRE(anchor && loc && label && argmax && (bbox || G == 0), TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(A > 0 && G >= 0 && n_pos >= 0 && n_sample >= 0, TSOD_ERR_INVALID_ARG);
+    // n_pos > n_sample (pos_ratio > 1) can make n_sample - pos_length negative, where the reference's i[n_neg:] disables
+    // only the last |n_neg| negatives; the label kernel does not restate that accident
+    TSOD_REQUIRE(n_pos <= n_sample, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(tsod_aligned16(anchor) && tsod_aligned16(loc) && (G == 0 || tsod_aligned16(bbox)), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace && workspace_bytes >= tsod_anchor_targets_workspace_bytes(A, G) && tsod_aligned16(workspace),
                  TSOD_ERR_WORKSPACE);
@@ -277,6 +280,9 @@ static int proposal_targets(const float *roi, int32_t R, const float *bbox, int3
                             size_t workspace_bytes, int32_t *sample_src, tsod_stream_t stream) {
     TSOD_REQUIRE(sample_roi && gt_roi_loc && gt_roi_label && counts, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(R >= 0 && G >= 0 && R + G > 0 && n_sample > 0 && pos_per_image >= 0, TSOD_ERR_INVALID_ARG);
+    // pos_per_image > n_sample (pos_ratio > 1): the reference's i[:n_sample - pos_length] takes a negative bound and drops only
+    // the last negatives; the select kernel clamps neg_len at 0 instead, so the arguments are refused
+    TSOD_REQUIRE(pos_per_image <= n_sample, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE((roi || R == 0) && ((bbox && gt_label) || G == 0), TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE((R == 0 || tsod_aligned16(roi)) && (G == 0 || tsod_aligned16(bbox)) && tsod_aligned16(sample_roi) &&
                      tsod_aligned16(gt_roi_loc), TSOD_ERR_ALIGNMENT);

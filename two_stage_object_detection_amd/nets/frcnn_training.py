@@ -29,8 +29,17 @@ from .rpn import RegionProposalNetwork
 from ..utils.metrics import COCOEvaluator, DetectionEvaluator
 
 
+def _check_pos_ratio(who, pos_ratio):
+    """With pos_ratio > 1 the positive cap exceeds n_sample and the reference's negative slices (``i[n_neg:]``,
+    ``i[:neg_roi_per_this_image]``) take a negative bound: they drop only the LAST |n_sample - positives| negatives.  The
+    kernels do not restate that accident (they clamp at zero), and a negative ratio is a negative cap, so both are refused."""
+    if not 0.0 <= pos_ratio <= 1.0:
+        raise ValueError(f"{who}: pos_ratio must lie in [0, 1], got {pos_ratio}")
+
+
 class AnchorTargetCreator:
     def __init__(self, n_sample=256, pos_iou_thresh=0.7, neg_iou_thresh=0.3, pos_ratio=0.5):
+        _check_pos_ratio("AnchorTargetCreator", pos_ratio)
         self.n_sample = n_sample
         self.pos_iou_thresh = pos_iou_thresh
         self.neg_iou_thresh = neg_iou_thresh
@@ -39,6 +48,7 @@ class AnchorTargetCreator:
     def __call__(self, bbox, anchor):
         """bbox [G,4] ground truth, anchor [A,4] -> (loc [A,4], label [A]: 1 positive / 0 negative / -1 ignored).
         Four launches (row arg-max, column arg-max, labels + positive cap, offsets), no host synchronisation."""
+        _check_pos_ratio("AnchorTargetCreator", self.pos_ratio)       # read here, not in __init__: it may have been reassigned
         require_cuda(anchor, "AnchorTargetCreator")
         loc, label, _ = hip_ops.anchor_targets(bbox, anchor, int(self.pos_ratio * self.n_sample), self.n_sample,
                                                self.pos_iou_thresh, self.neg_iou_thresh)
@@ -47,6 +57,7 @@ class AnchorTargetCreator:
 
 class ProposalTargetCreator(object):
     def __init__(self, n_sample=128, pos_ratio=0.5, pos_iou_thresh=0.5, neg_iou_thresh_high=0.5, neg_iou_thresh_low=0):
+        _check_pos_ratio("ProposalTargetCreator", pos_ratio)
         self.n_sample = n_sample
         self.pos_ratio = pos_ratio
         self.pos_roi_per_image = int(self.n_sample * self.pos_ratio)
