@@ -1062,6 +1062,54 @@ int tsod_adamw_step_f32(const tsod_adamw_tensor *table, int32_t n_tensors, const
 int tsod_adamw_step_host_f32(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                              const tsod_adamw_group *group, int32_t zero_grad);
 
+/* ---- gradient clipping by global norm, over the table and work list of tsod_adamw_step_f32 -------------
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) in front of the step: the 2-norm over every gradient of the table,
+ * coef = min(1, max_norm / (norm + 1e-6)), g = g * coef.  The norm is two launches, the multiplication rides in the step.
+ * No float atomics, no tickets: every sum order below depends on the element counts only, so the record is bit-identical
+ * from run to run and equal to tsod_grad_norm_host_f32's.
+ *   tsod_grad_norm_f32          launch 1, workgroup c = chunks[c] (256 threads): thread t owns quads t, t + 256, ... of its
+ *                               chunk, quads counted from the chunk's first element (not from an aligned address), and adds
+ *                               (double)g * (double)g - exact in f64 - over the elements of each quad in ascending order, a
+ *                               last short quad included; the 256 sums go through a binary tree (t += t + 128, then + 64,
+ *                               ... + 1) into one f64 partial per chunk, workspace[c].  16-byte loads where the chunk's
+ *                               gradient pointer is 16-byte aligned, 4-byte loads otherwise: the same order, the same bits.
+ *                               Launch 2, one workgroup: thread t adds partials t, t + 256, ... ascending, the same tree,
+ *                               and thread 0 stores
+ *                                   sum_sq
+ *                                   norm = (float)sqrt(sum_sq)
+ *                                   c    = max_norm / (norm + 1e-6f)          f32, one IEEE divide
+ *                                   coef = c > 1 ? 1 : c
+ *                               so a NaN norm gives a NaN coefficient and an infinite norm gives 0, as torch's
+ *                               clamp(max=1) does.  Records that point outside the table are skipped (their partial is 0);
+ *                               n_tensors == 0 or n_chunks == 0 stores {0, 0, 1}.  `result` and `workspace` are DEVICE
+ *                               memory, 8-byte aligned (TSOD_ERR_ALIGNMENT); workspace_bytes >=
+ *                               tsod_grad_norm_workspace_bytes(n_chunks) (8 per chunk), max_norm >= 0 and not a NaN,
+ *                               non-NULL pointers, 0 <= n_chunks <= INT32_MAX (TSOD_ERR_INVALID_ARG otherwise).  Only
+ *                               `grad` and `n` of a table record are read.
+ *   tsod_adamw_step_clipped_f32 tsod_adamw_step_f32 with g' = g * clip->coef (one f32 multiply, the coefficient read from
+ *                               DEVICE memory by the kernel) in front of the update; the gradient becomes 0 with zero_grad,
+ *                               g' otherwise (as after torch's clip).  clip == NULL is tsod_adamw_step_f32 itself.
+ *   tsod_grad_scale_f32         g = g * clip->coef over the same work list (only `grad` and `n` are read)
+ *   tsod_grad_norm_host_f32     HOST function: the whole norm over n_tensors host arrays - the work list of tensor-by-tensor
+ *                               chunks of TSOD_ADAMW_CHUNK elements (no chunk for an empty tensor), the thread-strided
+ *                               order, both trees and the coefficient, in the same arithmetic: equal bits */
+typedef struct tsod_grad_norm_result {
+    double sum_sq; /* the f64 sum of squares */
+    float norm;    /* before clipping */
+    float coef;    /* what the gradients are multiplied by */
+} tsod_grad_norm_result;
+size_t tsod_grad_norm_workspace_bytes(int64_t n_chunks);
+int tsod_grad_norm_f32(const tsod_adamw_tensor *table, int32_t n_tensors, const tsod_adamw_chunk *chunks, int64_t n_chunks,
+                       float max_norm, tsod_grad_norm_result *result, void *workspace, size_t workspace_bytes,
+                       tsod_stream_t stream);
+int tsod_adamw_step_clipped_f32(const tsod_adamw_tensor *table, int32_t n_tensors, const tsod_adamw_chunk *chunks,
+                                int64_t n_chunks, const tsod_adamw_group *groups, int32_t n_groups, int32_t zero_grad,
+                                const tsod_grad_norm_result *clip, tsod_stream_t stream);
+int tsod_grad_scale_f32(const tsod_adamw_tensor *table, int32_t n_tensors, const tsod_adamw_chunk *chunks, int64_t n_chunks,
+                        const tsod_grad_norm_result *clip, tsod_stream_t stream);
+int tsod_grad_norm_host_f32(const float *const *grads, const int64_t *numels, int32_t n_tensors, float max_norm,
+                            tsod_grad_norm_result *result);
+
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends
  * `count_per_rank` floats and receives n_ranks * count_per_rank in rank order.  Stream-ordered, no host synchronisation.

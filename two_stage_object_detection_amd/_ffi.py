@@ -141,6 +141,11 @@ class AdamWGroup(Structure):
                 ("step_size", c_float), ("bias2_sqrt", c_float), ("eps", c_float), ("reserved", c_float)]
 
 
+class GradNormResult(Structure):
+    """Mirror of ``tsod_grad_norm_result`` (include/tsod.h): the f64 sum of squares, the norm and the clip coefficient."""
+    _fields_ = [("sum_sq", c_double), ("norm", c_float), ("coef", c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/tsod.h declares
 _SIGNATURES = {
     "tsod_status_str": (c_char_p, [c_int]),
@@ -227,6 +232,12 @@ _SIGNATURES = {
     "tsod_augment_color_host": (c_int, [c_void_p, c_int64, POINTER(Photometric), c_float, c_void_p]),
     "tsod_adamw_step_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p]),
     "tsod_adamw_step_host_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(AdamWGroup), c_int32]),
+    "tsod_grad_norm_workspace_bytes": (c_size_t, [c_int64]),
+    "tsod_grad_norm_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_adamw_step_clipped_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p,
+                                            c_void_p]),
+    "tsod_grad_scale_f32": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "tsod_grad_norm_host_f32": (c_int, [c_void_p, c_void_p, c_int32, c_float, POINTER(GradNormResult)]),
     "tsod_detection_keys_f32": (c_int, [c_void_p, c_int64, c_float, c_int32, c_void_p, c_void_p]),
     "tsod_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "tsod_detection_nms_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p,

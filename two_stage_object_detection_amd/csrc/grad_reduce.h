@@ -1,5 +1,5 @@
 // grad_reduce.h -- what the backward files (head_grads.hip, pw_grads.hip, conv_grads.hip, conv_strided_grads.hip, conv3x3_grads.hip,
-// stem_grads.hip, dw_grads.hip) share, once: the
+// stem_grads.hip, dw_grads.hip) and optim.hip's gradient norm share, once: the
 // f32 MFMA weight-gradient tile with its slice plan, the fixed-order sum of a workgroup's waves through LDS, the sum of the
 // slices' partials in slice order, and the strict ReLU6 window.  The results of those files are bit-identical from run to run
 // because every order below depends on the shape only; it is stated here and nowhere else:
@@ -8,6 +8,11 @@
 //                             bias adds the two lane halves, then the waves as (w0 + w1) + (w2 + w3)
 //   tsod_sum_in_slice_order   0 + p[0] + p[1] + ..., one add after the other, whatever number of loads is in flight
 //   tsod_tree_sum_256         256 threads' values through LDS: t += t + 128, then + 64, ... + 1 (a binary tree, thread 0 has the sum)
+//   tsod_tree_sum_256_f64     the same tree over 256 doubles (optim.hip's gradient norm)
+//   optim.hip                 tsod_grad_norm_f32: per chunk of 2048 elements thread t adds the exact f64 squares of quads t, t + 256
+//                             (elements ascending, a last short quad included, quads counted from the chunk's first element),
+//                             then tsod_tree_sum_256_f64; the finish: thread t adds partials t, t + 256, ... ascending, then
+//                             tsod_tree_sum_256_f64 (the chunk count depends on the element counts only)
 //   tsod_wgrad_finish_row     dWraw[o][k] = the slabs in slice order; dscale[o]: thread t adds w[o][k] dWraw[o][k] over k = t,
 //                             t + 256, ... ascending, then tsod_tree_sum_256; dshift[o] = the slices' column sums in slice order
 //   tsod_strided_sum_256      a grid-stride loop's lane sum (elements t, t + G, ... ascending, a quad as x, y, z, w), then
@@ -60,6 +65,16 @@ __device__ __forceinline__ float tsod_tree_sum_256(float v, float *lds, int tid)
     __syncthreads();
     for (int st = 128; st >= 1; st >>= 1) {
         if (tid < st) lds[tid] += lds[tid + st];
+        __syncthreads();
+    }
+    return lds[0];
+}
+// its f64 twin (`lds`: 256 doubles), the same order
+__device__ __forceinline__ double tsod_tree_sum_256_f64(double v, double *lds, int tid) {
+    lds[tid] = v;
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) lds[tid] = lds[tid] + lds[tid + st];
         __syncthreads();
     }
     return lds[0];

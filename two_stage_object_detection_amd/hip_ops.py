@@ -6,6 +6,7 @@ only) and launches the HIP kernel on torch's current stream.  No fallback of any
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import math
 import threading
 from ctypes import byref, c_int32
@@ -1888,16 +1889,20 @@ def adamw_table(pointers, numels, groups, n_groups: int):
     return table
 
 
+def _check_work_list(table, chunks, what: str) -> None:
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int64 and table.dim() == 2
+            and table.shape[1] == 6 and table.is_contiguous()):
+        raise TsodError(f"{what}: table must be a contiguous int64 [n, 6] CUDA/ROCm tensor (there is no CPU fallback)")
+    if not (isinstance(chunks, torch.Tensor) and chunks.device == table.device and chunks.dtype == torch.int32
+            and chunks.dim() == 2 and chunks.shape[1] == 2 and chunks.is_contiguous()):
+        raise TsodError(f"{what}: chunks must be a contiguous int32 [n_chunks, 2] tensor on the table's device")
+
+
 def adamw_step(table: torch.Tensor, chunks: torch.Tensor, groups, zero_grad: bool = False) -> None:
     """One AdamW update of every tensor of ``table`` (device copy of ``adamw_table``) over the work list ``chunks`` (device
     copy of ``adamw_chunks``) in ONE launch on the current stream.  ``groups``: a sequence of ``adamw_group`` records; they
     travel by value.  With ``zero_grad`` the gradients are cleared in the same pass."""
-    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int64 and table.dim() == 2
-            and table.shape[1] == 6 and table.is_contiguous()):
-        raise TsodError("adamw_step: table must be a contiguous int64 [n, 6] CUDA/ROCm tensor (there is no CPU fallback)")
-    if not (isinstance(chunks, torch.Tensor) and chunks.device == table.device and chunks.dtype == torch.int32
-            and chunks.dim() == 2 and chunks.shape[1] == 2 and chunks.is_contiguous()):
-        raise TsodError("adamw_step: chunks must be a contiguous int32 [n_chunks, 2] tensor on the table's device")
+    _check_work_list(table, chunks, "adamw_step")
     arr = (_ffi.AdamWGroup * len(groups))(*groups)
     check(lib().tsod_adamw_step_f32(ptr(table), table.shape[0], ptr(chunks), chunks.shape[0], arr, len(groups),
                                     int(bool(zero_grad)), stream_ptr()), "adamw_step")
@@ -1914,3 +1919,75 @@ def adamw_step_host(param, grad, exp_avg, exp_avg_sq, group: _ffi.AdamWGroup, ze
             raise ValueError("adamw_step_host: four writeable contiguous float32 arrays of one size")
     check(lib().tsod_adamw_step_host_f32(*(a.ctypes.data for a in arrays), param.size, byref(group), int(bool(zero_grad))),
           "adamw_step_host")
+
+
+# ----------------------------------------------------------------------------- gradient clipping
+def _check_record(record, table, what: str) -> None:
+    if not (isinstance(record, torch.Tensor) and record.device == table.device and record.dtype == torch.float64
+            and record.shape == (2,) and record.is_contiguous()):
+        raise TsodError(f"{what}: the result record must be a float64 [2] tensor on the table's device (grad_norm_record)")
+
+
+def grad_norm_workspace_bytes(n_chunks: int) -> int:
+    """Bytes of workspace ``grad_norm`` needs for a work list of ``n_chunks`` rows: one f64 partial per chunk."""
+    return int(lib().tsod_grad_norm_workspace_bytes(int(n_chunks)))
+
+
+def grad_norm_record(device) -> torch.Tensor:
+    """A device buffer for one ``tsod_grad_norm_result`` (16 bytes), as float64 [2]: word 0 is ``sum_sq``, word 1 holds
+    ``norm`` and ``coef`` (``grad_norm_fields`` views them)."""
+    return torch.empty(2, dtype=torch.float64, device=device)
+
+
+def grad_norm_fields(record: torch.Tensor):
+    """(sum_sq, norm, coef) of a record as 0-d views into it: float64, float32, float32.  No copy, no synchronisation."""
+    f = record.view(torch.float32)
+    return record[0], f[2], f[3]
+
+
+def grad_norm(table: torch.Tensor, chunks: torch.Tensor, max_norm: float, record: torch.Tensor,
+              workspace: torch.Tensor) -> None:
+    """The 2-norm over every gradient of ``table`` and the clip coefficient min(1, max_norm / (norm + 1e-6)) into ``record``
+    (``grad_norm_record``), in two launches on the current stream: one f64 partial per row of ``chunks`` into
+    ``workspace`` (a contiguous device tensor of at least ``grad_norm_workspace_bytes`` bytes), then one workgroup.  Every
+    sum order depends on the element counts only (include/tsod.h); nothing is copied to the host."""
+    _check_work_list(table, chunks, "grad_norm")
+    _check_record(record, table, "grad_norm")
+    if not (isinstance(workspace, torch.Tensor) and workspace.device == table.device and workspace.is_contiguous()):
+        raise TsodError("grad_norm: workspace must be a contiguous tensor on the table's device")
+    check(lib().tsod_grad_norm_f32(ptr(table), table.shape[0], ptr(chunks), chunks.shape[0], float(max_norm), ptr(record),
+                                   ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr()), "grad_norm")
+
+
+def adamw_step_clipped(table: torch.Tensor, chunks: torch.Tensor, groups, zero_grad: bool, record: torch.Tensor) -> None:
+    """``adamw_step`` with every gradient multiplied by the coefficient of ``record`` (written by ``grad_norm`` earlier on
+    the stream; the kernel reads it from device memory) in the same launch.  The gradients are cleared with ``zero_grad``
+    and hold the clipped values otherwise."""
+    _check_work_list(table, chunks, "adamw_step_clipped")
+    _check_record(record, table, "adamw_step_clipped")
+    arr = (_ffi.AdamWGroup * len(groups))(*groups)
+    check(lib().tsod_adamw_step_clipped_f32(ptr(table), table.shape[0], ptr(chunks), chunks.shape[0], arr, len(groups),
+                                            int(bool(zero_grad)), ptr(record), stream_ptr()), "adamw_step_clipped")
+
+
+def grad_scale(table: torch.Tensor, chunks: torch.Tensor, record: torch.Tensor) -> None:
+    """Every gradient of ``table`` times the coefficient of ``record``, in one launch over ``chunks``."""
+    _check_work_list(table, chunks, "grad_scale")
+    _check_record(record, table, "grad_scale")
+    check(lib().tsod_grad_scale_f32(ptr(table), table.shape[0], ptr(chunks), chunks.shape[0], ptr(record), stream_ptr()),
+          "grad_scale")
+
+
+def grad_norm_host(grads, max_norm: float):
+    """HOST: ``grad_norm`` over contiguous f32 numpy arrays, in the kernels' arithmetic and order -> (sum_sq, norm, coef) as
+    numpy float64 / float32 / float32 scalars -- for checking the bits without a GPU."""
+    import numpy as np
+    grads = list(grads)
+    for a in grads:
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous):
+            raise ValueError("grad_norm_host: contiguous float32 arrays")
+    pointers = (ctypes.c_void_p * max(len(grads), 1))(*(a.ctypes.data for a in grads))
+    numels = (ctypes.c_int64 * max(len(grads), 1))(*(a.size for a in grads))
+    out = _ffi.GradNormResult()
+    check(lib().tsod_grad_norm_host_f32(pointers, numels, len(grads), float(max_norm), byref(out)), "grad_norm_host")
+    return np.float64(out.sum_sq), np.float32(out.norm), np.float32(out.coef)
