@@ -476,6 +476,15 @@ def coco_special_case(areas=COCO_RANGES, name="coco_special", derived=False):
     return match_case(name, [pad_update([_im(d, gb, [0, 1, 1, 2], [1, 0, 0, 0], area)])], 3, thr=(.5, .75), areas=areas)
 
 
+def negative_area_case():
+    """The smallest input on which the plain metric and the COCO metric with the one range "all" differ: class 0 has a
+    detection of area -100, which matches nothing, and a ground truth of area -200; class 1 an exact match.  The plain
+    metric compares no area: a false positive and a counted ground truth.  "all" ignores both boxes of class 0."""
+    d = [[10, 10, 5, 30, .9, 0], [100, 100, 120, 120, .8, 1]]
+    gb = [[50, 50, 40, 70], [100, 100, 120, 120]]
+    return match_case("negative_area", [pad_update([_im(d, gb, [0, 1])])], 2, thr=(.5, .75), areas=(COCO_RANGES[0],))
+
+
 def want_match(case, coco):
     """The records of every update in order and npig: int32 rows [n, 11] and npig [C,A] from coco_eval_restated.match_image,
     or rows [n, 3] and npig [C] from test_detection_eval.evaluate_np."""

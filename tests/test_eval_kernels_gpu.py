@@ -56,6 +56,7 @@ def match_cases():
     cases.update(K.tie_cases())
     cases["keep"] = K.keep_case()
     cases["odd_rows"] = K.odd_rows_case()
+    cases["negative_area"] = K.negative_area_case()
     cases["coco_special"] = K.coco_special_case()
     cases["coco_special_derived"] = K.coco_special_case(name="coco_special_derived", derived=True)
     cases["coco_special_A1"] = K.coco_special_case(areas=(K.COCO_RANGES[2],), name="coco_special_A1")
@@ -74,7 +75,7 @@ MATCH_FAMILIES = {
     "rows": [f"R{R}" for R in K.ROW_COUNTS],
     "gt": [f"gt{n}" for n in K.GT_COUNTS],
     "ties": ["equal_iou_later_gt", "duplicate_gt", "iou_at_threshold", "equal_scores_cap"],
-    "odd": ["keep", "odd_rows"],
+    "odd": ["keep", "odd_rows", "negative_area"],
 }
 COCO_ONLY = ["coco_special", "coco_special_derived", "coco_special_A1"]
 
@@ -104,20 +105,26 @@ def test_case_tables_straddle_the_constants_in_the_source():
     assert (const("kMaxR"), const("kMaxG"), const("kMaxT"), const("kMaxClasses")) == (K.MAX_R, K.MAX_G, K.MAX_T, K.MAX_CLASSES)
     assert "constexpr int kRadixTile = kThreads * kRadixItems;" in src
     # the loops whose trips the cases count
-    assert len(re.findall(r"for \(int c0 = s; c0 < e; c0 \+= kThreads \* kApItems\)", src)) == 2      # both AP scans
+    assert len(re.findall(r"for \(int c0 = s; c0 < e; c0 \+= kThreads \* kApItems\)", src)) == 1      # the AP scan
     assert len(re.findall(r"for \(int b0 = 0; b0 < B; b0 \+= kThreads\)", src)) == 1                  # the offsets scan
-    assert len(re.findall(r"int NP = 64;\s*while \(NP < R\) NP <<= 1;", src)) == 2                    # both match launchers
+    assert len(re.findall(r"int NP = 64;\s*while \(NP < R\) NP <<= 1;", src)) == 1                    # the match launcher
     assert "const int per = (NP + kThreads - 1) / kThreads;" in src
     assert re.search(r"int class_bits\(int C\) \{\s*int bits = 1;\s*while \(bits < 31 && \(1ll << bits\) < \(long long\)C\) "
                      r"\+\+bits;\s*return bits;\s*\}", src)
-    assert len(re.findall(r"launch_sort\(w\.keys, nullptr, capacity, nd, 0, 32 \+ class_bits\(num_classes\)", src)) == 2
+    assert len(re.findall(r"launch_sort\(w\.keys, nullptr, capacity, nd, 0, 32 \+ class_bits\(num_classes\)", src)) == 1
     assert "const int passes = (int)tsod_cdiv(end_bit - begin_bit, 8);" in src
     assert "const bool to_out = ((passes - 1 - i) & 1) == 0;" in src
-    assert len(re.findall(r"for \(int base = 0; base < NP; base \+= 64\)", src)) == 2                 # segment starts by ballot
-    assert len(re.findall(r"if \(\(seg\+\+ & 3\) != wave\) continue;", src)) == 2                     # four waves, round-robin
-    assert len(re.findall(r"for \(int q0 = 0; q0 < max_dets; q0 \+= 64\)", src)) == 2
-    assert len(re.findall(r"if \(nv < 64\) break;", src)) == 2
-    assert len(re.findall(r"for \(int g0 = 0; g0 < gn; g0 \+= 64\)", src)) == 2
+    assert len(re.findall(r"for \(int base = 0; base < NP; base \+= 64\)", src)) == 1                 # segment starts by ballot
+    assert len(re.findall(r"if \(\(seg\+\+ & 3\) != wave\) continue;", src)) == 1                     # four waves, round-robin
+    assert len(re.findall(r"for \(int q0 = 0; q0 < max_dets; q0 \+= 64\)", src)) == 1
+    assert len(re.findall(r"if \(nv < 64\) break;", src)) == 1
+    assert len(re.findall(r"for \(int g0 = 0; g0 < gn; g0 \+= 64\)", src)) == 1
+    # one kernel of each kind (every path runs the loops above), instantiated through its launcher for both record types
+    assert len(re.findall(r"\neval_match_kernel\(", src)) == len(re.findall(r"\neval_ap_kernel\(", src)) == 1
+    for kernel, launcher in (("eval_match_kernel", "launch_match"), ("eval_ap_kernel", "launch_accumulate")):
+        assert f"hipLaunchKernelGGL({kernel}<Rec>," in src
+        for rec in ("tsod_eval_record", "tsod_eval_record_coco"):
+            assert f"return {launcher}<{rec}>(" in src
     assert K.WAVE == 64
 
     chunk = K.AP_CHUNK
@@ -333,6 +340,13 @@ def test_match_case_conditions():
     recs = image_records("odd_rows", 0)
     assert [(r[1], float(r[0])) for r in recs] == [(0, np.inf), (0, -0.0), (0, 0.0), (0, 0.0), (2, .5), (2, -1.5)]
     assert np.float32(recs[1][0]).view(np.uint32) == 0x80000000                         # -0.0 == +0.0: the lower row first
+
+    # negative areas: counted by the plain metric, ignored by COCO's "all"; the two restatements must differ here
+    plain, coco = want_match("negative_area", False), want_match("negative_area", True)
+    assert plain[0].tolist() == [[1063675494, 0, 0], [1061997773, 1, 3]] and plain[1].tolist() == [1, 1]
+    assert coco[0].tolist() == [[1063675494, 0, 0, 0, 0, 0, 0, 3, 0, 0, 0], [1061997773, 1, 0, 3, 0, 0, 0, 0, 0, 0, 0]]
+    assert coco[1].tolist() == [[0], [1]]
+    assert plain[0][0, 2] == 0 and coco[0][0, 7] == 3 and plain[1][0] != coco[1][0, 0]   # an FP against ignored; npig 1 against 0
 
     # COCO only
     recs = image_records("coco_special", 0)

@@ -1,26 +1,29 @@
-// eval_metrics.hip -- detection mAP on the GPU: COCOeval's evaluateImg + accumulate, area "all",
-// no crowd / ignore regions, with an exact integer recall rule.
+// eval_metrics.hip -- detection mAP on the GPU: COCOeval's evaluateImg + accumulate with an exact integer recall rule, once for
+// both metrics.  Every kernel that sees a record is a template on its type: tsod_eval_record is the plain metric (DESIGN.md
+// section 4.14: area "all" without any area comparison, no crowd / ignore regions, one cap), tsod_eval_record_coco adds
+// COCOeval's area ranges, crowd regions, ignore rules and detection caps (section 4.25) behind `if constexpr`.
 //
 //   eval_match_kernel      one workgroup per image: order each class's detections (bitonic sort of (class, score, row) keys in
 //                          LDS), cap at max_dets per class, then the greedy one-to-one match, one wave per class chain: lanes
 //                          over the class's ground truth for the IoUs, then lanes over thresholds, each walking the IoUs for its
 //                          own arg-max (max IoU, then max index).  Records go to a per-image staging slot; per-class GT counts
-//                          are added with integer atomics.
+//                          are added with integer atomics.  COCO: the chain is walked once per area range over a GT list of
+//                          not-ignored, then ignored ground truth, and a record carries its rank and a mask pair per range.
 //   eval_offsets_kernel    one workgroup: exclusive scan of the per-image record counts on top of the device running total
 //   eval_compact_kernel    copies the staged records to their place in the caller's record buffer (update order, image order)
 //   radix_*                stable LSD radix sort of u64 keys + i32 payload: histogram / per-digit row scan / scatter passes of 8
 //                          bits, local ranks from wave ballots in index order (deterministic, no atomics on the output path)
 //   eval_keys_kernel, eval_segments_kernel, eval_ap_kernel
 //                          the accumulate: key = class << 32 | order-inverted score bits, sorted; per-class segments; one
-//                          workgroup per (class, threshold) scans TP over its segment in order, bins each position's f64 precision
-//                          by floor(100 tp / npig) (LDS integer max), and the suffix max over the 101 bins is the envelope sampled
-//                          at the 101 recall points.
-//   eval_match_coco_kernel, eval_ap_coco_kernel
-//                          the same two steps with COCOeval's area ranges, crowd regions, ignore rules and detection caps
-//                          (DESIGN.md section 4.25): the match walks each class chain once per area range, not-ignored ground
-//                          truth first; the AP scan runs per (class, range, cap, threshold) over the records the range does not
-//                          ignore and the cap admits.  Ordering, offsets, compaction, sort and segments are shared.
+//                          workgroup per (class, threshold) - COCO: per (class, range, cap, threshold) - scans TP over its
+//                          segment in order, counting every record - COCO: those the range does not ignore and the cap admits -,
+//                          bins each counted position's f64 precision by floor(100 tp / npig) (LDS integer max), and the suffix
+//                          max over the 101 bins is the envelope sampled at the 101 recall points.
+//   launch_match, launch_accumulate
+//                          the two launch sequences behind the four entry points, which keep their own argument checks.
 // Every count is an integer; every f64 value comes from one division or a fixed-order sum: two runs give identical bits.
+#include <type_traits>
+
 #include "tsod_internal.h"
 
 namespace {
@@ -38,6 +41,7 @@ constexpr int kMaxA = 4;              // area ranges: the words of a COCO record
 constexpr int kMaxM = 4;              // detection caps of one COCO accumulate
 constexpr unsigned kCrowdFlag = 1u << kMaxA;   // gflag: bit a = ignored in area range a, bit kMaxA = crowd
 static_assert(sizeof(tsod_eval_record_coco) == 44, "hip_ops.EVAL_COCO_RECORD_INTS rows of int32");
+template <typename Rec> constexpr bool is_coco = std::is_same<Rec, tsod_eval_record_coco>::value;   // else tsod_eval_record
 
 struct DetCaps { int v[kMaxM]; };
 
@@ -152,42 +156,86 @@ __device__ __forceinline__ int sort_and_cap_detections(unsigned long long *keys,
     return total;
 }
 
+// what only the COCO metric passes to the match (all unused by the plain instantiation)
+struct AreaRanges {
+    const unsigned char *gt_crowd;    // [B][G] or NULL
+    const float *gt_area;             // [B][G] or NULL: the boxes' own areas
+    const float *lo, *hi;             // [A], both inclusive
+    int A;
+};
+
+// IoU of detection A against a crowd region: the intersection of tsod_bbox_iou over the detection's own area
+__device__ __forceinline__ float crowd_iou(const float4 A, const float4 Bx, float area_a, float eps) {
+    const float tlx = fmaxf(A.x, Bx.x), tly = fmaxf(A.y, Bx.y);
+    const float brx = fminf(A.z, Bx.z), bry = fminf(A.w, Bx.w);
+    const float w = fmaxf(brx - tlx, 0.f), h = fmaxf(bry - tly, 0.f);
+    return (w * h) / (area_a + eps);
+}
+
+// One workgroup per image.  Rec = tsod_eval_record is the metric of DESIGN.md section 4.14: no area is ever compared, a class's
+// ground truth is one ascending list, a record is 12 bytes.  Rec = tsod_eval_record_coco adds COCOeval's ignore rules (section
+// 4.25), all of them behind `coco`: per class chain the area ranges one after the other; for range a the class's GT list is the
+// not-ignored ones (ascending), then the ignored ones (ascending), and a lane that found nothing in the first part walks the
+// second, where a crowd region may be taken again.
+template <typename Rec>
 __global__ void __launch_bounds__(kThreads)
 eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ counts, const int *__restrict__ keep,
                   const int *__restrict__ n_kept, const float *__restrict__ gt_boxes, const long long *__restrict__ gt_labels,
-                  const int *__restrict__ gt_counts, int G, const float *__restrict__ thr_in, int T, int C, int max_dets,
-                  int ignore_class, int NP, tsod_eval_record *__restrict__ stage, int *__restrict__ stage_counts,
+                  const int *__restrict__ gt_counts, int G, const float *__restrict__ thr_in, int T, AreaRanges ranges, int C,
+                  int max_dets, int ignore_class, int NP, Rec *__restrict__ stage, int *__restrict__ stage_counts,
                   unsigned long long *__restrict__ npig) {
+    constexpr bool coco = is_coco<Rec>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);          // [NP]
     float4 *gbox = reinterpret_cast<float4 *>(keys + NP);                              // [G]
     int *gcls = reinterpret_cast<int *>(gbox + G);                                     // [G]
-    unsigned *matched = reinterpret_cast<unsigned *>(gcls + G);                          // [G]: bit t = matched at threshold t
+    unsigned *gflag = reinterpret_cast<unsigned *>(gcls + G);                          // [G], coco only: ignore bits per range, crowd
+    unsigned *matched = coco ? gflag + G : gflag;                                      // [G]: bit t, for the chain being walked
     int *gmatch_list = reinterpret_cast<int *>(matched + G);                           // [4][G]: a wave's class GT list
     float *gmatch_iou = reinterpret_cast<float *>(gmatch_list + 4 * G);                // [4][G]: and their IoUs
     unsigned short *comp = reinterpret_cast<unsigned short *>(gmatch_iou + 4 * G);     // [NP]
     __shared__ float thr[kMaxT];
+    __shared__ float alo[kMaxA], ahi[kMaxA];                                           // coco only (not allocated otherwise)
     __shared__ int scr[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long drow0 = (long)b * R;
+    const int A = coco ? ranges.A : 1;
 
     int n = keep != nullptr ? n_kept[b] : counts[b];
     n = min(max(n, 0), R);
     const int gn = G > 0 ? min(max(gt_counts[b], 0), G) : 0;
     if (tid < T) thr[tid] = thr_in[tid];
     fill_detection_keys(det, R, keep, b, n, C, ignore_class, NP, keys);
+    if constexpr (coco) {
+        if (tid < A) { alo[tid] = ranges.lo[tid]; ahi[tid] = ranges.hi[tid]; }
+        __syncthreads();
+    }
     for (int g = tid; g < G; g += kThreads) {
         int cls = -1;
+        unsigned flag = 0u;
         if (g < gn) {
-            gbox[g] = reinterpret_cast<const float4 *>(gt_boxes)[(long)b * G + g];
+            const float4 box = reinterpret_cast<const float4 *>(gt_boxes)[(long)b * G + g];
+            gbox[g] = box;
             const long long l = gt_labels[(long)b * G + g];
             if (l >= 0 && l < C && l != ignore_class) {
                 cls = (int)l;
-                atomicAdd(npig + cls, 1ull);
+                if constexpr (coco) {
+                    const bool crowd = ranges.gt_crowd != nullptr && ranges.gt_crowd[(long)b * G + g] != 0;
+                    const float area = ranges.gt_area != nullptr ? ranges.gt_area[(long)b * G + g]
+                                                                 : (box.z - box.x) * (box.w - box.y);
+                    if (crowd) flag = kCrowdFlag;
+                    for (int a = 0; a < A; ++a) {
+                        if (crowd || area < alo[a] || area > ahi[a]) flag |= 1u << a;
+                        else atomicAdd(npig + (long)cls * A + a, 1ull);
+                    }
+                } else {
+                    atomicAdd(npig + cls, 1ull);
+                }
             }
         }
         gcls[g] = cls;
-        matched[g] = 0u;
+        if constexpr (coco) gflag[g] = flag;
+        else matched[g] = 0u;                                            // coco: cleared per chain and range below
     }
     __syncthreads();
 
@@ -195,7 +243,7 @@ eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ 
     if (tid == 0) stage_counts[b] = total;
 
     // greedy matching: class segments dealt round-robin to the four waves; a wave walks its chain in order.  Per detection the
-    // lanes first compute its IoU with the class's ground truth (the class's GT list, ascending, built once per segment), then
+    // lanes first compute its IoU with the class's ground truth (the class's GT list, built once per chain and range), then
     // lane t < T walks that list for threshold t on its own: the largest IoU >= t among the GT not yet matched at t, ties to the
     // later (higher) index.  matched[g] bit t is written only by lane t of the wave that owns g's class.
     int *glist = gmatch_list + wave * G;
@@ -217,149 +265,14 @@ eval_match_kernel(const float *__restrict__ det, int R, const int *__restrict__ 
             if ((seg++ & 3) != wave) continue;
             const unsigned long long cls_hi = keys[s] >> 45;
             const int cls = (int)cls_hi;
-            int nc = 0;
-            for (int g0 = 0; g0 < gn; g0 += 64) {
-                const int g = g0 + lane;
-                const bool in = g < gn && gcls[g] == cls;
-                const unsigned long long bal = __ballot(in);
-                if (in) glist[nc + __popcll(bal & lt)] = g;
-                nc += __popcll(bal);
-            }
-            wave_sync();
-            for (int q0 = 0; q0 < max_dets; q0 += 64) {
-                const int qi = q0 + lane, pq = s + qi;
-                const unsigned long long kq = (qi < max_dets && pq < NP) ? keys[pq] : ~0ull;
-                const bool mine = kq != ~0ull && (kq >> 45) == cls_hi;      // a prefix of the lanes: the keys are sorted
-                const int nv = __popcll(__ballot(mine));
-                float bx = 0.f, by = 0.f, bz = 0.f, bw = 0.f, sc = 0.f;
-                if (mine) {
-                    const float *dq = det + (drow0 + det_row(keep, b, R, (int)(kq & 0x1FFFu))) * 6;
-                    bx = dq[0]; by = dq[1]; bz = dq[2]; bw = dq[3]; sc = dq[4];
-                }
-                for (int qq = 0; qq < nv; ++qq) {
-                    const float4 dbox = make_float4(lane_value(bx, qq), lane_value(by, qq), lane_value(bz, qq), lane_value(bw, qq));
-                    for (int i = lane; i < nc; i += 64) giou[i] = tsod_bbox_iou(dbox, gbox[glist[i]], kIouEps);
-                    wave_sync();
-                    float best = -__builtin_inff();
-                    int bg = -1;
-                    if (lane < T) {
-                        for (int i = 0; i < nc; ++i) {
-                            const float v = giou[i];
-                            const int g = glist[i];
-                            if (v >= th && v >= best && !((matched[g] >> lane) & 1u)) { best = v; bg = g; }
-                        }
-                        if (bg >= 0) atomicOr(&matched[bg], 1u << lane);
-                    }
-                    const unsigned tp = (unsigned)__ballot(bg >= 0);         // lanes >= T never match: bits of thresholds only
-                    if (lane == qq) {
-                        tsod_eval_record rec;
-                        rec.score = sc;
-                        rec.cls = cls;
-                        rec.tp_mask = tp;
-                        stage[drow0 + comp[s + qi]] = rec;
-                    }
-                    wave_sync();
-                }
-                if (nv < 64) break;
-            }
-        }
-    }
-}
-
-// IoU of detection A against a crowd region: the intersection of tsod_bbox_iou over the detection's own area
-__device__ __forceinline__ float crowd_iou(const float4 A, const float4 Bx, float area_a, float eps) {
-    const float tlx = fmaxf(A.x, Bx.x), tly = fmaxf(A.y, Bx.y);
-    const float brx = fminf(A.z, Bx.z), bry = fminf(A.w, Bx.w);
-    const float w = fmaxf(brx - tlx, 0.f), h = fmaxf(bry - tly, 0.f);
-    return (w * h) / (area_a + eps);
-}
-
-// eval_match_kernel with COCOeval's ignore rules: the same ordering and cap, then per class chain the
-// area ranges one after the other over the same matched[] words.  For range a the class's GT list is the not-ignored ones
-// (ascending), then the ignored ones (ascending); lane t < T walks the first part for its arg-max as eval_match_kernel does and,
-// only when that found nothing, the second part, where a crowd region may be taken again.
-__global__ void __launch_bounds__(kThreads)
-eval_match_coco_kernel(const float *__restrict__ det, int R, const int *__restrict__ counts, const int *__restrict__ keep,
-                       const int *__restrict__ n_kept, const float *__restrict__ gt_boxes, const long long *__restrict__ gt_labels,
-                       const int *__restrict__ gt_counts, const unsigned char *__restrict__ gt_crowd,
-                       const float *__restrict__ gt_area, int G, const float *__restrict__ thr_in, int T,
-                       const float *__restrict__ area_lo, const float *__restrict__ area_hi, int A, int C, int max_dets,
-                       int ignore_class, int NP, tsod_eval_record_coco *__restrict__ stage, int *__restrict__ stage_counts,
-                       unsigned long long *__restrict__ npig) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);          // [NP]
-    float4 *gbox = reinterpret_cast<float4 *>(keys + NP);                              // [G]
-    int *gcls = reinterpret_cast<int *>(gbox + G);                                     // [G]
-    unsigned *gflag = reinterpret_cast<unsigned *>(gcls + G);                          // [G]: ignore bits per range, crowd
-    unsigned *matched = gflag + G;                                                     // [G]: bit t, for the range being walked
-    int *gmatch_list = reinterpret_cast<int *>(matched + G);                           // [4][G]: a wave's class GT list
-    float *gmatch_iou = reinterpret_cast<float *>(gmatch_list + 4 * G);                // [4][G]: and their IoUs
-    unsigned short *comp = reinterpret_cast<unsigned short *>(gmatch_iou + 4 * G);     // [NP]
-    __shared__ float thr[kMaxT];
-    __shared__ float alo[kMaxA], ahi[kMaxA];
-    __shared__ int scr[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long drow0 = (long)b * R;
-
-    int n = keep != nullptr ? n_kept[b] : counts[b];
-    n = min(max(n, 0), R);
-    const int gn = G > 0 ? min(max(gt_counts[b], 0), G) : 0;
-    if (tid < T) thr[tid] = thr_in[tid];
-    if (tid < A) { alo[tid] = area_lo[tid]; ahi[tid] = area_hi[tid]; }
-    fill_detection_keys(det, R, keep, b, n, C, ignore_class, NP, keys);
-    __syncthreads();
-    for (int g = tid; g < G; g += kThreads) {
-        int cls = -1;
-        unsigned flag = 0u;
-        if (g < gn) {
-            const float4 box = reinterpret_cast<const float4 *>(gt_boxes)[(long)b * G + g];
-            gbox[g] = box;
-            const long long l = gt_labels[(long)b * G + g];
-            if (l >= 0 && l < C && l != ignore_class) {
-                cls = (int)l;
-                const bool crowd = gt_crowd != nullptr && gt_crowd[(long)b * G + g] != 0;
-                const float area = gt_area != nullptr ? gt_area[(long)b * G + g] : (box.z - box.x) * (box.w - box.y);
-                if (crowd) flag = kCrowdFlag;
-                for (int a = 0; a < A; ++a) {
-                    if (crowd || area < alo[a] || area > ahi[a]) flag |= 1u << a;
-                    else atomicAdd(npig + (long)cls * A + a, 1ull);
-                }
-            }
-        }
-        gcls[g] = cls;
-        gflag[g] = flag;
-    }
-    __syncthreads();
-
-    const int total = sort_and_cap_detections(keys, comp, NP, max_dets, scr);
-    if (tid == 0) stage_counts[b] = total;
-
-    int *glist = gmatch_list + wave * G;
-    float *giou = gmatch_iou + wave * G;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const float th = lane < T ? thr[lane] : 0.f;
-    int seg = 0;
-    for (int base = 0; base < NP; base += 64) {
-        const int p = base + lane;
-        const unsigned long long key = p < NP ? keys[p] : ~0ull;
-        const bool valid = key != ~0ull;
-        const bool start = valid && (p == 0 || (keys[p - 1] >> 45) != (key >> 45));
-        unsigned long long starts = __ballot(start);
-        if (__ballot(valid) == 0ull) break;
-        while (starts) {
-            const int sl = __builtin_ctzll(starts);
-            starts &= starts - 1;
-            const int s = base + sl;
-            if ((seg++ & 3) != wave) continue;
-            const unsigned long long cls_hi = keys[s] >> 45;
-            const int cls = (int)cls_hi;
             for (int a = 0; a < A; ++a) {
-                const float lo = alo[a], hi = ahi[a];
-                int nn = 0, nc = 0;                                      // not-ignored GT of the class, all of them
-                for (unsigned part = 0; part < 2u; ++part) {
+                const float lo = coco ? alo[a] : 0.f, hi = coco ? ahi[a] : 0.f;
+                int nn = 0, nc = 0;                                     // not-ignored GT of the class, all of them
+                for (unsigned part = 0; part < (coco ? 2u : 1u); ++part) {
                     for (int g0 = 0; g0 < gn; g0 += 64) {
                         const int g = g0 + lane;
-                        const bool in = g < gn && gcls[g] == cls && ((gflag[g] >> a) & 1u) == part;
+                        bool in = g < gn && gcls[g] == cls;
+                        if constexpr (coco) in = in && ((gflag[g] >> a) & 1u) == part;
                         const unsigned long long bal = __ballot(in);
                         if (in) glist[nc + __popcll(bal & lt)] = g;
                         nc += __popcll(bal);
@@ -367,7 +280,9 @@ eval_match_coco_kernel(const float *__restrict__ det, int R, const int *__restri
                     if (part == 0u) nn = nc;
                 }
                 wave_sync();
-                for (int i = lane; i < nc; i += 64) matched[glist[i]] = 0u;
+                if constexpr (coco) {                                    // the ranges share the words; the wave_sync after the
+                    for (int i = lane; i < nc; i += 64) matched[glist[i]] = 0u;   // first IoUs orders the clear before the walk
+                }
                 for (int q0 = 0; q0 < max_dets; q0 += 64) {
                     const int qi = q0 + lane, pq = s + qi;
                     const unsigned long long kq = (qi < max_dets && pq < NP) ? keys[pq] : ~0ull;
@@ -380,13 +295,14 @@ eval_match_coco_kernel(const float *__restrict__ det, int R, const int *__restri
                     }
                     for (int qq = 0; qq < nv; ++qq) {
                         const float4 dbox = make_float4(lane_value(bx, qq), lane_value(by, qq), lane_value(bz, qq), lane_value(bw, qq));
-                        const float darea = (dbox.z - dbox.x) * (dbox.w - dbox.y);
+                        const float darea = (dbox.z - dbox.x) * (dbox.w - dbox.y);   // coco only
                         for (int i = lane; i < nc; i += 64) {
                             const int g = glist[i];
-                            giou[i] = (gflag[g] & kCrowdFlag) ? crowd_iou(dbox, gbox[g], darea, kIouEps)
-                                                              : tsod_bbox_iou(dbox, gbox[g], kIouEps);
+                            bool crowd = false;
+                            if constexpr (coco) crowd = gflag[g] & kCrowdFlag;
+                            giou[i] = crowd ? crowd_iou(dbox, gbox[g], darea, kIouEps) : tsod_bbox_iou(dbox, gbox[g], kIouEps);
                         }
-                        wave_sync();                                     // (also orders the reset of matched[] above)
+                        wave_sync();
                         float best = -__builtin_inff();
                         int bg = -1;
                         bool ignored = false;
@@ -396,31 +312,39 @@ eval_match_coco_kernel(const float *__restrict__ det, int R, const int *__restri
                                 const int g = glist[i];
                                 if (v >= th && v >= best && !((matched[g] >> lane) & 1u)) { best = v; bg = g; }
                             }
-                            if (bg < 0) {                                // nothing not-ignored: the ignored part, crowd re-matchable
-                                for (int i = nn; i < nc; ++i) {
-                                    const float v = giou[i];
-                                    const int g = glist[i];
-                                    if (v >= th && v >= best && (!((matched[g] >> lane) & 1u) || (gflag[g] & kCrowdFlag))) {
-                                        best = v;
-                                        bg = g;
+                            if constexpr (coco) {
+                                if (bg < 0) {                            // nothing not-ignored: the ignored part, crowd re-matchable
+                                    for (int i = nn; i < nc; ++i) {
+                                        const float v = giou[i];
+                                        const int g = glist[i];
+                                        if (v >= th && v >= best && (!((matched[g] >> lane) & 1u) || (gflag[g] & kCrowdFlag))) {
+                                            best = v;
+                                            bg = g;
+                                        }
                                     }
+                                    ignored = bg >= 0 || darea < lo || darea > hi;
                                 }
-                                ignored = bg >= 0 || darea < lo || darea > hi;
                             }
                             if (bg >= 0) atomicOr(&matched[bg], 1u << lane);
                         }
                         const unsigned tp = (unsigned)__ballot(bg >= 0 && !ignored);   // lanes >= T: neither
                         const unsigned ig = (unsigned)__ballot(ignored);
                         if (lane == qq) {
-                            tsod_eval_record_coco *rec = stage + drow0 + comp[s + qi];
+                            Rec *rec = stage + drow0 + comp[s + qi];
                             if (a == 0) {
                                 rec->score = sc;
                                 rec->cls = cls;
-                                rec->rank = qi;
-                                for (int k = 1; k < kMaxA; ++k) { rec->tp_mask[k] = 0u; rec->ig_mask[k] = 0u; }
                             }
-                            rec->tp_mask[a] = tp;
-                            rec->ig_mask[a] = ig;
+                            if constexpr (coco) {
+                                if (a == 0) {
+                                    rec->rank = qi;
+                                    for (int k = 1; k < kMaxA; ++k) { rec->tp_mask[k] = 0u; rec->ig_mask[k] = 0u; }
+                                }
+                                rec->tp_mask[a] = tp;
+                                rec->ig_mask[a] = ig;
+                            } else {
+                                rec->tp_mask = tp;
+                            }
                         }
                         wave_sync();
                     }
@@ -605,6 +529,7 @@ eval_keys_kernel(const Rec *__restrict__ records, long long n_max, const long lo
 
 // what the AP scan reads of a record, at its sorted position i: the TP mask, or for a COCO record planes of `plane` words each,
 // (rank, tp_mask[0..4), ig_mask[0..4))
+template <typename Rec> constexpr int kSortedPlanes = is_coco<Rec> ? 1 + 2 * kMaxA : 1;
 __device__ __forceinline__ void store_sorted(unsigned *masks, long long, long long i, const tsod_eval_record &r) {
     masks[i] = r.tp_mask;
 }
@@ -632,82 +557,22 @@ eval_segments_kernel(const unsigned long long *__restrict__ keys, const int *__r
     store_sorted(masks, n_max, i, records[perm[i]]);
 }
 
-// workgroup (c, t): TP / FP along the class's sorted segment, the precision envelope and its 101-point sample
+// workgroup (c, a, m, t), the plain metric's A = M = 1: TP / FP along the class's sorted segment, the precision envelope and its
+// 101-point sample.  `sorted` holds store_sorted's planes.  Every position of a plain record counts; a COCO record counts when
+// its rank is below cap[m] and range a does not ignore it at threshold t.
+template <typename Rec>
 __global__ void __launch_bounds__(kThreads)
-eval_ap_kernel(const unsigned *__restrict__ masks, const int *__restrict__ seg_begin, const int *__restrict__ seg_end,
-               const long long *__restrict__ npig, int T, double *__restrict__ ap, long long *__restrict__ tp_out,
-               long long *__restrict__ fp_out, long long *__restrict__ fn_out, double *__restrict__ recall) {
-    __shared__ unsigned long long bins[101];
-    __shared__ int scr[4];
-    const int c = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
-    const int s = seg_begin[c], e = seg_end[c];
-    const long long np = npig[c];
-    if (tid < 101) bins[tid] = 0ull;
-    long long carry = 0;
-    for (int c0 = s; c0 < e; c0 += kThreads * kApItems) {
-        const int j0 = c0 + tid * kApItems, j1 = min(j0 + kApItems, e);
-        int cnt = 0;
-        for (int j = j0; j < j1; ++j) cnt += (masks[j] >> t) & 1u;
-        int total = 0;
-        const int ex = block_exclusive_scan(cnt, scr, &total);        // (its first barrier also orders the bins' zeroing)
-        if (np > 0) {
-            long long tp = carry + ex;
-            int cur = -1;
-            unsigned long long best = 0ull;
-            for (int j = j0; j < j1; ++j) {
-                tp += (masks[j] >> t) & 1u;
-                const double prec = (double)tp / (double)(j - s + 1);
-                const long long q = (100 * tp) / np;
-                const int bin = q < 100 ? (int)q : 100;
-                if (bin != cur) {
-                    if (cur >= 0) atomicMax(&bins[cur], best);
-                    cur = bin;
-                    best = 0ull;
-                }
-                const unsigned long long pb = (unsigned long long)__double_as_longlong(prec);
-                best = pb > best ? pb : best;
-            }
-            if (cur >= 0) atomicMax(&bins[cur], best);
-        }
-        carry += total;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int k = c * T + t;
-        const long long n = (long long)(e - s);
-        tp_out[k] = carry;
-        fp_out[k] = n - carry;
-        fn_out[k] = np - carry;
-        if (np > 0) {
-            unsigned long long env = 0ull;                            // the envelope, right to left (bits of doubles >= 0)
-            for (int i = 100; i >= 0; --i) {
-                env = bins[i] > env ? bins[i] : env;
-                bins[i] = env;
-            }
-            double sum = 0.0;
-            for (int i = 0; i <= 100; ++i) sum += __longlong_as_double((long long)bins[i]);
-            ap[k] = sum / 101.0;
-            recall[k] = (double)carry / (double)np;
-        } else {
-            ap[k] = -1.0;
-            recall[k] = -1.0;
-        }
-    }
-}
-
-// workgroup (c, a, m, t) of the COCO accumulate: eval_ap_kernel over the class's records with rank < cap[m] that range a does
-// not ignore at threshold t; `sorted` holds store_sorted's planes.
-__global__ void __launch_bounds__(kThreads)
-eval_ap_coco_kernel(const unsigned *__restrict__ sorted, long long plane, const int *__restrict__ seg_begin,
-                    const int *__restrict__ seg_end, const long long *__restrict__ npig, int A, int M, int T, DetCaps caps,
-                    double *__restrict__ ap, long long *__restrict__ tp_out, long long *__restrict__ fp_out,
-                    long long *__restrict__ fn_out, double *__restrict__ recall) {
+eval_ap_kernel(const unsigned *__restrict__ sorted, long long plane, const int *__restrict__ seg_begin,
+               const int *__restrict__ seg_end, const long long *__restrict__ npig, int A, int M, int T, DetCaps caps,
+               double *__restrict__ ap, long long *__restrict__ tp_out, long long *__restrict__ fp_out,
+               long long *__restrict__ fn_out, double *__restrict__ recall) {
+    constexpr bool coco = is_coco<Rec>;
     __shared__ unsigned long long bins[101];
     __shared__ int scr[4];
     const int tid = threadIdx.x;
     const int t = blockIdx.x % T, m = (blockIdx.x / T) % M, a = (blockIdx.x / (T * M)) % A, c = blockIdx.x / (T * M * A);
     const unsigned cap = (unsigned)(m == 0 ? caps.v[0] : m == 1 ? caps.v[1] : m == 2 ? caps.v[2] : caps.v[3]);
-    const unsigned *rank = sorted, *tpw = sorted + (1 + a) * plane, *igw = sorted + (1 + kMaxA + a) * plane;
+    const unsigned *rank = sorted, *tpw = sorted + (coco ? (1 + a) * plane : 0), *igw = sorted + (1 + kMaxA + a) * plane;
     const int s = seg_begin[c], e = seg_end[c];
     const long long np = npig[(long)c * A + a];
     if (tid < 101) bins[tid] = 0ull;
@@ -716,11 +581,13 @@ eval_ap_coco_kernel(const unsigned *__restrict__ sorted, long long plane, const 
         const int j0 = c0 + tid * kApItems, j1 = min(j0 + kApItems, e);
         unsigned live = 0u, hit = 0u;                                 // bit j - j0: counted at all, counted as a TP
         for (int j = j0; j < j1; ++j) {
-            const unsigned l = (rank[j] < cap && !((igw[j] >> t) & 1u)) ? 1u : 0u;
+            unsigned l = 1u;
+            if constexpr (coco) l = (rank[j] < cap && !((igw[j] >> t) & 1u)) ? 1u : 0u;
             live |= l << (j - j0);
             hit |= (l & (tpw[j] >> t)) << (j - j0);
         }
-        int total = 0;                                                // TP in the low half, counted records in the high half
+        // TP in the low half, counted records in the high half (the scan's first barrier also orders the bins' zeroing)
+        int total = 0;
         const int ex = block_exclusive_scan(__popc(hit) | (__popc(live) << 16), scr, &total);
         if (np > 0) {
             long long tp = carry_tp + (ex & 0xFFFF), n = carry_n + (ex >> 16);
@@ -753,7 +620,7 @@ eval_ap_coco_kernel(const unsigned *__restrict__ sorted, long long plane, const 
         fp_out[k] = carry_n - carry_tp;
         fn_out[k] = np - carry_tp;
         if (np > 0) {
-            unsigned long long env = 0ull;
+            unsigned long long env = 0ull;                            // the envelope, right to left (bits of doubles >= 0)
             for (int i = 100; i >= 0; --i) {
                 env = bins[i] > env ? bins[i] : env;
                 bins[i] = env;
@@ -801,16 +668,77 @@ AccWs acc_ws_layout(void *ws, long long capacity, int C, int mask_planes = 1) {
     return w;
 }
 
-size_t match_lds_bytes(int NP, int G) { return (size_t)NP * 8 + (size_t)G * (16 + 4 + 4 + 4 * 8) + (size_t)NP * 2; }
-size_t match_coco_lds_bytes(int NP, int G) { return match_lds_bytes(NP, G) + (size_t)G * 4; }   // + gflag
-constexpr int kCocoPlanes = 1 + 2 * kMaxA;
+// dynamic LDS of the match: keys, per GT box / class / matched (+ gflag) / four waves' list and IoUs, comp
+size_t match_lds_bytes(int NP, int G, bool coco = false) {
+    return (size_t)NP * 8 + (size_t)G * (16 + 4 + 4 + 4 * 8 + (coco ? 4 : 0)) + (size_t)NP * 2;
+}
+
+// staging slots of B * R records, the per-image record counts, the per-image offsets
+template <typename Rec>
+size_t match_ws_bytes(int B, int R) {
+    return tsod_align_up((size_t)B * R * sizeof(Rec), 256) + tsod_align_up((size_t)B * 4, 256) + tsod_align_up((size_t)B * 8, 256);
+}
+
+// match -> offsets -> compact, after the entry point's checks
+template <typename Rec>
+int launch_match(const float *det, int B, int R, const int *counts, const int *keep, const int *n_kept, const float *gt_boxes,
+                 const int64_t *gt_labels, const int *gt_counts, int G, const float *iou_thr, int T, AreaRanges ranges,
+                 int num_classes, int max_dets, int ignore_class, Rec *records, int64_t capacity, int64_t *n_records,
+                 int64_t *npig, void *workspace, tsod_stream_t stream) {
+    char *p = static_cast<char *>(workspace);
+    const size_t stage_bytes = tsod_align_up((size_t)B * R * sizeof(Rec), 256);
+    Rec *stage = reinterpret_cast<Rec *>(p);
+    int *stage_counts = reinterpret_cast<int *>(p + stage_bytes);
+    long long *offsets = reinterpret_cast<long long *>(p + stage_bytes + tsod_align_up((size_t)B * 4, 256));
+    int NP = 64;
+    while (NP < R) NP <<= 1;
+    const size_t lds = match_lds_bytes(NP, G, is_coco<Rec>);
+    hipStream_t st = tsod_stream(stream);
+    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(eval_match_kernel<Rec>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return TSOD_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(eval_match_kernel<Rec>, dim3(B), dim3(kThreads), lds, st, det, R, counts, keep, n_kept, gt_boxes,
+                       reinterpret_cast<const long long *>(gt_labels), gt_counts, G, iou_thr, T, ranges, num_classes, max_dets,
+                       ignore_class, NP, stage, stage_counts, reinterpret_cast<unsigned long long *>(npig));
+    hipLaunchKernelGGL(eval_offsets_kernel, dim3(1), dim3(kThreads), 0, st, stage_counts, B, offsets,
+                       reinterpret_cast<long long *>(n_records));
+    hipLaunchKernelGGL(eval_compact_kernel<Rec>, dim3((unsigned)tsod_cdiv(R, kThreads), B), dim3(kThreads), 0, st, stage,
+                       stage_counts, offsets, R, records, (long long)capacity);
+    return tsod_launch_status();
+}
+
+// keys -> sort -> segments -> AP over [num_classes][A][M][T] cells (the plain metric: A = M = 1, caps unused)
+template <typename Rec>
+int launch_accumulate(const Rec *records, int64_t capacity, const int64_t *n_records, const int64_t *npig, int num_classes, int A,
+                      int M, int T, DetCaps caps, double *ap, int64_t *tp, int64_t *fp, int64_t *fn, double *recall,
+                      void *workspace, tsod_stream_t stream) {
+    const AccWs w = acc_ws_layout(workspace, capacity, num_classes, kSortedPlanes<Rec>);
+    hipStream_t st = tsod_stream(stream);
+    const long long *nd = reinterpret_cast<const long long *>(n_records);
+    const unsigned grid = (unsigned)tsod_cdiv(capacity, kThreads);
+    if (hipMemsetAsync(w.seg_begin, 0, (size_t)num_classes * 4, st) != hipSuccess ||
+        hipMemsetAsync(w.seg_end, 0, (size_t)num_classes * 4, st) != hipSuccess)
+        return TSOD_ERR_LAUNCH;
+    hipLaunchKernelGGL(eval_keys_kernel<Rec>, dim3(grid), dim3(kThreads), 0, st, records, (long long)capacity, nd, w.keys);
+    const int rc = launch_sort(w.keys, nullptr, capacity, nd, 0, 32 + class_bits(num_classes), w.sorted_keys, w.perm,
+                               sort_ws_layout(w.sort_ws, capacity), st);
+    if (rc != TSOD_OK) return rc;
+    hipLaunchKernelGGL(eval_segments_kernel<Rec>, dim3(grid), dim3(kThreads), 0, st, w.sorted_keys, w.perm, records,
+                       (long long)capacity, nd, w.seg_begin, w.seg_end, w.masks);
+    hipLaunchKernelGGL(eval_ap_kernel<Rec>, dim3((unsigned)num_classes * (unsigned)(A * M * T)), dim3(kThreads), 0, st, w.masks,
+                       (long long)capacity, w.seg_begin, w.seg_end, reinterpret_cast<const long long *>(npig), A, M, T, caps, ap,
+                       reinterpret_cast<long long *>(tp), reinterpret_cast<long long *>(fp), reinterpret_cast<long long *>(fn),
+                       recall);
+    return tsod_launch_status();
+}
 
 }  // namespace
 
 extern "C" size_t tsod_eval_match_workspace_bytes(int32_t B, int32_t R) {
     if (B <= 0 || R <= 0) return 0;
-    return tsod_align_up((size_t)B * R * sizeof(tsod_eval_record), 256) + tsod_align_up((size_t)B * 4, 256) +
-           tsod_align_up((size_t)B * 8, 256);
+    return match_ws_bytes<tsod_eval_record>(B, R);
 }
 
 extern "C" int tsod_eval_match_f32(const float *det, int32_t B, int32_t R, const int32_t *counts, const int32_t *keep,
@@ -826,28 +754,9 @@ extern "C" int tsod_eval_match_f32(const float *det, int32_t B, int32_t R, const
     TSOD_REQUIRE(R <= kMaxR && G <= kMaxG && T <= kMaxT && num_classes <= kMaxClasses && B <= 65535, TSOD_ERR_UNSUPPORTED);
     TSOD_REQUIRE(G == 0 || tsod_aligned16(gt_boxes), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_match_workspace_bytes(B, R), TSOD_ERR_WORKSPACE);
-    char *p = static_cast<char *>(workspace);
-    tsod_eval_record *stage = reinterpret_cast<tsod_eval_record *>(p);
-    int *stage_counts = reinterpret_cast<int *>(p + tsod_align_up((size_t)B * R * sizeof(tsod_eval_record), 256));
-    long long *offsets = reinterpret_cast<long long *>(p + tsod_align_up((size_t)B * R * sizeof(tsod_eval_record), 256) +
-                                                       tsod_align_up((size_t)B * 4, 256));
-    int NP = 64;
-    while (NP < R) NP <<= 1;
-    const size_t lds = match_lds_bytes(NP, G);
-    hipStream_t st = tsod_stream(stream);
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(eval_match_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return TSOD_ERR_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(kThreads), lds, st, det, R, counts, keep, n_kept, gt_boxes,
-                       reinterpret_cast<const long long *>(gt_labels), gt_counts, G, iou_thr, T, num_classes, max_dets,
-                       ignore_class, NP, stage, stage_counts, reinterpret_cast<unsigned long long *>(npig));
-    hipLaunchKernelGGL(eval_offsets_kernel, dim3(1), dim3(kThreads), 0, st, stage_counts, B, offsets,
-                       reinterpret_cast<long long *>(n_records));
-    hipLaunchKernelGGL(eval_compact_kernel<tsod_eval_record>, dim3((unsigned)tsod_cdiv(R, kThreads), B), dim3(kThreads), 0, st, stage, stage_counts,
-                       offsets, R, records, (long long)capacity);
-    return tsod_launch_status();
+    return launch_match<tsod_eval_record>(det, B, R, counts, keep, n_kept, gt_boxes, gt_labels, gt_counts, G, iou_thr, T,
+                                          AreaRanges{}, num_classes, max_dets, ignore_class, records, capacity, n_records, npig,
+                                          workspace, stream);
 }
 
 extern "C" size_t tsod_sort_pairs_workspace_bytes(int64_t n) {
@@ -872,7 +781,7 @@ extern "C" int tsod_sort_pairs_u64(const uint64_t *keys_in, const int32_t *vals_
 
 extern "C" size_t tsod_eval_accumulate_workspace_bytes(int64_t capacity, int32_t num_classes) {
     if (capacity <= 0 || num_classes <= 0) return 0;
-    return acc_ws_layout(nullptr, capacity, num_classes).bytes;
+    return acc_ws_layout(nullptr, capacity, num_classes, kSortedPlanes<tsod_eval_record>).bytes;
 }
 
 extern "C" int tsod_eval_accumulate_f64(const tsod_eval_record *records, int64_t capacity, const int64_t *n_records,
@@ -884,29 +793,13 @@ extern "C" int tsod_eval_accumulate_f64(const tsod_eval_record *records, int64_t
     TSOD_REQUIRE(T <= kMaxT && num_classes <= kMaxClasses && capacity <= (int64_t)INT32_MAX - kRadixTile, TSOD_ERR_UNSUPPORTED);
     TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_accumulate_workspace_bytes(capacity, num_classes),
                  TSOD_ERR_WORKSPACE);
-    const AccWs w = acc_ws_layout(workspace, capacity, num_classes);
-    hipStream_t st = tsod_stream(stream);
-    const long long *nd = reinterpret_cast<const long long *>(n_records);
-    const unsigned grid = (unsigned)tsod_cdiv(capacity, kThreads);
-    if (hipMemsetAsync(w.seg_begin, 0, (size_t)num_classes * 4, st) != hipSuccess ||
-        hipMemsetAsync(w.seg_end, 0, (size_t)num_classes * 4, st) != hipSuccess)
-        return TSOD_ERR_LAUNCH;
-    hipLaunchKernelGGL(eval_keys_kernel<tsod_eval_record>, dim3(grid), dim3(kThreads), 0, st, records, (long long)capacity, nd, w.keys);
-    const int rc = launch_sort(w.keys, nullptr, capacity, nd, 0, 32 + class_bits(num_classes), w.sorted_keys, w.perm,
-                               sort_ws_layout(w.sort_ws, capacity), st);
-    if (rc != TSOD_OK) return rc;
-    hipLaunchKernelGGL(eval_segments_kernel<tsod_eval_record>, dim3(grid), dim3(kThreads), 0, st, w.sorted_keys, w.perm, records,
-                       (long long)capacity, nd, w.seg_begin, w.seg_end, w.masks);
-    hipLaunchKernelGGL(eval_ap_kernel, dim3((unsigned)num_classes * (unsigned)T), dim3(kThreads), 0, st, w.masks, w.seg_begin,
-                       w.seg_end, reinterpret_cast<const long long *>(npig), T, ap, reinterpret_cast<long long *>(tp),
-                       reinterpret_cast<long long *>(fp), reinterpret_cast<long long *>(fn), recall);
-    return tsod_launch_status();
+    return launch_accumulate<tsod_eval_record>(records, capacity, n_records, npig, num_classes, 1, 1, T, DetCaps{}, ap, tp, fp, fn,
+                                               recall, workspace, stream);
 }
 
 extern "C" size_t tsod_eval_match_coco_workspace_bytes(int32_t B, int32_t R) {
     if (B <= 0 || R <= 0 || R > kMaxR || B > 65535) return 0;
-    return tsod_align_up((size_t)B * R * sizeof(tsod_eval_record_coco), 256) + tsod_align_up((size_t)B * 4, 256) +
-           tsod_align_up((size_t)B * 8, 256);
+    return match_ws_bytes<tsod_eval_record_coco>(B, R);
 }
 
 extern "C" int tsod_eval_match_coco_f32(const float *det, int32_t B, int32_t R, const int32_t *counts, const int32_t *keep,
@@ -925,34 +818,14 @@ extern "C" int tsod_eval_match_coco_f32(const float *det, int32_t B, int32_t R, 
                  TSOD_ERR_UNSUPPORTED);
     TSOD_REQUIRE(G == 0 || tsod_aligned16(gt_boxes), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_match_coco_workspace_bytes(B, R), TSOD_ERR_WORKSPACE);
-    char *p = static_cast<char *>(workspace);
-    const size_t stage_bytes = tsod_align_up((size_t)B * R * sizeof(tsod_eval_record_coco), 256);
-    tsod_eval_record_coco *stage = reinterpret_cast<tsod_eval_record_coco *>(p);
-    int *stage_counts = reinterpret_cast<int *>(p + stage_bytes);
-    long long *offsets = reinterpret_cast<long long *>(p + stage_bytes + tsod_align_up((size_t)B * 4, 256));
-    int NP = 64;
-    while (NP < R) NP <<= 1;
-    const size_t lds = match_coco_lds_bytes(NP, G);
-    hipStream_t st = tsod_stream(stream);
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(eval_match_coco_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return TSOD_ERR_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(eval_match_coco_kernel, dim3(B), dim3(kThreads), lds, st, det, R, counts, keep, n_kept, gt_boxes,
-                       reinterpret_cast<const long long *>(gt_labels), gt_counts, gt_crowd, gt_area, G, iou_thr, T, area_lo,
-                       area_hi, A, num_classes, max_dets, ignore_class, NP, stage, stage_counts,
-                       reinterpret_cast<unsigned long long *>(npig));
-    hipLaunchKernelGGL(eval_offsets_kernel, dim3(1), dim3(kThreads), 0, st, stage_counts, B, offsets,
-                       reinterpret_cast<long long *>(n_records));
-    hipLaunchKernelGGL(eval_compact_kernel<tsod_eval_record_coco>, dim3((unsigned)tsod_cdiv(R, kThreads), B), dim3(kThreads), 0,
-                       st, stage, stage_counts, offsets, R, records, (long long)capacity);
-    return tsod_launch_status();
+    return launch_match<tsod_eval_record_coco>(det, B, R, counts, keep, n_kept, gt_boxes, gt_labels, gt_counts, G, iou_thr, T,
+                                               AreaRanges{gt_crowd, gt_area, area_lo, area_hi, A}, num_classes, max_dets,
+                                               ignore_class, records, capacity, n_records, npig, workspace, stream);
 }
 
 extern "C" size_t tsod_eval_accumulate_coco_workspace_bytes(int64_t capacity, int32_t num_classes) {
     if (capacity <= 0 || num_classes <= 0 || num_classes > kMaxClasses || capacity > (int64_t)INT32_MAX - kRadixTile) return 0;
-    return acc_ws_layout(nullptr, capacity, num_classes, kCocoPlanes).bytes;
+    return acc_ws_layout(nullptr, capacity, num_classes, kSortedPlanes<tsod_eval_record_coco>).bytes;
 }
 
 extern "C" int tsod_eval_accumulate_coco_f64(const tsod_eval_record_coco *records, int64_t capacity, const int64_t *n_records,
@@ -973,23 +846,6 @@ extern "C" int tsod_eval_accumulate_coco_f64(const tsod_eval_record_coco *record
     TSOD_REQUIRE(caps.v[M - 1] <= max_dets, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(workspace != nullptr && workspace_bytes >= tsod_eval_accumulate_coco_workspace_bytes(capacity, num_classes),
                  TSOD_ERR_WORKSPACE);
-    const AccWs w = acc_ws_layout(workspace, capacity, num_classes, kCocoPlanes);
-    hipStream_t st = tsod_stream(stream);
-    const long long *nd = reinterpret_cast<const long long *>(n_records);
-    const unsigned grid = (unsigned)tsod_cdiv(capacity, kThreads);
-    if (hipMemsetAsync(w.seg_begin, 0, (size_t)num_classes * 4, st) != hipSuccess ||
-        hipMemsetAsync(w.seg_end, 0, (size_t)num_classes * 4, st) != hipSuccess)
-        return TSOD_ERR_LAUNCH;
-    hipLaunchKernelGGL(eval_keys_kernel<tsod_eval_record_coco>, dim3(grid), dim3(kThreads), 0, st, records, (long long)capacity,
-                       nd, w.keys);
-    const int rc = launch_sort(w.keys, nullptr, capacity, nd, 0, 32 + class_bits(num_classes), w.sorted_keys, w.perm,
-                               sort_ws_layout(w.sort_ws, capacity), st);
-    if (rc != TSOD_OK) return rc;
-    hipLaunchKernelGGL(eval_segments_kernel<tsod_eval_record_coco>, dim3(grid), dim3(kThreads), 0, st, w.sorted_keys, w.perm,
-                       records, (long long)capacity, nd, w.seg_begin, w.seg_end, w.masks);
-    hipLaunchKernelGGL(eval_ap_coco_kernel, dim3((unsigned)num_classes * (unsigned)(A * M * T)), dim3(kThreads), 0, st, w.masks,
-                       (long long)capacity, w.seg_begin, w.seg_end, reinterpret_cast<const long long *>(npig), A, M, T, caps, ap,
-                       reinterpret_cast<long long *>(tp), reinterpret_cast<long long *>(fp), reinterpret_cast<long long *>(fn),
-                       recall);
-    return tsod_launch_status();
+    return launch_accumulate<tsod_eval_record_coco>(records, capacity, n_records, npig, num_classes, A, M, T, caps, ap, tp, fp, fn,
+                                                    recall, workspace, stream);
 }

@@ -1380,38 +1380,57 @@ def sort_pairs_u64(keys: torch.Tensor, vals: torch.Tensor | None = None, begin_b
     return keys_out, vals_out
 
 
+def _eval_match_args(what: str, workspace_bytes, det, gt_boxes, gt_labels, gt_counts, counts, keep, n_kept, per_gt=()):
+    """The checks and arguments both match entry points share -> (the arguments up to G, the trailing workspace arguments).
+    ``per_gt``: (name, [B,G] tensor or None, dtype) of the arrays an entry point takes beside gt_counts."""
+    require_cuda(det, what)
+    B, R, six = det.shape
+    if six != 6:
+        raise ValueError(f"{what}: detection records are [B,R,6], got {tuple(det.shape)}")
+    G = gt_boxes.shape[1]
+    for name, x, dtype in per_gt:
+        if x is not None:
+            _require_cuda_any(x, f"{what}: {name}", dtype)
+            if tuple(x.shape) != (B, G) or not x.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous [{B},{G}] tensor, got {tuple(x.shape)}")
+    ws_bytes = workspace_bytes(B, R)
+    ws = EVAL_ARENA.get(det.device, ws_bytes)
+    gt = [ptr(x) if G else None for x in (gt_boxes, gt_labels, gt_counts, *(x for _, x, _ in per_gt))]
+    return (ptr(det), B, R, ptr(counts), ptr(keep), ptr(n_kept), *gt, G), (ptr(ws), ws_bytes, stream_ptr())
+
+
 def eval_match(det: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_counts: torch.Tensor,
                iou_thr: torch.Tensor, num_classes: int, max_dets: int, ignore_class: int, records: torch.Tensor,
                n_records: torch.Tensor, npig: torch.Tensor, *, counts=None, keep=None, n_kept=None) -> None:
     """One update of the evaluator's device state (tsod_eval_match_f32): det [B,R,6] with counts [B] int32 or keep [B,R] +
     n_kept [B] int32; gt_boxes [B,G,4] f32, gt_labels [B,G] int64, gt_counts [B] int32; iou_thr [T] f32.  Appends to
     records [capacity,3] int32 at n_records [1] int64 and adds to npig [num_classes] int64, in place."""
-    require_cuda(det, "eval_match")
-    B, R, six = det.shape
-    if six != 6:
-        raise ValueError(f"eval_match: detection records are [B,R,6], got {tuple(det.shape)}")
-    G = gt_boxes.shape[1]
     L = lib()
-    ws_bytes = L.tsod_eval_match_workspace_bytes(B, R)
-    ws = EVAL_ARENA.get(det.device, ws_bytes)
-    check(L.tsod_eval_match_f32(ptr(det), B, R, ptr(counts), ptr(keep), ptr(n_kept), ptr(gt_boxes) if G else None,
-                                ptr(gt_labels) if G else None, ptr(gt_counts) if G else None, G, ptr(iou_thr),
-                                iou_thr.shape[0], int(num_classes), int(max_dets), int(ignore_class), ptr(records),
-                                records.shape[0], ptr(n_records), ptr(npig), ptr(ws), ws_bytes, stream_ptr()), "eval_match")
+    head, tail = _eval_match_args("eval_match", L.tsod_eval_match_workspace_bytes, det, gt_boxes, gt_labels, gt_counts, counts,
+                                  keep, n_kept)
+    check(L.tsod_eval_match_f32(*head, ptr(iou_thr), iou_thr.shape[0], int(num_classes), int(max_dets), int(ignore_class),
+                                ptr(records), records.shape[0], ptr(n_records), ptr(npig), *tail), "eval_match")
+
+
+def _eval_accumulate(what: str, workspace_bytes, entry, records, n_records, npig, cells, shape) -> torch.Tensor:
+    """One accumulate entry point over every record so far -> one int64 tensor [5, *shape] on the device: the bits of AP
+    (f64), TP, FP, FN, the bits of recall (f64), in that order (one buffer, so the caller reads the results with one copy).
+    ``cells``: the entry point's arguments between npig and its outputs."""
+    out = torch.empty((5, *shape), dtype=torch.int64, device=records.device)
+    ws_bytes = workspace_bytes(records.shape[0], shape[0])
+    ws = EVAL_ARENA.get(records.device, ws_bytes)
+    check(entry(ptr(records), records.shape[0], ptr(n_records), ptr(npig), *cells, ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                ptr(out[3]), ptr(out[4]), ptr(ws), ws_bytes, stream_ptr()), what)
+    return out
 
 
 def eval_accumulate(records: torch.Tensor, n_records: torch.Tensor, npig: torch.Tensor, T: int) -> torch.Tensor:
     """tsod_eval_accumulate_f64 over every record so far -> one int64 tensor [5, C, T] on the device: the bits of AP (f64),
     TP, FP, FN, the bits of recall (f64), in that order (one buffer, so the caller reads the results with one copy)."""
     C = npig.shape[0]
-    out = torch.empty((5, C, T), dtype=torch.int64, device=records.device)
     L = lib()
-    ws_bytes = L.tsod_eval_accumulate_workspace_bytes(records.shape[0], C)
-    ws = EVAL_ARENA.get(records.device, ws_bytes)
-    check(L.tsod_eval_accumulate_f64(ptr(records), records.shape[0], ptr(n_records), ptr(npig), C, int(T), ptr(out[0]),
-                                     ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(ws), ws_bytes, stream_ptr()),
-          "eval_accumulate")
-    return out
+    return _eval_accumulate("eval_accumulate", L.tsod_eval_accumulate_workspace_bytes, L.tsod_eval_accumulate_f64, records,
+                            n_records, npig, (C, int(T)), (C, T))
 
 
 EVAL_COCO_RECORD_INTS = 11           # tsod_eval_record_coco = (score f32, class, rank, tp_mask[4], ig_mask[4]), int32 rows
@@ -1426,25 +1445,13 @@ def eval_match_coco(det: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.
     """One update of the COCO evaluator's device state (tsod_eval_match_coco_f32): eval_match's inputs plus gt_crowd [B,G]
     uint8 and gt_area [B,G] f32 (either may be None) and the area ranges area_lo / area_hi [A] f32 on the device.  Appends to
     records [capacity,11] int32 at n_records [1] int64 and adds to npig [num_classes,A] int64, in place."""
-    require_cuda(det, "eval_match_coco")
-    B, R, six = det.shape
-    if six != 6:
-        raise ValueError(f"eval_match_coco: detection records are [B,R,6], got {tuple(det.shape)}")
-    G = gt_boxes.shape[1]
-    for name, x, dtype in (("gt_crowd", gt_crowd, torch.uint8), ("gt_area", gt_area, torch.float32)):
-        if x is not None:
-            _require_cuda_any(x, f"eval_match_coco: {name}", dtype)
-            if tuple(x.shape) != (B, G) or not x.is_contiguous():
-                raise ValueError(f"eval_match_coco: {name} must be a contiguous [{B},{G}] tensor, got {tuple(x.shape)}")
     L = lib()
-    ws_bytes = L.tsod_eval_match_coco_workspace_bytes(B, R)
-    ws = EVAL_ARENA.get(det.device, ws_bytes)
-    check(L.tsod_eval_match_coco_f32(ptr(det), B, R, ptr(counts), ptr(keep), ptr(n_kept), ptr(gt_boxes) if G else None,
-                                     ptr(gt_labels) if G else None, ptr(gt_counts) if G else None,
-                                     ptr(gt_crowd) if G else None, ptr(gt_area) if G else None, G, ptr(iou_thr),
-                                     iou_thr.shape[0], ptr(area_lo), ptr(area_hi), area_lo.shape[0], int(num_classes),
-                                     int(max_dets), int(ignore_class), ptr(records), records.shape[0], ptr(n_records), ptr(npig),
-                                     ptr(ws), ws_bytes, stream_ptr()), "eval_match_coco")
+    head, tail = _eval_match_args("eval_match_coco", L.tsod_eval_match_coco_workspace_bytes, det, gt_boxes, gt_labels,
+                                  gt_counts, counts, keep, n_kept,
+                                  per_gt=(("gt_crowd", gt_crowd, torch.uint8), ("gt_area", gt_area, torch.float32)))
+    check(L.tsod_eval_match_coco_f32(*head, ptr(iou_thr), iou_thr.shape[0], ptr(area_lo), ptr(area_hi), area_lo.shape[0],
+                                     int(num_classes), int(max_dets), int(ignore_class), ptr(records), records.shape[0],
+                                     ptr(n_records), ptr(npig), *tail), "eval_match_coco")
 
 
 def eval_accumulate_coco(records: torch.Tensor, n_records: torch.Tensor, npig: torch.Tensor, T: int, max_dets_list,
@@ -1455,15 +1462,10 @@ def eval_accumulate_coco(records: torch.Tensor, n_records: torch.Tensor, npig: t
     C, A = npig.shape
     caps = (c_int32 * len(max_dets_list))(*[int(m) for m in max_dets_list])
     M = len(caps)
-    out = torch.empty((5, C, A, M, int(T)), dtype=torch.int64, device=records.device)
     L = lib()
-    ws_bytes = L.tsod_eval_accumulate_coco_workspace_bytes(records.shape[0], C)
-    ws = EVAL_ARENA.get(records.device, ws_bytes)
-    check(L.tsod_eval_accumulate_coco_f64(ptr(records), records.shape[0], ptr(n_records), ptr(npig), C, A, int(T),
-                                          caps, M, int(max_dets), ptr(out[0]), ptr(out[1]),
-                                          ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(ws), ws_bytes, stream_ptr()),
-          "eval_accumulate_coco")
-    return out
+    return _eval_accumulate("eval_accumulate_coco", L.tsod_eval_accumulate_coco_workspace_bytes,
+                            L.tsod_eval_accumulate_coco_f64, records, n_records, npig, (C, A, int(T), caps, M, int(max_dets)),
+                            (C, A, M, int(T)))
 
 
 # ----------------------------------------------------------------------------- training-side box ops

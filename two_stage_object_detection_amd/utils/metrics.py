@@ -193,15 +193,24 @@ class DetectionEvaluator:
         return _aligned(gt_boxes), gt_labels.to(dev, torch.int64).contiguous(), gc
 
     def update(self, det, gt_boxes, gt_labels, *, counts=None, keep=None, n_kept=None, gt_counts=None):
+        self._update(det, gt_boxes, gt_labels, counts, keep, n_kept, gt_counts)
+
+    def _update(self, det, gt_boxes, gt_labels, counts, keep, n_kept, gt_counts, **per_gt):
+        """``update`` of both evaluators; ``per_gt``: a subclass's arrays beside the labels, padded by its ``_per_gt`` and
+        passed on to its ``_match``."""
         det, counts, keep, n_kept = self._detections(det, counts, keep, n_kept)
         B, R = det.shape[:2]
         dev = det.device
         gb, gl, gc = self._ground_truth(gt_boxes, gt_labels, B, dev, gt_counts)
+        per_gt = {what: self._per_gt(x, what, gl) for what, x in per_gt.items()}
         self._state(dev)
         self._reserve(B * R)
-        hip_ops.eval_match(det, gb, gl, gc, self._thr, self.num_classes, self.max_dets, self.ignore_class, self._records,
-                           self._n, self._npig, counts=counts, keep=keep, n_kept=n_kept)
+        self._match(det, gb, gl, gc, counts=counts, keep=keep, n_kept=n_kept, **per_gt)
         self._bound += B * R
+
+    def _match(self, det, gb, gl, gc, **rows):
+        hip_ops.eval_match(det, gb, gl, gc, self._thr, self.num_classes, self.max_dets, self.ignore_class, self._records,
+                           self._n, self._npig, **rows)
 
     # ------------------------------------------------------------------------------------------------------------ results
     def records(self):
@@ -213,27 +222,31 @@ class DetectionEvaluator:
         r = self._records[:n].cpu().numpy()
         return r[:, 0].view(np.float32).copy(), r[:, 1].copy(), r[:, 2].view(np.uint32).copy()
 
-    def compute(self) -> dict:
+    def _accumulate(self, T):
+        return hip_ops.eval_accumulate(self._records, self._n, self._npig, T)
+
+    def _compute(self):
+        """The accumulate and the one host read -> (AP, recall) as f64 arrays and the result entries both evaluators have."""
         if self._device is None:
-            raise RuntimeError("DetectionEvaluator.compute: nothing was passed to update()")
-        C, T = self.num_classes, len(self.iou_thresholds)
+            raise RuntimeError(f"{type(self).__name__}.compute: nothing was passed to update()")
         self._reserve(1)                                                  # capacity > 0 even when every batch was empty
-        out = hip_ops.eval_accumulate(self._records, self._n, self._npig, T)
-        host = torch.cat([out.view(-1), self._npig]).cpu().numpy()       # the one host read
-        body = host[:5 * C * T].reshape(5, C, T)
+        out = self._accumulate(len(self.iou_thresholds))
+        host = torch.cat([out.view(-1), self._npig.view(-1)]).cpu().numpy()   # the one host read
+        body = host[:out.numel()].reshape(tuple(out.shape))
         ap, recall = body[0].view(np.float64), body[4].view(np.float64)
-        npig = host[5 * C * T:]
-        has_gt = npig > 0
-        res = {
-            "mAP": _mean(ap[has_gt].ravel()),
-            "AP": torch.from_numpy(ap.copy()),
+        return ap, recall, {
             "recall": torch.from_numpy(recall.copy()),
             "TP": torch.from_numpy(body[1].copy()),
             "FP": torch.from_numpy(body[2].copy()),
             "FN": torch.from_numpy(body[3].copy()),
-            "npig": torch.from_numpy(npig.copy()),
+            "npig": torch.from_numpy(host[out.numel():].reshape(tuple(self._npig.shape)).copy()),
             "iou_thresholds": self.iou_thresholds,
         }
+
+    def compute(self) -> dict:
+        ap, _, common = self._compute()
+        has_gt = common["npig"].numpy() > 0
+        res = {"mAP": _mean(ap[has_gt].ravel()), "AP": torch.from_numpy(ap.copy()), **common}
         for name, v in (("AP50", 0.5), ("AP75", 0.75)):
             for t, thr in enumerate(self.iou_thresholds):
                 if thr == float(np.float32(v)):
@@ -282,10 +295,11 @@ class COCOEvaluator(DetectionEvaluator):
             self._hi = torch.tensor([r[2] for r in self.area_ranges], dtype=torch.float32, device=dev)
 
     @staticmethod
-    def _per_gt(x, what, like, dtype):
-        """gt_crowd / gt_area as a padded [B,G] tensor of ``dtype`` beside the padded labels ``like`` (None stays None)."""
+    def _per_gt(x, what, like):
+        """gt_crowd (uint8) / gt_area (f32) as a padded [B,G] tensor beside the padded labels ``like`` (None stays None)."""
         if x is None:
             return None
+        dtype = {"gt_crowd": torch.uint8, "gt_area": torch.float32}[what]
         B, G = like.shape
         rows = _as_list(x, what)
         if rows is None:
@@ -305,18 +319,11 @@ class COCOEvaluator(DetectionEvaluator):
 
     def update(self, det, gt_boxes, gt_labels, *, gt_crowd=None, gt_area=None, counts=None, keep=None, n_kept=None,
                gt_counts=None):
-        det, counts, keep, n_kept = self._detections(det, counts, keep, n_kept)
-        B, R = det.shape[:2]
-        dev = det.device
-        gb, gl, gc = self._ground_truth(gt_boxes, gt_labels, B, dev, gt_counts)
-        crowd = self._per_gt(gt_crowd, "gt_crowd", gl, torch.uint8)
-        area = self._per_gt(gt_area, "gt_area", gl, torch.float32)
-        self._state(dev)
-        self._reserve(B * R)
+        self._update(det, gt_boxes, gt_labels, counts, keep, n_kept, gt_counts, gt_crowd=gt_crowd, gt_area=gt_area)
+
+    def _match(self, det, gb, gl, gc, **rows):
         hip_ops.eval_match_coco(det, gb, gl, gc, self._thr, self._lo, self._hi, self.num_classes, self.max_dets,
-                                self.ignore_class, self._records, self._n, self._npig, gt_crowd=crowd, gt_area=area,
-                                counts=counts, keep=keep, n_kept=n_kept)
-        self._bound += B * R
+                                self.ignore_class, self._records, self._n, self._npig, **rows)
 
     def records(self):
         """The records so far, in record order, read back to the host (a test / debugging accessor): (score [N] f32,
@@ -326,26 +333,12 @@ class COCOEvaluator(DetectionEvaluator):
         return (r[:, 0].view(np.float32).copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3:7].view(np.uint32).copy(),
                 r[:, 7:11].view(np.uint32).copy())
 
+    def _accumulate(self, T):
+        return hip_ops.eval_accumulate_coco(self._records, self._n, self._npig, T, self.caps, self.max_dets)
+
     def compute(self) -> dict:
-        if self._device is None:
-            raise RuntimeError("COCOEvaluator.compute: nothing was passed to update()")
-        C, A, M, T = self.num_classes, len(self.area_ranges), len(self.caps), len(self.iou_thresholds)
-        self._reserve(1)                                                  # capacity > 0 even when every batch was empty
-        out = hip_ops.eval_accumulate_coco(self._records, self._n, self._npig, T, self.caps, self.max_dets)
-        host = torch.cat([out.view(-1), self._npig.view(-1)]).cpu().numpy()   # the one host read
-        body = host[:5 * C * A * M * T].reshape(5, C, A, M, T)
-        ap, recall = body[0].view(np.float64), body[4].view(np.float64)
-        res = {
-            "precision": torch.from_numpy(ap.copy()),
-            "recall": torch.from_numpy(recall.copy()),
-            "TP": torch.from_numpy(body[1].copy()),
-            "FP": torch.from_numpy(body[2].copy()),
-            "FN": torch.from_numpy(body[3].copy()),
-            "npig": torch.from_numpy(host[5 * C * A * M * T:].reshape(C, A).copy()),
-            "iou_thresholds": self.iou_thresholds,
-            "area_ranges": self.area_ranges,
-            "max_dets": self.caps,
-        }
+        ap, recall, common = self._compute()
+        res = {"precision": torch.from_numpy(ap.copy()), **common, "area_ranges": self.area_ranges, "max_dets": self.caps}
         res.update(coco_summary(ap, recall, self.iou_thresholds, [r[0] for r in self.area_ranges], self.caps))
         return res
 
