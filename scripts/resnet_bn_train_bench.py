@@ -5,7 +5,7 @@
 (a) wall time per forward + backward of resnet50 at 1 x 3 x 600 x 600 in the modes "layer4" and "stem", folded BatchNorm under
     .eval() (the path of sections 4.22 / 4.23) against ``batch_stats=True`` under .train(): ``iters`` iterations after
     ``warmup``, one synchronize at the end;
-(b) per kernel group of csrc/bn_prelu_train.hip, at (M, C) = (22 500, 256) (layer1's output at 600 x 600) and (361, 2048)
+(b) per kernel group of csrc/bn_train.hip, at (M, C) = (22 500, 256) (layer1's output at 600 x 600) and (361, 2048)
 (layer4's), HIP-event time of ``reps`` back-to-back calls of the C entry points on preallocated tensors (no Python wrapper, no
 allocation inside the window), beside a device copy (``Tensor.copy_``) of one tensor of the same shape:
   stats + apply          tsod_bn_stats_f32 + tsod_bn_apply_prelu_f32 with a residual tensor (4 passes over the tensor's bytes)

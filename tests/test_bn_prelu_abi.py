@@ -1,4 +1,4 @@
-"""The C ABI of train-mode BatchNorm with ResNet's epilogue (csrc/bn_prelu_train.hip) and the float64
+"""The C ABI of train-mode BatchNorm with ResNet's epilogue (csrc/bn_train.hip) and the float64
 restatement of tests/bn_prelu_restated.py: everything here runs without a GPU."""
 import ctypes
 import os

@@ -1,4 +1,4 @@
-"""hip_ops.batch_norm_prelu_train / batch_norm_prelu_train_grad (csrc/bn_prelu_train.hip) against float64
+"""hip_ops.batch_norm_prelu_train / batch_norm_prelu_train_grad (csrc/bn_train.hip) against float64
 on the sweep of tests/bn_prelu_restated.py: every quantity within 4 x what torch's own float32 CPU evaluation of the same
 expression shows in the same (data, M, form) cell; no cell is skipped."""
 import os
@@ -9,7 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bn_prelu_restated as R  # noqa: E402
-from resnet_grads_restated import prelu_reference  # noqa: E402
+from resnet_grads_restated import assert_within, prelu_reference  # noqa: E402
 
 from two_stage_object_detection_amd import _ffi  # noqa: E402
 
@@ -135,3 +135,36 @@ def test_optional_outputs_and_refusals(dev):
     _, _, sc, sh = hip_ops.batch_norm_stats(z, gamma, beta, 1e-5, 0.1)
     with pytest.raises(ValueError, match="not both"):
         hip_ops.batch_norm_prelu_train(z, gamma, beta, 1e-5, 0.1, 0.25, residual=r, second=(z, sc, sh, 0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,C,cp", [(3, 10, 12), (RW + 1, 68, 68), (3 * RW + 5, 258, 260)], ids=lambda v: str(v))
+def test_slope_one_is_the_plain_path_bit_for_bit(dev, M, C, cp):
+    """One kernel family: at slope 1 the PReLU forward is ``batch_norm_train(act=ACT_NONE)`` and the
+    backward from the saved output is ``batch_norm_train_grad`` on dy, in every bit; the slope's sum is the float64 one within
+    tests/test_resnet_grads_gpu.py's bound.  Cells: one workgroup with pad channels and fewer rows than row lanes; a one-row
+    second workgroup; two chunks of 64 quads with pad channels in the last quad.  z sits 50 off zero per channel, so scale * z
+    and shift cancel."""
+    from two_stage_object_detection_amd import hip_ops
+    gen = torch.Generator().manual_seed(1000 * M + C)
+    z = torch.randn(M, cp, generator=gen) + 50.0 * (1 + torch.arange(cp) % 3)
+    y, dy = torch.randn(M, cp, generator=gen), torch.randn(M, cp, generator=gen)
+    y[torch.rand(M, cp, generator=gen) < 0.1] = 0.0
+    assert bool((y > 0).any() and (y < 0).any() and (y == 0).any())
+    gamma, beta = torch.rand(C, generator=gen) + 0.5, torch.randn(C, generator=gen)
+    z, y, dy, gamma, beta = (t.to(dev) for t in (z, y, dy, gamma, beta))
+    fwd = []
+    for f, extra in ((hip_ops.batch_norm_prelu_train, (1.0,)), (hip_ops.batch_norm_train, ())):
+        rm, rv, words = torch.zeros(C, device=dev), torch.ones(C, device=dev), hip_ops.new_amax_words(dev)
+        kw = dict(act=hip_ops.ACT_NONE) if not extra else {}
+        out = f(z, gamma, beta, 1e-5, 0.1, *extra, rm, rv, C_real=C, amax_out=words, **kw)
+        fwd.append(out + (rm, rv, torch.tensor(hip_ops.amax_value(words))))
+    for name, a, b in zip(("y", "mean", "invstd", "running_mean", "running_var", "range word"), *fwd):
+        assert torch.equal(a, b), name
+    mean, invstd = fwd[0][1:3]
+    fused = hip_ops.batch_norm_prelu_train_grad(y, dy, z, mean, invstd, gamma, 1.0, C_real=C)
+    plain = hip_ops.batch_norm_train_grad(dy, z, mean, invstd, gamma, C_real=C)
+    for name, a, b in zip(("dz", "dgamma", "dbeta"), fused, plain):
+        assert torch.equal(a, b), name
+    num, T, n = prelu_reference(y[:, :C].cpu(), dy[:, :C].cpu(), 1.0)["dslope_num"]
+    assert_within(fused[3], num.reshape(1), T.reshape(1), n, f"slope sum {M}x{C}")

@@ -801,6 +801,55 @@ def _bn_rows(t: torch.Tensor, what: str):
     return t.numel() // t.shape[-1], t.shape[-1]
 
 
+def _bn_channels(gamma, C_real):
+    C_real = int(gamma.numel() if C_real is None else C_real)
+    return C_real, (C_real + 3) // 4 * 4
+
+
+def _bn_pitches(what: str, lead: str, M: int, dev, named) -> dict:
+    """name -> pitch of the (name, tensor) pairs ``named`` (None: absent), each contiguous float32 on ``dev`` with M rows."""
+    lds = {}
+    for name, t in named:
+        if t is None:
+            continue
+        Mt, lds[name] = _bn_rows(t, what)
+        if Mt != M or t.device != dev or t.dtype != torch.float32:
+            raise ValueError(f"{what}: {lead} has {M} float32 rows on {dev}, {name} is {tuple(t.shape)} {t.dtype} on {t.device}")
+    return lds
+
+
+def _bn_train_forward(what, z, gamma, beta, eps, momentum, running_mean, running_var, off, out, C_real, num_batches_tracked,
+                      operands=()):
+    """What both forwards do before their apply launch; ``operands``: (name, tensor) pairs with z's rows
+    -> (M, C_real, C_pad, out, pitches by name, mean, invstd, scale, shift)."""
+    require_cuda(z, what)
+    M, ld = _bn_rows(z, what)
+    if M < 2:
+        raise ValueError(f"{what}: more than one value per channel is needed in training mode, got {M} row(s)")
+    C_real, cp = _bn_channels(gamma, C_real)
+    if out is None:
+        out = torch.empty(z.shape[:-1] + (cp,), dtype=torch.float32, device=z.device)
+    lds = dict(_bn_pitches(what, "z", M, z.device, (("out", out),) + operands), z=ld)
+    return (M, C_real, cp, out, lds) + batch_norm_stats(z, gamma, beta, eps, momentum, running_mean, running_var, off=off,
+                                                        C_real=C_real, num_batches_tracked=num_batches_tracked)
+
+
+def _bn_train_backward(what, lead, t0, named, mean, invstd, gamma, C_real, dz, workspace_bytes):
+    """What both backwards do before their three launches; ``t0`` is the tensor called ``lead``, ``named`` (name, tensor) pairs
+    with its rows, ``workspace_bytes`` the entry point's query -> (M, C_real, C_pad, dz, pitches by name, dgamma, dbeta, ws, ws_bytes)."""
+    require_cuda(t0, what)
+    M, ld = _bn_rows(t0, what)
+    cp, dev = mean.numel(), t0.device
+    if M < 2 or invstd.numel() != cp:
+        raise ValueError(f"{what}: {lead} has {M} rows (at least 2), mean {cp} / invstd {invstd.numel()} channels")
+    if dz is None:
+        dz = torch.empty(t0.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
+    lds = dict(_bn_pitches(what, lead, M, dev, named + (("dz", dz),)), **{lead: ld})
+    dgamma, dbeta = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
+    ws_bytes = workspace_bytes(M, cp)
+    return M, _bn_channels(gamma, C_real)[0], cp, dz, lds, dgamma, dbeta, ARENA.get(dev, ws_bytes), ws_bytes
+
+
 def batch_norm_train(z, gamma, beta, eps, momentum, running_mean=None, running_var=None, *, act=ACT_NONE, off=0, out=None,
                      out_off=0, C_real=None, num_batches_tracked=None, amax_out=None):
     """Train-mode BatchNorm of NHWC rows (tsod_bn_stats_f32, tsod_bn_apply_f32) -> (y, mean, invstd).
@@ -814,21 +863,9 @@ def batch_norm_train(z, gamma, beta, eps, momentum, running_mean=None, running_v
     torch's: (1 - momentum) * old + momentum * (mean | unbiased variance); ``num_batches_tracked`` (int64 scalar tensor) is
     incremented; ``amax_out``: the range words of ``out``'s tensor.  ValueError for fewer than 2 rows (torch refuses one value
     per channel in training mode).  Launches: two for the statistics (workgroup partials, their merge), one for y."""
-    require_cuda(z, "batch_norm_train")
-    M, ld = _bn_rows(z, "batch_norm_train")
-    if M < 2:
-        raise ValueError(f"batch_norm_train: more than one value per channel is needed in training mode, got {M} row(s)")
-    C_real = int(gamma.numel() if C_real is None else C_real)
-    cp = (C_real + 3) // 4 * 4
-    dev = z.device
-    if out is None:
-        out = torch.empty(z.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
-    Mo, ld_out = _bn_rows(out, "batch_norm_train")
-    if Mo != M:
-        raise ValueError(f"batch_norm_train: z has {M} rows, out {Mo}")
-    mean, invstd, scale, shift = batch_norm_stats(z, gamma, beta, eps, momentum, running_mean, running_var, off=off, C_real=C_real,
-                                                  num_batches_tracked=num_batches_tracked)
-    check(lib().tsod_bn_apply_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(scale), ptr(shift), int(act), ptr(out), ld_out,
+    M, C_real, cp, out, lds, mean, invstd, scale, shift = _bn_train_forward(
+        "batch_norm_train", z, gamma, beta, eps, momentum, running_mean, running_var, off, out, C_real, num_batches_tracked)
+    check(lib().tsod_bn_apply_f32(ptr(z), M, C_real, cp, lds["z"], int(off), ptr(scale), ptr(shift), int(act), ptr(out), lds["out"],
                                   int(out_off), _word_ptr(amax_out), stream_ptr()), "bn_apply")
     return out, mean, invstd
 
@@ -842,26 +879,12 @@ def batch_norm_train_grad(g, z, mean, invstd, gamma, *, g_off=0, z_off=0, dz=Non
     default: its length).  With xhat = (z - mean) * invstd: dgamma = sum g xhat, dbeta = sum g, dz = gamma * invstd * (g -
     dbeta / M - xhat * dgamma / M), written to channels [dz_off, dz_off + C_pad) of ``dz`` (default: a new [..., C_pad] tensor);
     pad channels of all three are exact zeros.  Launches: the workgroups' partial sums, their sum, the elementwise pass."""
-    require_cuda(g, "batch_norm_train_grad")
-    M, ld_g = _bn_rows(g, "batch_norm_train_grad")
-    Mz, ld_z = _bn_rows(z, "batch_norm_train_grad")
-    cp = mean.numel()
-    C_real = int(gamma.numel() if C_real is None else C_real)
-    if Mz != M or M < 2 or invstd.numel() != cp:
-        raise ValueError(f"batch_norm_train_grad: g has {M} rows, z {Mz} (at least 2), mean {cp} / invstd {invstd.numel()} channels")
-    dev = g.device
-    if dz is None:
-        dz = torch.empty(g.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
-    Md, ld_d = _bn_rows(dz, "batch_norm_train_grad")
-    if Md != M:
-        raise ValueError(f"batch_norm_train_grad: g has {M} rows, dz {Md}")
-    dgamma, dbeta = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
     L = lib()
-    ws_bytes = L.tsod_bn_train_workspace_bytes(M, cp)
-    ws = ARENA.get(dev, ws_bytes)
-    check(L.tsod_bn_train_grad_f32(ptr(g), ld_g, int(g_off), ptr(z), ld_z, int(z_off), M, C_real, cp, ptr(mean), ptr(invstd),
-                                   ptr(gamma), ptr(dz), ld_d, int(dz_off), ptr(dgamma), ptr(dbeta), ptr(ws), ws_bytes, stream_ptr()),
-          "bn_train_grad")
+    M, C_real, cp, dz, lds, dgamma, dbeta, ws, ws_bytes = _bn_train_backward(
+        "batch_norm_train_grad", "g", g, (("z", z),), mean, invstd, gamma, C_real, dz, L.tsod_bn_train_workspace_bytes)
+    check(L.tsod_bn_train_grad_f32(ptr(g), lds["g"], int(g_off), ptr(z), lds["z"], int(z_off), M, C_real, cp, ptr(mean), ptr(invstd),
+                                   ptr(gamma), ptr(dz), lds["dz"], int(dz_off), ptr(dgamma), ptr(dbeta), ptr(ws), ws_bytes,
+                                   stream_ptr()), "bn_train_grad")
     return dz, dgamma, dbeta
 
 
@@ -876,8 +899,7 @@ def batch_norm_stats(z, gamma, beta, eps, momentum, running_mean=None, running_v
     M, ld = _bn_rows(z, "batch_norm_stats")
     if M < 2:
         raise ValueError(f"batch_norm_stats: more than one value per channel is needed in training mode, got {M} row(s)")
-    C_real = int(gamma.numel() if C_real is None else C_real)
-    cp = (C_real + 3) // 4 * 4
+    C_real, cp = _bn_channels(gamma, C_real)
     dev = z.device
     mean, invstd = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
     scale, shift = (torch.empty((2, cp), dtype=torch.float32, device=dev) for _ in range(2))      # (value, f32 remainder)
@@ -905,33 +927,17 @@ def batch_norm_prelu_train(z, gamma, beta, eps, momentum, slope, running_mean=No
                     the scale / shift ``batch_norm_stats`` gave for it: a projection block's downsample.1.
     The BatchNorm's terms and R are added in float64 and rounded to float32 once; the PReLU (one ``slope``, by value, not
     checked here: the module keeps it finite and > 0) runs on that.  Launches: two for the statistics, one for y."""
-    require_cuda(z, "batch_norm_prelu_train")
-    M, ld = _bn_rows(z, "batch_norm_prelu_train")
     if residual is not None and second is not None:
         raise ValueError("batch_norm_prelu_train: a residual tensor or a second normalised operand, not both")
-    C_real = int(gamma.numel() if C_real is None else C_real)
-    cp = (C_real + 3) // 4 * 4
-    dev = z.device
-    if out is None:
-        out = torch.empty(z.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
-    rows = [("out", out)]
-    if residual is not None:
-        rows.append(("residual", residual))
-    z2 = scale2 = shift2 = None
-    z2_off = 0
+    z2, scale2, shift2, z2_off = (None, None, None, 0) if second is None else second
     if second is not None:
-        z2, scale2, shift2, z2_off = second
-        rows.append(("second", z2))
+        cp = _bn_channels(gamma, C_real)[1]
         if tuple(scale2.shape) != (2, cp) or tuple(shift2.shape) != (2, cp):
             raise ValueError(f"batch_norm_prelu_train: the second operand's scale / shift must be [2, {cp}]")
-    lds = {}
-    for what, t in rows:
-        Mt, lds[what] = _bn_rows(t, "batch_norm_prelu_train")
-        if Mt != M or t.device != dev or t.dtype != torch.float32:
-            raise ValueError(f"batch_norm_prelu_train: z has {M} float32 rows on {dev}, {what} is {tuple(t.shape)} {t.dtype} on {t.device}")
-    mean, invstd, scale, shift = batch_norm_stats(z, gamma, beta, eps, momentum, running_mean, running_var, off=off, C_real=C_real,
-                                                  num_batches_tracked=num_batches_tracked)
-    check(lib().tsod_bn_apply_prelu_f32(ptr(z), M, C_real, cp, ld, int(off), ptr(scale), ptr(shift), ptr(residual),
+    M, C_real, cp, out, lds, mean, invstd, scale, shift = _bn_train_forward(
+        "batch_norm_prelu_train", z, gamma, beta, eps, momentum, running_mean, running_var, off, out, C_real, num_batches_tracked,
+        (("residual", residual), ("second", z2)))
+    check(lib().tsod_bn_apply_prelu_f32(ptr(z), M, C_real, cp, lds["z"], int(off), ptr(scale), ptr(shift), ptr(residual),
                                         lds.get("residual", 0), int(residual_off), ptr(z2), lds.get("second", 0), int(z2_off),
                                         ptr(scale2), ptr(shift2), float(slope), ptr(out), lds["out"], int(out_off),
                                         _word_ptr(amax_out), stream_ptr()), "bn_apply_prelu")
@@ -953,31 +959,14 @@ def batch_norm_prelu_train_grad(y, dy, z, mean, invstd, gamma, slope, *, y_off=0
     ``want_dslope``.  ``want_g`` (or a ``g`` [..., ld_g] to write at channels [g_off, ...)): g itself - what the residual branch
     of a block's last stage reads.  Whatever R the forward added needs no term here: d(z_bn + R) = g for both.  Pad channels
     of every output are exact zeros.  All tensors contiguous float32 with as many rows, at least 2."""
-    require_cuda(y, "batch_norm_prelu_train_grad")
-    M, ld_y = _bn_rows(y, "batch_norm_prelu_train_grad")
-    cp = mean.numel()
-    C_real = int(gamma.numel() if C_real is None else C_real)
-    if M < 2 or invstd.numel() != cp:
-        raise ValueError(f"batch_norm_prelu_train_grad: y has {M} rows (at least 2), mean {cp} / invstd {invstd.numel()} channels")
-    dev = y.device
-    if dz is None:
-        dz = torch.empty(y.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
     if g is None and want_g:
-        g = torch.empty(y.shape[:-1] + (cp,), dtype=torch.float32, device=dev)
-    lds = {}
-    for what, t in (("dy", dy), ("z", z), ("dz", dz), ("g", g)):
-        if t is None:
-            continue
-        Mt, lds[what] = _bn_rows(t, "batch_norm_prelu_train_grad")
-        if Mt != M or t.device != dev or t.dtype != torch.float32:
-            raise ValueError(f"batch_norm_prelu_train_grad: y has {M} float32 rows on {dev}, {what} is {tuple(t.shape)} {t.dtype} on "
-                             f"{t.device}")
-    dgamma, dbeta = (torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(2))
-    num = torch.empty(1, dtype=torch.float32, device=dev) if want_dslope else None
+        g = torch.empty(y.shape[:-1] + (mean.numel(),), dtype=torch.float32, device=y.device)
     L = lib()
-    ws_bytes = L.tsod_bn_prelu_train_grad_workspace_bytes(M, cp)
-    ws = ARENA.get(dev, ws_bytes)
-    check(L.tsod_bn_prelu_train_grad_f32(ptr(y), ld_y, int(y_off), ptr(dy), lds["dy"], int(dy_off), ptr(z), lds["z"], int(z_off), M,
+    M, C_real, cp, dz, lds, dgamma, dbeta, ws, ws_bytes = _bn_train_backward(
+        "batch_norm_prelu_train_grad", "y", y, (("dy", dy), ("z", z), ("g", g)), mean, invstd, gamma, C_real, dz,
+        L.tsod_bn_prelu_train_grad_workspace_bytes)
+    num = torch.empty(1, dtype=torch.float32, device=y.device) if want_dslope else None
+    check(L.tsod_bn_prelu_train_grad_f32(ptr(y), lds["y"], int(y_off), ptr(dy), lds["dy"], int(dy_off), ptr(z), lds["z"], int(z_off), M,
                                          C_real, cp, ptr(mean), ptr(invstd), ptr(gamma), float(slope), ptr(dz), lds["dz"],
                                          int(dz_off), ptr(dgamma), ptr(dbeta), ptr(num), ptr(g), lds.get("g", 0), int(g_off), ptr(ws),
                                          ws_bytes, stream_ptr()), "bn_prelu_train_grad")
