@@ -504,6 +504,44 @@ int tsod_proposal_targets_f32(const float *roi, int32_t R, const float *bbox, in
                               float neg_iou_thresh_low, float *sample_roi, float *gt_roi_loc, int64_t *gt_roi_label,
                               int32_t *counts, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
 
+/* The same two assignments for a whole batch in one pass: the image index rides on a grid dimension (the two one-workgroup
+ * kernels run one workgroup per image), four launches (three when Gmax == 0) and two launches for all B images, no host
+ * synchronisation, no float atomics, and no result depends on what the workspace held before the call.  Ground truth is padded
+ * as for tsod_eval_match_f32: bbox [B][Gmax][4], gt_label [B][Gmax] int64, gt_counts [B] int32 ON THE DEVICE.  gt_counts[b] is
+ * read by the kernels and clamped to [0, Gmax]; rows [gt_counts[b], Gmax) of image b are never read (they may hold anything, NaN
+ * included).  Gmax == 0 is legal: bbox, gt_label and gt_counts may then be NULL and every image has no ground truth.
+ * Image b's results are bit for bit those of the single-image entry points on (anchor, bbox[b][:gt_counts[b]]) and
+ * (roi[b], bbox[b][:gt_counts[b]], gt_label[b][:gt_counts[b]]): the kernels share their bodies, quirks T1, T2 and T4 included.
+ *
+ * tsod_anchor_targets_batch_f32: anchor [A][4] is shared by the batch -> loc [B][A][4], label [B][A] int64, argmax [B][A] int32.
+ *   workspace: tsod_anchor_targets_batch_workspace_bytes(B, A, Gmax) = B * (align16(4 A) + align16(4 max(Gmax, 1)) + 16)
+ *   = B * tsod_anchor_targets_workspace_bytes(A, Gmax); 0 for B outside [1, 65535], A <= 0 or Gmax < 0.
+ * tsod_proposal_targets_batch_f32: roi [B][R][4] -> sample_roi / gt_roi_loc [B][n_sample][4], gt_roi_label [B][n_sample] int64,
+ *   counts [B][4] int32 = per image (S, kept positives, kept negatives, status), sample_src [B][n_sample] int32 or NULL (the rows
+ *   of cat(roi[b], bbox[b][:gt_counts[b]]), as tsod_proposal_targets_src_f32).  One behaviour the single-image entry points do
+ *   not have: rows [counts[b][0], n_sample) of image b are WRITTEN - zeros in sample_roi, gt_roi_loc and gt_roi_label, -1 in
+ *   sample_src - so a caller that defers reading counts runs the head and the losses on defined memory.  An image with
+ *   R + gt_counts[b] == 0 candidates keeps nothing: counts[b] = (0, 0, 0, 0).
+ *   workspace:
+ *   tsod_proposal_targets_batch_workspace_bytes(B, R, Gmax, n_sample) = B * (2 align16(4 (R + Gmax)) + align16(4 n_sample))
+ *   = B * tsod_proposal_targets_workspace_bytes(R, Gmax, n_sample); 0 for B outside [1, 65535], R < 0, Gmax < 0, R + Gmax <= 0
+ *   or n_sample <= 0.
+ * Both refuse what the single-image entry points refuse (n_pos / pos_per_image > n_sample: TSOD_ERR_INVALID_ARG; anchor, roi,
+ * bbox, loc, sample_roi, gt_roi_loc or the workspace not 16-byte aligned: TSOD_ERR_ALIGNMENT / TSOD_ERR_WORKSPACE; a short
+ * workspace: TSOD_ERR_WORKSPACE) and B outside [1, 65535] (it is a grid dimension), before any launch; the anchor call also
+ * refuses pos_iou_thresh <= 0, with which an image without ground truth would have positives and no box to take offsets to. */
+size_t tsod_anchor_targets_batch_workspace_bytes(int32_t B, int32_t A, int32_t Gmax);
+int tsod_anchor_targets_batch_f32(const float *anchor, int32_t A, const float *bbox, const int32_t *gt_counts, int32_t B,
+                                  int32_t Gmax, float pos_iou_thresh, float neg_iou_thresh, int32_t n_pos, int32_t n_sample,
+                                  float *loc, int64_t *label, int32_t *argmax, void *workspace, size_t workspace_bytes,
+                                  tsod_stream_t stream);
+size_t tsod_proposal_targets_batch_workspace_bytes(int32_t B, int32_t R, int32_t Gmax, int32_t n_sample);
+int tsod_proposal_targets_batch_f32(const float *roi, int32_t R, const float *bbox, const int64_t *gt_label,
+                                    const int32_t *gt_counts, int32_t B, int32_t Gmax, int32_t n_sample, int32_t pos_per_image,
+                                    float pos_iou_thresh, float neg_iou_thresh_high, float neg_iou_thresh_low, float *sample_roi,
+                                    float *gt_roi_loc, int64_t *gt_roi_label, int32_t *counts, int32_t *sample_src,
+                                    void *workspace, size_t workspace_bytes, tsod_stream_t stream);
+
 /* ---- the losses of the ground-truth-conditioned forward (FasterRCNNTrainer, nets/frcnn_training.py:179-342) ----------
  * Both are additive restatements of the reference's loss arithmetic on the outputs of the kernels above; one workgroup per
  * image, sums in f64 in a fixed order (deterministic, no atomics, no workspace), each loss rounded once to f32.

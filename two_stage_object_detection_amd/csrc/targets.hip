@@ -41,11 +41,17 @@ __device__ __forceinline__ float4 bbox2loc_dev(const float4 s, const float4 d) {
     return make_float4((bcx - cx) / w, (bcy - cy) / h, logf(bw / w), logf(bh / h));
 }
 
+// Every kernel body below is a __device__ function over ONE image's pointers: the single-image kernel calls it as it is, the
+// batched kernel offsets the pointers by its image index, reads G from gt_counts and calls the same function - one body, the
+// same bits.  The bodies index with blockIdx.x only; the batched kernels keep the image on blockIdx.y (or, for the two
+// one-workgroup bodies, which never read blockIdx, on blockIdx.x), so a workgroup never straddles two images and every
+// __syncthreads() below is reached by all threads of its workgroup with the same per-image trip count.
+
 // row-wise torch.max(ious, dim=1): first maximum wins.  One thread per candidate box; the G ground-truth boxes are
 // walked through LDS in chunks of 256.  cand = concat(a [na], b [nb]) (ProposalTargetCreator appends the gt boxes).
-__global__ void __launch_bounds__(256)
-rowmax_kernel(const float4 *__restrict__ a, int na, const float4 *__restrict__ b, int nb,
-              const float4 *__restrict__ gt, int G, float eps, float *__restrict__ max_iou, int *__restrict__ argmax) {
+__device__ __forceinline__ void
+rowmax_image(const float4 *__restrict__ a, int na, const float4 *__restrict__ b, int nb,
+             const float4 *__restrict__ gt, int G, float eps, float *__restrict__ max_iou, int *__restrict__ argmax) {
     __shared__ float4 s_gt[256];
     const int n = blockIdx.x * 256 + threadIdx.x;
     const int N = na + nb;
@@ -65,9 +71,36 @@ rowmax_kernel(const float4 *__restrict__ a, int na, const float4 *__restrict__ b
     if (n < N) { max_iou[n] = best; argmax[n] = bi; }
 }
 
-// column-wise ious.argmax(dim=0): for every gt box the FIRST anchor of maximal IoU.  One workgroup per gt box.
 __global__ void __launch_bounds__(256)
-colargmax_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, float eps, int *__restrict__ gt_argmax) {
+rowmax_kernel(const float4 *__restrict__ a, int na, const float4 *__restrict__ b, int nb,
+              const float4 *__restrict__ gt, int G, float eps, float *__restrict__ max_iou, int *__restrict__ argmax) {
+    rowmax_image(a, na, b, nb, gt, G, eps, max_iou, argmax);
+}
+
+// gt_counts[b] clamped to [0, Gmax]; Gmax == 0: gt_counts is not read (it may be NULL)
+__device__ __forceinline__ int image_gt_count(const int *__restrict__ gt_counts, int b, int Gmax) {
+    return Gmax > 0 ? min(max(gt_counts[b], 0), Gmax) : 0;
+}
+
+// grid (ceil((na + Gmax) / 256) or ceil(na / 256), B).  Image b's candidates are concat(a + b * a_stride [na], gt[b][:G] when
+// append_gt); its row maxima go to max_iou + b * max_stride bytes, its arg-maxima to argmax + b * arg_stride bytes.  A workgroup
+// past this image's candidates leaves as a whole, before any barrier.
+__global__ void __launch_bounds__(256)
+rowmax_batch_kernel(const float4 *__restrict__ a, int na, size_t a_stride, int append_gt, const float4 *__restrict__ gt,
+                    const int *__restrict__ gt_counts, int Gmax, float eps, char *__restrict__ max_iou, size_t max_stride,
+                    char *__restrict__ argmax, size_t arg_stride) {
+    const int b = blockIdx.y;
+    const int G = image_gt_count(gt_counts, b, Gmax);
+    const int nb = append_gt ? G : 0;
+    if ((int)blockIdx.x * 256 >= na + nb) return;
+    const float4 *g = gt + (size_t)b * Gmax;
+    rowmax_image(a + b * a_stride, na, g, nb, g, G, eps, reinterpret_cast<float *>(max_iou + b * max_stride),
+                 reinterpret_cast<int *>(argmax + b * arg_stride));
+}
+
+// column-wise ious.argmax(dim=0): for every gt box the FIRST anchor of maximal IoU.  One workgroup per gt box.
+__device__ __forceinline__ void
+colargmax_image(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, float eps, int *__restrict__ gt_argmax) {
     __shared__ float s_v[4];
     __shared__ int s_i[4];
     const float4 g = gt[blockIdx.x];
@@ -89,6 +122,20 @@ colargmax_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restr
             if (s_v[w] > best || (s_v[w] == best && s_i[w] < bi)) { best = s_v[w]; bi = s_i[w]; }
         gt_argmax[blockIdx.x] = bi == INT_MAX ? 0 : bi;
     }
+}
+
+__global__ void __launch_bounds__(256)
+colargmax_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, float eps, int *__restrict__ gt_argmax) {
+    colargmax_image(anchor, A, gt, eps, gt_argmax);
+}
+
+// grid (Gmax, B): the surplus workgroups of an image (blockIdx.x >= its count) leave before touching memory
+__global__ void __launch_bounds__(256)
+colargmax_batch_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, const int *__restrict__ gt_counts,
+                       int Gmax, float eps, int *__restrict__ gt_argmax, size_t ws_stride /* ints */) {
+    const int b = blockIdx.y;
+    if ((int)blockIdx.x >= image_gt_count(gt_counts, b, Gmax)) return;
+    colargmax_image(anchor, A, gt + (size_t)b * Gmax, eps, gt_argmax + b * ws_stride);
 }
 
 // exclusive prefix of one int per thread over a 1024-thread workgroup (wave shuffles + 16 wave totals in LDS);
@@ -113,11 +160,11 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int *s_wave /* [17] *
     return s_wave[wave] + inc - v;
 }
 
-// _create_label (:70-103) + the override loop of _calc_ious (:61-63).  ONE workgroup: the positive cap is a prefix
+// _create_label (:70-103) + the override loop of _calc_ious (:61-63).  ONE workgroup per image: the positive cap is a prefix
 // count over all anchors in index order.
-__global__ void __launch_bounds__(1024)
-anchor_label_kernel(const float *__restrict__ max_iou, int *__restrict__ argmax, const int *__restrict__ gt_argmax, int A, int G,
-                    float pos_thr, float neg_thr, int n_pos, int n_sample, long long *__restrict__ label, int *__restrict__ flag) {
+__device__ __forceinline__ void
+anchor_label_image(const float *__restrict__ max_iou, int *__restrict__ argmax, const int *__restrict__ gt_argmax, int A, int G,
+                   float pos_thr, float neg_thr, int n_pos, int n_sample, long long *__restrict__ label, int *__restrict__ flag) {
     __shared__ int s_wave[17];
     const int tid = threadIdx.x;
     const int chunk = (A + 1023) / 1024;
@@ -157,23 +204,59 @@ anchor_label_kernel(const float *__restrict__ max_iou, int *__restrict__ argmax,
     if (tid == 0) *flag = pos_length > 0 ? 1 : 0;                      // (label > 0).any() (:33)
 }
 
-__global__ void __launch_bounds__(256)
-anchor_loc_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, const int *__restrict__ argmax,
-                  const int *__restrict__ flag, float4 *__restrict__ loc) {
+__global__ void __launch_bounds__(1024)
+anchor_label_kernel(const float *__restrict__ max_iou, int *__restrict__ argmax, const int *__restrict__ gt_argmax, int A, int G,
+                    float pos_thr, float neg_thr, int n_pos, int n_sample, long long *__restrict__ label, int *__restrict__ flag) {
+    anchor_label_image(max_iou, argmax, gt_argmax, A, G, pos_thr, neg_thr, n_pos, n_sample, label, flag);
+}
+
+// grid (B): workgroup b owns image b.  ws = this call's workspace, ws_stride bytes per image: max_iou [A], gt_argmax at
+// gt_argmax_off, flag at flag_off (the single-image layout, once per image).
+__global__ void __launch_bounds__(1024)
+anchor_label_batch_kernel(char *__restrict__ ws, size_t ws_stride, size_t gt_argmax_off, size_t flag_off, int *__restrict__ argmax,
+                          int A, const int *__restrict__ gt_counts, int Gmax, float pos_thr, float neg_thr, int n_pos, int n_sample,
+                          long long *__restrict__ label) {
+    const int b = blockIdx.x;
+    char *w = ws + b * ws_stride;
+    anchor_label_image(reinterpret_cast<const float *>(w), argmax + (size_t)b * A, reinterpret_cast<const int *>(w + gt_argmax_off), A,
+                       image_gt_count(gt_counts, b, Gmax), pos_thr, neg_thr, n_pos, n_sample, label + (size_t)b * A,
+                       reinterpret_cast<int *>(w + flag_off));
+}
+
+__device__ __forceinline__ void
+anchor_loc_image(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, const int *__restrict__ argmax,
+                 const int *__restrict__ flag, float4 *__restrict__ loc) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= A) return;
     loc[n] = *flag ? bbox2loc_dev(anchor[n], gt[argmax[n]]) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+__global__ void __launch_bounds__(256)
+anchor_loc_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, const int *__restrict__ argmax,
+                  const int *__restrict__ flag, float4 *__restrict__ loc) {
+    anchor_loc_image(anchor, A, gt, argmax, flag, loc);
+}
+
+// grid (ceil(A / 256), B).  A flag of 1 means the image has a positive, hence ground truth: gt is read only then.
+__global__ void __launch_bounds__(256)
+anchor_loc_batch_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, int Gmax,
+                        const int *__restrict__ argmax, const char *__restrict__ ws, size_t ws_stride, size_t flag_off,
+                        float4 *__restrict__ loc) {
+    const int b = blockIdx.y;
+    anchor_loc_image(anchor, A, gt + (size_t)b * Gmax, argmax + (size_t)b * A,
+                     reinterpret_cast<const int *>(ws + b * ws_stride + flag_off), loc + (size_t)b * A);
+}
+
 // ProposalTargetCreator.__call__ after the row maxima: thresholds, "first n by index" selection, gathers, bbox2loc,
-// labels and quirk T2.  ONE workgroup (the selection is a prefix count in index order).
-__global__ void __launch_bounds__(1024)
-proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__restrict__ gt, int G,
-                       const long long *__restrict__ gt_label, const float *__restrict__ max_iou, const int *__restrict__ assign,
-                       int n_sample, int pos_per_image, float pos_thr, float neg_hi, float neg_lo,
-                       float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc, long long *__restrict__ gt_roi_label,
-                       int *__restrict__ neg_orig /* [n_sample] scratch */, int *__restrict__ counts /* [4] */,
-                       int *__restrict__ sample_src /* [n_sample] or nullptr: the candidate each slot came from */) {
+// labels and quirk T2.  ONE workgroup per image (the selection is a prefix count in index order).  Returns S, the rows kept
+// (the same value in every thread).
+__device__ __forceinline__ int
+proposal_select_image(const float4 *__restrict__ roi, int R, const float4 *__restrict__ gt, int G,
+                      const long long *__restrict__ gt_label, const float *__restrict__ max_iou, const int *__restrict__ assign,
+                      int n_sample, int pos_per_image, float pos_thr, float neg_hi, float neg_lo,
+                      float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc, long long *__restrict__ gt_roi_label,
+                      int *__restrict__ neg_orig /* [n_sample] scratch */, int *__restrict__ counts /* [4] */,
+                      int *__restrict__ sample_src /* [n_sample] or nullptr: the candidate each slot came from */) {
     __shared__ int s_wave[17];
     const int tid = threadIdx.x;
     const int N = R + G;
@@ -224,6 +307,43 @@ proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__re
     }
     bad = __syncthreads_or(bad);
     if (tid == 0) { counts[0] = S; counts[1] = pos_len; counts[2] = neg_len; counts[3] = bad ? 1 : 0; }
+    return S;
+}
+
+__global__ void __launch_bounds__(1024)
+proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__restrict__ gt, int G,
+                       const long long *__restrict__ gt_label, const float *__restrict__ max_iou, const int *__restrict__ assign,
+                       int n_sample, int pos_per_image, float pos_thr, float neg_hi, float neg_lo,
+                       float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc, long long *__restrict__ gt_roi_label,
+                       int *__restrict__ neg_orig, int *__restrict__ counts, int *__restrict__ sample_src) {
+    proposal_select_image(roi, R, gt, G, gt_label, max_iou, assign, n_sample, pos_per_image, pos_thr, neg_hi, neg_lo, sample_roi,
+                          gt_roi_loc, gt_roi_label, neg_orig, counts, sample_src);
+}
+
+// grid (B): workgroup b owns image b.  ws_stride bytes of workspace per image: max_iou, assign at assign_off, neg_orig at
+// neg_off (the single-image layout at R + Gmax candidates).  The batched call alone defines the rows the image did not fill:
+// zeros (-1 in sample_src) from S to n_sample; no other thread writes those rows, so no barrier is needed before them.
+__global__ void __launch_bounds__(1024)
+proposal_select_batch_kernel(const float4 *__restrict__ roi, int R, const float4 *__restrict__ gt, const int *__restrict__ gt_counts,
+                             int Gmax, const long long *__restrict__ gt_label, char *__restrict__ ws, size_t ws_stride,
+                             size_t assign_off, size_t neg_off, int n_sample, int pos_per_image, float pos_thr, float neg_hi,
+                             float neg_lo, float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc,
+                             long long *__restrict__ gt_roi_label, int *__restrict__ counts, int *__restrict__ sample_src) {
+    const int b = blockIdx.x;
+    char *w = ws + b * ws_stride;
+    const size_t row = (size_t)b * n_sample;
+    int *src = sample_src != nullptr ? sample_src + row : nullptr;
+    const int S = proposal_select_image(roi + (size_t)b * R, R, gt + (size_t)b * Gmax, image_gt_count(gt_counts, b, Gmax),
+                                        gt_label + (size_t)b * Gmax, reinterpret_cast<const float *>(w),
+                                        reinterpret_cast<const int *>(w + assign_off), n_sample, pos_per_image, pos_thr, neg_hi,
+                                        neg_lo, sample_roi + row, gt_roi_loc + row, gt_roi_label + row,
+                                        reinterpret_cast<int *>(w + neg_off), counts + 4 * b, src);
+    for (int j = S + (int)threadIdx.x; j < n_sample; j += 1024) {
+        sample_roi[row + j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        gt_roi_loc[row + j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        gt_roi_label[row + j] = 0;
+        if (src != nullptr) src[j] = -1;
+    }
 }
 
 
@@ -326,6 +446,82 @@ extern "C" int tsod_proposal_targets_src_f32(const float *roi, int32_t R, const 
     return proposal_targets(roi, R, bbox, G, gt_label, n_sample, pos_per_image, pos_iou_thresh, neg_iou_thresh_high,
                             neg_iou_thresh_low, sample_roi, gt_roi_loc, gt_roi_label, counts, workspace, workspace_bytes,
                             sample_src, stream);
+}
+
+constexpr int kMaxBatch = 65535;                     // the image index rides on gridDim.y
+
+extern "C" size_t tsod_anchor_targets_batch_workspace_bytes(int32_t B, int32_t A, int32_t Gmax) {
+    if (B <= 0 || B > kMaxBatch) return 0;
+    return (size_t)B * tsod_anchor_targets_workspace_bytes(A, Gmax);
+}
+
+// the single-image call's four launches with the image index on a grid dimension; the workspace is the single-image layout
+// (at Gmax boxes) once per image
+extern "C" int tsod_anchor_targets_batch_f32(const float *anchor, int32_t A, const float *bbox, const int32_t *gt_counts,
+                                             int32_t B, int32_t Gmax, float pos_iou_thresh, float neg_iou_thresh, int32_t n_pos,
+                                             int32_t n_sample, float *loc, int64_t *label, int32_t *argmax, void *workspace,
+                                             size_t workspace_bytes, tsod_stream_t stream) {
+    TSOD_REQUIRE(anchor && loc && label && argmax && ((bbox && gt_counts) || Gmax == 0), TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(B > 0 && B <= kMaxBatch && A > 0 && Gmax >= 0 && n_pos >= 0 && n_sample >= 0, TSOD_ERR_INVALID_ARG);
+    // an image without ground truth has max_iou = 0 everywhere: with pos_iou_thresh <= 0 it would be all positives and the
+    // offsets would read a box that does not exist (the reference's bbox[argmax_ious] raises there)
+    TSOD_REQUIRE(pos_iou_thresh > 0.f, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(n_pos <= n_sample, TSOD_ERR_INVALID_ARG);           // (as tsod_anchor_targets_f32)
+    TSOD_REQUIRE(tsod_aligned16(anchor) && tsod_aligned16(loc) && (Gmax == 0 || tsod_aligned16(bbox)), TSOD_ERR_ALIGNMENT);
+    TSOD_REQUIRE(workspace && workspace_bytes >= tsod_anchor_targets_batch_workspace_bytes(B, A, Gmax) && tsod_aligned16(workspace),
+                 TSOD_ERR_WORKSPACE);
+    char *ws = static_cast<char *>(workspace);
+    const size_t stride = tsod_anchor_targets_workspace_bytes(A, Gmax);
+    const size_t gt_argmax_off = tsod_align_up((size_t)A * 4, 16);
+    const size_t flag_off = gt_argmax_off + tsod_align_up((size_t)(Gmax > 0 ? Gmax : 1) * 4, 16);
+    hipStream_t s = tsod_stream(stream);
+    const float4 *a4 = reinterpret_cast<const float4 *>(anchor), *g4 = reinterpret_cast<const float4 *>(bbox);
+    hipLaunchKernelGGL(rowmax_batch_kernel, dim3((A + 255) / 256, B), dim3(256), 0, s, a4, A, (size_t)0, 0, g4, gt_counts, Gmax,
+                       1e-8f, ws, stride, reinterpret_cast<char *>(argmax), (size_t)A * 4);
+    if (Gmax > 0)
+        hipLaunchKernelGGL(colargmax_batch_kernel, dim3(Gmax, B), dim3(256), 0, s, a4, A, g4, gt_counts, Gmax, 1e-8f,
+                           reinterpret_cast<int *>(ws + gt_argmax_off), stride / 4);
+    hipLaunchKernelGGL(anchor_label_batch_kernel, dim3(B), dim3(1024), 0, s, ws, stride, gt_argmax_off, flag_off, argmax, A,
+                       gt_counts, Gmax, pos_iou_thresh, neg_iou_thresh, n_pos, n_sample, reinterpret_cast<long long *>(label));
+    hipLaunchKernelGGL(anchor_loc_batch_kernel, dim3((A + 255) / 256, B), dim3(256), 0, s, a4, A, g4, Gmax, argmax, ws, stride,
+                       flag_off, reinterpret_cast<float4 *>(loc));
+    return tsod_launch_status();
+}
+
+extern "C" size_t tsod_proposal_targets_batch_workspace_bytes(int32_t B, int32_t R, int32_t Gmax, int32_t n_sample) {
+    if (B <= 0 || B > kMaxBatch) return 0;
+    return (size_t)B * tsod_proposal_targets_workspace_bytes(R, Gmax, n_sample);
+}
+
+// the single-image call's two launches with the image index on a grid dimension; sample_src may be NULL
+extern "C" int tsod_proposal_targets_batch_f32(const float *roi, int32_t R, const float *bbox, const int64_t *gt_label,
+                                               const int32_t *gt_counts, int32_t B, int32_t Gmax, int32_t n_sample,
+                                               int32_t pos_per_image, float pos_iou_thresh, float neg_iou_thresh_high,
+                                               float neg_iou_thresh_low, float *sample_roi, float *gt_roi_loc,
+                                               int64_t *gt_roi_label, int32_t *counts, int32_t *sample_src, void *workspace,
+                                               size_t workspace_bytes, tsod_stream_t stream) {
+    TSOD_REQUIRE(sample_roi && gt_roi_loc && gt_roi_label && counts, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(B > 0 && B <= kMaxBatch && R >= 0 && Gmax >= 0 && R + Gmax > 0 && n_sample > 0 && pos_per_image >= 0,
+                 TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(pos_per_image <= n_sample, TSOD_ERR_INVALID_ARG);   // (as tsod_proposal_targets_f32)
+    TSOD_REQUIRE((roi || R == 0) && ((bbox && gt_label && gt_counts) || Gmax == 0), TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE((R == 0 || tsod_aligned16(roi)) && (Gmax == 0 || tsod_aligned16(bbox)) && tsod_aligned16(sample_roi) &&
+                     tsod_aligned16(gt_roi_loc), TSOD_ERR_ALIGNMENT);
+    TSOD_REQUIRE(workspace && workspace_bytes >= tsod_proposal_targets_batch_workspace_bytes(B, R, Gmax, n_sample) &&
+                     tsod_aligned16(workspace), TSOD_ERR_WORKSPACE);
+    const int Nmax = R + Gmax;
+    char *ws = static_cast<char *>(workspace);
+    const size_t stride = tsod_proposal_targets_workspace_bytes(R, Gmax, n_sample);
+    const size_t assign_off = tsod_align_up((size_t)Nmax * 4, 16), neg_off = 2 * assign_off;
+    hipStream_t s = tsod_stream(stream);
+    const float4 *r4 = reinterpret_cast<const float4 *>(roi), *g4 = reinterpret_cast<const float4 *>(bbox);
+    hipLaunchKernelGGL(rowmax_batch_kernel, dim3((Nmax + 255) / 256, B), dim3(256), 0, s, r4, R, (size_t)R, 1, g4, gt_counts, Gmax,
+                       1e-8f, ws, stride, ws + assign_off, stride);
+    hipLaunchKernelGGL(proposal_select_batch_kernel, dim3(B), dim3(1024), 0, s, r4, R, g4, gt_counts, Gmax,
+                       reinterpret_cast<const long long *>(gt_label), ws, stride, assign_off, neg_off, n_sample, pos_per_image,
+                       pos_iou_thresh, neg_iou_thresh_high, neg_iou_thresh_low, reinterpret_cast<float4 *>(sample_roi),
+                       reinterpret_cast<float4 *>(gt_roi_loc), reinterpret_cast<long long *>(gt_roi_label), counts, sample_src);
+    return tsod_launch_status();
 }
 
 extern "C" int tsod_bbox2loc_f32(const float *src, const float *dst, int64_t n, float *out, tsod_stream_t stream) {

@@ -1498,6 +1498,74 @@ def proposal_targets(roi: torch.Tensor, bbox: torch.Tensor, label: torch.Tensor,
     return sample_roi, gt_roi_loc, gt_roi_label, counts
 
 
+def _batch_ground_truth(what: str, bbox: torch.Tensor, gt_counts: torch.Tensor, dev):
+    """Padded ground truth of a batched target call -> (bbox [B,Gmax,4] f32 contiguous, gt_counts [B] int32, B, Gmax), on ``dev``."""
+    if bbox.dim() != 3 or bbox.shape[2] != 4:
+        raise ValueError(f"{what}: bbox must be padded ground truth [B,Gmax,4], got {tuple(bbox.shape)}")
+    B, Gmax = bbox.shape[:2]
+    if not isinstance(gt_counts, torch.Tensor) or not gt_counts.is_cuda or tuple(gt_counts.shape) != (B,):
+        raise ValueError(f"{what}: gt_counts must be a [B={B}] integer tensor on the GPU (the kernels read it there)")
+    return bbox.to(dev, torch.float32).contiguous(), gt_counts.to(dev, torch.int32).contiguous(), B, Gmax
+
+
+def anchor_targets_batch(bbox: torch.Tensor, gt_counts: torch.Tensor, anchor: torch.Tensor, n_pos: int, n_sample: int,
+                         pos_iou_thresh: float, neg_iou_thresh: float):
+    """``anchor_targets`` for a whole batch in four launches (tsod_anchor_targets_batch_f32): anchor [A,4] shared by the
+    batch, bbox [B,Gmax,4] padded, gt_counts [B] int32 on the device (read there, clamped to [0, Gmax]; pad rows are never
+    read) -> (loc [B,A,4] f32, label [B,A] int64, argmax [B,A] int32).  Image b's rows are bit for bit
+    ``anchor_targets(bbox[b, :gt_counts[b]], anchor, ...)``.  No host synchronisation."""
+    require_cuda(anchor, "anchor_targets_batch")
+    dev = anchor.device
+    anchor = anchor.contiguous()
+    bbox, gt_counts, B, Gmax = _batch_ground_truth("anchor_targets_batch", bbox, gt_counts, dev)
+    A = anchor.shape[0]
+    loc = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
+    label = torch.empty((B, A), dtype=torch.int64, device=dev)
+    argmax = torch.empty((B, A), dtype=torch.int32, device=dev)
+    ws_bytes = lib().tsod_anchor_targets_batch_workspace_bytes(B, A, Gmax)
+    ws = ARENA.get(dev, ws_bytes)
+    check(lib().tsod_anchor_targets_batch_f32(ptr(anchor), A, ptr(bbox) if Gmax else None, ptr(gt_counts) if Gmax else None, B,
+                                              Gmax, float(pos_iou_thresh), float(neg_iou_thresh), int(n_pos), int(n_sample),
+                                              ptr(loc), ptr(label), ptr(argmax), ptr(ws), ws_bytes, stream_ptr()),
+          "anchor_targets_batch")
+    return loc, label, argmax
+
+
+def proposal_targets_batch(roi: torch.Tensor, bbox: torch.Tensor, label: torch.Tensor, gt_counts: torch.Tensor, n_sample: int,
+                           pos_per_image: int, pos_iou_thresh: float, neg_iou_thresh_high: float, neg_iou_thresh_low: float,
+                           want_src: bool = False):
+    """``proposal_targets`` / ``proposal_targets_src`` for a whole batch in two launches (tsod_proposal_targets_batch_f32):
+    roi [B,R,4], bbox [B,Gmax,4] and label [B,Gmax] padded, gt_counts [B] int32 on the device ->
+    (sample_roi [B,n_sample,4], gt_roi_loc [B,n_sample,4], gt_roi_label [B,n_sample] int64, counts [B,4] int32 = per image
+    (rows kept, positives, negatives, status), sample_src [B,n_sample] int32 or None).  The first counts[b,0] rows of image b
+    are bit for bit the single-image call's; the rows behind them are zeros (-1 in sample_src) - the single-image calls leave
+    those untouched.  Nothing is read back: ``counts`` stays on the device."""
+    require_cuda(roi, "proposal_targets_batch")
+    dev = roi.device
+    if roi.dim() != 3 or roi.shape[2] != 4:
+        raise ValueError(f"proposal_targets_batch: roi must be [B,R,4], got {tuple(roi.shape)}")
+    roi = roi.contiguous()
+    bbox, gt_counts, B, Gmax = _batch_ground_truth("proposal_targets_batch", bbox, gt_counts, dev)
+    if roi.shape[0] != B or tuple(label.shape) != (B, Gmax):
+        raise ValueError(f"proposal_targets_batch: roi {tuple(roi.shape)} / label {tuple(label.shape)} for bbox {tuple(bbox.shape)}")
+    label = label.to(dev, torch.int64).contiguous()
+    R = roi.shape[1]
+    sample_roi = torch.empty((B, n_sample, 4), dtype=torch.float32, device=dev)
+    gt_roi_loc = torch.empty((B, n_sample, 4), dtype=torch.float32, device=dev)
+    gt_roi_label = torch.empty((B, n_sample), dtype=torch.int64, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    src = torch.empty((B, n_sample), dtype=torch.int32, device=dev) if want_src else None
+    ws_bytes = lib().tsod_proposal_targets_batch_workspace_bytes(B, R, Gmax, n_sample)
+    ws = ARENA.get(dev, ws_bytes)
+    gt = [ptr(t) if Gmax else None for t in (bbox, label, gt_counts)]
+    check(lib().tsod_proposal_targets_batch_f32(ptr(roi) if R else None, R, *gt, B, Gmax, int(n_sample), int(pos_per_image),
+                                                float(pos_iou_thresh), float(neg_iou_thresh_high), float(neg_iou_thresh_low),
+                                                ptr(sample_roi), ptr(gt_roi_loc), ptr(gt_roi_label), ptr(counts),
+                                                ptr(src) if want_src else None, ptr(ws), ws_bytes, stream_ptr()),
+          "proposal_targets_batch")
+    return sample_roi, gt_roi_loc, gt_roi_label, counts, src
+
+
 def rpn_losses(rpn_out: torch.Tensor, A: int, gt_loc: torch.Tensor, gt_label: torch.Tensor, sigma: float = 1.0):
     """The RPN's two losses per image (tsod_rpn_losses_f32; nets/frcnn_training.py:220-238, 262-274).
     rpn_out [B*h*w, >= 6A] with row stride = pitch: the fused loc + score conv output (``RegionProposalNetwork.propose``),

@@ -8,6 +8,9 @@ classes produced):
     ProposalTargetCreator(n_sample, pos_ratio, pos_iou_thresh, neg_iou_thresh_high, neg_iou_thresh_low)
         (roi, bbox, label, loc_normalize_std) -> (sample_roi [S,4], gt_roi_loc [S,4], gt_roi_label [S] int64)
 
+Beyond the reference, both have ``batch``: the same assignment for every image of a batch in one pass (four and two launches
+for all of them, nothing read back), which is what ``FasterRCNNTrainer.forward`` calls.
+
 ``FasterRCNNTrainer`` (nets/frcnn_training.py:179-342) is the class the reference's scripts instantiate: its forward runs
 the detector conditioned on ground truth and returns the four losses, their sum and the head's per-RoI predictions
 (pinned by tests/golden/trainer_ref.npz, made by the reference's own class).  Its ``eval_fn`` / ``calculate_metrics``
@@ -16,6 +19,8 @@ calculate_metrics loops over an empty range and calls the one-argument compute_a
 reference mAP to match.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -26,7 +31,7 @@ from ..models.hardnet import HarNetClassifier
 from .classify import HarNetRoIHead
 from .frcnn import _UID, _make_extractor
 from .rpn import RegionProposalNetwork
-from ..utils.metrics import COCOEvaluator, DetectionEvaluator
+from ..utils.metrics import COCOEvaluator, DetectionEvaluator, pack_ground_truth
 
 
 def _check_pos_ratio(who, pos_ratio):
@@ -35,6 +40,75 @@ def _check_pos_ratio(who, pos_ratio):
     kernels do not restate that accident (they clamp at zero), and a negative ratio is a negative cap, so both are refused."""
     if not 0.0 <= pos_ratio <= 1.0:
         raise ValueError(f"{who}: pos_ratio must lie in [0, 1], got {pos_ratio}")
+
+
+class PackedGroundTruth(NamedTuple):
+    """A batch's ground truth as the batched target kernels take it (``pack_targets``): both creators' ``batch`` accept it in
+    place of ``bboxes``, so a caller packs and uploads once."""
+    boxes: torch.Tensor            # [B,Gmax,4] f32 on the device
+    labels: torch.Tensor           # [B,Gmax] on the device (any value in the pad rows)
+    counts: torch.Tensor           # [B] int32 on the device
+    host_counts: tuple             # the same numbers on the host, each in [0, Gmax]
+
+
+def host_gt_counts(gt_counts, bboxes, who):
+    """``gt_counts`` (a sequence of ints or a CPU integer tensor) checked on the host against padded ``bboxes`` [B,Gmax,4] ->
+    a tuple of B ints, each in [0, Gmax]; ValueError otherwise."""
+    if not isinstance(bboxes, torch.Tensor) or bboxes.dim() != 3:
+        raise ValueError(f"{who}: gt_counts goes with padded tensors [B,Gmax,4] / [B,Gmax], not with lists")
+    if isinstance(gt_counts, torch.Tensor) and gt_counts.is_cuda:
+        raise ValueError(f"{who}: gt_counts must be known on the host (a sequence of ints or a CPU integer tensor)")
+    host = tuple(int(v) for v in (gt_counts.tolist() if isinstance(gt_counts, torch.Tensor) else gt_counts))
+    B, Gmax = bboxes.shape[:2]
+    if len(host) != B:
+        raise ValueError(f"{who}: {len(host)} gt_counts for {B} images")
+    bad = [v for v in host if not 0 <= v <= Gmax]
+    if bad:
+        raise ValueError(f"{who}: gt_counts must lie in [0, Gmax = {Gmax}], got {bad[0]}")
+    return host
+
+
+def pack_targets(bboxes, labels, gt_counts, dev, who) -> PackedGroundTruth:
+    """Lists of [G_i,4] / [G_i] tensors, or padded [B,Gmax,4] / [B,Gmax] tensors with ``gt_counts`` (a sequence of ints or a CPU
+    integer tensor; None: every row counts) -> ``PackedGroundTruth`` on ``dev``.  Lists are packed by the evaluators' helper
+    (``utils.metrics.pack_ground_truth``).  ``labels=None``: zeros (the anchor targets do not read them).  ``gt_counts`` is
+    validated here, on the host: a value outside [0, Gmax] raises ValueError before anything is launched; it is uploaded
+    without blocking."""
+    if isinstance(bboxes, torch.Tensor):
+        bboxes = bboxes.to(dev, torch.float32)
+        if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+            raise ValueError(f"{who}: padded ground truth [B,Gmax,4], got {tuple(bboxes.shape)}")
+        B, Gmax = bboxes.shape[:2]
+        labels = torch.zeros((B, Gmax), dtype=torch.int64, device=dev) if labels is None else labels.to(dev)
+        host = (Gmax,) * B if gt_counts is None else host_gt_counts(gt_counts, bboxes, who)
+    else:
+        if gt_counts is not None:
+            host_gt_counts(gt_counts, bboxes, who)                   # (raises: lists carry their own counts)
+        bboxes = [b.to(dev, torch.float32) for b in bboxes]
+        labels = ([torch.zeros(b.shape[:1], dtype=torch.int64, device=dev) for b in bboxes] if labels is None else
+                  [lb.to(dev) for lb in labels])
+        B, host = len(bboxes), tuple(b.shape[0] for b in bboxes)
+    dtype = labels.dtype if isinstance(labels, torch.Tensor) else (labels[0].dtype if labels else torch.int64)
+    pb, pl, gc = pack_ground_truth(bboxes, labels, B, dev, None if gt_counts is None else torch.tensor(host, dtype=torch.int32),
+                                   who=who)
+    return PackedGroundTruth(pb, pl.to(dtype), gc, host)
+
+
+T2_INDEX_ERROR = ("index of a sampled negative is out of bounds for the kept labels "
+                  "(the reference raises IndexError at nets/frcnn_training.py:175)")
+Q5_TOO_FEW = ("ProposalTargetCreator kept {} samples for image {}, fewer than n_sample = {}: the reference's head fails on that "
+              "(quirk Q5)")
+
+
+def raise_for_counts(counts, n_sample=None):
+    """A host copy of ProposalTargetCreator's count words - rows of (kept, positives, negatives, status), one per image - into
+    the reference's exceptions, in image order: status 1 is the IndexError of quirk T2; with ``n_sample`` (the trainer), fewer
+    kept rows than that is the RuntimeError of quirk Q5."""
+    for i, (n_keep, _, _, status) in enumerate(counts):
+        if status:
+            raise IndexError(T2_INDEX_ERROR)
+        if n_sample is not None and n_keep < n_sample:
+            raise RuntimeError(Q5_TOO_FEW.format(n_keep, i, n_sample))
 
 
 class AnchorTargetCreator:
@@ -52,6 +126,19 @@ class AnchorTargetCreator:
         require_cuda(anchor, "AnchorTargetCreator")
         loc, label, _ = hip_ops.anchor_targets(bbox, anchor, int(self.pos_ratio * self.n_sample), self.n_sample,
                                                self.pos_iou_thresh, self.neg_iou_thresh)
+        return loc, label
+
+    def batch(self, bboxes, anchor, gt_counts=None):
+        """``__call__`` for every image of a batch at once: ``bboxes`` a list of [G_i,4] tensors, a padded [B,Gmax,4] tensor with
+        ``gt_counts`` (host ints, validated against Gmax here), or a ``PackedGroundTruth`` -> (loc [B,A,4], label [B,A]).
+        Image b's rows are bit for bit ``self(bboxes[b][:gt_counts[b]], anchor)``.  Four launches for the whole batch
+        (tsod_anchor_targets_batch_f32), no host synchronisation."""
+        _check_pos_ratio("AnchorTargetCreator", self.pos_ratio)
+        require_cuda(anchor, "AnchorTargetCreator.batch")
+        gt = bboxes if isinstance(bboxes, PackedGroundTruth) else pack_targets(bboxes, None, gt_counts, anchor.device,
+                                                                               "AnchorTargetCreator.batch")
+        loc, label, _ = hip_ops.anchor_targets_batch(gt.boxes, gt.counts, anchor, int(self.pos_ratio * self.n_sample),
+                                                     self.n_sample, self.pos_iou_thresh, self.neg_iou_thresh)
         return loc, label
 
 
@@ -73,10 +160,9 @@ class ProposalTargetCreator(object):
         sample_roi, gt_roi_loc, gt_roi_label, counts = hip_ops.proposal_targets(
             roi, bbox, label, self.n_sample, self.pos_roi_per_image, self.pos_iou_thresh, self.neg_iou_thresh_high,
             self.neg_iou_thresh_low)
-        n_keep, _, _, status = counts.tolist()
-        if status:
-            raise IndexError("index of a sampled negative is out of bounds for the kept labels "
-                             "(the reference raises IndexError at nets/frcnn_training.py:175)")
+        host = counts.tolist()
+        raise_for_counts([host])
+        n_keep = host[0]
         return sample_roi[:n_keep], gt_roi_loc[:n_keep], gt_roi_label[:n_keep].to(label.dtype)
 
     def with_sources(self, roi, bbox, label):
@@ -86,11 +172,27 @@ class ProposalTargetCreator(object):
         sample_roi, gt_roi_loc, gt_roi_label, counts, src = hip_ops.proposal_targets_src(
             roi, bbox, label, self.n_sample, self.pos_roi_per_image, self.pos_iou_thresh, self.neg_iou_thresh_high,
             self.neg_iou_thresh_low)
-        n_keep, _, _, status = counts.tolist()
-        if status:
-            raise IndexError("index of a sampled negative is out of bounds for the kept labels "
-                             "(the reference raises IndexError at nets/frcnn_training.py:175)")
+        host = counts.tolist()
+        raise_for_counts([host])
+        n_keep = host[0]
         return sample_roi[:n_keep], gt_roi_loc[:n_keep], gt_roi_label[:n_keep].to(label.dtype), src[:n_keep]
+
+    def batch(self, rois, bboxes, labels, gt_counts=None, with_sources=False):
+        """``__call__`` / ``with_sources`` for every image of a batch at once, WITHOUT reading anything back: rois [B,R,4];
+        ``bboxes`` / ``labels`` lists of [G_i,4] / [G_i] tensors, padded [B,Gmax,4] / [B,Gmax] tensors with ``gt_counts`` (host
+        ints, validated against Gmax here), or ``bboxes`` a ``PackedGroundTruth`` (``labels`` is then ignored) ->
+        (sample_roi [B,n_sample,4], gt_roi_loc [B,n_sample,4], gt_roi_label [B,n_sample], counts [B,4] int32 on the device,
+        sample_src [B,n_sample] int32 or None).  The first counts[b,0] rows of image b are bit for bit what ``__call__`` returns
+        for it; the rows behind them are zeros (-1 in sample_src).  Two launches for the whole batch
+        (tsod_proposal_targets_batch_f32).  Reading ``counts`` - and raising what the reference raises, ``raise_for_counts`` on
+        a host copy - stays with the caller: that is the point of this method."""
+        require_cuda(rois, "ProposalTargetCreator.batch")
+        gt = bboxes if isinstance(bboxes, PackedGroundTruth) else pack_targets(bboxes, labels, gt_counts, rois.device,
+                                                                               "ProposalTargetCreator.batch")
+        sample_roi, gt_roi_loc, gt_roi_label, counts, src = hip_ops.proposal_targets_batch(
+            rois, gt.boxes, gt.labels, gt.counts, self.n_sample, self.pos_roi_per_image, self.pos_iou_thresh,
+            self.neg_iou_thresh_high, self.neg_iou_thresh_low, want_src=with_sources)
+        return sample_roi, gt_roi_loc, gt_roi_label.to(gt.labels.dtype), counts, src
 
 
 HEAD_PARAMS = ("rpn.loc.weight", "rpn.loc.bias", "rpn.score.weight", "rpn.score.bias",
@@ -191,10 +293,18 @@ class FasterRCNNTrainer(nn.Module):
     ``imgs``: [B,3,H,W] on the GPU or a list of [3,H,W]; ``bboxes`` / ``labels``: lists (or batched tensors) of [G,4] / [G].
 
     The stages are the detector's own NHWC entry points, composed as ``FasterRCNN.forward`` composes them: the backbone
-    plan, ``rpn.propose`` (train numbers with mode="train": 12000 -> 600), per image the two target creators, the head's
-    fused GEMM on the stacked samples, then tsod_rpn_losses_f32 (reads the fused RPN output in place) and
-    tsod_roi_losses_f32.  The host synchronises where ProposalTargetCreator does, once per image, and reads the two
-    kernels' status words once after the last launch.
+    plan, ``rpn.propose`` (train numbers with mode="train": 12000 -> 600), the two target creators' ``batch`` - six launches
+    for all B images on ground truth packed once -, the head's fused GEMM on the [B, n_sample]
+    samples, then tsod_rpn_losses_f32 (reads the fused RPN output in place) and tsod_roi_losses_f32.  The host reads once per
+    forward, after the last launch: the creators' count words and the two loss kernels' status words in one transfer, from
+    which it raises what the reference raises - per image the IndexError of quirk T2, then the RuntimeError of quirk Q5, then
+    the losses' IndexError.  A creator that has been replaced by a plain callable (no ``batch``) puts the forward on the
+    per-image route: each image through both creators, one host synchronisation per image.
+
+    ``forward(..., gt_counts=c)`` (keyword-only): ``bboxes`` / ``labels`` are padded tensors [B,Gmax,4] / [B,Gmax] as a collate
+    function makes them and ``c`` (a sequence of ints or a CPU integer tensor, each in [0, Gmax]: ValueError otherwise, before
+    any launch) says how many rows of each image count; the rows behind them are never read.  The last two return values are
+    then cut to ``c[0]`` rows.
 
     Decisions (DESIGN.md "The trainer's forward"):
       * img_size: the reference hands imgs.shape[1:] = (C,H,W) to the RPN (quirk Q1) AND to the head (:252, quirk Q2 -
@@ -258,8 +368,8 @@ class FasterRCNNTrainer(nn.Module):
     ResNeXt's grouped 3x3 (``head_grads`` fine-tunes the heads
     on a frozen backbone, ``backbone_grads="tail"`` adds the backbone's tail, an int its last HarDBlocks, ``"full"`` the whole
     HarDNet; ``features=`` trains a
-    backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture
-    and tuning (the forward runs whatever plan the backbone holds).  ``eval_fn`` / ``calculate_metrics``: see there."""
+    backbone that has autograd of its own); gradients w.r.t. RoI coordinates; graph capture (the forward's one host read
+    is what is left in its way) and tuning (the forward runs whatever plan the backbone holds).  ``eval_fn`` / ``calculate_metrics``: see there."""
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
                  backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False, backbone_grads=None,
@@ -343,7 +453,44 @@ class FasterRCNNTrainer(nn.Module):
             raise ValueError(f"FasterRCNNTrainer.forward: features must be [B={B}, C={C}, h, w] (the RPN's in_channels), got "
                              f"{tuple(features.shape)}")
 
-    def forward(self, imgs, bboxes, labels, scale=1, *, features=None):
+    def _targets(self, bboxes, labels, gt_counts, anchor, rois, dev, want_src):
+        """Both target assignments of one forward -> (gt_loc [B,A,4], gt_label [B,A], sample_roi [B,n,4], gt_roi_loc [B,n,4],
+        gt_roi_label [B,n], sample_src [B,n] or None, counts [B,4] on the device or None).
+
+        When both creators offer ``batch`` the ground truth is packed once and each creator is called once for the whole batch:
+        six launches, nothing read back - ``counts`` is returned for the forward's one host read.  Otherwise (a creator replaced
+        by a plain callable) every image goes through the creators on its own, the host synchronising once per image where
+        ProposalTargetCreator does, and the exceptions are raised here; ``counts`` is then None."""
+        B, n_sample = len(bboxes), self.proposal_target_creator.n_sample
+        a_batch = getattr(self.anchor_target_creator, "batch", None)
+        p_batch = getattr(self.proposal_target_creator, "batch", None)
+        if a_batch is not None and p_batch is not None:
+            gt = pack_targets(bboxes, labels, gt_counts, dev, "FasterRCNNTrainer.forward")
+            gt_loc_all, gt_label_all = a_batch(gt, anchor)
+            s_roi, s_loc, s_label, counts, s_src = p_batch(rois, gt, None, with_sources=want_src)
+            return gt_loc_all, gt_label_all, s_roi, s_loc, s_label, s_src, counts
+        gt_locs, gt_labels, s_rois, s_locs, s_labels, s_srcs = [], [], [], [], [], []
+        for i in range(B):
+            g = bboxes[i].shape[0] if gt_counts is None else int(gt_counts[i])
+            bbox = bboxes[i][:g].to(dev, torch.float32)
+            label = labels[i][:g].to(dev)
+            gt_loc, gt_label = self.anchor_target_creator(bbox, anchor)
+            gt_locs.append(gt_loc)
+            gt_labels.append(gt_label)
+            if want_src:
+                s_roi, s_loc, s_label, s_src = self.proposal_target_creator.with_sources(rois[i], bbox, label)
+                s_srcs.append(s_src)
+            else:
+                s_roi, s_loc, s_label = self.proposal_target_creator(rois[i], bbox, label, self.loc_normalize_std)
+            if s_roi.shape[0] < n_sample:
+                raise RuntimeError(Q5_TOO_FEW.format(s_roi.shape[0], i, n_sample))
+            s_rois.append(s_roi)
+            s_locs.append(s_loc)
+            s_labels.append(s_label)
+        return (torch.stack(gt_locs), torch.stack(gt_labels), torch.stack(s_rois), torch.stack(s_locs), torch.stack(s_labels),
+                torch.stack(s_srcs) if want_src else None, None)
+
+    def forward(self, imgs, bboxes, labels, scale=1, *, features=None, gt_counts=None):
         if self.training and not self.bn_batch_stats:
             raise TsodError("the HIP path implements the inference forward only: call .eval() first")
         if features is None:
@@ -357,6 +504,8 @@ class FasterRCNNTrainer(nn.Module):
         B = shape[0]
         if len(bboxes) != B or len(labels) != B:
             raise ValueError(f"FasterRCNNTrainer.forward: {B} images, {len(bboxes)} box sets, {len(labels)} label sets")
+        if gt_counts is not None:                                        # on the host, before anything is launched
+            gt_counts = host_gt_counts(gt_counts, bboxes, "FasterRCNNTrainer.forward")
         img_size = shape[1:]                                             # (C,H,W): quirk Q1 (RPN), Q2 (head)
         head_size = img_size if self.head_img_size == "chw" else shape[2:]
         n_sample = self.proposal_target_creator.n_sample
@@ -396,40 +545,21 @@ class FasterRCNNTrainer(nn.Module):
             proposed = self.rpn.propose(feat, img_size, scale, want_anchors=True, feat_amax=feat_amax, range_flag=flag,
                                         want_index=grads or feat_grad)
             rpn_out, rois, anchor = proposed[:3]
-            gt_locs, gt_labels, s_rois, s_locs, s_labels, s_srcs = [], [], [], [], [], []
-            for i in range(B):
-                bbox = bboxes[i].to(dev, torch.float32)
-                label = labels[i].to(dev)
-                gt_loc, gt_label = self.anchor_target_creator(bbox, anchor)
-                gt_locs.append(gt_loc)
-                gt_labels.append(gt_label)
-                if grads or feat_grad:
-                    s_roi, s_loc, s_label, s_src = self.proposal_target_creator.with_sources(rois[i], bbox, label)
-                    s_srcs.append(s_src)
-                else:
-                    s_roi, s_loc, s_label = self.proposal_target_creator(rois[i], bbox, label, self.loc_normalize_std)
-                if s_roi.shape[0] < n_sample:
-                    raise RuntimeError(f"ProposalTargetCreator kept {s_roi.shape[0]} samples for image {i}, fewer than "
-                                       f"n_sample = {n_sample}: the reference's head fails on that (quirk Q5)")
-                s_rois.append(s_roi)
-                s_locs.append(s_loc)
-                s_labels.append(s_label)
-            gt_loc_all, gt_label_all = torch.stack(gt_locs), torch.stack(gt_labels)
+            (gt_loc_all, gt_label_all, sample_rois, s_locs_all, s_labels_all, sample_src, counts) = self._targets(
+                bboxes, labels, gt_counts, anchor, rois, dev, grads or feat_grad)
             rpn_loss, rpn_status = hip_ops.rpn_losses(rpn_out, self.rpn.anchor_base.shape[0], gt_loc_all, gt_label_all,
                                                       self.rpn_sigma)
-            sample_rois = torch.stack(s_rois)
             roi_indices = torch.arange(B, dtype=torch.int32, device=dev)
             fc7, both, n_loc, n_sc = self.head.forward_fused(feat, sample_rois, roi_indices, head_size, feat_amax=feat_amax,
                                                              range_flag=flag)
             roi_cls_locs, roi_scores = both[:, :n_loc].view(B, -1, n_loc), both[:, n_loc:n_loc + n_sc].view(B, -1, n_sc)
-            s_locs_all, s_labels_all = torch.stack(s_locs), torch.stack(s_labels)
             anchors_pred, classes_pred, classes_score_pred, roi_loss, roi_status = hip_ops.roi_losses(
                 roi_cls_locs, roi_scores, sample_rois, s_locs_all, s_labels_all, self.roi_sigma)
             if grads or feat_grad:
                 saved = dict(feat=feat.clone() if features is None else feat,   # (the plan's buffer: the next forward
                              rpn_out=rpn_out, anchor=anchor, sort_idx=proposed[3], keep_idx=proposed[4],  # overwrites it)
                              gt_loc=gt_loc_all, gt_label=gt_label_all, sample_roi=sample_rois, gt_roi_loc=s_locs_all,
-                             gt_roi_label=s_labels_all, sample_src=torch.stack(s_srcs), fc7=fc7, both=both,
+                             gt_roi_label=s_labels_all, sample_src=sample_src, fc7=fc7, both=both,
                              A=self.rpn.anchor_base.shape[0], n_class=n_sc, rpn_sigma=self.rpn_sigma,
                              roi_sigma=self.roi_sigma, inv_B=1.0 / B, clamp_x=img_size[1], clamp_y=img_size[2])
                 if feat_grad:
@@ -437,9 +567,15 @@ class FasterRCNNTrainer(nn.Module):
                                  head_wt=self.head._dgrad_weight(dev), roi_indices=roi_indices, head_size=head_size)
             if features is None:
                 self.feat_extra.publish_range_word(plan)
-        # (one read of the two status words, after the last launch: the reference raises IndexError there)
-        bad = rpn_status.sum() + roi_status.sum()
-        if int(bad):
+        # the one host read of the forward, after the last launch: the creators' count words (batched route) and the two loss
+        # kernels' status words together; the reference raises per image in the creator, then IndexError in the losses
+        if counts is None:
+            bad = int(rpn_status.sum() + roi_status.sum())
+        else:
+            host = torch.cat([counts.view(-1), rpn_status, roi_status]).tolist()
+            raise_for_counts([host[4 * i:4 * i + 4] for i in range(B)], n_sample)
+            bad = sum(host[4 * B:])
+        if bad:
             raise IndexError("a target class index is out of bounds for the logits it indexes "
                              "(the reference raises IndexError at nets/frcnn_training.py:274 / 313-331)")
         per = torch.cat([rpn_loss, roi_loss], dim=1).sum(0) / B        # [rpn_loc, rpn_cls, roi_loc, roi_cls]
@@ -449,8 +585,9 @@ class FasterRCNNTrainer(nn.Module):
         else:
             losses = list(per.unbind(0))
             losses = losses + [sum(losses)]
-        return (losses, anchors_pred, classes_pred, classes_score_pred, torch.unsqueeze(bboxes[0], dim=0),
-                torch.unsqueeze(labels[0] + 1, dim=0))
+        g0 = bboxes[0].shape[0] if gt_counts is None else int(gt_counts[0])    # (a host value: the cut costs no synchronisation)
+        return (losses, anchors_pred, classes_pred, classes_score_pred, torch.unsqueeze(bboxes[0][:g0], dim=0),
+                torch.unsqueeze(labels[0][:g0] + 1, dim=0))
 
     # ------------------------------------------------------------------------------------------------------- evaluation
     def _records(self, anchors_pred, classes_pred, classes_score_pred, nms_iou_threshold):

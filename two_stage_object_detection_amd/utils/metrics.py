@@ -39,12 +39,12 @@ COCO_AREA_RANGES = (("all", 0, 1e10), ("small", 0, 32 ** 2), ("medium", 32 ** 2,
 MAX_THRESHOLDS = 32
 
 
-def _as_list(x, what):
+def _as_list(x, what, who="DetectionEvaluator.update"):
     if isinstance(x, torch.Tensor):
         return None
     if isinstance(x, (list, tuple)):
         return list(x)
-    raise TypeError(f"DetectionEvaluator.update: {what} must be a tensor or a list of tensors, got {type(x).__name__}")
+    raise TypeError(f"{who}: {what} must be a tensor or a list of tensors, got {type(x).__name__}")
 
 
 def _aligned(t: torch.Tensor) -> torch.Tensor:
@@ -56,6 +56,51 @@ def _require_gpu(t, what):
     """require_cuda without its float32 rule (flags and labels)."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         require_cuda(t, what)
+
+
+def pack_ground_truth(gt_boxes, gt_labels, B, dev, gt_counts=None, who="DetectionEvaluator.update"):
+    """Ground truth as the kernels take it -> (boxes [B,G,4] f32, labels [B,G] int64, counts [B] int32), all on ``dev``.
+    Lists of [G_i,4] / [G_i] GPU tensors are padded to the largest G_i (zero boxes, label -1; the counts are uploaded without
+    blocking; lists of equal lengths are stacked, there is nothing to pad); padded tensors [B,G,4] / [B,G] pass through with
+    ``gt_counts`` (None: every row counts).  ``who`` names the caller in the messages.  Shared by both evaluators and the
+    trainer's batched target assignment."""
+    boxes, labels = _as_list(gt_boxes, "gt_boxes", who), _as_list(gt_labels, "gt_labels", who)
+    if (boxes is None) != (labels is None):
+        raise ValueError(f"{who}: gt_boxes and gt_labels are both lists or both tensors")
+    if boxes is not None:
+        if len(boxes) != B or len(labels) != B:
+            raise ValueError(f"{who}: {B} images, {len(boxes)} box sets, {len(labels)} label sets")
+        for bx, lb in zip(boxes, labels):
+            require_cuda(bx, who)
+            if not isinstance(lb, torch.Tensor) or not lb.is_cuda:
+                require_cuda(lb, who)
+            if bx.dim() != 2 or bx.shape[1] != 4 or lb.shape != bx.shape[:1]:
+                raise ValueError(f"{who}: ground truth [G,4] / [G], got {tuple(bx.shape)} / "
+                                 f"{tuple(lb.shape)}")
+        G = max(bx.shape[0] for bx in boxes)
+        if min(bx.shape[0] for bx in boxes) == G:                     # nothing to pad (B = 1 among them): one copy each
+            return (torch.stack(boxes).to(dev), torch.stack(labels).to(dev, torch.int64),
+                    torch.full((B,), G, dtype=torch.int32, device=dev))
+        pb = torch.zeros((B, G, 4), dtype=torch.float32, device=dev)
+        pl = torch.full((B, G), -1, dtype=torch.int64, device=dev)
+        for b in range(B):
+            g = boxes[b].shape[0]
+            pb[b, :g].copy_(boxes[b])
+            pl[b, :g].copy_(labels[b])
+        gc = torch.tensor([bx.shape[0] for bx in boxes], dtype=torch.int32).to(dev, non_blocking=True)
+        return pb, pl, gc
+    require_cuda(gt_boxes, who)
+    if not gt_labels.is_cuda:
+        require_cuda(gt_labels, who)
+    if gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 4 or tuple(gt_labels.shape) != tuple(gt_boxes.shape[:2]):
+        raise ValueError(f"{who}: padded ground truth [B,G,4] / [B,G] for B={B}, got "
+                         f"{tuple(gt_boxes.shape)} / {tuple(gt_labels.shape)}")
+    G = gt_boxes.shape[1]
+    if gt_counts is None:
+        gc = torch.full((B,), G, dtype=torch.int32, device=dev)
+    else:
+        gc = torch.as_tensor(gt_counts).to(dev, torch.int32, non_blocking=True).contiguous()
+    return _aligned(gt_boxes), gt_labels.to(dev, torch.int64).contiguous(), gc
 
 
 class DetectionEvaluator:
@@ -157,40 +202,7 @@ class DetectionEvaluator:
         return det, counts.to(det.device, torch.int32).contiguous(), None, None
 
     def _ground_truth(self, gt_boxes, gt_labels, B, dev, gt_counts):
-        boxes, labels = _as_list(gt_boxes, "gt_boxes"), _as_list(gt_labels, "gt_labels")
-        if (boxes is None) != (labels is None):
-            raise ValueError("DetectionEvaluator.update: gt_boxes and gt_labels are both lists or both tensors")
-        if boxes is not None:
-            if len(boxes) != B or len(labels) != B:
-                raise ValueError(f"DetectionEvaluator.update: {B} images, {len(boxes)} box sets, {len(labels)} label sets")
-            for bx, lb in zip(boxes, labels):
-                require_cuda(bx, "DetectionEvaluator.update")
-                if not isinstance(lb, torch.Tensor) or not lb.is_cuda:
-                    require_cuda(lb, "DetectionEvaluator.update")
-                if bx.dim() != 2 or bx.shape[1] != 4 or lb.shape != bx.shape[:1]:
-                    raise ValueError(f"DetectionEvaluator.update: ground truth [G,4] / [G], got {tuple(bx.shape)} / "
-                                     f"{tuple(lb.shape)}")
-            G = max(bx.shape[0] for bx in boxes)
-            pb = torch.zeros((B, G, 4), dtype=torch.float32, device=dev)
-            pl = torch.full((B, G), -1, dtype=torch.int64, device=dev)
-            for b in range(B):
-                g = boxes[b].shape[0]
-                pb[b, :g].copy_(boxes[b])
-                pl[b, :g].copy_(labels[b])
-            gc = torch.tensor([bx.shape[0] for bx in boxes], dtype=torch.int32).to(dev, non_blocking=True)
-            return pb, pl, gc
-        require_cuda(gt_boxes, "DetectionEvaluator.update")
-        if not gt_labels.is_cuda:
-            require_cuda(gt_labels, "DetectionEvaluator.update")
-        if gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 4 or tuple(gt_labels.shape) != tuple(gt_boxes.shape[:2]):
-            raise ValueError(f"DetectionEvaluator.update: padded ground truth [B,G,4] / [B,G] for B={B}, got "
-                             f"{tuple(gt_boxes.shape)} / {tuple(gt_labels.shape)}")
-        G = gt_boxes.shape[1]
-        if gt_counts is None:
-            gc = torch.full((B,), G, dtype=torch.int32, device=dev)
-        else:
-            gc = gt_counts.to(dev, torch.int32).contiguous()
-        return _aligned(gt_boxes), gt_labels.to(dev, torch.int64).contiguous(), gc
+        return pack_ground_truth(gt_boxes, gt_labels, B, dev, gt_counts)
 
     def update(self, det, gt_boxes, gt_labels, *, counts=None, keep=None, n_kept=None, gt_counts=None):
         self._update(det, gt_boxes, gt_labels, counts, keep, n_kept, gt_counts)
