@@ -883,6 +883,41 @@ int tsod_bn_prelu_train_grad_f32(const float *y, int32_t y_ld, int32_t y_off, co
                                  int32_t dz_ld, int32_t dz_off, float *dgamma, float *dbeta, float *dslope_num, float *g_out,
                                  int32_t g_ld, int32_t g_off, void *workspace, size_t workspace_bytes, tsod_stream_t stream);
 
+/* ---- active dropout: nn.Dropout(p) under .train() on channel slices of an NHWC buffer ----------------
+ * models/hardnet.py:182-183 (HarDNet-85: between the last HarDBlock and its transition ConvLayer).  The mask is the project's own
+ * definition (torch's stream depends on its launch shape): a logical tensor [N][H][W][C], C the REAL channels of the slices in
+ * the order of their `first` fields.
+ *     e    = e0 + ((n H + h) W + w) C + c                         (uint64)
+ *     word = lane (e & 3) of Philox4x32-10(counter (lo32(e >> 2), hi32(e >> 2), ordinal, 0), key (key[0], key[1]))
+ *     thr  = (uint64) llround((double)p * 4294967296.0)           keep iff (uint64) word >= thr
+ *     y    = keep ? x * scale : 0                                 scale = p < 1 ? (float)(1.0 / (1.0 - (double)p)) : 0.f
+ * (one f32 multiply; a dropped NaN is 0).  The mask depends on nothing else: not on pitches, channel padding, where the slices
+ * lie in the pixel, the grid or any chunking.  The backward is the same call on the gradient with the same key.
+ * tsod_dropout_segs_f32: slice s = channels [off, off + real) of every pixel of src [N][H][W][src_pitch] and dst
+ *   [N][H][W][dst_pitch], logical channels [first, first + real); `segs` is a HOST array of n_segs <=
+ *   TSOD_DROPOUT_MAX_SEGMENTS records that travels by value with the launch, `key` a DEVICE pointer to two uint32 words read by
+ *   the kernel (tsod_dropout_key_set writes them by a kernel of its own: stream-ordered, no copy).  dst == src is allowed
+ *   (otherwise the two must not overlap).  Lanes [real, real rounded up to 4) of a slice are written as 0 in dst and never read
+ *   from src; channels outside the slices are not touched.  16-byte accesses; a short last quad is loaded lane by lane.
+ *   TSOD_ERR_INVALID_ARG: a NULL pointer, a non-positive size, p outside [0, 1] or NaN, a slice that does not fit a pitch with its
+ *   pad lanes, logical channels beyond C, two slices that share a logical channel or a lane.  TSOD_ERR_ALIGNMENT: a pitch or
+ *   an offset that is no multiple of 4, src / dst not 16-byte or key not 4-byte aligned.  TSOD_ERR_UNSUPPORTED: n_segs >
+ *   TSOD_DROPOUT_MAX_SEGMENTS.
+ * tsod_dropout_params / tsod_philox4x32_host: HOST functions - (thr, scale) of p as above (TSOD_ERR_INVALID_ARG as above), and
+ *   the generator itself, ctr [4], key [2] -> out [4] (csrc/philox.h, the function the kernel calls). */
+#define TSOD_DROPOUT_MAX_SEGMENTS 16
+typedef struct tsod_dropout_seg {
+    int32_t off;   /* first channel of the slice in the pixel; multiple of 4 */
+    int32_t real;  /* real width, >= 1 */
+    int32_t first; /* first logical channel */
+} tsod_dropout_seg;
+int tsod_dropout_segs_f32(const float *src, float *dst, int32_t N, int32_t H, int32_t W, int32_t src_pitch, int32_t dst_pitch,
+                          const tsod_dropout_seg *segs, int32_t n_segs, int32_t C, float p, const uint32_t *key, uint32_t ordinal,
+                          uint64_t e0, tsod_stream_t stream);
+int tsod_dropout_key_set(uint32_t *key, uint32_t lo, uint32_t hi, tsod_stream_t stream);
+int tsod_dropout_params(float p, uint64_t *thr, float *scale);
+void tsod_philox4x32_host(const uint32_t *ctr, const uint32_t *key, uint32_t *out);
+
 /* ---- detection mAP: COCOeval's evaluateImg + accumulate, area range "all", no crowd / ignore flags ------
  * The reference's calculate_metrics (nets/frcnn_training.py:372-565) defines no usable metric; this is the project's own.
  * IoU is tsod_bbox_iou_f32's expression (eps 1e-8, no +1), compared as IoU >= t in f32.  Three steps:

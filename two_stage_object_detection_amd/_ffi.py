@@ -7,7 +7,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64,
+                    c_void_p)
 from typing import NamedTuple
 
 import torch
@@ -133,6 +134,12 @@ class PwSegs(Structure):
 
 ADAMW_CHUNK, ADAMW_MAX_GROUPS = 2048, 32         # TSOD_ADAMW_CHUNK, TSOD_ADAMW_MAX_GROUPS
 BN_ROWS_PER_WORKGROUP = 128                      # TSOD_BN_ROWS_PER_WORKGROUP: the rows one workgroup of bn_train.hip reduces
+DROPOUT_MAX_SEGMENTS = 16                        # TSOD_DROPOUT_MAX_SEGMENTS
+
+
+class DropoutSeg(Structure):
+    """Mirror of ``tsod_dropout_seg`` (include/tsod.h): a slice's channel offset in the pixel, real width, first logical channel."""
+    _fields_ = [("off", c_int32), ("real", c_int32), ("first", c_int32)]
 
 
 class AdamWGroup(Structure):
@@ -339,6 +346,11 @@ _SIGNATURES = {
                                              c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32,
                                              c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t,
                                              c_void_p]),
+    "tsod_dropout_segs_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                      c_float, c_void_p, c_uint32, c_uint64, c_void_p]),
+    "tsod_dropout_key_set": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p]),
+    "tsod_dropout_params": (c_int, [c_float, POINTER(c_uint64), POINTER(c_float)]),
+    "tsod_philox4x32_host": (None, [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
     "tsod_eval_match_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "tsod_eval_match_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,

@@ -320,6 +320,7 @@ class Plan:
         self.bn_steps: list = []             # (launch, where its two workspace arguments are, M, C_pad) per statistics launch
         self.bn_bound: list = []             # (module, attribute, pointer) of every tensor of a BatchNorm module a launch holds
         self.bn_workspace: torch.Tensor | None = None
+        self.dropout_key: torch.Tensor | None = None             # int32 [2]: the key words the plan's dropout launches read (4.26)
         self.graph = None
         # fp16x2 layers OR 1 into this word when a launch ends with non-finite accumulators (include/tsod.h: range_flag);
         # a PlanOwner hands its plans one word per (device, in-flight slot) out of a tensor of its own (PlanOwner._new_plan): the
@@ -1209,6 +1210,9 @@ class PlanOwner:
         """True where the plan about to be built is one for ``.train()`` (HarDNet's batch-statistics BatchNorm)."""
         return False
 
+    def _before_train_run(self, plan) -> None:
+        """What a training forward writes per call where the plan's launches read it (HarDNet: the dropout key)."""
+
     def _plan_for(self, x, slot: int = 0) -> "Plan":
         _ffi.require_cuda(x, type(self).__name__ + ".forward")
         if x.dim() != 4 or x.shape[1] != 3:
@@ -1231,6 +1235,7 @@ class PlanOwner:
                 del self._plans[key]
             plan = self._plan_for(x, slot)
         stage_input(plan, x)
+        self._before_train_run(plan)
         plan.run()
         self.publish_range_word(plan)                            # (fp16x2 range violations of this forward: raise_if_error)
         if batch_stats:                                          # the launches wrote the section's buffers: torch must know

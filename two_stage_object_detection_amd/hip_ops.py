@@ -998,6 +998,55 @@ class _DWConv3x3(torch.autograd.Function):
                 dshift if need[3] and sh is not None else None, None, None)
 
 
+def dropout_key(device, lo: int, hi: int, out=None) -> torch.Tensor:
+    """The two 32-bit key words of a dropout mask in device memory (an int32 [2] tensor; ``out``: written in place), by a kernel
+    of tsod_dropout_key_set: stream-ordered, no copy, no synchronisation."""
+    key = torch.empty(2, dtype=torch.int32, device=device) if out is None else out
+    if not key.is_cuda or key.dtype != torch.int32 or key.numel() != 2 or not key.is_contiguous():
+        raise ValueError("dropout_key: the key is a contiguous int32 [2] tensor on the GPU")
+    check(lib().tsod_dropout_key_set(ptr(key), int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, stream_ptr()), "dropout_key_set")
+    return key
+
+
+def dropout_seg_table(segs):
+    """[(channel offset in the pixel, real width, first logical channel)] -> the ``tsod_dropout_seg`` array of the launch."""
+    table = (_ffi.DropoutSeg * max(1, len(segs)))()
+    for t, (off, real, first) in zip(table, segs):
+        t.off, t.real, t.first = int(off), int(real), int(first)
+    return table
+
+
+def dropout(x: torch.Tensor, p: float, key, *, segs=None, C=None, out=None, ordinal: int = 0, e0: int = 0) -> torch.Tensor:
+    """Active dropout (tsod_dropout_segs_f32): out = keep ? x / (1 - p) : 0 on channel slices of the NHWC
+    tensor x [..., P], the mask from Philox4x32-10 words of every element's index in the LOGICAL tensor [pixels, C].
+
+    ``key``: an int32 [2] device tensor (``dropout_key``) or two ints.  ``segs``: [(channel offset in the pixel, real width, first
+    logical channel)], ``C`` the logical channels; default: the whole pixel as one slice (P % 4 == 0).  ``out`` [..., Pd]
+    (default: like x, untouched outside the slices - zeros where it is allocated here): ``out is x`` works in place.  Lanes
+    between a slice's real and padded width become 0.  The backward is the same call on the gradient with the same key."""
+    require_cuda(x, "dropout")
+    if not x.is_contiguous() or x.dim() < 2:
+        raise ValueError("dropout: x must be a contiguous [..., P] tensor")
+    P = x.shape[-1]
+    if segs is None:
+        segs, C = [(0, P, 0)], P
+    if C is None:
+        C = sum(real for _, real, _ in segs)
+    if out is None:
+        out = torch.zeros_like(x)
+    require_cuda(out, "dropout")
+    if not out.is_contiguous() or out.shape[:-1] != x.shape[:-1]:
+        raise ValueError(f"dropout: out must be contiguous with x's leading dimensions, got {tuple(out.shape)} for {tuple(x.shape)}")
+    if not isinstance(key, torch.Tensor):
+        key = dropout_key(x.device, *key)
+    if not key.is_cuda or key.dtype != torch.int32 or key.numel() != 2:
+        raise ValueError("dropout: key is an int32 [2] tensor on the GPU or two ints")
+    N, H, W = x.shape[:3] if x.dim() == 4 else (1, 1, x.numel() // P)
+    check(lib().tsod_dropout_segs_f32(ptr(x), ptr(out), N, H, W, P, out.shape[-1], dropout_seg_table(segs), len(segs), int(C), float(p),
+                                      ptr(key), int(ordinal), int(e0), stream_ptr()), "dropout")
+    return out
+
+
 def gconv1x1_pair_grad(x, w_g2, d_out, *, want_dx=True, want_dw=True, want_dbias=True):
     """The backward of ``gconv1x1_pair_nhwc`` (tsod_gconv1x1_pair_grad_f32) -> (d x [..., 2G], dw [G,2], dbias [G]; None where
     not wanted).  x [..., P] with P >= 2G, d_out [..., G] contiguous."""

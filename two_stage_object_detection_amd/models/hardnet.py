@@ -210,6 +210,9 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
     _train_mode = None           # set_train_mode(): a plain instance attribute once set - pickled and deep-copied, never in
                                  # the state_dict
     _batch_stats = False         # set_train_mode(batch_stats=): likewise
+    _dropout = False             # set_train_mode(dropout=): likewise
+    dropout_generator = None     # a CPU torch.Generator the dropout keys are drawn from (None: torch.default_generator)
+    last_dropout_key = None      # (key_lo, key_hi) of the last forward that ran with active dropout
     _grads = hardnet_grads       # (PlanOwner._forward_train: its refresh_packs and feature_map_with_grads)
 
     def __init__(self, depth_wise=True, arch=39):
@@ -315,7 +318,7 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
             return 0
         return self._tail_indices()[0] if mode in (None, "tail") else self._block_indices()[-mode]
 
-    def set_train_mode(self, mode, batch_stats=False):
+    def set_train_mode(self, mode, batch_stats=False, dropout=False):
         """How much of the backbone is differentiable: None (nothing, the default), "tail" (the last four modules of ``base``:
         the two depthwise 3x3 stride-2 convs, the ReLU between them, the grouped 1x1), ``n`` >= 1 (the tail and the last ``n``
         HarDBlocks: every ``CombConvLayer`` of those blocks, each block's transition ``ConvLayer``, any ``DWConvLayer`` between
@@ -358,23 +361,43 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         tsod_bn_apply_f32 write where the folded launch wrote; the backward runs tsod_bn_train_grad_f32
         on the masked gradient and feeds dz to the conv backward with unit scale.  The records then carry ``bnt`` / ``dw_bnt`` /
         ``bnt0`` (``z``, ``mean``, ``invstd``, ``gamma``, ``C``) where they carried ``bn`` / ``dw_bn`` / ``bn0`` (then None), and
-        ``scale`` is ones.  A difference from the reference: the ``nn.Dropout`` modules of ``base`` (HarDNet-85) stay the
-        identity, as on every other path.  Under ``.train()`` with grad mode off, or without ``batch_stats``, the forward raises
-        ``call .eval() first`` as before.  A BatchNorm of the section with ``momentum=None`` or ``track_running_stats=False``:
-        NotImplementedError here.  Memory on top of the mode's: the raw z of every BatchNorm of the section, N x h x w x C_pad
-        floats each, twice (plan and node) - for ``n = 1``, HarDNet-39, 600 x 600, batch 1: 150 x 150 pixels x (2 x 988 + 1 024)
-        channels x 4 B = 270 MB, twice."""
+        ``scale`` is ones.  Without ``dropout`` the ``nn.Dropout`` modules of ``base`` (HarDNet-85) stay the identity, as on
+        every other path - a difference from the reference.  Under ``.train()`` with grad mode off, or without ``batch_stats``,
+        the forward raises ``call .eval() first`` as before.  A BatchNorm of the section with ``momentum=None`` or
+        ``track_running_stats=False``: NotImplementedError here.  Memory on top of the mode's: the raw z of every BatchNorm of
+        the section, N x h x w x C_pad floats each, twice (plan and node) - for ``n = 1``, HarDNet-39, 600 x 600, batch 1:
+        150 x 150 pixels x (2 x 988 + 1 024) channels x 4 B = 270 MB, twice.
+
+        ``dropout=True`` (only with ``batch_stats=True``, i.e. modes ``n`` and "full": ValueError otherwise - nothing else runs
+        under ``.train()``) makes the ``nn.Dropout`` modules of the mode's section active wherever the batch-statistics variant
+        runs: the transition ConvLayer behind such a module (HarDNet-85: ``base.18`` behind the last
+        HarDBlock and ``base.17`` = ``nn.Dropout(0.1)``; ``p`` is read when the plan is built) and its weight gradient read a
+        DROPPED copy of the block's output slices (tsod_dropout_segs_f32: a Philox4x32-10 mask of the logical concatenated
+        tensor, kept values times 1 / (1 - p)) at the same slice offsets, the layers inside the block keep reading the block buffer itself, and the
+        backward masks the transition's input gradient in place with the same key before anything else adds to the block's
+        gradient buffer.  Every such forward draws one 64-bit key on the host - from ``self.dropout_generator`` (a CPU
+        ``torch.Generator``) if one is assigned, else ``torch.default_generator`` - without any device synchronisation, a kernel
+        puts its two words where the plan's launches read them, the node keeps its own copy, and ``self.last_dropout_key`` =
+        (lo, hi) afterwards.  No mask is stored: the node holds the key (``blocks[i]["dropout"]``: ``p``, ``ordinal``, ``segs``,
+        ``C``, ``key``) and makes the dropped copy again from its copy of the block buffer when the backward runs.  Memory on top
+        of ``batch_stats``: one more buffer of the block buffer's shape in the plan and one for the duration of the backward -
+        HarDNet-85, 600 x 600, batch 1: 150 x 150 pixels x 2 408 channels x 4 B = 217 MB each; nothing more in the node.
+        Where the section holds no ``nn.Dropout`` with p > 0 (HarDNet-39 / 68), under ``.eval()`` and with grad mode off the flag
+        changes nothing: same plan-cache keys, same launches, same bits."""
         if mode not in (None, "tail", "full"):
             mode = int(mode)
             if mode < 1 or mode > self.n_blocks:
                 raise ValueError(f"train_blocks: n must be 0..{self.n_blocks} (the HarDBlocks of this backbone), got {mode}")
+        if dropout and (not batch_stats or mode in (None, "tail")):
+            raise ValueError("dropout=True needs batch_stats=True and a mode with BatchNorm (a number of HarDBlocks or 'full'): "
+                             f"only the batch-statistics variant runs under .train(); got mode={mode!r}, batch_stats={batch_stats!r}")
         batch_stats = bool(batch_stats) and mode not in (None, "tail")
         if batch_stats:
             for name, bn in self._section_norms(self._mode_start(mode)):
                 if bn.momentum is None or not bn.track_running_stats or not bn.affine:
                     raise NotImplementedError(f"batch_stats: {name} has momentum=None, track_running_stats=False or affine=False; "
                                               "only the reference's BatchNorm2d (momentum, running statistics, affine) is built")
-        self._train_mode, self._batch_stats = mode, batch_stats
+        self._train_mode, self._batch_stats, self._dropout = mode, batch_stats, bool(dropout)
         if mode is not None:                                     # the widest mode ever set: where the refresh starts
             self.__dict__["_watch_from"] = min(self._mode_start(mode), self.__dict__.get("_watch_from", len(self.base)))
         return self
@@ -386,20 +409,21 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         the node is freed; the plan for grad mode off is a second plan of the same shape."""
         return self.set_train_mode((self._train_mode or "tail") if enabled else None)
 
-    def train_blocks(self, n: int, batch_stats=False):
-        """``set_train_mode(n, batch_stats)``; ``n = 0`` is "tail".  The stem is never reached (``train_full`` adds it).
+    def train_blocks(self, n: int, batch_stats=False, dropout=False):
+        """``set_train_mode(n, batch_stats, dropout)``; ``n = 0`` is "tail".  The stem is never reached (``train_full`` adds it).
         Memory: the plan keeps the section's block buffers, 1x1 outputs and transition outputs out of its pool and the node
         copies them, per block N x h x w x (P + sum of the layers' padded widths + the transition's width) floats: for
         ``n = 1``, HarDNet-39, 600 x 600, batch 1 that is 150 x 150 pixels x (1 628 + 988 + 1 024) channels x 4 B = 328 MB,
         twice (plan and node), plus one zeroed gradient buffer of the block buffer's size per block during the backward."""
-        return self.set_train_mode(int(n) or "tail", batch_stats)
+        return self.set_train_mode(int(n) or "tail", batch_stats, dropout)
 
-    def train_full(self, batch_stats=False):
-        """``set_train_mode("full", batch_stats)``: ``trainable_parameters()`` is then every parameter of the module in ``base`` order.
+    def train_full(self, batch_stats=False, dropout=False):
+        """``set_train_mode("full", batch_stats, dropout)``: ``trainable_parameters()`` is then every parameter of the module in
+        ``base`` order.
         Memory on top of ``train_blocks(all)``: N x H x W x 4 floats of image and N x H/2 x W/2 x (c0 + c1) floats of stem
         outputs, twice (plan and node), plus one gradient buffer of ``base.0``'s output during the backward: HarDNet-39 at
         600 x 600, batch 1: 5.8 + 25.9 MB; at 800 x 1333, batch 8: 137 + 615 MB."""
-        return self.set_train_mode("full", batch_stats)
+        return self.set_train_mode("full", batch_stats, dropout)
 
     def trainable_parameters(self):
         """The parameters the feature map's autograd node reaches, in ``base`` order: everything from the first module of the
@@ -421,12 +445,28 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         """The batch-statistics variant is on: ``batch_stats`` set, ``.train()``, grad mode on."""
         return self._batch_stats and self.training and self._active_mode() not in (None, "tail")
 
+    def _drops_in_plan(self) -> bool:
+        """Active dropout is on: ``dropout`` set, the batch-statistics variant on, and an ``nn.Dropout`` with p > 0 in the section."""
+        return (self._dropout and self._trains_in_plan()
+                and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.base[self._mode_start(self._active_mode()):]))
+
+    def _before_train_run(self, plan):
+        """One 64-bit key per training forward with active dropout: drawn on the host, written by a kernel where the plan's
+        dropout launches read it (stream-ordered, no synchronisation)."""
+        if plan.dropout_key is not None:
+            gen = self.dropout_generator if self.dropout_generator is not None else torch.default_generator
+            lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64, generator=gen).tolist()
+            hip_ops.dropout_key(plan.device, lo, hi, out=plan.dropout_key)
+            self.last_dropout_key = (lo, hi)
+
     def _plan_variant(self):
         mode = self._active_mode()
         if mode is None:
             return ()
         key = ("train_" + mode,) if isinstance(mode, str) else ("train_blocks", mode)
-        return key + ("batch_stats",) if self._trains_in_plan() else key
+        if self._trains_in_plan():
+            key += ("batch_stats", "dropout") if self._drops_in_plan() else ("batch_stats",)
+        return key
 
     def _mode_norms(self):
         return self._section_norms(self._mode_start(self._train_mode))
@@ -453,6 +493,7 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
         # the batch-statistics variant (section 4.20): a BatchNorm at base[i], i >= start, runs as conv with identity epilogue ->
         # raw z (kept for the node, outside the pool) -> tsod_bn_stats_f32 -> tsod_bn_apply_f32 into the folded launch's place
         batch_stats = plan.batch_stats = self._trains_in_plan()
+        drops, n_dropouts = self._drops_in_plan(), 0             # (n_dropouts: the nn.Dropout modules met so far = the next ordinal)
 
         def pack(name, raw=False):
             pc = plan.packed(name, lambda: units[name].make(device))
@@ -572,14 +613,28 @@ class HarDNetFeatureExtraction(PlanOwner, nn.Module):
                 # transition 1x1 conv gathers the block's output slices (oldest first)
                 outs = m.output_slices()
                 i += 1
+                src = buf
                 if isinstance(mods[i], nn.Dropout):
+                    if drops and rec is not None and mods[i].p > 0:
+                        # active dropout (section 4.26): the transition reads a dropped copy of the output slices, at their offsets
+                        if plan.dropout_key is None:
+                            plan.dropout_key = torch.zeros(2, dtype=torch.int32, device=device)
+                        dsegs, C_out = [], 0
+                        for k in outs:                           # (offset in the pixel, real width, first logical channel)
+                            dsegs.append((offs[k], real[k], C_out))
+                            C_out += real[k]
+                        src, table = torch.empty_like(buf), hip_ops.dropout_seg_table(dsegs)
+                        plan.call(L.tsod_dropout_segs_f32, ptr(buf), ptr(src), N, h, w, P, P, table, len(dsegs), C_out, float(mods[i].p),
+                                  ptr(plan.dropout_key), n_dropouts, 0, keep=(buf, src, table, plan.dropout_key))
+                        rec["dropout"] = dict(p=float(mods[i].p), ordinal=n_dropouts, segs=dsegs, C=C_out, key=plan.dropout_key)
+                    n_dropouts += 1
                     i += 1
                 rc = pack(f"base.{i}", batch_stats and rec is not None)
                 dst, dst_off = dest_for(i + 1, rc.cout, h, w)
                 if isinstance(mods[i + 1], DWConvLayer):          # "downsample" dw3x3 at stride 1 follows
                     plan.pool.release(dst)
                     dst, dst_off = plan.pool.alloc((N, h, w, rc.cout)), 0
-                bnt = conv_bn(f"base.{i}", mods[i], rc, buf, dst, dst_off, rc.cout_real, batch_stats and rec is not None,
+                bnt = conv_bn(f"base.{i}", mods[i], rc, src, dst, dst_off, rc.cout_real, batch_stats and rec is not None,
                               segs=[(offs[k], _pad4(real[k])) for k in outs])
                 if rec is not None:
                     # (the last block's transition output is the tail's first input: its mask is taken there)

@@ -10,7 +10,9 @@ the copies the node keeps of what ``build_plan`` recorded, and the refresh of th
     = (input, channel offset) where no 1x1 record holds that input as its ``y`` (the tail), else None.
 Where the layer's BatchNorm ran on batch statistics the record carries ``bnt`` (1x1) / ``dw_bnt``
 (depthwise) = ``z`` (the conv's raw output [N,h,w,C_pad]), ``mean``, ``invstd``, ``gamma`` (the module's ``weight``), ``C``; its
-pack then has unit scale and ``bn`` / ``dw_bn`` are None."""
+pack then has unit scale and ``bn`` / ``dw_bn`` are None.  A block whose transition read a dropped copy of its output slices
+(active dropout) carries ``dropout``: ``p``, ``ordinal``, ``segs`` [(channel offset, real width, first
+logical channel)], ``C`` and ``key`` (the plan's two key words; the node clones them)."""
 from __future__ import annotations
 
 import torch
@@ -123,7 +125,17 @@ class _BackboneGrads(torch.autograd.Function):
             dbuf = torch.zeros_like(buf)
             tr = blk["transition"]
             skip0 = first and stem is None                        # the first block's input slice: wanted by the stem only
-            pw_layer(f"base.{tr['index']}", buf, tr, g, dbuf, [not (skip0 and k == 0) for k in tr["slices"]])
+            drop = blk.get("dropout")
+            if drop is None:
+                pw_layer(f"base.{tr['index']}", buf, tr, g, dbuf, [not (skip0 and k == 0) for k in tr["slices"]])
+            else:
+                # active dropout (section 4.26): the transition read a dropped copy of its slices - made again here from the
+                # node's key - and its input gradient, the first thing written into dbuf, passes the same mask in place
+                mask = dict(segs=drop["segs"], C=drop["C"], ordinal=drop["ordinal"])
+                xd = hip_ops.dropout(buf, drop["p"], drop["key"], out=torch.empty_like(buf), **mask)
+                pw_layer(f"base.{tr['index']}", xd, tr, g, dbuf, [not (skip0 and k == 0) for k in tr["slices"]])
+                del xd
+                hip_ops.dropout(dbuf, drop["p"], drop["key"], out=dbuf, **mask)
             for li in range(len(blk["layers"]), 0, -1):
                 lay = blk["layers"][li - 1]
                 prefix = f"base.{blk['index']}.layers.{li - 1}"
@@ -170,7 +182,8 @@ def feature_map_with_grads(plan, nchw, named):
                  inputs=[t["x"] for t in tail], packs=[t["dw"] for t in tail], tail_indices=tuple(t["index"] for t in tail),
                  C=tail[0]["C"],
                  blocks=[dict(index=b["index"], buf=b["buf"].clone(), layers=[{**dw_copy(d), **pw_copy(p)} for p, d in b["layers"]],
-                              transition=pw_copy(b["transition"]), down=None if b["down"] is None else dw_copy(b["down"]))
+                              transition=pw_copy(b["transition"]), down=None if b["down"] is None else dw_copy(b["down"]),
+                              dropout=None if b.get("dropout") is None else dict(b["dropout"], key=b["dropout"]["key"].clone()))
                          for b in plan.block_records])
     if plan.stem_record is not None:
         sr = plan.stem_record

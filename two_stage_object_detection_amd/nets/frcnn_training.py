@@ -338,7 +338,13 @@ class FasterRCNNTrainer(nn.Module):
     contract for the trainable section - ``forward`` is then allowed under ``.train()``, the mode is set with
     ``batch_stats=True`` and every BatchNorm the mode reaches normalises with the statistics of the batch, backpropagates
     through them and moves its running statistics (``HarDNetFeatureExtraction.set_train_mode``); the
-    frozen section below stays folded, dropout stays the identity.  Under ``.eval()`` nothing changes.
+    frozen section below stays folded.  Under ``.eval()`` nothing changes.
+
+    ``dropout=True`` (keyword-only, needs ``bn_batch_stats=True``: ValueError otherwise): the mode is set with ``dropout=True``
+    too, so the ``nn.Dropout`` of the trainable section (HarDNet-85: p = 0.1 in front of the last transition layer) is active
+    under ``.train()`` - a Philox mask on HIP with one host-drawn key per forward (DESIGN.md section 4.26;
+    ``feat_extra.last_dropout_key``, ``feat_extra.dropout_generator``).  Without it dropout stays the identity, as on every
+    other path; backbones without an ``nn.Dropout`` in the section run exactly as with ``dropout=False``.
 
     ``backbone_grads="layer4" | "layer3" | "layer2"`` (ResNet backbones that offer the stage: ``feat_extra.trainable_stages``,
     resnet50 / resnet101): the same with ``feat_extra.train_from(stage)`` - every Bottleneck from the first block of that stage to
@@ -373,7 +379,7 @@ class FasterRCNNTrainer(nn.Module):
 
     def __init__(self, mode, num_classes, feat_stride=16, anchor_scales=[8, 16, 32], ratios=[0.5, 1, 2], *,
                  backbone="hardnet39", roi_op="pool", head_img_size="chw", head_grads=False, backbone_grads=None,
-                 bn_batch_stats=False):
+                 bn_batch_stats=False, dropout=False):
         super().__init__()
         if head_img_size not in ("chw", "hw"):
             raise ValueError(f"head_img_size must be 'chw' (the reference's) or 'hw', got {head_img_size!r}")
@@ -416,6 +422,9 @@ class FasterRCNNTrainer(nn.Module):
             raise ValueError("bn_batch_stats=True needs backbone_grads = a number of HarDBlocks or 'full' (the tail has no "
                              f"BatchNorm), got backbone_grads={backbone_grads!r}")
         self.bn_batch_stats = bool(bn_batch_stats)
+        if dropout and not self.bn_batch_stats:
+            raise ValueError("dropout=True needs bn_batch_stats=True: only the batch-statistics variant runs under .train()")
+        self.dropout = bool(dropout)
         self.__dict__["_uid"] = next(_UID)          # scratch ownership, as FasterRCNN's
         self.__dict__["_head_versions"] = None
 
@@ -513,7 +522,7 @@ class FasterRCNNTrainer(nn.Module):
         tail = self.backbone_grads is not None and features is None and torch.is_grad_enabled()
         if tail or (grads and features is None):                         # what the mode does not reach must be frozen
             stage = isinstance(self.backbone_grads, str) and self.backbone_grads not in ("tail", "full")       # a ResNet stage
-            mode_args = (self.backbone_grads,) if stage else (self.backbone_grads, self.bn_batch_stats)
+            mode_args = (self.backbone_grads,) if stage else (self.backbone_grads, self.bn_batch_stats, self.dropout)
             ours = {id(p) for p in self.feat_extra.set_train_mode(*mode_args).trainable_parameters()} if tail else ()
             frozen = [k for k, p in self.feat_extra.named_parameters() if p.requires_grad and id(p) not in ours]
             if frozen:
