@@ -493,7 +493,9 @@ int tsod_detection_nms_f32(const float *det_sorted, const int32_t *counts, int32
  *   counts [4] int32 = (S, kept positives, kept negatives, status): status 1 = the reference raises IndexError here
  *   (quirk T2: a sampled negative's original index lies beyond the kept list).
  * Both need 0 <= n_pos (pos_per_image) <= n_sample, i.e. pos_ratio in [0, 1]: beyond it the reference's negative slices take a
- * negative bound (they drop only the last negatives), which is not restated - TSOD_ERR_INVALID_ARG. */
+ * negative bound (they drop only the last negatives), which is not restated - TSOD_ERR_INVALID_ARG.
+ * tsod_anchor_targets_f32 also refuses G == 0 with pos_iou_thresh <= 0 (TSOD_ERR_INVALID_ARG, before any launch): every anchor
+ * would be positive with no box to take offsets to; G > 0 with pos_iou_thresh <= 0 is legal (all positive, every box exists). */
 size_t tsod_anchor_targets_workspace_bytes(int32_t A, int32_t G);
 int tsod_anchor_targets_f32(const float *anchor, int32_t A, const float *bbox, int32_t G, float pos_iou_thresh,
                             float neg_iou_thresh, int32_t n_pos, int32_t n_sample, float *loc, int64_t *label,
@@ -511,7 +513,8 @@ int tsod_proposal_targets_f32(const float *roi, int32_t R, const float *bbox, in
  * read by the kernels and clamped to [0, Gmax]; rows [gt_counts[b], Gmax) of image b are never read (they may hold anything, NaN
  * included).  Gmax == 0 is legal: bbox, gt_label and gt_counts may then be NULL and every image has no ground truth.
  * Image b's results are bit for bit those of the single-image entry points on (anchor, bbox[b][:gt_counts[b]]) and
- * (roi[b], bbox[b][:gt_counts[b]], gt_label[b][:gt_counts[b]]): the kernels share their bodies, quirks T1, T2 and T4 included.
+ * (roi[b], bbox[b][:gt_counts[b]], gt_label[b][:gt_counts[b]]), quirks T1, T2 and T4 included: they are the same kernels and the
+ * same launch sequences - a single-image call is a batch of one whose box count is passed by value.
  *
  * tsod_anchor_targets_batch_f32: anchor [A][4] is shared by the batch -> loc [B][A][4], label [B][A] int64, argmax [B][A] int32.
  *   workspace: tsod_anchor_targets_batch_workspace_bytes(B, A, Gmax) = B * (align16(4 A) + align16(4 max(Gmax, 1)) + 16)
@@ -575,8 +578,9 @@ int tsod_roi_losses_f32(const float *cls_locs, int32_t loc_pitch, const float *s
  * times inv_B (the batch mean).  No host synchronisation, no float atomics: run to run bit-identical.  Torch's empty sets:
  * no positive / no counted row gives zero gradients from that term (its loss is NaN); |d| == 0 gives abs's zero subgradient.
  *
- * tsod_proposal_targets_src_f32: tsod_proposal_targets_f32 plus sample_src [n_sample] int32 = the row of cat(roi, bbox) each
- *   sample was taken from (the reference's keep_index, nets/frcnn_training.py:165): < R a proposal, >= R a ground-truth box.
+ * tsod_proposal_targets_src_f32: tsod_proposal_targets_f32 (the same checks, the same two launches) plus sample_src [n_sample]
+ *   int32 = the row of cat(roi, bbox) each sample was taken from (the reference's keep_index, nets/frcnn_training.py:165): < R a
+ *   proposal, >= R a ground-truth box.  Like it, and unlike the batched call, it leaves rows [counts[0], n_sample) untouched.
  * tsod_rpn_losses_grad_f32: d rpn_out [B*n_pix][d_pitch] of the two RPN losses, in the fused layout tsod_rpn_losses_f32 reads
  *   (loc columns [0,4A), logits [4A,6A), zero columns after); n_rows [B][2] int32 out = (positives, counted rows).
  * tsod_roi_losses_grad_f32: d both [B*S][d_pitch] of the two head losses in the fused head GEMM's layout (cls_loc columns

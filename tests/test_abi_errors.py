@@ -109,6 +109,8 @@ def test_target_creator_validation():
     assert L.tsod_anchor_targets_f32(None, 10, P, 2, 0.7, 0.3, 128, 256, P, P, P, P, 1 << 20, None) == INVALID
     assert L.tsod_anchor_targets_f32(P, 0, P, 2, 0.7, 0.3, 128, 256, P, P, P, P, 1 << 20, None) == INVALID
     assert L.tsod_anchor_targets_f32(P, 10, None, 2, 0.7, 0.3, 128, 256, P, P, P, P, 1 << 20, None) == INVALID   # G > 0 needs boxes
+    # no ground truth and pos_iou_thresh <= 0: every anchor would be positive with no box to take offsets to
+    assert L.tsod_anchor_targets_f32(P, 10, None, 0, 0.0, 0.3, 128, 256, P, P, P, P, 1 << 20, None) == INVALID
     assert L.tsod_anchor_targets_f32(ODD, 10, P, 2, 0.7, 0.3, 128, 256, P, P, P, P, 1 << 20, None) == ALIGNMENT
     assert L.tsod_anchor_targets_f32(P, 10, P, 2, 0.7, 0.3, 128, 256, P, P, P, P, 8, None) == WORKSPACE
     assert L.tsod_anchor_targets_f32(P, 10, P, 2, 0.7, 0.3, 128, 256, P, P, P, None, 0, None) == WORKSPACE

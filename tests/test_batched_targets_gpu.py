@@ -5,7 +5,7 @@ References: tests/targets_restated.py per image (the CPU restatement test_target
 reference's recordings) and the single-image entry points on the same device.  Bars, the project's existing ones: labels,
 argmax, gt_roi_label, the count words and sample_src exact; gathered sample_roi rows bit-exact; loc / gt_roi_loc with the same
 finiteness pattern and a relative error <= LOC_REL_BAR against the restatement; against the single-image calls everything is
-torch.equal, locs included (the kernels share their bodies).  The facts that make the inputs worth running (which images are
+torch.equal, locs included (they are the same kernels: a single image is a batch of one).  The facts that make the inputs worth running (which images are
 cut by the cap, where T1 and T2 fire, how many LDS trips and which chunk each image takes) are asserted from the restatement
 before the GPU is looked at."""
 import os

@@ -232,6 +232,22 @@ def test_a_positive_cap_above_n_sample_is_refused(ops, ffi, dev):
     ops.anchor_targets(a["bbox"].to(dev), a["anchor"].to(dev), 100, 100, 0.5, 0.25)               # the edge itself is served
 
 
+def test_single_image_anchor_call_serves_a_zero_threshold_with_ground_truth(ffi, dev):
+    """pos_iou_thresh = 0.0 with ground truth present: every anchor is positive and every box exists, so the single-image entry
+    point serves it (the batched one refuses pos_iou_thresh <= 0 outright; the single-image one only at G == 0, which
+    test_abi_errors.py holds).  A = 65, G = 2, n_sample = 256, pos_ratio = 0.5: all 65 anchors are positive and, n_pos being
+    128, the cap keeps them all; the second call (n_sample = 64, n_pos = 32) is the one where the cap cuts."""
+    g = torch.Generator().manual_seed(65)
+    anchor, bbox = T.grid_boxes(g, 65, 8), T.grid_boxes(g, 2, 8)
+    for n_sample, cuts in ((256, False), (64, True)):
+        kw = dict(n_sample=n_sample, pos_ratio=0.5, pos_iou_thresh=0.0, neg_iou_thresh=T.ANCHOR_THR["neg_iou_thresh"])
+        want = T.anchor_stages(bbox, anchor, **kw)
+        assert want["total_pos"] == 65 and (want["label_claim"] == 1).all() and want["flag"] == 1    # before the GPU is looked at
+        assert (want["total_pos"] > want["n_pos"]) == cuts and int((want["label"] == 1).sum()) == min(65, n_sample // 2)
+        assert (want["max_iou"] == 0).any() and (want["max_iou"] > 0).any()                      # at the threshold and above it
+        check_anchor(abi_anchor(ffi, dev, dict(anchor=anchor, bbox=bbox, kw=kw)), want)
+
+
 # ================================================================================================ stale state
 def test_anchor_targets_leave_no_state_in_the_workspace(ffi, dev):
     """A large case with ground truth and a flag of 1, then small ones without (G = 0, flag 0) and with ground truth, on the same

@@ -103,7 +103,8 @@ def test_restated_geometry_is_the_one_in_the_source():
     assert f"for (int g = tid; g < G; g += {T.THREADS})" in src
     assert f"for (int j = tid; j < neg_len; j += {T.THREADS})" in src
     assert "if (1 > n_neg)" in src
-    assert len(re.findall(rf"dim3\(1\), dim3\({T.THREADS}\)", src)) == 2                              # both one-workgroup kernels
+    assert len(re.findall(rf"dim3\(B\), dim3\({T.THREADS}\)", src)) == 2             # both kernels of one workgroup per image
+    assert len(re.findall(r"\b__global__\b", src)) == 6 and "_batch_kernel" not in src         # five steps and bbox2loc_kernel
     assert f"(n + 255) / 256 < {T.B2L_BLOCKS} ? (n + 255) / 256 : {T.B2L_BLOCKS}" in src
     # the argument ranges for which the workspace sizes are 0
     assert "if (A <= 0 || G < 0) return 0;" in src

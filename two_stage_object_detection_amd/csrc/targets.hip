@@ -41,10 +41,10 @@ __device__ __forceinline__ float4 bbox2loc_dev(const float4 s, const float4 d) {
     return make_float4((bcx - cx) / w, (bcy - cy) / h, logf(bw / w), logf(bh / h));
 }
 
-// Every kernel body below is a __device__ function over ONE image's pointers: the single-image kernel calls it as it is, the
-// batched kernel offsets the pointers by its image index, reads G from gt_counts and calls the same function - one body, the
-// same bits.  The bodies index with blockIdx.x only; the batched kernels keep the image on blockIdx.y (or, for the two
-// one-workgroup bodies, which never read blockIdx, on blockIdx.x), so a workgroup never straddles two images and every
+// One kernel per step, for one image or a batch: the image index rides on blockIdx.y (or, for the two one-workgroup
+// steps, on blockIdx.x), the kernel offsets its pointers by it, takes the image's box count from image_gt_count() and calls
+// the step's __device__ ..._image() body, which sees ONE image's pointers and indexes with blockIdx.x only.  A single image is
+// a batch of one whose count is passed by value (gt_counts == nullptr).  A workgroup never straddles two images, so every
 // __syncthreads() below is reached by all threads of its workgroup with the same per-image trip count.
 
 // row-wise torch.max(ious, dim=1): first maximum wins.  One thread per candidate box; the G ground-truth boxes are
@@ -71,24 +71,19 @@ rowmax_image(const float4 *__restrict__ a, int na, const float4 *__restrict__ b,
     if (n < N) { max_iou[n] = best; argmax[n] = bi; }
 }
 
-__global__ void __launch_bounds__(256)
-rowmax_kernel(const float4 *__restrict__ a, int na, const float4 *__restrict__ b, int nb,
-              const float4 *__restrict__ gt, int G, float eps, float *__restrict__ max_iou, int *__restrict__ argmax) {
-    rowmax_image(a, na, b, nb, gt, G, eps, max_iou, argmax);
-}
-
-// gt_counts[b] clamped to [0, Gmax]; Gmax == 0: gt_counts is not read (it may be NULL)
+// image b's box count: gt_counts[b] clamped to [0, Gmax], or Gmax itself when gt_counts == nullptr (the single-image entry
+// points: the count by value).  Gmax == 0: gt_counts is not read.
 __device__ __forceinline__ int image_gt_count(const int *__restrict__ gt_counts, int b, int Gmax) {
-    return Gmax > 0 ? min(max(gt_counts[b], 0), Gmax) : 0;
+    return gt_counts != nullptr && Gmax > 0 ? min(max(gt_counts[b], 0), Gmax) : Gmax;
 }
 
 // grid (ceil((na + Gmax) / 256) or ceil(na / 256), B).  Image b's candidates are concat(a + b * a_stride [na], gt[b][:G] when
 // append_gt); its row maxima go to max_iou + b * max_stride bytes, its arg-maxima to argmax + b * arg_stride bytes.  A workgroup
 // past this image's candidates leaves as a whole, before any barrier.
 __global__ void __launch_bounds__(256)
-rowmax_batch_kernel(const float4 *__restrict__ a, int na, size_t a_stride, int append_gt, const float4 *__restrict__ gt,
-                    const int *__restrict__ gt_counts, int Gmax, float eps, char *__restrict__ max_iou, size_t max_stride,
-                    char *__restrict__ argmax, size_t arg_stride) {
+rowmax_kernel(const float4 *__restrict__ a, int na, size_t a_stride, int append_gt, const float4 *__restrict__ gt,
+              const int *__restrict__ gt_counts, int Gmax, float eps, char *__restrict__ max_iou, size_t max_stride,
+              char *__restrict__ argmax, size_t arg_stride) {
     const int b = blockIdx.y;
     const int G = image_gt_count(gt_counts, b, Gmax);
     const int nb = append_gt ? G : 0;
@@ -124,15 +119,10 @@ colargmax_image(const float4 *__restrict__ anchor, int A, const float4 *__restri
     }
 }
 
-__global__ void __launch_bounds__(256)
-colargmax_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, float eps, int *__restrict__ gt_argmax) {
-    colargmax_image(anchor, A, gt, eps, gt_argmax);
-}
-
 // grid (Gmax, B): the surplus workgroups of an image (blockIdx.x >= its count) leave before touching memory
 __global__ void __launch_bounds__(256)
-colargmax_batch_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, const int *__restrict__ gt_counts,
-                       int Gmax, float eps, int *__restrict__ gt_argmax, size_t ws_stride /* ints */) {
+colargmax_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, const int *__restrict__ gt_counts,
+                 int Gmax, float eps, int *__restrict__ gt_argmax, size_t ws_stride /* ints */) {
     const int b = blockIdx.y;
     if ((int)blockIdx.x >= image_gt_count(gt_counts, b, Gmax)) return;
     colargmax_image(anchor, A, gt + (size_t)b * Gmax, eps, gt_argmax + b * ws_stride);
@@ -204,18 +194,12 @@ anchor_label_image(const float *__restrict__ max_iou, int *__restrict__ argmax, 
     if (tid == 0) *flag = pos_length > 0 ? 1 : 0;                      // (label > 0).any() (:33)
 }
 
-__global__ void __launch_bounds__(1024)
-anchor_label_kernel(const float *__restrict__ max_iou, int *__restrict__ argmax, const int *__restrict__ gt_argmax, int A, int G,
-                    float pos_thr, float neg_thr, int n_pos, int n_sample, long long *__restrict__ label, int *__restrict__ flag) {
-    anchor_label_image(max_iou, argmax, gt_argmax, A, G, pos_thr, neg_thr, n_pos, n_sample, label, flag);
-}
-
 // grid (B): workgroup b owns image b.  ws = this call's workspace, ws_stride bytes per image: max_iou [A], gt_argmax at
 // gt_argmax_off, flag at flag_off (the single-image layout, once per image).
 __global__ void __launch_bounds__(1024)
-anchor_label_batch_kernel(char *__restrict__ ws, size_t ws_stride, size_t gt_argmax_off, size_t flag_off, int *__restrict__ argmax,
-                          int A, const int *__restrict__ gt_counts, int Gmax, float pos_thr, float neg_thr, int n_pos, int n_sample,
-                          long long *__restrict__ label) {
+anchor_label_kernel(char *__restrict__ ws, size_t ws_stride, size_t gt_argmax_off, size_t flag_off, int *__restrict__ argmax,
+                    int A, const int *__restrict__ gt_counts, int Gmax, float pos_thr, float neg_thr, int n_pos, int n_sample,
+                    long long *__restrict__ label) {
     const int b = blockIdx.x;
     char *w = ws + b * ws_stride;
     anchor_label_image(reinterpret_cast<const float *>(w), argmax + (size_t)b * A, reinterpret_cast<const int *>(w + gt_argmax_off), A,
@@ -231,17 +215,11 @@ anchor_loc_image(const float4 *__restrict__ anchor, int A, const float4 *__restr
     loc[n] = *flag ? bbox2loc_dev(anchor[n], gt[argmax[n]]) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__global__ void __launch_bounds__(256)
-anchor_loc_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, const int *__restrict__ argmax,
-                  const int *__restrict__ flag, float4 *__restrict__ loc) {
-    anchor_loc_image(anchor, A, gt, argmax, flag, loc);
-}
-
 // grid (ceil(A / 256), B).  A flag of 1 means the image has a positive, hence ground truth: gt is read only then.
 __global__ void __launch_bounds__(256)
-anchor_loc_batch_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, int Gmax,
-                        const int *__restrict__ argmax, const char *__restrict__ ws, size_t ws_stride, size_t flag_off,
-                        float4 *__restrict__ loc) {
+anchor_loc_kernel(const float4 *__restrict__ anchor, int A, const float4 *__restrict__ gt, int Gmax,
+                  const int *__restrict__ argmax, const char *__restrict__ ws, size_t ws_stride, size_t flag_off,
+                  float4 *__restrict__ loc) {
     const int b = blockIdx.y;
     anchor_loc_image(anchor, A, gt + (size_t)b * Gmax, argmax + (size_t)b * A,
                      reinterpret_cast<const int *>(ws + b * ws_stride + flag_off), loc + (size_t)b * A);
@@ -310,25 +288,16 @@ proposal_select_image(const float4 *__restrict__ roi, int R, const float4 *__res
     return S;
 }
 
-__global__ void __launch_bounds__(1024)
-proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__restrict__ gt, int G,
-                       const long long *__restrict__ gt_label, const float *__restrict__ max_iou, const int *__restrict__ assign,
-                       int n_sample, int pos_per_image, float pos_thr, float neg_hi, float neg_lo,
-                       float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc, long long *__restrict__ gt_roi_label,
-                       int *__restrict__ neg_orig, int *__restrict__ counts, int *__restrict__ sample_src) {
-    proposal_select_image(roi, R, gt, G, gt_label, max_iou, assign, n_sample, pos_per_image, pos_thr, neg_hi, neg_lo, sample_roi,
-                          gt_roi_loc, gt_roi_label, neg_orig, counts, sample_src);
-}
-
 // grid (B): workgroup b owns image b.  ws_stride bytes of workspace per image: max_iou, assign at assign_off, neg_orig at
-// neg_off (the single-image layout at R + Gmax candidates).  The batched call alone defines the rows the image did not fill:
-// zeros (-1 in sample_src) from S to n_sample; no other thread writes those rows, so no barrier is needed before them.
+// neg_off (the single-image layout at R + Gmax candidates).  fill_rest != 0 (the batched call alone) defines the rows the image
+// did not fill: zeros (-1 in sample_src) from S to n_sample; no other thread writes those rows, so no barrier is needed before
+// them.  fill_rest == 0 (the single-image calls) leaves them untouched.
 __global__ void __launch_bounds__(1024)
-proposal_select_batch_kernel(const float4 *__restrict__ roi, int R, const float4 *__restrict__ gt, const int *__restrict__ gt_counts,
-                             int Gmax, const long long *__restrict__ gt_label, char *__restrict__ ws, size_t ws_stride,
-                             size_t assign_off, size_t neg_off, int n_sample, int pos_per_image, float pos_thr, float neg_hi,
-                             float neg_lo, float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc,
-                             long long *__restrict__ gt_roi_label, int *__restrict__ counts, int *__restrict__ sample_src) {
+proposal_select_kernel(const float4 *__restrict__ roi, int R, const float4 *__restrict__ gt, const int *__restrict__ gt_counts,
+                       int Gmax, const long long *__restrict__ gt_label, char *__restrict__ ws, size_t ws_stride,
+                       size_t assign_off, size_t neg_off, int n_sample, int pos_per_image, float pos_thr, float neg_hi,
+                       float neg_lo, float4 *__restrict__ sample_roi, float4 *__restrict__ gt_roi_loc,
+                       long long *__restrict__ gt_roi_label, int *__restrict__ counts, int *__restrict__ sample_src, int fill_rest) {
     const int b = blockIdx.x;
     char *w = ws + b * ws_stride;
     const size_t row = (size_t)b * n_sample;
@@ -338,6 +307,7 @@ proposal_select_batch_kernel(const float4 *__restrict__ roi, int R, const float4
                                         reinterpret_cast<const int *>(w + assign_off), n_sample, pos_per_image, pos_thr, neg_hi,
                                         neg_lo, sample_roi + row, gt_roi_loc + row, gt_roi_label + row,
                                         reinterpret_cast<int *>(w + neg_off), counts + 4 * b, src);
+    if (!fill_rest) return;
     for (int j = S + (int)threadIdx.x; j < n_sample; j += 1024) {
         sample_roi[row + j] = make_float4(0.f, 0.f, 0.f, 0.f);
         gt_roi_loc[row + j] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -345,7 +315,6 @@ proposal_select_batch_kernel(const float4 *__restrict__ roi, int R, const float4
         if (src != nullptr) src[j] = -1;
     }
 }
-
 
 // utils/loc_bbox_iou.py:63-88 as a stand-alone op: one thread per box pair
 __global__ void __launch_bounds__(256)
@@ -361,31 +330,46 @@ extern "C" size_t tsod_anchor_targets_workspace_bytes(int32_t A, int32_t G) {
     return tsod_align_up((size_t)A * 4, 16) + tsod_align_up((size_t)(G > 0 ? G : 1) * 4, 16) + 16;
 }
 
+// The four launches (three when Gmax == 0) of both anchor entry points, for B images whose workspaces - the single-image layout
+// at Gmax boxes: max_iou [A], gt_argmax, flag - lie back to back.  gt_counts == nullptr: every image has Gmax boxes (the
+// single-image call, B = 1).  No argument checks: those are the entry points'.
+static int launch_anchor_targets(const float *anchor, int32_t A, const float *bbox, const int32_t *gt_counts, int32_t B, int32_t Gmax,
+                                 float pos_iou_thresh, float neg_iou_thresh, int32_t n_pos, int32_t n_sample, float *loc,
+                                 int64_t *label, int32_t *argmax, void *workspace, tsod_stream_t stream) {
+    char *ws = static_cast<char *>(workspace);
+    const size_t stride = tsod_anchor_targets_workspace_bytes(A, Gmax);
+    const size_t gt_argmax_off = tsod_align_up((size_t)A * 4, 16);
+    const size_t flag_off = gt_argmax_off + tsod_align_up((size_t)(Gmax > 0 ? Gmax : 1) * 4, 16);
+    hipStream_t s = tsod_stream(stream);
+    const float4 *a4 = reinterpret_cast<const float4 *>(anchor), *g4 = reinterpret_cast<const float4 *>(bbox);
+    hipLaunchKernelGGL(rowmax_kernel, dim3((A + 255) / 256, B), dim3(256), 0, s, a4, A, (size_t)0, 0, g4, gt_counts, Gmax, 1e-8f, ws,
+                       stride, reinterpret_cast<char *>(argmax), (size_t)A * 4);
+    if (Gmax > 0)
+        hipLaunchKernelGGL(colargmax_kernel, dim3(Gmax, B), dim3(256), 0, s, a4, A, g4, gt_counts, Gmax, 1e-8f,
+                           reinterpret_cast<int *>(ws + gt_argmax_off), stride / 4);
+    hipLaunchKernelGGL(anchor_label_kernel, dim3(B), dim3(1024), 0, s, ws, stride, gt_argmax_off, flag_off, argmax, A, gt_counts,
+                       Gmax, pos_iou_thresh, neg_iou_thresh, n_pos, n_sample, reinterpret_cast<long long *>(label));
+    hipLaunchKernelGGL(anchor_loc_kernel, dim3((A + 255) / 256, B), dim3(256), 0, s, a4, A, g4, Gmax, argmax, ws, stride, flag_off,
+                       reinterpret_cast<float4 *>(loc));
+    return tsod_launch_status();
+}
+
 extern "C" int tsod_anchor_targets_f32(const float *anchor, int32_t A, const float *bbox, int32_t G, float pos_iou_thresh,
                                        float neg_iou_thresh, int32_t n_pos, int32_t n_sample, float *loc, int64_t *label,
                                        int32_t *argmax, void *workspace, size_t workspace_bytes, tsod_stream_t stream) {
     TSOD_REQUIRE(anchor && loc && label && argmax && (bbox || G == 0), TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(A > 0 && G >= 0 && n_pos >= 0 && n_sample >= 0, TSOD_ERR_INVALID_ARG);
+    // without ground truth max_iou = 0 everywhere: with pos_iou_thresh <= 0 it would be all positives and the offsets would
+    // read a box that does not exist (the reference's bbox[argmax_ious] raises there).  With G > 0 every box exists: legal.
+    TSOD_REQUIRE(G > 0 || pos_iou_thresh > 0.f, TSOD_ERR_INVALID_ARG);
     // n_pos > n_sample (pos_ratio > 1) can make n_sample - pos_length negative, where the reference's i[n_neg:] disables
     // only the last |n_neg| negatives; the label kernel does not restate that accident
     TSOD_REQUIRE(n_pos <= n_sample, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(tsod_aligned16(anchor) && tsod_aligned16(loc) && (G == 0 || tsod_aligned16(bbox)), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace && workspace_bytes >= tsod_anchor_targets_workspace_bytes(A, G) && tsod_aligned16(workspace),
                  TSOD_ERR_WORKSPACE);
-    char *ws = static_cast<char *>(workspace);
-    float *max_iou = reinterpret_cast<float *>(ws);
-    int *gt_argmax = reinterpret_cast<int *>(ws + tsod_align_up((size_t)A * 4, 16));
-    int *flag = reinterpret_cast<int *>(ws + tsod_align_up((size_t)A * 4, 16) + tsod_align_up((size_t)(G > 0 ? G : 1) * 4, 16));
-    hipStream_t s = tsod_stream(stream);
-    const float4 *a4 = reinterpret_cast<const float4 *>(anchor), *g4 = reinterpret_cast<const float4 *>(bbox);
-    hipLaunchKernelGGL(rowmax_kernel, dim3((A + 255) / 256), dim3(256), 0, s, a4, A, (const float4 *)nullptr, 0, g4, G, 1e-8f,
-                       max_iou, argmax);
-    if (G > 0) hipLaunchKernelGGL(colargmax_kernel, dim3(G), dim3(256), 0, s, a4, A, g4, 1e-8f, gt_argmax);
-    hipLaunchKernelGGL(anchor_label_kernel, dim3(1), dim3(1024), 0, s, max_iou, argmax, gt_argmax, A, G, pos_iou_thresh,
-                       neg_iou_thresh, n_pos, n_sample, reinterpret_cast<long long *>(label), flag);
-    hipLaunchKernelGGL(anchor_loc_kernel, dim3((A + 255) / 256), dim3(256), 0, s, a4, A, g4, argmax, flag,
-                       reinterpret_cast<float4 *>(loc));
-    return tsod_launch_status();
+    return launch_anchor_targets(anchor, A, bbox, nullptr, 1, G, pos_iou_thresh, neg_iou_thresh, n_pos, n_sample, loc, label, argmax,
+                                 workspace, stream);
 }
 
 extern "C" size_t tsod_proposal_targets_workspace_bytes(int32_t R, int32_t G, int32_t n_sample) {
@@ -393,6 +377,32 @@ extern "C" size_t tsod_proposal_targets_workspace_bytes(int32_t R, int32_t G, in
     return 2 * tsod_align_up((size_t)(R + G) * 4, 16) + tsod_align_up((size_t)n_sample * 4, 16);
 }
 
+// The two launches of all three proposal entry points, for B images whose workspaces - the single-image layout at R + Gmax
+// candidates: max_iou, assign, neg_orig - lie back to back.  gt_counts == nullptr: every image has Gmax boxes (the single-image
+// calls, B = 1); sample_src may be nullptr; fill_rest: see proposal_select_kernel.  No argument checks.
+static int launch_proposal_targets(const float *roi, int32_t R, const float *bbox, const int64_t *gt_label, const int32_t *gt_counts,
+                                   int32_t B, int32_t Gmax, int32_t n_sample, int32_t pos_per_image, float pos_iou_thresh,
+                                   float neg_iou_thresh_high, float neg_iou_thresh_low, float *sample_roi, float *gt_roi_loc,
+                                   int64_t *gt_roi_label, int32_t *counts, int32_t *sample_src, int fill_rest, void *workspace,
+                                   tsod_stream_t stream) {
+    const int Nmax = R + Gmax;
+    char *ws = static_cast<char *>(workspace);
+    const size_t stride = tsod_proposal_targets_workspace_bytes(R, Gmax, n_sample);
+    const size_t assign_off = tsod_align_up((size_t)Nmax * 4, 16), neg_off = 2 * assign_off;
+    hipStream_t s = tsod_stream(stream);
+    const float4 *r4 = reinterpret_cast<const float4 *>(roi), *g4 = reinterpret_cast<const float4 *>(bbox);
+    // roi = torch.cat((roi, bbox)) (:133) is never materialised: candidate n >= R is gt box n - R
+    hipLaunchKernelGGL(rowmax_kernel, dim3((Nmax + 255) / 256, B), dim3(256), 0, s, r4, R, (size_t)R, 1, g4, gt_counts, Gmax, 1e-8f,
+                       ws, stride, ws + assign_off, stride);
+    hipLaunchKernelGGL(proposal_select_kernel, dim3(B), dim3(1024), 0, s, r4, R, g4, gt_counts, Gmax,
+                       reinterpret_cast<const long long *>(gt_label), ws, stride, assign_off, neg_off, n_sample, pos_per_image,
+                       pos_iou_thresh, neg_iou_thresh_high, neg_iou_thresh_low, reinterpret_cast<float4 *>(sample_roi),
+                       reinterpret_cast<float4 *>(gt_roi_loc), reinterpret_cast<long long *>(gt_roi_label), counts, sample_src,
+                       fill_rest);
+    return tsod_launch_status();
+}
+
+// the checks of both single-image proposal entry points; the rows behind counts[0] stay untouched
 static int proposal_targets(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
                             int32_t n_sample, int32_t pos_per_image, float pos_iou_thresh,
                             float neg_iou_thresh_high, float neg_iou_thresh_low, float *sample_roi,
@@ -408,21 +418,9 @@ static int proposal_targets(const float *roi, int32_t R, const float *bbox, int3
                      tsod_aligned16(gt_roi_loc), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace && workspace_bytes >= tsod_proposal_targets_workspace_bytes(R, G, n_sample) &&
                      tsod_aligned16(workspace), TSOD_ERR_WORKSPACE);
-    const int N = R + G;
-    char *ws = static_cast<char *>(workspace);
-    float *max_iou = reinterpret_cast<float *>(ws);
-    int *assign = reinterpret_cast<int *>(ws + tsod_align_up((size_t)N * 4, 16));
-    int *neg_orig = reinterpret_cast<int *>(ws + 2 * tsod_align_up((size_t)N * 4, 16));
-    hipStream_t s = tsod_stream(stream);
-    const float4 *r4 = reinterpret_cast<const float4 *>(roi), *g4 = reinterpret_cast<const float4 *>(bbox);
-    // roi = torch.cat((roi, bbox)) (:133) is never materialised: candidate n >= R is gt box n - R
-    hipLaunchKernelGGL(rowmax_kernel, dim3((N + 255) / 256), dim3(256), 0, s, r4, R, g4, G, g4, G, 1e-8f, max_iou, assign);
-    hipLaunchKernelGGL(proposal_select_kernel, dim3(1), dim3(1024), 0, s, r4, R, g4, G,
-                       reinterpret_cast<const long long *>(gt_label), max_iou, assign, n_sample, pos_per_image, pos_iou_thresh,
-                       neg_iou_thresh_high, neg_iou_thresh_low, reinterpret_cast<float4 *>(sample_roi),
-                       reinterpret_cast<float4 *>(gt_roi_loc), reinterpret_cast<long long *>(gt_roi_label), neg_orig, counts,
-                       sample_src);
-    return tsod_launch_status();
+    return launch_proposal_targets(roi, R, bbox, gt_label, nullptr, 1, G, n_sample, pos_per_image, pos_iou_thresh,
+                                   neg_iou_thresh_high, neg_iou_thresh_low, sample_roi, gt_roi_loc, gt_roi_label, counts, sample_src,
+                                   0, workspace, stream);
 }
 
 extern "C" int tsod_proposal_targets_f32(const float *roi, int32_t R, const float *bbox, int32_t G, const int64_t *gt_label,
@@ -455,8 +453,6 @@ extern "C" size_t tsod_anchor_targets_batch_workspace_bytes(int32_t B, int32_t A
     return (size_t)B * tsod_anchor_targets_workspace_bytes(A, Gmax);
 }
 
-// the single-image call's four launches with the image index on a grid dimension; the workspace is the single-image layout
-// (at Gmax boxes) once per image
 extern "C" int tsod_anchor_targets_batch_f32(const float *anchor, int32_t A, const float *bbox, const int32_t *gt_counts,
                                              int32_t B, int32_t Gmax, float pos_iou_thresh, float neg_iou_thresh, int32_t n_pos,
                                              int32_t n_sample, float *loc, int64_t *label, int32_t *argmax, void *workspace,
@@ -470,22 +466,8 @@ extern "C" int tsod_anchor_targets_batch_f32(const float *anchor, int32_t A, con
     TSOD_REQUIRE(tsod_aligned16(anchor) && tsod_aligned16(loc) && (Gmax == 0 || tsod_aligned16(bbox)), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace && workspace_bytes >= tsod_anchor_targets_batch_workspace_bytes(B, A, Gmax) && tsod_aligned16(workspace),
                  TSOD_ERR_WORKSPACE);
-    char *ws = static_cast<char *>(workspace);
-    const size_t stride = tsod_anchor_targets_workspace_bytes(A, Gmax);
-    const size_t gt_argmax_off = tsod_align_up((size_t)A * 4, 16);
-    const size_t flag_off = gt_argmax_off + tsod_align_up((size_t)(Gmax > 0 ? Gmax : 1) * 4, 16);
-    hipStream_t s = tsod_stream(stream);
-    const float4 *a4 = reinterpret_cast<const float4 *>(anchor), *g4 = reinterpret_cast<const float4 *>(bbox);
-    hipLaunchKernelGGL(rowmax_batch_kernel, dim3((A + 255) / 256, B), dim3(256), 0, s, a4, A, (size_t)0, 0, g4, gt_counts, Gmax,
-                       1e-8f, ws, stride, reinterpret_cast<char *>(argmax), (size_t)A * 4);
-    if (Gmax > 0)
-        hipLaunchKernelGGL(colargmax_batch_kernel, dim3(Gmax, B), dim3(256), 0, s, a4, A, g4, gt_counts, Gmax, 1e-8f,
-                           reinterpret_cast<int *>(ws + gt_argmax_off), stride / 4);
-    hipLaunchKernelGGL(anchor_label_batch_kernel, dim3(B), dim3(1024), 0, s, ws, stride, gt_argmax_off, flag_off, argmax, A,
-                       gt_counts, Gmax, pos_iou_thresh, neg_iou_thresh, n_pos, n_sample, reinterpret_cast<long long *>(label));
-    hipLaunchKernelGGL(anchor_loc_batch_kernel, dim3((A + 255) / 256, B), dim3(256), 0, s, a4, A, g4, Gmax, argmax, ws, stride,
-                       flag_off, reinterpret_cast<float4 *>(loc));
-    return tsod_launch_status();
+    return launch_anchor_targets(anchor, A, bbox, gt_counts, B, Gmax, pos_iou_thresh, neg_iou_thresh, n_pos, n_sample, loc, label,
+                                 argmax, workspace, stream);
 }
 
 extern "C" size_t tsod_proposal_targets_batch_workspace_bytes(int32_t B, int32_t R, int32_t Gmax, int32_t n_sample) {
@@ -493,7 +475,7 @@ extern "C" size_t tsod_proposal_targets_batch_workspace_bytes(int32_t B, int32_t
     return (size_t)B * tsod_proposal_targets_workspace_bytes(R, Gmax, n_sample);
 }
 
-// the single-image call's two launches with the image index on a grid dimension; sample_src may be NULL
+// sample_src may be NULL; the rows behind counts[b][0] are written (fill_rest = 1)
 extern "C" int tsod_proposal_targets_batch_f32(const float *roi, int32_t R, const float *bbox, const int64_t *gt_label,
                                                const int32_t *gt_counts, int32_t B, int32_t Gmax, int32_t n_sample,
                                                int32_t pos_per_image, float pos_iou_thresh, float neg_iou_thresh_high,
@@ -509,19 +491,9 @@ extern "C" int tsod_proposal_targets_batch_f32(const float *roi, int32_t R, cons
                      tsod_aligned16(gt_roi_loc), TSOD_ERR_ALIGNMENT);
     TSOD_REQUIRE(workspace && workspace_bytes >= tsod_proposal_targets_batch_workspace_bytes(B, R, Gmax, n_sample) &&
                      tsod_aligned16(workspace), TSOD_ERR_WORKSPACE);
-    const int Nmax = R + Gmax;
-    char *ws = static_cast<char *>(workspace);
-    const size_t stride = tsod_proposal_targets_workspace_bytes(R, Gmax, n_sample);
-    const size_t assign_off = tsod_align_up((size_t)Nmax * 4, 16), neg_off = 2 * assign_off;
-    hipStream_t s = tsod_stream(stream);
-    const float4 *r4 = reinterpret_cast<const float4 *>(roi), *g4 = reinterpret_cast<const float4 *>(bbox);
-    hipLaunchKernelGGL(rowmax_batch_kernel, dim3((Nmax + 255) / 256, B), dim3(256), 0, s, r4, R, (size_t)R, 1, g4, gt_counts, Gmax,
-                       1e-8f, ws, stride, ws + assign_off, stride);
-    hipLaunchKernelGGL(proposal_select_batch_kernel, dim3(B), dim3(1024), 0, s, r4, R, g4, gt_counts, Gmax,
-                       reinterpret_cast<const long long *>(gt_label), ws, stride, assign_off, neg_off, n_sample, pos_per_image,
-                       pos_iou_thresh, neg_iou_thresh_high, neg_iou_thresh_low, reinterpret_cast<float4 *>(sample_roi),
-                       reinterpret_cast<float4 *>(gt_roi_loc), reinterpret_cast<long long *>(gt_roi_label), counts, sample_src);
-    return tsod_launch_status();
+    return launch_proposal_targets(roi, R, bbox, gt_label, gt_counts, B, Gmax, n_sample, pos_per_image, pos_iou_thresh,
+                                   neg_iou_thresh_high, neg_iou_thresh_low, sample_roi, gt_roi_loc, gt_roi_label, counts, sample_src,
+                                   1, workspace, stream);
 }
 
 extern "C" int tsod_bbox2loc_f32(const float *src, const float *dst, int64_t n, float *out, tsod_stream_t stream) {

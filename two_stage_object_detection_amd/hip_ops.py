@@ -1525,26 +1525,42 @@ def anchor_targets(bbox: torch.Tensor, anchor: torch.Tensor, n_pos: int, n_sampl
     return loc, label, argmax
 
 
-def proposal_targets(roi: torch.Tensor, bbox: torch.Tensor, label: torch.Tensor, n_sample: int, pos_per_image: int,
-                     pos_iou_thresh: float, neg_iou_thresh_high: float, neg_iou_thresh_low: float):
-    """roi [R,4], bbox [G,4], label [G] int64 -> (sample_roi [n_sample,4], gt_roi_loc [n_sample,4], gt_roi_label [n_sample]
-    int64, counts [4] int32 = (rows kept, positives, negatives, status)) (tsod_proposal_targets_f32)."""
-    require_cuda(roi, "proposal_targets")
+def _proposal_outputs(lead: tuple, n_sample: int, dev, want_src: bool):
+    """The uninitialised outputs of a proposal-target call, ``lead`` = () or (B,): (sample_roi [..., n_sample, 4],
+    gt_roi_loc [..., n_sample, 4], gt_roi_label [..., n_sample] int64, counts [..., 4] int32, sample_src [..., n_sample] int32
+    or None)."""
+    return (torch.empty((*lead, n_sample, 4), dtype=torch.float32, device=dev),
+            torch.empty((*lead, n_sample, 4), dtype=torch.float32, device=dev),
+            torch.empty((*lead, n_sample), dtype=torch.int64, device=dev),
+            torch.empty((*lead, 4), dtype=torch.int32, device=dev),
+            torch.empty((*lead, n_sample), dtype=torch.int32, device=dev) if want_src else None)
+
+
+def _proposal_targets(what: str, want_src: bool, roi, bbox, label, n_sample, pos_per_image, pos_iou_thresh, neg_iou_thresh_high,
+                      neg_iou_thresh_low):
+    """One image through tsod_proposal_targets_f32 or, with ``want_src``, tsod_proposal_targets_src_f32, which takes
+    sample_src after counts -> (sample_roi, gt_roi_loc, gt_roi_label, counts, sample_src or None)."""
+    require_cuda(roi, what)
     dev = roi.device
     roi, bbox = roi.contiguous(), bbox.to(dev, torch.float32).contiguous()
     label = label.to(dev, torch.int64).contiguous()
     R, G = roi.shape[0], bbox.shape[0]
-    sample_roi = torch.empty((n_sample, 4), dtype=torch.float32, device=dev)
-    gt_roi_loc = torch.empty((n_sample, 4), dtype=torch.float32, device=dev)
-    gt_roi_label = torch.empty((n_sample,), dtype=torch.int64, device=dev)
-    counts = torch.empty((4,), dtype=torch.int32, device=dev)
+    out = _proposal_outputs((), n_sample, dev, want_src)
     ws_bytes = lib().tsod_proposal_targets_workspace_bytes(R, G, n_sample)
     ws = ARENA.get(dev, ws_bytes)
-    check(lib().tsod_proposal_targets_f32(ptr(roi) if R else None, R, ptr(bbox) if G else None, G, ptr(label) if G else None,
-                                          int(n_sample), int(pos_per_image), float(pos_iou_thresh), float(neg_iou_thresh_high),
-                                          float(neg_iou_thresh_low), ptr(sample_roi), ptr(gt_roi_loc), ptr(gt_roi_label),
-                                          ptr(counts), ptr(ws), ws_bytes, stream_ptr()), "proposal_targets")
-    return sample_roi, gt_roi_loc, gt_roi_label, counts
+    entry = lib().tsod_proposal_targets_src_f32 if want_src else lib().tsod_proposal_targets_f32
+    check(entry(ptr(roi) if R else None, R, ptr(bbox) if G else None, G, ptr(label) if G else None, int(n_sample),
+                int(pos_per_image), float(pos_iou_thresh), float(neg_iou_thresh_high), float(neg_iou_thresh_low),
+                *(ptr(t) for t in out if t is not None), ptr(ws), ws_bytes, stream_ptr()), what)
+    return out
+
+
+def proposal_targets(roi: torch.Tensor, bbox: torch.Tensor, label: torch.Tensor, n_sample: int, pos_per_image: int,
+                     pos_iou_thresh: float, neg_iou_thresh_high: float, neg_iou_thresh_low: float):
+    """roi [R,4], bbox [G,4], label [G] int64 -> (sample_roi [n_sample,4], gt_roi_loc [n_sample,4], gt_roi_label [n_sample]
+    int64, counts [4] int32 = (rows kept, positives, negatives, status)) (tsod_proposal_targets_f32)."""
+    return _proposal_targets("proposal_targets", False, roi, bbox, label, n_sample, pos_per_image, pos_iou_thresh,
+                             neg_iou_thresh_high, neg_iou_thresh_low)[:4]
 
 
 def _batch_ground_truth(what: str, bbox: torch.Tensor, gt_counts: torch.Tensor, dev):
@@ -1599,11 +1615,7 @@ def proposal_targets_batch(roi: torch.Tensor, bbox: torch.Tensor, label: torch.T
         raise ValueError(f"proposal_targets_batch: roi {tuple(roi.shape)} / label {tuple(label.shape)} for bbox {tuple(bbox.shape)}")
     label = label.to(dev, torch.int64).contiguous()
     R = roi.shape[1]
-    sample_roi = torch.empty((B, n_sample, 4), dtype=torch.float32, device=dev)
-    gt_roi_loc = torch.empty((B, n_sample, 4), dtype=torch.float32, device=dev)
-    gt_roi_label = torch.empty((B, n_sample), dtype=torch.int64, device=dev)
-    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    src = torch.empty((B, n_sample), dtype=torch.int32, device=dev) if want_src else None
+    sample_roi, gt_roi_loc, gt_roi_label, counts, src = _proposal_outputs((B,), n_sample, dev, want_src)
     ws_bytes = lib().tsod_proposal_targets_batch_workspace_bytes(B, R, Gmax, n_sample)
     ws = ARENA.get(dev, ws_bytes)
     gt = [ptr(t) if Gmax else None for t in (bbox, label, gt_counts)]
@@ -1676,24 +1688,8 @@ def proposal_targets_src(roi: torch.Tensor, bbox: torch.Tensor, label: torch.Ten
                          pos_iou_thresh: float, neg_iou_thresh_high: float, neg_iou_thresh_low: float):
     """``proposal_targets`` plus sample_src [n_sample] int32: the row of cat(roi, bbox) each sample came from (< R: a
     proposal; the reference's keep_index) (tsod_proposal_targets_src_f32)."""
-    require_cuda(roi, "proposal_targets_src")
-    dev = roi.device
-    roi, bbox = roi.contiguous(), bbox.to(dev, torch.float32).contiguous()
-    label = label.to(dev, torch.int64).contiguous()
-    R, G = roi.shape[0], bbox.shape[0]
-    sample_roi = torch.empty((n_sample, 4), dtype=torch.float32, device=dev)
-    gt_roi_loc = torch.empty((n_sample, 4), dtype=torch.float32, device=dev)
-    gt_roi_label = torch.empty((n_sample,), dtype=torch.int64, device=dev)
-    counts = torch.empty((4,), dtype=torch.int32, device=dev)
-    src = torch.empty((n_sample,), dtype=torch.int32, device=dev)
-    ws_bytes = lib().tsod_proposal_targets_workspace_bytes(R, G, n_sample)
-    ws = ARENA.get(dev, ws_bytes)
-    check(lib().tsod_proposal_targets_src_f32(ptr(roi) if R else None, R, ptr(bbox) if G else None, G,
-                                              ptr(label) if G else None, int(n_sample), int(pos_per_image),
-                                              float(pos_iou_thresh), float(neg_iou_thresh_high), float(neg_iou_thresh_low),
-                                              ptr(sample_roi), ptr(gt_roi_loc), ptr(gt_roi_label), ptr(counts), ptr(src),
-                                              ptr(ws), ws_bytes, stream_ptr()), "proposal_targets_src")
-    return sample_roi, gt_roi_loc, gt_roi_label, counts, src
+    return _proposal_targets("proposal_targets_src", True, roi, bbox, label, n_sample, pos_per_image, pos_iou_thresh,
+                             neg_iou_thresh_high, neg_iou_thresh_low)
 
 
 def _upstream(up: torch.Tensor) -> torch.Tensor:

@@ -152,30 +152,27 @@ class ProposalTargetCreator(object):
         self.neg_iou_thresh_high = neg_iou_thresh_high
         self.neg_iou_thresh_low = neg_iou_thresh_low
 
+    def _sample(self, fn, roi, bbox, label):
+        """``fn`` = hip_ops.proposal_targets or proposal_targets_src -> its outputs cut to the S kept rows (counts dropped)."""
+        require_cuda(roi, "ProposalTargetCreator")
+        sample_roi, gt_roi_loc, gt_roi_label, counts, *src = fn(
+            roi, bbox, label, self.n_sample, self.pos_roi_per_image, self.pos_iou_thresh, self.neg_iou_thresh_high,
+            self.neg_iou_thresh_low)
+        host = counts.tolist()
+        raise_for_counts([host])
+        n_keep = host[0]
+        return (sample_roi[:n_keep], gt_roi_loc[:n_keep], gt_roi_label[:n_keep].to(label.dtype), *(t[:n_keep] for t in src))
+
     def __call__(self, roi, bbox, label, loc_normalize_std=(0.1, 0.1, 0.2, 0.2)):
         """roi [R,4], bbox [G,4], label [G] -> (sample_roi [S,4], gt_roi_loc [S,4], gt_roi_label [S]), S <= n_sample.
         ``loc_normalize_std`` is accepted and unused, as in the reference (the division is commented out there).
         Two launches; reading S (and the IndexError flag of the reference's quirk T2) is the one host synchronisation."""
-        require_cuda(roi, "ProposalTargetCreator")
-        sample_roi, gt_roi_loc, gt_roi_label, counts = hip_ops.proposal_targets(
-            roi, bbox, label, self.n_sample, self.pos_roi_per_image, self.pos_iou_thresh, self.neg_iou_thresh_high,
-            self.neg_iou_thresh_low)
-        host = counts.tolist()
-        raise_for_counts([host])
-        n_keep = host[0]
-        return sample_roi[:n_keep], gt_roi_loc[:n_keep], gt_roi_label[:n_keep].to(label.dtype)
+        return self._sample(hip_ops.proposal_targets, roi, bbox, label)
 
     def with_sources(self, roi, bbox, label):
         """``__call__`` plus sample_src [S] int32: the row of cat(roi, bbox) each sample came from (the reference's keep_index;
         < len(roi): a proposal).  What FasterRCNNTrainer(head_grads=True) maps the regression target's gradient back with."""
-        require_cuda(roi, "ProposalTargetCreator")
-        sample_roi, gt_roi_loc, gt_roi_label, counts, src = hip_ops.proposal_targets_src(
-            roi, bbox, label, self.n_sample, self.pos_roi_per_image, self.pos_iou_thresh, self.neg_iou_thresh_high,
-            self.neg_iou_thresh_low)
-        host = counts.tolist()
-        raise_for_counts([host])
-        n_keep = host[0]
-        return sample_roi[:n_keep], gt_roi_loc[:n_keep], gt_roi_label[:n_keep].to(label.dtype), src[:n_keep]
+        return self._sample(hip_ops.proposal_targets_src, roi, bbox, label)
 
     def batch(self, rois, bboxes, labels, gt_counts=None, with_sources=False):
         """``__call__`` / ``with_sources`` for every image of a batch at once, WITHOUT reading anything back: rois [B,R,4];
