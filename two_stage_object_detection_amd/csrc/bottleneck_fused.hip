@@ -29,7 +29,8 @@
 //   * conv1's activations: the x halo tile, one 32-channel K-step at a time through LDS (split into pieces on the way in);
 //     conv2's: y1 planes in LDS, the im2col gather is the fragment's row address; conv3's: y2 planes (the y1 region re-used).
 //   * a wave owns one 32-channel block of the step's 64 and every second pixel block: ONE weight fragment pair per 16-k chunk
-//     feeds up to four activation fragments.
+//     feeds up to four activation fragments.  How many blocks a wave owns is a template parameter of the tile pipeline
+//     (bottleneck_tile<TH, PROJ, NB1, NB2>), picked once per wave by a scalar branch: no per-block EXEC masks.
 #include "tsod_internal.h"
 #include <type_traits>
 
@@ -40,8 +41,8 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Tile: TH x 16 output pixels, TH = 10 (160 pixels = 5 blocks of 32, halo 12 x 18 = 216 -> 224 rows = 7 blocks) or 8 (128 = 4 blocks,
 // halo 180 -> 192 rows = 6 blocks).  10 rows make one round of a batch-1 launch (420 tiles on 512 slots); 8 rows split evenly over the
-// waves (3 + 3 halo blocks, 2 + 2 tile blocks: the slowest wave issues 456 MFMAs for 128 pixels instead of 660 for 160) and win
-// from two images on.  The launcher picks by rounds x MFMAs of the slowest wave.
+// waves (3 + 3 halo blocks, 2 + 2 tile blocks: the slowest wave issues 456 MFMAs for 128 pixels instead of 660 for 160).  The
+// launcher picks by rounds x MFMAs of the slowest wave: 8 rows from two images on (DESIGN.md 4.8 has both heights measured).
 constexpr int TW = 16, HW_ = TW + 2;
 constexpr int CMID = 64;
 // y planes: [rows][64 channels] fp16 at a pitch of 144 bytes (9 x 16: the 16 rows of a ds_read_b128 lane group land in 16 distinct
@@ -87,17 +88,18 @@ __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned off)
 struct WFrag { u32x4 h[2], l[2]; };
 struct AFrag { u32x4 h, l; };
 
-template <int TH, bool PROJ = false>
-__global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
+// The tile pipeline of one wave that owns NB1 pixel blocks of the halo and NB2 of the tile (pb0, pb0 + 2, ...).  The counts are
+// compile-time: every loop over a wave's blocks unrolls without a guard, so a K-step's MFMAs and fragment reads are ONE basic
+// block the scheduler can interleave (with `b < nb1` guards on a per-lane `tid >> 6` every tsod_mfma3 sat alone in an
+// EXEC-masked block behind an lgkmcnt(0)).  `wave` is a scalar (readfirstlane): cb and pb0 only feed addresses.
+template <int TH, bool PROJ, int NB1, int NB2>
+__device__ __forceinline__ void bottleneck_tile(const Params &p, unsigned char *lds, const int wave) {
     using G = Geo<TH>;
-    constexpr int HALO = G::HALO, PB1 = G::PB1, PB2 = G::PB2, Y_PLANE = G::Y_PLANE, A_PLANE = G::A_PLANE, A_STAGE = G::A_STAGE,
-                  SCR_OFF = G::SCR_OFF, LDS_BYTES = G::LDS_BYTES;
-    __shared__ __align__(16) unsigned char lds[LDS_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int HALO = G::HALO, PB1 = G::PB1, Y_PLANE = G::Y_PLANE, A_PLANE = G::A_PLANE, A_STAGE = G::A_STAGE, SCR_OFF = G::SCR_OFF;
+    static_assert(NB2 <= NB1 && NB1 <= 4 && NB2 <= 3, "the accumulators of conv1 serve conv2 and conv3");
+    const int tid = threadIdx.x, lane = tid & 63;
     const int j = lane & 31, hh = lane >> 5;             // fragment column (pixel) / row (weight row) index, k half
     const int cb = wave & 1, pb0 = wave >> 1;            // this wave's channel block of the step's 64, its first pixel block (stride 2)
-    // pixel blocks this wave owns (pb0, pb0 + 2, ...): of the halo's PB1, of the tile's PB2
-    const int nb1 = (PB1 - pb0 + 1) / 2, nb2 = (PB2 - pb0 + 1) / 2;
     float *scr = reinterpret_cast<float *>(lds + SCR_OFF);
 
     // ---- the tile.  Blocks b, b + 8, ... share an XCD (private L2; observed round-robin placement - a speed matter only): XCD x takes
@@ -127,11 +129,16 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
     // step, and the weights are the same 272 KB for every workgroup of the launch: L2-resident), two steps ahead of their use
     // steps of one 64-channel slice of conv3: two over y2 and, PROJ, Cin / 32 more over x (the stacked projection shortcut)
     const int n_steps1 = p.Cin / 32, sps = PROJ ? 2 + n_steps1 : 2, n_steps = n_steps1 + 18 + (p.Cout / 64) * sps;
-    const u32x4 *wbase = reinterpret_cast<const u32x4 *>(p.wstream + cb * (W_STEP / 2) + lane * 64);
+    // Through a buffer descriptor of exactly the stream's extent: the two requests past the last step (every step asks for step
+    // s + 2) are out of range and return zeros nobody reads - no branch in the step loops.
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void *)p.wstream, (short)0, n_steps * W_STEP, 0x00020000);
+    const unsigned wbase = (unsigned)(cb * (W_STEP / 2) + lane * 64);
     auto w_load = [&](int s, WFrag &f) {
-        if (s >= n_steps) return;
-        const u32x4 *src = wbase + (size_t)s * (W_STEP / 16);
-        f.h[0] = src[0]; f.l[0] = src[1]; f.h[1] = src[2]; f.l[1] = src[3];
+        const unsigned o = wbase + (unsigned)s * (unsigned)W_STEP;
+        f.h[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, o, 0, 0);
+        f.l[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, o + 16u, 0, 0);
+        f.h[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, o + 32u, 0, 0);
+        f.l[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, o + 48u, 0, 0);
     };
     WFrag wf[3];                                         // steps s, s + 1, s + 2 rotate through these (compile-time indices only)
     w_load(0, wf[0]);
@@ -151,10 +158,10 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
         xdst[i] = off64(row, q >> 1) + (q & 1) * 8;
     }
     float4 xr[NX];
-    auto x_load = [&](int ks) {
-        if (ks >= n_steps1) return;
+    auto x_load = [&](int ks) {                          // (past the last K-step: out-of-range requests, zeros nobody reads - no branch)
+        const bool live = ks < n_steps1;
 #pragma unroll
-        for (int i = 0; i < NX; ++i) xr[i] = bload4(rs_x, xoff[i] != kOOB ? xoff[i] + (unsigned)ks * 128u : kOOB);
+        for (int i = 0; i < NX; ++i) xr[i] = bload4(rs_x, live && xoff[i] != kOOB ? xoff[i] + (unsigned)ks * 128u : kOOB);
     };
     auto x_store = [&](int stage) {
 #pragma unroll
@@ -167,16 +174,16 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
         }
     };
     // x fragments of the wave's pixel blocks: row (pb0 + 2 b) * 32 + j, chunk c
-    int xfa[4][2];                                       // (LDS byte offsets, not pointers: a pointer into LDS costs two registers)
+    int xfa[NB1][2];                                     // (LDS byte offsets, not pointers: a pointer into LDS costs two registers)
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < NB1; ++b)
 #pragma unroll
         for (int c = 0; c < 2; ++c) xfa[b][c] = off64((pb0 + 2 * b) * 32 + j, 2 * c + hh);
 
     // ================= conv1: y1[224 x 64] = x_halo[224 x Cin] . W1^T =================
-    f32x16 acc[4];
+    f32x16 acc[NB1];
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < NB1; ++b)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[b][e] = 0.f;
     x_load(0);
@@ -195,12 +202,10 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
 #pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (b < nb1) {
-                    const u32x4 ah = *reinterpret_cast<const u32x4 *>(lds + xfa[b][c] + stage * A_STAGE);
-                    const u32x4 al = *reinterpret_cast<const u32x4 *>(lds + xfa[b][c] + stage * A_STAGE + A_PLANE);
-                    tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], ah, al);
-                }
+            for (int b = 0; b < NB1; ++b) {
+                const u32x4 ah = *reinterpret_cast<const u32x4 *>(lds + xfa[b][c] + stage * A_STAGE);
+                const u32x4 al = *reinterpret_cast<const u32x4 *>(lds + xfa[b][c] + stage * A_STAGE + A_PLANE);
+                tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], ah, al);
             }
         }
         wf[0] = wf[1];
@@ -226,8 +231,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
             bv[4 * v] = b4.x; bv[4 * v + 1] = b4.y; bv[4 * v + 2] = b4.z; bv[4 * v + 3] = b4.w;
         }
 #pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            if (b >= nb1) continue;
+        for (int b = 0; b < NB1; ++b) {
             const int row = (pb0 + 2 * b) * 32 + j, hr = row / HW_, hc = row - hr * HW_;
             const bool ok = row < HALO && (unsigned)(h0 - 1 + hr) < (unsigned)p.H && (unsigned)(w0 - 1 + hc) < (unsigned)p.W;
             const float keep = ok ? 1.f : 0.f;
@@ -254,35 +258,33 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
         *reinterpret_cast<u32x4 *>(dst + Y_PLANE + 16) = u32x4{lq[4], lq[5], lq[6], lq[7]};
     };
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (b < nb1) y_store(acc[b], (pb0 + 2 * b) * 32 + j, ys1);
+    for (int b = 0; b < NB1; ++b) y_store(acc[b], (pb0 + 2 * b) * 32 + j, ys1);
     __syncthreads();
 
     // ================= conv2: y2[160 x 64] = im2col(y1)[160 x 576] . W2^T (18 steps: tap, channel half) =================
     // No barrier inside: y1 is read-only, the weights come from registers.  The fragments of chunk n + 1 are read while chunk n's MFMAs
     // run (two register sets), the weights of step t + 2 are requested at step t.
-    int yfa[3];                                          // this lane's output pixels: LDS offset of the halo row at tap (0, 0), k half included
+    int yfa[NB2];                                        // this lane's output pixels: LDS offset of the halo row at tap (0, 0), k half included
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
+    for (int b = 0; b < NB2; ++b) {
         int pidx = (pb0 + 2 * b) * 32 + j;
         pidx = pidx < TH * TW ? pidx : TH * TW - 1;      // (rows of a block past the tile compute a duplicate, never stored)
         yfa[b] = ((pidx / TW) * HW_ + (pidx % TW)) * Y_PITCH + hh * 16;
     }
 #pragma unroll
-    for (int b = 0; b < 3; ++b)
+    for (int b = 0; b < NB2; ++b)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[b][e] = 0.f;
     const int s2base = n_steps1;
-    AFrag af[2][3];
-    auto y1_frags = [&](int n, AFrag (&f)[3]) {          // chunk n = 2 t + c of conv2: tap t >> 1, channels 32 (t & 1) + 16 c
+    AFrag af[2][NB2];
+    auto y1_frags = [&](int n, AFrag (&f)[NB2]) {        // chunk n = 2 t + c of conv2: tap t >> 1, channels 32 (t & 1) + 16 c
         const int t = n >> 1, c = n & 1, tap = t >> 1, kh = tap / 3, kw = tap - kh * 3;
         const int imm = (kh * HW_ + kw) * Y_PITCH + (t & 1) * 64 + c * 32;            // an immediate after unrolling
 #pragma unroll
-        for (int b = 0; b < 3; ++b)
-            if (b < nb2) {
-                f[b].h = *reinterpret_cast<const u32x4 *>(lds + yfa[b] + imm);
-                f[b].l = *reinterpret_cast<const u32x4 *>(lds + yfa[b] + imm + Y_PLANE);
-            }
+        for (int b = 0; b < NB2; ++b) {
+            f[b].h = *reinterpret_cast<const u32x4 *>(lds + yfa[b] + imm);
+            f[b].l = *reinterpret_cast<const u32x4 *>(lds + yfa[b] + imm + Y_PLANE);
+        }
     };
     y1_frags(0, af[0]);
 #pragma unroll
@@ -292,9 +294,11 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
         for (int c = 0; c < 2; ++c) {
             const int n = 2 * t + c;
             if (n + 1 < 36) y1_frags(n + 1, af[(n + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);           // (the requests stay ABOVE chunk n's MFMAs: left alone the scheduler sinks them
+                                                         //  below, and the next chunk opens by waiting for reads issued just before it)
 #pragma unroll
-            for (int b = 0; b < 3; ++b)
-                if (b < nb2) tsod_mfma3(acc[b], wf[t % 3].h[c], wf[t % 3].l[c], af[n & 1][b].h, af[n & 1][b].l);
+            for (int b = 0; b < NB2; ++b)
+                tsod_mfma3(acc[b], wf[t % 3].h[c], wf[t % 3].l[c], af[n & 1][b].h, af[n & 1][b].l);
             __builtin_amdgcn_sched_barrier(0);           // (the unrolled loop is one basic block: keep the scheduler from hoisting every
                                                          //  later chunk's loads to the top - 400+ live registers, scratch spills)
         }
@@ -313,8 +317,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
             bv[4 * v] = b4.x; bv[4 * v + 1] = b4.y; bv[4 * v + 2] = b4.z; bv[4 * v + 3] = b4.w;
         }
 #pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            if (b >= nb2) continue;
+        for (int b = 0; b < NB2; ++b) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 chk = fmaf(acc[b][e], 0.f, chk);
@@ -328,8 +331,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
     const int e2 = tsod_fp16x2_exp_from_bits(__float_as_uint(mx));
     const float ys2 = __uint_as_float((unsigned)(127 + e2) << 23);
 #pragma unroll
-    for (int b = 0; b < 3; ++b)
-        if (b < nb2) y_store(acc[b], (pb0 + 2 * b) * 32 + j, ys2);
+    for (int b = 0; b < NB2; ++b) y_store(acc[b], (pb0 + 2 * b) * 32 + j, ys2);
     __syncthreads();
 
     // ================= conv3: out[160 x Cout] = y2[160 x 64] . W3^T + x, 64 output channels (two weight steps) at a time ======
@@ -346,99 +348,100 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
     static_assert(2 * P_BYTES <= Y_PLANE - TH * TW * Y_PITCH, "two patches per gap of the y region");
     unsigned char *patch = lds + (wave >> 1) * Y_PLANE + TH * TW * Y_PITCH + (wave & 1) * P_BYTES;
     const int ep_px = lane >> 3, ep_q = lane & 7;        // this lane's pixel (+ 8 i) and 4-channel piece of a block in the coalesced layout
-    int y2a[3];
-    unsigned xpix[3][4], opix[3][4];                     // byte offsets of the lane's piece in x and in out (kOOB: not a pixel of the image)
+    int y2a[NB2];
+    unsigned xpix[NB2][4], opix[NB2][4];                 // byte offsets of the lane's piece in x and in out (kOOB: not a pixel of the image)
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
+    for (int b = 0; b < NB2; ++b) {
         const int pidx = (pb0 + 2 * b) * 32 + j;
         y2a[b] = (pidx < TH * TW ? pidx : TH * TW - 1) * Y_PITCH + hh * 16;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int pe = (pb0 + 2 * b) * 32 + ep_px + 8 * i, pr = pe >> 4, pc = pe & 15;      // (TW == 16)
-            const bool ok = b < nb2 && pe < TH * TW && h0 + pr < p.H && w0 + pc < p.W;
+            const bool ok = pe < TH * TW && h0 + pr < p.H && w0 + pc < p.W;
             const long gp = ((long)img * p.H + h0 + pr) * p.W + w0 + pc;
             xpix[b][i] = ok ? (unsigned)(gp * p.in_pitch + cb * 32 + ep_q * 4) * 4u : kOOB;
             opix[b][i] = ok ? (unsigned)(gp * p.out_pitch + cb * 32 + ep_q * 4) * 4u : kOOB;
         }
     }
-    static_assert(TW == 16 && (PB1 + 1) / 2 <= 4 && (PB2 + 1) / 2 <= 3, "pixel index -> (row, column) by shifts; blocks per wave");
-    auto y2_frags = [&](int n, AFrag (&f)[3]) {          // chunk n (16 channels of y2)
+    static_assert(TW == 16, "pixel index -> (row, column) by shifts");
+    auto y2_frags = [&](int n, AFrag (&f)[NB2]) {        // chunk n (16 channels of y2)
 #pragma unroll
-        for (int b = 0; b < 3; ++b)
-            if (b < nb2) {
-                f[b].h = *reinterpret_cast<const u32x4 *>(lds + y2a[b] + n * 32);
-                f[b].l = *reinterpret_cast<const u32x4 *>(lds + y2a[b] + n * 32 + Y_PLANE);
-            }
+        for (int b = 0; b < NB2; ++b) {
+            f[b].h = *reinterpret_cast<const u32x4 *>(lds + y2a[b] + n * 32);
+            f[b].l = *reinterpret_cast<const u32x4 *>(lds + y2a[b] + n * 32 + Y_PLANE);
+        }
     };
     const int s3base = n_steps1 + 18;
   if constexpr (PROJ) {
     // ---- stacked-K slices: steps 0, 1 contract y2 (LDS), steps 2 .. sps - 1 contract x (the tile's own pixels, from L2).  The two
     // operands carry different scales (y2: this tile's, x: its tensor's): the accumulators change scale between them (a power of two:
     // exact).  Weights rotate through wf[0 .. 2] by register moves as in conv1 (steps s, s + 1, s + 2).
-    unsigned xfo[3];                                     // byte offset in x of this lane's fragment pixel (channel 8 hh), kOOB outside the image
+    unsigned xfo[NB2];                                   // byte offset in x of this lane's fragment pixel (channel 8 hh), kOOB outside the image
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
+    for (int b = 0; b < NB2; ++b) {
         const int pidx = (pb0 + 2 * b) * 32 + j, pr = pidx >> 4, pc = pidx & 15;
-        const bool ok = b < nb2 && pidx < TH * TW && h0 + pr < p.H && w0 + pc < p.W;
+        const bool ok = pidx < TH * TW && h0 + pr < p.H && w0 + pc < p.W;
         xfo[b] = ok ? (unsigned)((((long)img * p.H + h0 + pr) * p.W + w0 + pc) * p.in_pitch + 8 * hh) * 4u : kOOB;
     }
     const float rescale = __uint_as_float((unsigned)(127 + e_x - e2) << 23);           // from 2^e2 y2 to 2^e_x x
     const float sc3x = __uint_as_float((unsigned)(127 - e_x - p.w_exp3) << 23);
-    float4 xraw[2][3][2];                                // the x floats of one step (two chunks), requested one step ahead
-    auto x_frag_load = [&](int xs) {                     // x step xs: channels 32 xs + 16 c + 8 hh .. + 7
+    float4 xraw[2][NB2][2];                              // the x floats of one step (two chunks), requested one step ahead
+    auto x_frag_load = [&](int xs) {                     // x step xs: channels 32 xs + 16 c + 8 hh .. + 7 (past the last: out of range)
+        const bool live = xs < n_steps1;
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const unsigned o = xfo[b] != kOOB ? xfo[b] + (unsigned)(32 * xs + 16 * c) * 4u : kOOB;
+            for (int b = 0; b < NB2; ++b) {
+                const unsigned o = live && xfo[b] != kOOB ? xfo[b] + (unsigned)(32 * xs + 16 * c) * 4u : kOOB;
                 xraw[c][b][0] = bload4(rs_x, o);
                 xraw[c][b][1] = bload4(rs_x, o != kOOB ? o + 16u : kOOB);
             }
     };
     for (int q = 0; q < p.Cout / 64; ++q) {
 #pragma unroll
-        for (int b = 0; b < 3; ++b)
+        for (int b = 0; b < NB2; ++b)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[b][e] = 0.f;
         const unsigned chq = (unsigned)(q * 64) * 4u;
         const int sbase = s3base + q * sps;
-        for (int st = 0; st < sps; ++st) {
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {                 // the two y2 steps: straight-line
             w_load(sbase + st + 2, wf[2]);
-            if (st < 2) {
-                if (st == 1) x_frag_load(0);             // the first x step flies under the second y2 step's MFMAs
+            if (st == 1) x_frag_load(0);                 // the first x step flies under the second y2 step's MFMAs
 #pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    y2_frags(2 * st + c, af[c]);
+            for (int c = 0; c < 2; ++c) {
+                y2_frags(2 * st + c, af[c]);
 #pragma unroll
-                    for (int b = 0; b < 3; ++b)
-                        if (b < nb2) tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
-                }
-                if (st == 1) {
-#pragma unroll
-                    for (int b = 0; b < 3; ++b)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[b][e] *= rescale;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int b = 0; b < 3; ++b) {
-                        unsigned h0_, l0_, h1_, l1_, h2_, l2_, h3_, l3_;
-                        tsod_split2_pair(xraw[c][b][0].x, xraw[c][b][0].y, a_scale, h0_, l0_);
-                        tsod_split2_pair(xraw[c][b][0].z, xraw[c][b][0].w, a_scale, h1_, l1_);
-                        tsod_split2_pair(xraw[c][b][1].x, xraw[c][b][1].y, a_scale, h2_, l2_);
-                        tsod_split2_pair(xraw[c][b][1].z, xraw[c][b][1].w, a_scale, h3_, l3_);
-                        af[c][b].h = u32x4{h0_, h1_, h2_, h3_};
-                        af[c][b].l = u32x4{l0_, l1_, l2_, l3_};
-                    }
-                if (st + 1 < sps) x_frag_load(st - 1);   // the next x step's floats (their registers are free now)
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int b = 0; b < 3; ++b)
-                        if (b < nb2) tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
+                for (int b = 0; b < NB2; ++b) tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
             }
+            if (st == 1) {
+#pragma unroll
+                for (int b = 0; b < NB2; ++b)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[b][e] *= rescale;
+            }
+            wf[0] = wf[1];
+            wf[1] = wf[2];
+        }
+        for (int st = 2; st < sps; ++st) {               // the x steps
+            w_load(sbase + st + 2, wf[2]);
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int b = 0; b < NB2; ++b) {
+                    unsigned h0_, l0_, h1_, l1_, h2_, l2_, h3_, l3_;
+                    tsod_split2_pair(xraw[c][b][0].x, xraw[c][b][0].y, a_scale, h0_, l0_);
+                    tsod_split2_pair(xraw[c][b][0].z, xraw[c][b][0].w, a_scale, h1_, l1_);
+                    tsod_split2_pair(xraw[c][b][1].x, xraw[c][b][1].y, a_scale, h2_, l2_);
+                    tsod_split2_pair(xraw[c][b][1].z, xraw[c][b][1].w, a_scale, h3_, l3_);
+                    af[c][b].h = u32x4{h0_, h1_, h2_, h3_};
+                    af[c][b].l = u32x4{l0_, l1_, l2_, l3_};
+                }
+            x_frag_load(st - 1);                         // the next x step's floats (their registers are free now)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int b = 0; b < NB2; ++b) tsod_mfma3(acc[b], wf[0].h[c], wf[0].l[c], af[c][b].h, af[c][b].l);
             wf[0] = wf[1];
             wf[1] = wf[2];
         }
@@ -446,8 +449,7 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
         const float4 b4 = *reinterpret_cast<const float4 *>(p.bn + 256 + p.Cout + q * 64 + cb * 32 + ep_q * 4);
         const float4 sv = make_float4(s4.x * sc3x, s4.y * sc3x, s4.z * sc3x, s4.w * sc3x);
 #pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            if (b >= nb2) continue;
+        for (int b = 0; b < NB2; ++b) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 chk = fmaf(acc[b][4 * v], 0.f, fmaf(acc[b][4 * v + 1], 0.f, fmaf(acc[b][4 * v + 2], 0.f, fmaf(acc[b][4 * v + 3], 0.f, chk))));
@@ -480,14 +482,14 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
       // at the start, its second into wf[0] as soon as that is dead (after two chunks); the slice ends by moving them into place
       for (int q = 0; q < p.Cout / 64; ++q) {
   #pragma unroll
-          for (int b = 0; b < 3; ++b)
+          for (int b = 0; b < NB2; ++b)
   #pragma unroll
               for (int e = 0; e < 16; ++e) acc[b][e] = 0.f;
           const unsigned chq = (unsigned)(q * 64) * 4u;                    // byte offset of the slice inside a pixel
           w_load(s3base + 2 * q + 2, wf[2]);                               // (the weights first: in-order returns - they are needed first)
-          float4 res[3][4];                                                // the residual of this slice: requested before the MFMAs
+          float4 res[NB2][4];                                              // the residual of this slice: requested before the MFMAs
   #pragma unroll
-          for (int b = 0; b < 3; ++b)
+          for (int b = 0; b < NB2; ++b)
   #pragma unroll
               for (int i = 0; i < 4; ++i) res[b][i] = bload4(rs_x, xpix[b][i] != kOOB ? xpix[b][i] + chq : kOOB);
           y2_frags(0, af[0]);
@@ -495,17 +497,17 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
           for (int n = 0; n < 4; ++n) {
               if (n == 2) w_load(s3base + 2 * q + 3, wf[0]);
               if (n + 1 < 4) y2_frags(n + 1, af[(n + 1) & 1]);
+              __builtin_amdgcn_sched_barrier(0);                           // (requests above the MFMAs, as in conv2)
   #pragma unroll
-              for (int b = 0; b < 3; ++b)
-                  if (b < nb2) tsod_mfma3(acc[b], wf[n >> 1].h[n & 1], wf[n >> 1].l[n & 1], af[n & 1][b].h, af[n & 1][b].l);
+              for (int b = 0; b < NB2; ++b)
+                  tsod_mfma3(acc[b], wf[n >> 1].h[n & 1], wf[n >> 1].l[n & 1], af[n & 1][b].h, af[n & 1][b].l);
               __builtin_amdgcn_sched_barrier(0);
           }
           const float4 s4 = *reinterpret_cast<const float4 *>(p.bn + 256 + q * 64 + cb * 32 + ep_q * 4);
           const float4 b4 = *reinterpret_cast<const float4 *>(p.bn + 256 + p.Cout + q * 64 + cb * 32 + ep_q * 4);
           const float4 sv = make_float4(s4.x * sc3, s4.y * sc3, s4.z * sc3, s4.w * sc3);
   #pragma unroll
-          for (int b = 0; b < 3; ++b) {
-              if (b >= nb2) continue;
+          for (int b = 0; b < NB2; ++b) {
               // accumulators -> patch: row j, channels 16 hh + 4 v .. + 3 (only this wave touches its patch: in-order LDS + the waits)
   #pragma unroll
               for (int v = 0; v < 4; ++v) {
@@ -539,6 +541,23 @@ __global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
   }
     if (p.range_flag != nullptr && __any(!(chk == 0.f)) && lane == 0) atomicOr(p.range_flag, 1);
     if (p.amax_out != nullptr) tsod_amax_commit(p.amax_out, amax, scr, tid, 256);
+}
+
+// Waves 0, 1 own the even pixel blocks, waves 2, 3 the odd ones: ONE scalar branch on the first block picks the tile pipeline
+// with that wave's block counts (TH = 10: 4 + 3 halo blocks, 3 + 2 tile blocks; TH = 8: 3 + 3 and 2 + 2 - one pipeline).  Both
+// pipelines pass the same barriers in the same order.
+template <int TH, bool PROJ = false>
+__global__ void __launch_bounds__(256, 2) bottleneck_kernel(const Params p) {
+    using G = Geo<TH>;
+    __shared__ __align__(16) unsigned char lds[G::LDS_BYTES];
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    constexpr int NB1_0 = (G::PB1 + 1) / 2, NB1_1 = G::PB1 / 2, NB2_0 = (G::PB2 + 1) / 2, NB2_1 = G::PB2 / 2;
+    if constexpr (NB1_0 == NB1_1 && NB2_0 == NB2_1) {
+        bottleneck_tile<TH, PROJ, NB1_0, NB2_0>(p, lds, wave);
+    } else {
+        if ((wave >> 1) == 0) bottleneck_tile<TH, PROJ, NB1_0, NB2_0>(p, lds, wave);
+        else bottleneck_tile<TH, PROJ, NB1_1, NB2_1>(p, lds, wave);
+    }
 }
 
 }  // namespace
