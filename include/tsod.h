@@ -1187,6 +1187,80 @@ int tsod_grad_scale_f32(const tsod_adamw_tensor *table, int32_t n_tensors, const
 int tsod_grad_norm_host_f32(const float *const *grads, const int64_t *numels, int32_t n_tensors, float max_norm,
                             tsod_grad_norm_result *result);
 
+/* ---- detection overlay: the last step of the reference's multi_inference.py:104-154 on the GPU -------------
+ * tsod_draw_groups_u8 paints up to TSOD_DRAW_MAX_GROUPS groups of boxes, with text tags, in place onto B u8 RGB images
+ * [B][H][W][3] (row_bytes >= 3 W between rows, image_bytes >= H row_bytes between images) in ONE launch.  Integer arithmetic
+ * only, no atomics: the result depends on the arguments alone.  Bytes of a row beyond 3 W and pixels that no item covers
+ * are neither read nor written.
+ *
+ * A group (tsod_draw_group) is one style over one box array `boxes` f32 [B][R][pitch], columns 0..3 = x1 y1 x2 y2; pitch 4,
+ * or 6 for detection records (x1 y1 x2 y2 score class).
+ *   Rows drawn, in this order (the conventions of DetectionEvaluator.update): keep == NULL and counts == NULL: rows 0..R-1;
+ *     counts i32 [B]: rows 0..counts[b]-1; keep i32 [B][R] with n_kept i32 [B]: rows keep[b][0 .. n_kept[b]).  A count
+ *     outside [0, R] is clamped into it; a keep entry outside [0, R) draws nothing.
+ *   Label index of a row: labels i64 [B][R] when given; else with pitch 6 column 5 converted to int32 (truncated towards
+ *     zero, saturating, NaN -> 0); else (pitch 4) the row has no label and gets no tag.  label_offset is added (in 64 bits).
+ *   Box to pixels: X1 = rintf(clamp(sx * x1)), Y1 = rintf(clamp(sy * y1)), X2 = rintf(clamp(sx * x2)), Y2 = rintf(clamp(sy *
+ *     y2)), each product ONE f32 multiply, clamp to [-2^24, 2^24], bounds inclusive.  A row with a non-finite coordinate, a
+ *     NaN product, X2 < X1 or Y2 < Y1 draws nothing: no outline and no tag.
+ *   Outline: the pixels (x, y) of [X1, X2] x [Y1, Y2] with x - X1 < t, X2 - x < t, y - Y1 < t or Y2 - y < t (t = thickness;
+ *     it grows inwards, a box thinner than 2 t is filled), blended with color[0..2] at alpha color[3].
+ *   Blend, per channel: out = (a c + (255 - a) src + 127) / 255 in integers (a = 255 stores c); a = 0 leaves the pixel alone.
+ *   Tag (tag != TSOD_DRAW_TAG_NONE and the row has a label): the group reads rows [string_first, string_first +
+ *     string_count) of the table `strings` (u8 [n_strings][32], zero-terminated, at most 31 bytes are read; DEVICE memory,
+ *     4-byte aligned; one group: string_first = 0, string_count = n_strings).  Line 1 is strings[string_first + index] when
+ *     0 <= index < string_count, else "class_" followed by the decimal index ('-' first when negative) - with string_count
+ *     == 0 every label takes that route.  With score_line (pitch 6) line 2 is "Conf: d.ddd" of the score s = column
+ *     4: m = (int)rintf(fminf(fmaxf(s, 0), 1) * 1000), printed as m / 1000, '.', three digits of m % 1000; a NaN score
+ *     prints "Conf: -.---".  Glyphs are 5x7 in a 6x8 cell (the glyph in the cell's upper left), every glyph pixel
+ *     font_scale x font_scale image pixels.  With cols = the longer line's length and lines = 1 or 2, the tag is the
+ *     rectangle of w = cols 6 font_scale + 2 padding by h = lines 8 font_scale + 2 padding pixels whose left edge is X1 and
+ *       TSOD_DRAW_TAG_ABOVE: whose bottom row is Y1 - 1 (top = Y1 - h); when top < 0, top = Y1;
+ *       TSOD_DRAW_TAG_BELOW: whose top row is Y2 + 1; when top + h > H, its bottom row is Y2 (top = Y2 - h + 1);
+ *     then, when left > 0 and left + w > W, left = max(W - w, 0); what still lies outside the image is clipped.  The
+ *     rectangle is blended with tag_bg[0..2] at alpha tag_bg[3]; then the set pixels of character k of line l - cell origin
+ *     (left + padding + 6 k font_scale, top + padding + 8 l font_scale) - are stored opaque with text_rgb.
+ *   Order: first every outline - groups ascending, rows in drawn order -, then every tag in the same order; a later item
+ *     paints over an earlier one.
+ * The kernel: one workgroup per 64x16 tile of one image collects the items that meet its tile into a list of
+ * TSOD_DRAW_LIST_CAPACITY entries in LDS and every thread walks that list for its pixels; a tile met by more items paints
+ * the list and refills it, in item order, before its single store per pixel.
+ * TSOD_ERR_INVALID_ARG: images NULL; B, H or W <= 0; row_bytes < 3 W; image_bytes < H row_bytes; n_groups outside
+ *   [0, TSOD_DRAW_MAX_GROUPS] (or groups NULL with n_groups > 0); n_strings < 0 (or strings NULL with n_strings > 0); in a
+ *   group: R < 0, boxes NULL with R > 0, pitch not 4 or 6, keep without n_kept or the reverse, keep and counts together,
+ *   thickness < 1, font_scale < 1, padding < 0, tag outside the enum, score_line not 0 / 1, score_line with pitch 4,
+ *   string_first < 0, string_count < 0 or string_first + string_count > n_strings.
+ * TSOD_ERR_UNSUPPORTED: H W or B R beyond 2^31 - 1, more than 2^31 - 1 tiles, thickness, font_scale or padding above
+ *   TSOD_DRAW_MAX_STYLE (the geometry is 32-bit).  TSOD_ERR_ALIGNMENT: strings not 4-byte aligned.
+ * n_groups == 0 or R == 0 in every group: TSOD_OK, nothing is launched.
+ * tsod_draw_font5x7: HOST function, the font of csrc/font5x7.h: out[c][r] = row r (0 = top) of the glyph of byte c, 5 low
+ *   bits, bit 4 the leftmost column.  Bytes without a glyph of their own (and bytes >= 128) print a filled block, 0x1f. */
+#define TSOD_DRAW_MAX_GROUPS 4
+#define TSOD_DRAW_LIST_CAPACITY 64
+#define TSOD_DRAW_STRING_BYTES 32
+#define TSOD_DRAW_MAX_STYLE 32767
+enum { TSOD_DRAW_TAG_NONE = 0, TSOD_DRAW_TAG_ABOVE = 1, TSOD_DRAW_TAG_BELOW = 2 };
+typedef struct tsod_draw_group {
+    const float *boxes;     /* [B][R][pitch] */
+    const int32_t *counts;  /* [B] or NULL */
+    const int32_t *keep;    /* [B][R] or NULL */
+    const int32_t *n_kept;  /* [B], with keep */
+    const int64_t *labels;  /* [B][R] or NULL */
+    int32_t R, pitch, label_offset;
+    int32_t string_first, string_count; /* the group's rows of `strings` */
+    float sx, sy;           /* box coordinates -> image pixels */
+    uint8_t color[4];       /* outline R G B, alpha */
+    int32_t thickness;
+    int32_t tag;            /* TSOD_DRAW_TAG_* */
+    uint8_t text_rgb[4];    /* tag text R G B, [3] unused */
+    uint8_t tag_bg[4];      /* tag background R G B, alpha */
+    int32_t font_scale, padding, score_line;
+} tsod_draw_group;
+int tsod_draw_groups_u8(uint8_t *images, int32_t B, int32_t H, int32_t W, int64_t row_bytes, int64_t image_bytes,
+                        const tsod_draw_group *groups, int32_t n_groups, const uint8_t *strings, int32_t n_strings,
+                        tsod_stream_t stream);
+int tsod_draw_font5x7(uint8_t out[128][7]);
+
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends
  * `count_per_rank` floats and receives n_ranks * count_per_rank in rank order.  Stream-ordered, no host synchronisation.

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64,
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_uint64,
                     c_void_p)
 from typing import NamedTuple
 
@@ -140,6 +140,19 @@ DROPOUT_MAX_SEGMENTS = 16                        # TSOD_DROPOUT_MAX_SEGMENTS
 class DropoutSeg(Structure):
     """Mirror of ``tsod_dropout_seg`` (include/tsod.h): a slice's channel offset in the pixel, real width, first logical channel."""
     _fields_ = [("off", c_int32), ("real", c_int32), ("first", c_int32)]
+
+
+DRAW_MAX_GROUPS, DRAW_LIST_CAPACITY, DRAW_STRING_BYTES, DRAW_MAX_STYLE = 4, 64, 32, 32767   # TSOD_DRAW_*
+DRAW_TAG_NONE, DRAW_TAG_ABOVE, DRAW_TAG_BELOW = 0, 1, 2
+
+
+class DrawGroup(Structure):
+    """Mirror of ``tsod_draw_group`` (include/tsod.h): one style over one box array of the overlay."""
+    _fields_ = [("boxes", c_void_p), ("counts", c_void_p), ("keep", c_void_p), ("n_kept", c_void_p), ("labels", c_void_p),
+                ("R", c_int32), ("pitch", c_int32), ("label_offset", c_int32), ("string_first", c_int32),
+                ("string_count", c_int32), ("sx", c_float), ("sy", c_float),
+                ("color", c_uint8 * 4), ("thickness", c_int32), ("tag", c_int32), ("text_rgb", c_uint8 * 4),
+                ("tag_bg", c_uint8 * 4), ("font_scale", c_int32), ("padding", c_int32), ("score_line", c_int32)]
 
 
 class AdamWGroup(Structure):
@@ -369,6 +382,9 @@ _SIGNATURES = {
     "tsod_eval_accumulate_coco_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32,
                                               c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
+    "tsod_draw_groups_u8": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, POINTER(DrawGroup), c_int32, c_void_p,
+                                    c_int32, c_void_p]),
+    "tsod_draw_font5x7": (c_int, [c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

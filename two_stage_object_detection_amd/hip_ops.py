@@ -2095,3 +2095,84 @@ def grad_norm_host(grads, max_norm: float):
     out = _ffi.GradNormResult()
     check(lib().tsod_grad_norm_host_f32(pointers, numels, len(grads), float(max_norm), byref(out)), "grad_norm_host")
     return np.float64(out.sum_sq), np.float32(out.norm), np.float32(out.coef)
+
+
+# ----------------------------------------------------------------------------- detection overlay
+DRAW_TAGS = {None: _ffi.DRAW_TAG_NONE, "none": _ffi.DRAW_TAG_NONE, "above": _ffi.DRAW_TAG_ABOVE, "below": _ffi.DRAW_TAG_BELOW}
+
+
+def draw_font5x7():
+    """HOST: the overlay's font as a numpy u8 [128,7] array (``tsod_draw_font5x7``): row r of byte c's glyph in the 5 low
+    bits, bit 4 the leftmost column."""
+    import numpy as np
+    out = np.zeros((128, 7), dtype=np.uint8)
+    check(lib().tsod_draw_font5x7(out.ctypes.data), "draw_font5x7")
+    return out
+
+
+def draw_groups(images: torch.Tensor, groups, strings=None) -> torch.Tensor:
+    """Paint up to ``_ffi.DRAW_MAX_GROUPS`` groups of boxes with their tags onto ``images`` (u8 [B,H,W,3] on the device, rows
+    and images may be pitched) IN PLACE, in one launch (``tsod_draw_groups_u8``; the pixel rules are in include/tsod.h).
+
+    ``groups``: dicts with ``boxes`` (f32 [B,R,4] or [B,R,6], contiguous) and optionally ``counts`` (i32 [B]), ``keep`` (i32
+    [B,R]) with ``n_kept`` (i32 [B]), ``labels`` (i64 [B,R]), ``label_offset``, ``strings`` = (first, count) rows of the
+    table (default: all of it), ``scale`` = (sx, sy), ``color`` (R, G, B),
+    ``alpha``, ``width``, ``tag`` ("none" | "above" | "below"), ``text_color``, ``tag_bg``, ``tag_alpha``, ``font_scale``,
+    ``padding``, ``score_line``.  ``strings``: u8 [n,32] zero-terminated rows on the device, or None.  Returns ``images``."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda:
+        require_cuda(images, "draw_groups")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError(f"draw_groups: images are u8 [B,H,W,3], got {images.dtype} {tuple(images.shape)}")
+    B, H, W, _ = images.shape
+    # (torch reports any stride for a dimension of size 1)
+    row_bytes = images.stride(1) if H > 1 else 3 * W
+    image_bytes = images.stride(0) if B > 1 else H * row_bytes
+    if images.stride(3) != 1 or (W > 1 and images.stride(2) != 3) or row_bytes < 3 * W or image_bytes < H * row_bytes:
+        raise ValueError("draw_groups: pixels must be interleaved, rows and images may only be padded at their ends")
+    dev = images.device
+    if len(groups) > _ffi.DRAW_MAX_GROUPS:
+        raise ValueError(f"draw_groups: at most {_ffi.DRAW_MAX_GROUPS} groups in one launch, got {len(groups)}")
+    n_strings = 0
+    if strings is not None:
+        if (not isinstance(strings, torch.Tensor) or strings.device != dev or strings.dtype != torch.uint8 or strings.dim() != 2
+                or strings.shape[1] != _ffi.DRAW_STRING_BYTES or not strings.is_contiguous()):
+            raise ValueError(f"draw_groups: strings are a contiguous u8 [n,{_ffi.DRAW_STRING_BYTES}] tensor on {dev}")
+        n_strings = strings.shape[0]
+
+    def opt(g, name, dtype, shape):
+        t = g.get(name)
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"draw_groups: {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}")
+        return t
+
+    arr = (_ffi.DrawGroup * max(len(groups), 1))()
+    for rec, g in zip(arr, groups):
+        boxes = g["boxes"]
+        require_cuda(boxes, "draw_groups")
+        if boxes.device != dev or boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] not in (4, 6) or not boxes.is_contiguous():
+            raise ValueError(f"draw_groups: boxes are contiguous f32 [{B},R,4|6] on {dev}, got {tuple(boxes.shape)}")
+        R = boxes.shape[1]
+        rec.boxes, rec.R, rec.pitch = ptr(boxes), R, boxes.shape[2]
+        rec.counts, rec.keep = ptr(opt(g, "counts", torch.int32, (B,))), ptr(opt(g, "keep", torch.int32, (B, R)))
+        rec.n_kept, rec.labels = ptr(opt(g, "n_kept", torch.int32, (B,))), ptr(opt(g, "labels", torch.int64, (B, R)))
+        rec.label_offset = int(g.get("label_offset", 0))
+        rec.string_first, rec.string_count = (int(v) for v in g.get("strings", (0, n_strings)))
+        rec.sx, rec.sy = (float(v) for v in g.get("scale", (1.0, 1.0)))
+        tag = g.get("tag", "none")
+        if tag not in DRAW_TAGS:
+            raise ValueError(f"draw_groups: tag is 'none', 'above' or 'below', got {tag!r}")
+        rec.tag = DRAW_TAGS[tag]
+        for field, rgb, a in (("color", g.get("color", (255, 0, 0)), g.get("alpha", 255)),
+                              ("text_rgb", g.get("text_color", g.get("color", (255, 0, 0))), 0),
+                              ("tag_bg", g.get("tag_bg", (255, 255, 255)), g.get("tag_alpha", 255))):
+            vals = tuple(int(v) for v in rgb) + (int(a),)
+            if len(vals) != 4 or not all(0 <= v <= 255 for v in vals):
+                raise ValueError(f"draw_groups: {field} is (R, G, B) with an alpha, each 0..255, got {vals}")
+            setattr(rec, field, (ctypes.c_uint8 * 4)(*vals))
+        rec.thickness, rec.font_scale = int(g.get("width", 1)), int(g.get("font_scale", 1))
+        rec.padding, rec.score_line = int(g.get("padding", 0)), int(bool(g.get("score_line", False)))
+    check(lib().tsod_draw_groups_u8(ptr(images), B, H, W, row_bytes, image_bytes, arr, len(groups), ptr(strings),
+                                    n_strings, stream_ptr()), "draw_groups")
+    return images
