@@ -1261,6 +1261,118 @@ int tsod_draw_groups_u8(uint8_t *images, int32_t B, int32_t H, int32_t W, int64_
                         tsod_stream_t stream);
 int tsod_draw_font5x7(uint8_t out[128][7]);
 
+/* ---- training curves: the loss bookkeeping of the reference's train/train.py:147-160 and the figure of its
+ * utils/draw.py:plot_training_metrics on the GPU.  Four calls; none reads device memory on the host, every result depends
+ * on the arguments alone (integer atomicOr on LDS and min / max are the only order-free combinations used).  The library is
+ * built with -ffp-contract=off: every f32 operation named below is ONE rounding.
+ *
+ * K1  tsod_ema_scan_f32: rows of n samples, x f32 [rows][x_pitch], out f32 [rows][out_pitch] (pitches in elements, >= n):
+ *     out[r][0] = x[r][0];  out[r][i] = fadd(fmul(a, x[r][i]), fmul(b, out[r][i-1])) - two f32 products and one f32 sum,
+ *     no FMA.  With a = (float)alpha and b = (float)(1.0 - alpha) (the subtraction in double) this is the reference's
+ *     update_ema loop bit for bit.  Non-finite samples propagate by IEEE rules.  One wave per row: 64 samples are loaded
+ *     coalesced, every lane forms its product, the wave walks the 64 steps on wave-uniform values (lane k's product is
+ *     broadcast to step k), step k's value goes to word k of an LDS row and every lane stores its own, coalesced.  x and
+ *     out may be the same array.
+ *     TSOD_ERR_INVALID_ARG: rows or n < 0; x or out NULL with rows n > 0; a pitch < n.  rows == 0 or n == 0: TSOD_OK, no launch.
+ *
+ * K2  tsod_plot_limits_f32: the axis limits of a panel.  series: HOST array of n_series DEVICE pointers (f32), lengths:
+ *     HOST array of their lengths; limits: DEVICE f32 [2] = (lo, hi).  With m / M the minimum / maximum over every FINITE
+ *     sample of every series:  none finite -> (0, 1);  M == m -> (m - 0.5f, m + 0.5f);  otherwise pad = 0.1f * (0.5f * M -
+ *     0.5f * m) (= 0.05 (M - m), formed from the halves so that it is finite for samples near +-FLT_MAX), lo = m - pad, hi =
+ *     M + pad; lo and hi are then clamped into [-FLT_MAX, FLT_MAX].  Two launches on the stream (per-workgroup partial
+ *     minima / maxima, then the rule); workspace: DEVICE, TSOD_PLOT_LIMITS_WORKSPACE_BYTES, 4-byte aligned.
+ *     TSOD_ERR_INVALID_ARG: limits NULL; n_series outside [0, TSOD_PLOT_MAX_SERIES]; series or lengths NULL with n_series > 0;
+ *     a length < 0; a NULL series with length > 0.  TSOD_ERR_WORKSPACE: workspace NULL or too small.  No series or only
+ *     empty ones: (0, 1) is still written (one launch).
+ *
+ * K3  tsod_plot_series_u8: paints up to TSOD_PLOT_MAX_SERIES series, in order, into the plot rectangle [px0, px0 + pw) x
+ *     [py0, py0 + ph) of ONE u8 RGB image [H][W][3] (row_bytes >= 3 W between rows).  Nothing outside the rectangle and no
+ *     byte of a row beyond 3 W is read or written; a pixel no series covers is neither read nor written.
+ *     A series (tsod_plot_series): y DEVICE f32 [n]; the abscissa of sample i is the integer x_i = x_first + i x_step
+ *     (x_step >= 1), and x_lo <= x_first, x_first + (n - 1) x_step <= x_hi must hold; color = R G B alpha; width w in [0,
+ *     TSOD_PLOT_MAX_WIDTH]; marker TSOD_PLOT_MARKER_*; marker_size odd, in [1, TSOD_PLOT_MAX_WIDTH].
+ *     limits: DEVICE f32 [2] = (lo, hi), e.g. from K2.
+ *       Column: c_i = px0 + floor((x_i - x_lo) (pw - 1) / (x_hi - x_lo)) in 64-bit integers; x_hi == x_lo: c_i = px0.
+ *       Row:    r_i = py0 + (ph - 1) - (int)rintf(fminf(fmaxf((v - lo) * s, 0), ph - 1)) with s = (float)(ph - 1) / (hi -
+ *               lo): one f32 difference hi - lo, one quotient, one difference v - lo, one product; fmaxf / fminf drop a NaN
+ *               product (lo == hi), which so maps to the bottom row.
+ *       Points: sample i is a point when y[i] is finite.  A non-finite sample is no point and the two segments that touch
+ *               it are not drawn; a finite sample between two non-finite ones still paints its point.
+ *       Line (w >= 1): the skeleton is every point's pixel (c_i, r_i) and, for consecutive points (c0, r0), (c1, r1) (c0 <=
+ *               c1, the abscissa is monotone), the segment's pixels: c0 == c1: rows min(r0, r1) .. max(r0, r1) of the
+ *               column.  Else with dx = c1 - c0, dy = r1 - r0 and B(c) = r0 + floor(((2 (c - c0) - 1) dy + dx) / (2 dx))
+ *               (floor division, 64-bit): column c of c0 .. c1 paints the rows between (c == c0 ? r0 : B(c)) and (c == c1 ?
+ *               r1 : B(c + 1)), both included.  (Both endpoints are painted, rows stay within min(r0, r1) .. max(r0, r1),
+ *               consecutive columns share a row, a horizontal segment paints one row; the rows of column c are a function
+ *               of (c0, r0, c1, r1, c) alone.)  Every skeleton pixel (c, r) covers the w x w pixels of columns c - w / 2 ..
+ *               c - w / 2 + w - 1 and the same rows (integer division: odd w is centred).  w == 0 draws no line.
+ *       Marker (marker != NONE), at every point, k = marker_size / 2, (u, v) = pixel - (c_i, r_i), |u| <= k, |v| <= k:
+ *               SQUARE: all of them; CIRCLE: u u + v v <= k k + k; TRIANGLE (apex up): 2 |u| <= v + k.
+ *       Coverage of a series = line pixels and marker pixels, clipped to the rectangle; every covered pixel is blended
+ *               ONCE per series with the overlay's rule, out = (a c + (255 - a) src + 127) / 255 per channel; alpha 0
+ *               leaves the series out.  A later series paints over an earlier one.
+ *     The kernel: one workgroup per block of TSOD_PLOT_BLOCK_COLUMNS columns over the rectangle's height.  Per series it
+ *     clears a row bitmask in LDS, finds by bisection (c_i is monotone in i) the samples whose column lies within a halo of
+ *     its block, one more on each side, lets its threads stride over them setting row ranges with atomicOr, and after a
+ *     barrier blends the set pixels: O(n + pixels) work, no pixel looks at all samples.
+ *     TSOD_ERR_INVALID_ARG: image or limits NULL; H, W, pw or ph <= 0; row_bytes < 3 W; the rectangle not inside the image;
+ *     x_hi < x_lo; n_series outside [0, TSOD_PLOT_MAX_SERIES] (or series NULL with n_series > 0); in a series: n < 0, y NULL
+ *     with n > 0, x_step < 1, an abscissa outside [x_lo, x_hi], width or marker_size outside their ranges, an even
+ *     marker_size, a marker outside the enum.  TSOD_ERR_UNSUPPORTED: H W beyond 2^31 - 1; ph > TSOD_PLOT_MAX_HEIGHT (the
+ *     bitmask); |x_lo|, |x_hi| beyond 2^31 - 1.  n_series == 0 or n == 0 in every series: TSOD_OK, no launch.
+ *
+ * K4  tsod_plot_items_u8: paints n_items decorations (items: DEVICE array of tsod_plot_item, 8-byte aligned), in order,
+ *     onto one image; everything is clipped to the image.
+ *       TSOD_PLOT_ITEM_RECT: the pixels of [x, x + w) x [y, y + h), blended with color (alpha color[3]).  dash_period > 0
+ *         keeps only the rows with (row - y) % dash_period < dash_on (a dashed vertical line); dash_period == 0: all rows.
+ *       TSOD_PLOT_ITEM_TEXT: the bytes text[0 .. len) in the glyphs of csrc/font5x7.h (5x7 in a 6x8 cell, every glyph
+ *         pixel scale x scale image pixels), set pixels blended with color; the string is len 6 scale pixels wide and its
+ *         left edge is x (align 0), x - len 6 scale (align 1: x is its right edge) or x - (len 6 scale) / 2 (align 2); its
+ *         top row is y.
+ *       TSOD_PLOT_ITEM_NUMBER: the same, the string made on the device from limits (DEVICE f32 [2], the item's pointer): v
+ *         = lo + ((float)tick * (hi - lo)) / (float)ticks, four f32 operations; p = fabsf(v) * 1000.f; when !(p < 1e9f) (too
+ *         large to print, or not a number) the string is "-.---"; else m = (int)rintf(p) and the string is '-' (only when v
+ *         < 0 and m > 0), the decimal digits of m / 1000, '.', and the three digits of m % 1000.
+ *       An item of another kind, or with w, h, scale < 1 or len outside [0, TSOD_PLOT_STRING_BYTES], paints nothing.
+ *     The kernel: one workgroup per 64x4 tile; it tests the items 256 at a time (one per thread) against its tile, keeps the
+ *     hits as wave ballots and every thread walks the set bits, in item order, for its pixel; one load and one store per
+ *     touched pixel.
+ *     TSOD_ERR_INVALID_ARG: image NULL; H or W <= 0; row_bytes < 3 W; n_items < 0; items NULL with n_items > 0.
+ *     TSOD_ERR_UNSUPPORTED: H W beyond 2^31 - 1.  TSOD_ERR_ALIGNMENT: items not 8-byte aligned.  n_items == 0: TSOD_OK, no launch. */
+#define TSOD_PLOT_MAX_SERIES 4
+#define TSOD_PLOT_MAX_WIDTH 15
+#define TSOD_PLOT_MAX_HEIGHT 4096
+#define TSOD_PLOT_BLOCK_COLUMNS 32
+#define TSOD_PLOT_STRING_BYTES 32
+#define TSOD_PLOT_LIMITS_WORKSPACE_BYTES 2048
+enum { TSOD_PLOT_MARKER_NONE = 0, TSOD_PLOT_MARKER_CIRCLE = 1, TSOD_PLOT_MARKER_SQUARE = 2, TSOD_PLOT_MARKER_TRIANGLE = 3 };
+enum { TSOD_PLOT_ITEM_RECT = 0, TSOD_PLOT_ITEM_TEXT = 1, TSOD_PLOT_ITEM_NUMBER = 2 };
+typedef struct tsod_plot_series {
+    const float *y;         /* [n], device */
+    int32_t n, x_first, x_step;
+    uint8_t color[4];       /* R G B, alpha */
+    int32_t width, marker, marker_size;
+} tsod_plot_series;
+typedef struct tsod_plot_item {
+    const float *limits;    /* NUMBER: device f32 [2] */
+    int32_t kind;           /* TSOD_PLOT_ITEM_* */
+    int32_t x, y, w, h;     /* RECT: the rectangle; TEXT / NUMBER: the anchor (x, y) */
+    int32_t dash_period, dash_on; /* RECT */
+    int32_t scale, align, len; /* TEXT / NUMBER (len: TEXT) */
+    int32_t tick, ticks;    /* NUMBER */
+    uint8_t color[4];       /* R G B, alpha */
+    uint8_t text[32];       /* TEXT */
+} tsod_plot_item;
+int tsod_ema_scan_f32(const float *x, int32_t rows, int64_t n, int64_t x_pitch, float a, float b, float *out, int64_t out_pitch,
+                      tsod_stream_t stream);
+int tsod_plot_limits_f32(const float *const *series, const int64_t *lengths, int32_t n_series, float *limits, void *workspace,
+                         size_t workspace_bytes, tsod_stream_t stream);
+int tsod_plot_series_u8(uint8_t *image, int32_t H, int32_t W, int64_t row_bytes, int32_t px0, int32_t py0, int32_t pw, int32_t ph,
+                        const tsod_plot_series *series, int32_t n_series, int64_t x_lo, int64_t x_hi, const float *limits,
+                        tsod_stream_t stream);
+int tsod_plot_items_u8(uint8_t *image, int32_t H, int32_t W, int64_t row_bytes, const tsod_plot_item *items, int32_t n_items,
+                       tsod_stream_t stream);
+
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends
  * `count_per_rank` floats and receives n_ranks * count_per_rank in rank order.  Stream-ordered, no host synchronisation.

@@ -155,6 +155,25 @@ class DrawGroup(Structure):
                 ("tag_bg", c_uint8 * 4), ("font_scale", c_int32), ("padding", c_int32), ("score_line", c_int32)]
 
 
+PLOT_MAX_SERIES, PLOT_MAX_WIDTH, PLOT_MAX_HEIGHT, PLOT_BLOCK_COLUMNS = 4, 15, 4096, 32        # TSOD_PLOT_*
+PLOT_STRING_BYTES, PLOT_LIMITS_WORKSPACE_BYTES = 32, 2048
+PLOT_MARKER_NONE, PLOT_MARKER_CIRCLE, PLOT_MARKER_SQUARE, PLOT_MARKER_TRIANGLE = 0, 1, 2, 3
+PLOT_ITEM_RECT, PLOT_ITEM_TEXT, PLOT_ITEM_NUMBER = 0, 1, 2
+
+
+class PlotSeries(Structure):
+    """Mirror of ``tsod_plot_series`` (include/tsod.h): one curve of a plot rectangle."""
+    _fields_ = [("y", c_void_p), ("n", c_int32), ("x_first", c_int32), ("x_step", c_int32), ("color", c_uint8 * 4),
+                ("width", c_int32), ("marker", c_int32), ("marker_size", c_int32)]
+
+
+class PlotItem(Structure):
+    """Mirror of ``tsod_plot_item`` (include/tsod.h): one decoration - a rectangle, a string or a device-formatted number."""
+    _fields_ = [("limits", c_void_p), ("kind", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
+                ("dash_period", c_int32), ("dash_on", c_int32), ("scale", c_int32), ("align", c_int32), ("len", c_int32),
+                ("tick", c_int32), ("ticks", c_int32), ("color", c_uint8 * 4), ("text", c_uint8 * 32)]
+
+
 class AdamWGroup(Structure):
     """Mirror of ``tsod_adamw_group`` (include/tsod.h): the f32 scalars of one AdamW step."""
     _fields_ = [("decay", c_float), ("one_minus_beta1", c_float), ("beta2", c_float), ("one_minus_beta2", c_float),
@@ -385,6 +404,11 @@ _SIGNATURES = {
     "tsod_draw_groups_u8": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, POINTER(DrawGroup), c_int32, c_void_p,
                                     c_int32, c_void_p]),
     "tsod_draw_font5x7": (c_int, [c_void_p]),
+    "tsod_ema_scan_f32": (c_int, [c_void_p, c_int32, c_int64, c_int64, c_float, c_float, c_void_p, c_int64, c_void_p]),
+    "tsod_plot_limits_f32": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tsod_plot_series_u8": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(PlotSeries),
+                                    c_int32, c_int64, c_int64, c_void_p, c_void_p]),
+    "tsod_plot_items_u8": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

@@ -2176,3 +2176,159 @@ def draw_groups(images: torch.Tensor, groups, strings=None) -> torch.Tensor:
     check(lib().tsod_draw_groups_u8(ptr(images), B, H, W, row_bytes, image_bytes, arr, len(groups), ptr(strings),
                                     n_strings, stream_ptr()), "draw_groups")
     return images
+
+
+# ----------------------------------------------------------------------------- training curves
+PLOT_MARKERS = {None: _ffi.PLOT_MARKER_NONE, "none": _ffi.PLOT_MARKER_NONE, "o": _ffi.PLOT_MARKER_CIRCLE,
+                "circle": _ffi.PLOT_MARKER_CIRCLE, "s": _ffi.PLOT_MARKER_SQUARE, "square": _ffi.PLOT_MARKER_SQUARE,
+                "^": _ffi.PLOT_MARKER_TRIANGLE, "triangle": _ffi.PLOT_MARKER_TRIANGLE}
+PLOT_ITEM_KINDS = {"rect": _ffi.PLOT_ITEM_RECT, "text": _ffi.PLOT_ITEM_TEXT, "number": _ffi.PLOT_ITEM_NUMBER}
+PLOT_ALIGN = {"left": 0, "right": 1, "center": 2}
+
+
+def _rgba(what, rgb, alpha):
+    vals = tuple(int(v) for v in rgb) + (int(alpha),)
+    if len(vals) != 4 or not all(0 <= v <= 255 for v in vals):
+        raise ValueError(f"{what}: a colour is (R, G, B) with an alpha, each 0..255, got {vals}")
+    return (ctypes.c_uint8 * 4)(*vals)
+
+
+def _plot_image(image, what):
+    """-> (H, W, row_bytes) of one u8 [H,W,3] device image whose rows may be padded at their ends."""
+    if not isinstance(image, torch.Tensor) or not image.is_cuda:
+        require_cuda(image, what)
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+        raise ValueError(f"{what}: the image is u8 [H,W,3], got {image.dtype} {tuple(image.shape)}")
+    H, W, _ = image.shape
+    row_bytes = image.stride(0) if H > 1 else 3 * W
+    if image.stride(2) != 1 or (W > 1 and image.stride(1) != 3) or row_bytes < 3 * W:
+        raise ValueError(f"{what}: pixels must be interleaved, rows may only be padded at their ends")
+    return H, W, row_bytes
+
+
+def ema_scan(x: torch.Tensor, alpha: float, out: torch.Tensor = None) -> torch.Tensor:
+    """The reference's ``update_ema`` loop (train/train.py:147-153) over every row of ``x`` in one launch (``tsod_ema_scan_f32``):
+    ``out[r, 0] = x[r, 0]``, ``out[r, i] = a x[r, i] + b out[r, i-1]`` with a = f32(alpha), b = f32(1 - alpha), two products and
+    one sum in f32, no FMA.  ``x``: f32 [n] or [rows, n] on the device, rows may be pitched.  No host read."""
+    require_cuda(x, "ema_scan")
+    if x.dim() not in (1, 2) or (x.shape[-1] > 1 and x.stride(-1) != 1):
+        raise ValueError(f"ema_scan: x is f32 [n] or [rows, n] with unit stride along n, got {tuple(x.shape)} strides {x.stride()}")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    else:
+        require_cuda(out, "ema_scan")
+        if out.shape != x.shape or out.device != x.device or (out.shape[-1] > 1 and out.stride(-1) != 1):
+            raise ValueError("ema_scan: out must have x's shape and device and unit stride along n")
+    n = x.shape[-1]
+    rows = 1 if x.dim() == 1 else x.shape[0]
+    pitch = lambda t: n if t.dim() == 1 or rows == 1 else t.stride(0)
+    a, b = float(alpha), 1.0 - float(alpha)                      # (the subtraction in double; ctypes rounds both to f32)
+    check(lib().tsod_ema_scan_f32(ptr(x), rows, n, pitch(x), a, b, ptr(out), pitch(out), stream_ptr()), "ema_scan")
+    return out
+
+
+def plot_limits(series, out: torch.Tensor = None, device=None) -> torch.Tensor:
+    """The axis limits (lo, hi) of a panel over the finite samples of up to ``_ffi.PLOT_MAX_SERIES`` f32 [n] device tensors
+    (``tsod_plot_limits_f32``; the rule is in include/tsod.h), written into ``out`` (f32 [2] on the device).  No host read."""
+    series = [s for s in series if s is not None]
+    if len(series) > _ffi.PLOT_MAX_SERIES:
+        raise ValueError(f"plot_limits: at most {_ffi.PLOT_MAX_SERIES} series, got {len(series)}")
+    for s in series:
+        require_cuda(s, "plot_limits")
+        if s.dim() != 1 or not s.is_contiguous():
+            raise ValueError(f"plot_limits: a series is a contiguous f32 [n] tensor, got {tuple(s.shape)}")
+    dev = out.device if out is not None else (series[0].device if series else torch.device(device))
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+    require_cuda(out, "plot_limits")
+    if out.numel() != 2 or not out.is_contiguous():
+        raise ValueError("plot_limits: out is a contiguous f32 [2] tensor")
+    ws = torch.empty(_ffi.PLOT_LIMITS_WORKSPACE_BYTES // 4, dtype=torch.float32, device=dev)
+    k = max(len(series), 1)
+    pointers, lengths = (ctypes.c_void_p * k)(*[ptr(s) for s in series]), (ctypes.c_int64 * k)(*[s.numel() for s in series])
+    check(lib().tsod_plot_limits_f32(pointers, lengths, len(series), ptr(out), ptr(ws), _ffi.PLOT_LIMITS_WORKSPACE_BYTES,
+                                     stream_ptr()), "plot_limits")
+    return out
+
+
+def plot_series(image: torch.Tensor, rect, series, x_range, limits: torch.Tensor) -> torch.Tensor:
+    """Paint up to ``_ffi.PLOT_MAX_SERIES`` curves, in order, into the rectangle ``rect`` = (px0, py0, pw, ph) of ``image`` (u8
+    [H,W,3] on the device) IN PLACE, one launch (``tsod_plot_series_u8``; the pixel rules are in include/tsod.h).
+
+    ``series``: dicts with ``y`` (contiguous f32 [n] on the device) and optionally ``x_first`` (0), ``x_step`` (1), ``color``,
+    ``alpha`` (255), ``width`` (1), ``marker`` (None | "o" | "s" | "^"), ``marker_size`` (1, odd).  ``x_range`` = (x_lo, x_hi)
+    are the abscissae of the rectangle's first and last column, ``limits`` the f32 [2] device record (lo, hi) of its bottom
+    and top row.  Returns ``image``."""
+    H, W, row_bytes = _plot_image(image, "plot_series")
+    require_cuda(limits, "plot_series")
+    if limits.numel() != 2 or not limits.is_contiguous() or limits.device != image.device:
+        raise ValueError("plot_series: limits is a contiguous f32 [2] tensor on the image's device")
+    if len(series) > _ffi.PLOT_MAX_SERIES:
+        raise ValueError(f"plot_series: at most {_ffi.PLOT_MAX_SERIES} series in one launch, got {len(series)}")
+    arr = (_ffi.PlotSeries * max(len(series), 1))()
+    for rec, s in zip(arr, series):
+        y = s["y"]
+        require_cuda(y, "plot_series")
+        if y.dim() != 1 or not y.is_contiguous() or y.device != image.device:
+            raise ValueError(f"plot_series: y is a contiguous f32 [n] tensor on the image's device, got {tuple(y.shape)}")
+        marker = s.get("marker")
+        if marker not in PLOT_MARKERS:
+            raise ValueError(f"plot_series: marker is None, 'o', 's' or '^', got {marker!r}")
+        rec.y, rec.n, rec.x_first, rec.x_step = ptr(y), y.numel(), int(s.get("x_first", 0)), int(s.get("x_step", 1))
+        rec.color = _rgba("plot_series", s.get("color", (0, 0, 0)), s.get("alpha", 255))
+        rec.width, rec.marker, rec.marker_size = int(s.get("width", 1)), PLOT_MARKERS[marker], int(s.get("marker_size", 1))
+    px0, py0, pw, ph = (int(v) for v in rect)
+    check(lib().tsod_plot_series_u8(ptr(image), H, W, row_bytes, px0, py0, pw, ph, arr, len(series), int(x_range[0]),
+                                    int(x_range[1]), ptr(limits), stream_ptr()), "plot_series")
+    return image
+
+
+def pack_plot_items(items) -> torch.Tensor:
+    """HOST: a list of item dicts as the records of ``tsod_plot_items_u8``, a u8 [n, sizeof(tsod_plot_item)] CPU tensor.
+    ``kind`` "rect": ``x, y, w, h`` and optionally ``dash`` = (period, on); "text": ``x, y, text`` (str or bytes, at most 32
+    bytes); "number": ``x, y, limits`` (f32 [2] device tensor, which must outlive the launch), ``tick``, ``ticks``.  All:
+    ``color`` (black), ``alpha`` (255); the text kinds: ``scale`` (1), ``align`` ("left" | "right" | "center")."""
+    size = ctypes.sizeof(_ffi.PlotItem)
+    arr = (_ffi.PlotItem * max(len(items), 1))()
+    for rec, it in zip(arr, items):
+        kind = it["kind"]
+        if kind not in PLOT_ITEM_KINDS:
+            raise ValueError(f"plot_items: kind is 'rect', 'text' or 'number', got {kind!r}")
+        rec.kind, rec.x, rec.y = PLOT_ITEM_KINDS[kind], int(it["x"]), int(it["y"])
+        rec.color = _rgba("plot_items", it.get("color", (0, 0, 0)), it.get("alpha", 255))
+        rec.scale, rec.align = int(it.get("scale", 1)), PLOT_ALIGN[it.get("align", "left")]
+        if kind == "rect":
+            rec.w, rec.h = int(it["w"]), int(it["h"])
+            rec.dash_period, rec.dash_on = (int(v) for v in it.get("dash", (0, 0)))
+        elif kind == "text":
+            raw = it["text"].encode("utf-8") if isinstance(it["text"], str) else bytes(it["text"])
+            if len(raw) > _ffi.PLOT_STRING_BYTES:
+                raise ValueError(f"plot_items: {raw!r} is {len(raw)} bytes; a text item holds at most {_ffi.PLOT_STRING_BYTES}")
+            rec.len = len(raw)
+            rec.text = (ctypes.c_uint8 * _ffi.PLOT_STRING_BYTES)(*raw)
+        else:
+            limits = it["limits"]
+            require_cuda(limits, "plot_items")
+            if limits.numel() != 2 or not limits.is_contiguous():
+                raise ValueError("plot_items: limits is a contiguous f32 [2] device tensor")
+            rec.limits, rec.tick, rec.ticks = ptr(limits), int(it["tick"]), int(it["ticks"])
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).reshape(max(len(items), 1), size)
+    return raw[:len(items)]
+
+
+def plot_items(image: torch.Tensor, items) -> torch.Tensor:
+    """Paint decorations - filled or dashed rectangles, strings in the overlay's 5x7 font, numbers formatted on the device from
+    a limits record - in order onto ``image`` (u8 [H,W,3] on the device) IN PLACE, one launch (``tsod_plot_items_u8``).
+    ``items``: a list of dicts (``pack_plot_items``; uploaded here through pinned memory, no host wait), or the packed records
+    already on the device.  Returns ``image``."""
+    H, W, row_bytes = _plot_image(image, "plot_items")
+    if not isinstance(items, torch.Tensor):
+        packed = pack_plot_items(items)
+        items = packed.pin_memory().to(image.device, non_blocking=True) if len(packed) else packed
+    size = ctypes.sizeof(_ffi.PlotItem)
+    n = items.shape[0]
+    if n and (not items.is_cuda or items.device != image.device or items.dtype != torch.uint8 or items.dim() != 2
+              or items.shape[1] != size or not items.is_contiguous()):
+        raise ValueError(f"plot_items: packed items are a contiguous u8 [n,{size}] tensor on the image's device")
+    check(lib().tsod_plot_items_u8(ptr(image), H, W, row_bytes, ptr(items) if n else None, n, stream_ptr()), "plot_items")
+    return image
