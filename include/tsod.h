@@ -1373,6 +1373,89 @@ int tsod_plot_series_u8(uint8_t *image, int32_t H, int32_t W, int64_t row_bytes,
 int tsod_plot_items_u8(uint8_t *image, int32_t H, int32_t W, int64_t row_bytes, const tsod_plot_item *items, int32_t n_items,
                        tsod_stream_t stream);
 
+/* ---- JPEG decoding: the reference's Image.open(path).convert("RGB") for baseline files, bit-equal
+ * to Pillow (libjpeg-turbo's default islow / fancy upsampling / YCbCr path).  The bit-serial Huffman pass runs on the HOST
+ * (csrc/jpeg_entropy.h); everything that is arithmetic over pixels runs in two launches for a whole batch.
+ *
+ * HOST, re-entrant, no allocation, never reads outside [data, data + n):
+ *   tsod_jpeg_parse: markers up to the first scan into *info.  Supported: 8-bit SOF0 / SOF1 (Huffman), one component (grey)
+ *     or three (YCbCr) with luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma in one interleaved scan.
+ *     TSOD_ERR_UNSUPPORTED: any other SOF (progressive, lossless, arithmetic), another precision, two or four components,
+ *     another sampling, a scan that does not hold every component in frame order, an Adobe APP14 marker with transform 0 on
+ *     a three-component file (RGB-coded).  TSOD_ERR_INVALID_ARG: data or info NULL, no SOI, a segment length past the end, a
+ *     cut-short or over-full DQT / DHT, zero dimensions, a scan before the frame, a table the scan names but no segment
+ *     defined, spectral selection other than 0..63, the end of the data before a scan.
+ *   tsod_jpeg_entropy_decode: the Huffman pass of the same file into coef[0 .. info.coef_total): int16, NOT dequantised, in
+ *     natural (row-major) order inside each block of 64, component after component, the blocks of a component in raster
+ *     order over its padded grid blocks_w x blocks_h (whole MCUs).  DC predictions are summed in wrapping 32-bit arithmetic
+ *     and stored as their low 16 bits.  FF 00 is unstuffed; at every restart interval the next marker must be the expected
+ *     RSTn (the DC predictors reset).  capacity (in int16) must be >= info.coef_total; nothing beyond coef_total is written.
+ *     What tsod_jpeg_parse refuses is refused alike; TSOD_ERR_INVALID_ARG also for: coef NULL or capacity too small, entropy
+ *     bits that end before the last MCU does, a code no table holds, a DC category above 15, a run (ZRL included) past
+ *     coefficient 63, a wrong or missing restart marker.  After a negative status coef holds unspecified values inside
+ *     [0, capacity).  A missing EOI after the last MCU is accepted.
+ *
+ * DEVICE, both in the pattern of tsod_adamw_step_f32: a table of per-image records and a flat work list, in device memory,
+ * so that images of different sizes and samplings share ONE launch.  Each entry also takes the HOST copy of both arrays and
+ * checks every record and every work item against the buffer sizes before it launches: every address the kernels form
+ * comes from these checked integers, the only file-derived data they read are coefficient, quantiser and sample VALUES.
+ * (The device copies must equal the host copies.)
+ *   tsod_jpeg_idct_u8: plane sample = range(idct(coef * quant)): for every component the u8 plane [8 blocks_h][8 blocks_w]
+ *     at planes + plane_offset[c].  The arithmetic, all in wrapping 32-bit integers (the kernel computes in uint32_t):
+ *       d = (int32)coef * (int32)quant; two passes of the Loeffler-Ligtenberg-Moschytz 8-point inverse DCT with 13-bit
+ *       constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172 (libjpeg's jidctint.c): columns first,
+ *       descaled by 11, then rows, descaled by 18 - descale(x, n) = (x + (1 << (n - 1))) >> n, arithmetic shift; the sample
+ *       is looked up at j = v & 1023: j < 128 -> j + 128, j < 512 -> 255, j < 896 -> 0, else j - 896.
+ *     Work item (image, component, first_block, 0): the blocks [first_block, first_block + TSOD_JPEG_IDCT_BLOCKS) of that
+ *     component that exist; first_block is a multiple of TSOD_JPEG_IDCT_BLOCKS.  One workgroup of 256 per item, 8 lanes per
+ *     block: a lane loads one coefficient row and one quantiser row (16 bytes each), the column pass runs on a transposed
+ *     copy in LDS, the row pass ends in one 8-byte store.
+ *   tsod_jpeg_to_rgb_u8: out + out_offset = packed u8 [H][W][3] from the planes.
+ *       Grey: R = G = B = Y.  Otherwise chroma sample (x, y) of a plane cropped to its true size dw = ceil(W / hs), dh =
+ *       ceil(H / vs), indices beyond it clamped to its edge:  hs == 1: a[y][x].  dw <= 2: a[y / vs][x / 2] (replication).
+ *       hs == 2, vs == 1: i = x / 2; (3 a[y][i] + a[y][i - 1] + 1) >> 2 for even x, (3 a[y][i] + a[y][i + 1] + 2) >> 2 for odd.
+ *       hs == 2, vs == 2: r = y / 2, t[i] = 3 a[r][i] + a[r - 1][i] for even y, 3 a[r][i] + a[r + 1][i] for odd;
+ *       (3 t[i] + t[i - 1] + 8) >> 4 for even x, (3 t[i] + t[i + 1] + 7) >> 4 for odd.
+ *       With cb, cr minus 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *       B = Y + ((116130 cb + 32768) >> 16), each clamped to 0..255.
+ *     Work item (image, tile_y, tile_x, 0): the pixels of rows [TSOD_JPEG_RGB_TILE_H tile_y, +TSOD_JPEG_RGB_TILE_H) and
+ *     columns [TSOD_JPEG_RGB_TILE_W tile_x, +TSOD_JPEG_RGB_TILE_W) inside the image; a thread makes four pixels of one row.
+ *   TSOD_ERR_INVALID_ARG: a NULL pointer with work to do; a negative count; a record with n_comp not 1 or 3, a non-positive
+ *     size, a sampling other than the above, a block grid smaller than the image needs, an offset that is negative, not a
+ *     multiple of its unit (coef and quant: 64 elements, plane: 8 bytes) or whose extent ends beyond its buffer; a work item
+ *     outside [0, n_images) or outside its image.  TSOD_ERR_ALIGNMENT: coef, quant, table or work not 16-byte, planes not
+ *     8-byte aligned.  n_work == 0: TSOD_OK, nothing is launched. */
+#define TSOD_JPEG_IDCT_BLOCKS 32
+#define TSOD_JPEG_RGB_TILE_W 256
+#define TSOD_JPEG_RGB_TILE_H 4
+typedef struct tsod_jpeg_info {
+    int32_t H, W, n_comp, hmax, vmax, mcus_x, mcus_y, restart_interval;
+    int32_t h[3], v[3], tq[3];     /* sampling factors and quantiser selector of each component */
+    int32_t blocks_w[3], blocks_h[3]; /* the padded block grid: mcus_x h, mcus_y v */
+    int32_t plane_w[3], plane_h[3]; /* 8 blocks_w, 8 blocks_h */
+    int32_t reserved;
+    int64_t coef_count[3];         /* 64 blocks_w blocks_h: coefficients, and bytes of the plane */
+    int64_t coef_total;
+    uint16_t quant[3][64];         /* each component's quantiser, natural order */
+} tsod_jpeg_info;
+typedef struct tsod_jpeg_image {
+    int64_t coef_offset[3];        /* int16 elements from coef */
+    int64_t plane_offset[3];       /* bytes from planes */
+    int64_t quant_offset;          /* uint16 elements from quant: [n_comp][64] */
+    int64_t out_offset;            /* bytes from out */
+    int32_t H, W, n_comp, hs, vs;  /* hs x vs: the luma sampling (1x1 for grey) */
+    int32_t blocks_w[3], blocks_h[3];
+    int32_t reserved;
+} tsod_jpeg_image;
+int tsod_jpeg_parse(const uint8_t *data, size_t n, tsod_jpeg_info *info);
+int tsod_jpeg_entropy_decode(const uint8_t *data, size_t n, int16_t *coef, size_t capacity);
+int tsod_jpeg_idct_u8(const tsod_jpeg_image *table_host, const tsod_jpeg_image *table, int32_t n_images, const int32_t *work_host,
+                      const int32_t *work, int32_t n_work, const int16_t *coef, int64_t coef_count, const uint16_t *quant,
+                      int64_t quant_count, uint8_t *planes, int64_t plane_bytes, tsod_stream_t stream);
+int tsod_jpeg_to_rgb_u8(const tsod_jpeg_image *table_host, const tsod_jpeg_image *table, int32_t n_images, const int32_t *work_host,
+                        const int32_t *work, int32_t n_work, const uint8_t *planes, int64_t plane_bytes, uint8_t *out,
+                        int64_t out_bytes, tsod_stream_t stream);
+
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends
  * `count_per_rank` floats and receives n_ranks * count_per_rank in rank order.  Stream-ordered, no host synchronisation.

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_uint64,
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint16, c_uint32, c_uint64,
                     c_void_p)
 from typing import NamedTuple
 
@@ -172,6 +172,24 @@ class PlotItem(Structure):
     _fields_ = [("limits", c_void_p), ("kind", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
                 ("dash_period", c_int32), ("dash_on", c_int32), ("scale", c_int32), ("align", c_int32), ("len", c_int32),
                 ("tick", c_int32), ("ticks", c_int32), ("color", c_uint8 * 4), ("text", c_uint8 * 32)]
+
+
+JPEG_IDCT_BLOCKS, JPEG_RGB_TILE_W, JPEG_RGB_TILE_H = 32, 256, 4                              # TSOD_JPEG_*
+
+
+class JpegInfo(Structure):
+    """Mirror of ``tsod_jpeg_info`` (include/tsod.h): what the markers of one JPEG file say, and the sizes that follow."""
+    _fields_ = [("H", c_int32), ("W", c_int32), ("n_comp", c_int32), ("hmax", c_int32), ("vmax", c_int32), ("mcus_x", c_int32),
+                ("mcus_y", c_int32), ("restart_interval", c_int32), ("h", c_int32 * 3), ("v", c_int32 * 3), ("tq", c_int32 * 3),
+                ("blocks_w", c_int32 * 3), ("blocks_h", c_int32 * 3), ("plane_w", c_int32 * 3), ("plane_h", c_int32 * 3),
+                ("reserved", c_int32), ("coef_count", c_int64 * 3), ("coef_total", c_int64), ("quant", (c_uint16 * 64) * 3)]
+
+
+class JpegImage(Structure):
+    """Mirror of ``tsod_jpeg_image`` (include/tsod.h): one image of a batch, as the two JPEG kernels see it."""
+    _fields_ = [("coef_offset", c_int64 * 3), ("plane_offset", c_int64 * 3), ("quant_offset", c_int64), ("out_offset", c_int64),
+                ("H", c_int32), ("W", c_int32), ("n_comp", c_int32), ("hs", c_int32), ("vs", c_int32),
+                ("blocks_w", c_int32 * 3), ("blocks_h", c_int32 * 3), ("reserved", c_int32)]
 
 
 class AdamWGroup(Structure):
@@ -409,6 +427,12 @@ _SIGNATURES = {
     "tsod_plot_series_u8": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(PlotSeries),
                                     c_int32, c_int64, c_int64, c_void_p, c_void_p]),
     "tsod_plot_items_u8": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p]),
+    "tsod_jpeg_parse": (c_int, [c_void_p, c_size_t, POINTER(JpegInfo)]),
+    "tsod_jpeg_entropy_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t]),
+    "tsod_jpeg_idct_u8": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                  c_void_p, c_int64, c_void_p]),
+    "tsod_jpeg_to_rgb_u8": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

@@ -2332,3 +2332,117 @@ def plot_items(image: torch.Tensor, items) -> torch.Tensor:
         raise ValueError(f"plot_items: packed items are a contiguous u8 [n,{size}] tensor on the image's device")
     check(lib().tsod_plot_items_u8(ptr(image), H, W, row_bytes, ptr(items) if n else None, n, stream_ptr()), "plot_items")
     return image
+
+
+# ----------------------------------------------------------------------------- JPEG decoding
+def jpeg_bytes(data):
+    """HOST: ``bytes`` / ``bytearray`` / ``memoryview`` / a u8 ndarray as a contiguous u8 ndarray, without a copy when the
+    memory is already contiguous."""
+    import numpy as np
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8:
+            raise ValueError(f"a JPEG file in an ndarray is uint8, got {data.dtype}")
+        return np.ascontiguousarray(data).reshape(-1)
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(data, dtype=np.uint8)
+    raise TypeError(f"a JPEG file is bytes, bytearray, memoryview or a uint8 ndarray, not {type(data).__name__}")
+
+
+def jpeg_parse(data):
+    """HOST: ``(status, JpegInfo)`` of one file's markers (``tsod_jpeg_parse``); status 0, or the negative ``tsod_status`` of a
+    file this build does not decode (-2) or that is damaged (-1).  No exception: the caller names the file."""
+    raw = jpeg_bytes(data)
+    info = _ffi.JpegInfo()
+    return int(lib().tsod_jpeg_parse(raw.ctypes.data, raw.size, byref(info))), info
+
+
+def jpeg_entropy_decode(data, coef) -> int:
+    """HOST: the Huffman pass of one file into ``coef``, a writeable contiguous int16 ndarray of at least
+    ``JpegInfo.coef_total`` elements (``tsod_jpeg_entropy_decode``).  Returns the status.  ctypes releases the GIL for the
+    call and the library keeps no state, so any number of threads may decode at once."""
+    import numpy as np
+    raw = jpeg_bytes(data)
+    if not (isinstance(coef, np.ndarray) and coef.dtype == np.int16 and coef.flags.c_contiguous and coef.flags.writeable):
+        raise ValueError("jpeg_entropy_decode: coef is a writeable contiguous int16 ndarray")
+    return int(lib().tsod_jpeg_entropy_decode(raw.ctypes.data, raw.size, coef.ctypes.data, coef.size))
+
+
+def jpeg_plan(infos):
+    """HOST: the launch plan of a batch from its ``JpegInfo`` records: a dict with ``table`` (a ctypes array of
+    ``tsod_jpeg_image``), ``idct_work`` and ``rgb_work`` (int32 [n, 4] ndarrays, the work lists of the two kernels) and the
+    buffer sizes ``coef_count`` / ``quant_count`` (elements), ``plane_bytes`` / ``out_bytes``.  Image i's coefficients start at
+    ``table[i].coef_offset[0]`` and its pixels at ``table[i].out_offset``, a multiple of 256."""
+    import numpy as np
+    table = (_ffi.JpegImage * max(len(infos), 1))()
+    coef = quant = out = 0
+    idct_work, rgb_work = [], []
+    for i, info in enumerate(infos):
+        rec = table[i]
+        rec.H, rec.W, rec.n_comp, rec.hs, rec.vs = info.H, info.W, info.n_comp, info.hmax, info.vmax
+        rec.quant_offset, rec.out_offset = quant, out
+        quant += 64 * info.n_comp
+        out += (3 * info.H * info.W + 255) // 256 * 256
+        for c in range(info.n_comp):
+            rec.blocks_w[c], rec.blocks_h[c] = info.blocks_w[c], info.blocks_h[c]
+            rec.coef_offset[c] = rec.plane_offset[c] = coef          # one sample per coefficient: the planes share the layout
+            n_blocks = info.blocks_w[c] * info.blocks_h[c]
+            coef += 64 * n_blocks
+            first = np.arange(0, n_blocks, _ffi.JPEG_IDCT_BLOCKS, dtype=np.int32)
+            idct_work.append(np.stack([np.full_like(first, i), np.full_like(first, c), first, np.zeros_like(first)], axis=1))
+        ty, tx = np.meshgrid(np.arange(-(-info.H // _ffi.JPEG_RGB_TILE_H), dtype=np.int32),
+                             np.arange(-(-info.W // _ffi.JPEG_RGB_TILE_W), dtype=np.int32), indexing="ij")
+        rgb_work.append(np.stack([np.full(ty.size, i, dtype=np.int32), ty.reshape(-1), tx.reshape(-1),
+                                  np.zeros(ty.size, dtype=np.int32)], axis=1))
+    empty = np.zeros((0, 4), dtype=np.int32)
+    return dict(table=table, n_images=len(infos), coef_count=coef, quant_count=quant, plane_bytes=coef, out_bytes=out,
+                idct_work=np.ascontiguousarray(np.concatenate(idct_work or [empty])),
+                rgb_work=np.ascontiguousarray(np.concatenate(rgb_work or [empty])))
+
+
+def _jpeg_lists(table, table_dev, work, work_dev, what: str):
+    import numpy as np
+    n_images = len(table)
+    if not (isinstance(work, np.ndarray) and work.dtype == np.int32 and work.ndim == 2 and work.shape[1] == 4
+            and work.flags.c_contiguous):
+        raise ValueError(f"{what}: the host work list is a contiguous int32 [n, 4] ndarray")
+    for t, nbytes, name in ((table_dev, n_images * ctypes.sizeof(_ffi.JpegImage), "table"), (work_dev, work.nbytes, "work list")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= nbytes):
+            raise TsodError(f"{what}: the device {name} must be a contiguous CUDA/ROCm tensor of at least {nbytes} bytes "
+                            "(there is no CPU fallback)")
+    return n_images, work.shape[0]
+
+
+def _jpeg_buffer(t, dtype, device, what: str):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == dtype and t.dim() == 1
+            and t.is_contiguous()):
+        raise TsodError(f"{what} must be a contiguous 1-d {dtype} tensor on the table's CUDA/ROCm device (there is no CPU fallback)")
+    return t
+
+
+def jpeg_idct(table, table_dev, work, work_dev, coef, quant, planes) -> torch.Tensor:
+    """Dequantise and inverse-transform every block of a batch into its u8 component planes: ONE launch on the current stream
+    (``tsod_jpeg_idct_u8``).  ``table`` / ``work``: the host arrays of ``jpeg_plan``; ``table_dev`` / ``work_dev``: their copies in
+    device memory (any dtype, 16-byte aligned).  ``coef``: int16 device tensor; ``quant``: int16 device tensor holding the uint16
+    quantiser entries; ``planes``: u8 device tensor.  The library checks every record and work item against the sizes of
+    these buffers before it launches.  Returns ``planes``."""
+    n_images, n_work = _jpeg_lists(table, table_dev, work, work_dev, "jpeg_idct")
+    dev = table_dev.device
+    _jpeg_buffer(coef, torch.int16, dev, "jpeg_idct: coef")
+    _jpeg_buffer(quant, torch.int16, dev, "jpeg_idct: quant")
+    _jpeg_buffer(planes, torch.uint8, dev, "jpeg_idct: planes")
+    check(lib().tsod_jpeg_idct_u8(table, ptr(table_dev), n_images, work.ctypes.data, ptr(work_dev), n_work, ptr(coef), coef.numel(),
+                                  ptr(quant), quant.numel(), ptr(planes), planes.numel(), stream_ptr()), "jpeg_idct")
+    return planes
+
+
+def jpeg_to_rgb(table, table_dev, work, work_dev, planes, out) -> torch.Tensor:
+    """Upsample the chroma planes, convert to RGB and crop, every image of a batch into its packed u8 [H,W,3] at
+    ``out[table[i].out_offset:]``: ONE launch on the current stream (``tsod_jpeg_to_rgb_u8``).  Arguments as ``jpeg_idct``;
+    ``out``: u8 device tensor.  Returns ``out``."""
+    n_images, n_work = _jpeg_lists(table, table_dev, work, work_dev, "jpeg_to_rgb")
+    dev = table_dev.device
+    _jpeg_buffer(planes, torch.uint8, dev, "jpeg_to_rgb: planes")
+    _jpeg_buffer(out, torch.uint8, dev, "jpeg_to_rgb: out")
+    check(lib().tsod_jpeg_to_rgb_u8(table, ptr(table_dev), n_images, work.ctypes.data, ptr(work_dev), n_work, ptr(planes),
+                                    planes.numel(), ptr(out), out.numel(), stream_ptr()), "jpeg_to_rgb")
+    return out
