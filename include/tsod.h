@@ -1375,7 +1375,8 @@ int tsod_plot_items_u8(uint8_t *image, int32_t H, int32_t W, int64_t row_bytes, 
 
 /* ---- JPEG decoding: the reference's Image.open(path).convert("RGB") for baseline files, bit-equal
  * to Pillow (libjpeg-turbo's default islow / fancy upsampling / YCbCr path).  The bit-serial Huffman pass runs on the HOST
- * (csrc/jpeg_entropy.h); everything that is arithmetic over pixels runs in two launches for a whole batch.
+ * (csrc/jpeg_entropy.h) or, from the file's own unstuffed bytes, on the DEVICE (csrc/jpeg_huffman.hip, the section after this
+ * one): the two write the same coefficients.  Everything that is arithmetic over pixels runs in two launches for a whole batch.
  *
  * HOST, re-entrant, no allocation, never reads outside [data, data + n):
  *   tsod_jpeg_parse: markers up to the first scan into *info.  Supported: 8-bit SOF0 / SOF1 (Huffman), one component (grey)
@@ -1455,6 +1456,83 @@ int tsod_jpeg_idct_u8(const tsod_jpeg_image *table_host, const tsod_jpeg_image *
 int tsod_jpeg_to_rgb_u8(const tsod_jpeg_image *table_host, const tsod_jpeg_image *table, int32_t n_images, const int32_t *work_host,
                         const int32_t *work, int32_t n_work, const uint8_t *planes, int64_t plane_bytes, uint8_t *out,
                         int64_t out_bytes, tsod_stream_t stream);
+
+/* ---- The Huffman pass on the DEVICE ("entropy on the device"): an alternative to
+ * tsod_jpeg_entropy_decode that uploads the file's own entropy-coded bytes instead of 6 bytes of coefficients per pixel.
+ * The host does a byte-speed sweep (tsod_jpeg_scan_prepare), the device decodes (tsod_jpeg_huffman_i16) into the same
+ * coefficient layout, bit for bit, that tsod_jpeg_idct_u8 reads.
+ *
+ * HOST, re-entrant, no allocation, never reads outside [data, data + n) nor writes outside the stated capacities:
+ *   tsod_jpeg_scan_sizes: from the info of tsod_jpeg_parse and the file length n, the capacities tsod_jpeg_scan_prepare needs
+ *     at most: *n_segments = min(ceil(mcus / restart_interval) or 1, n / 2 + 1), *stream_bytes = n + 4 *n_segments rounded up
+ *     to 4.  TSOD_ERR_INVALID_ARG: a NULL pointer, an info with no MCUs.
+ *   tsod_jpeg_scan_prepare: for a file tsod_jpeg_parse accepts,
+ *     stream: the entropy-coded bytes with FF 00 unstuffed and the restart markers removed; every restart interval
+ *       ("segment") starts on a 4-byte boundary of stream and is zero-padded to the next.  *stream_bytes: bytes written.
+ *     segments[0 .. *n_segments): one record per restart interval (one for a file without restarts): first_mcu, n_mcu,
+ *       stream_offset (bytes from stream, a multiple of 4), bit_length (8 x the segment's real bytes), flags (bit 0: a restart
+ *       marker followed the segment - the decoder then requires fewer than 8 leftover bits), image = 0.
+ *     tables[TSOD_JPEG_HUFF_TABLES]: the scan's code tables in the fixed layout below, tables[2 c] the DC and tables[2 c + 1]
+ *       the AC table of component c; the tables of components the file does not have are zero.
+ *     Markers are checked exactly as tsod_jpeg_entropy_decode checks them: every interval but the last is followed by at
+ *     least one FF and the expected RSTn; a missing EOI after the last is accepted.  TSOD_ERR_INVALID_ARG: a NULL pointer, a
+ *     capacity too small, a missing or wrong restart marker; what tsod_jpeg_parse refuses is refused alike.  After a negative
+ *     status the buffers hold unspecified values inside their capacities.
+ *
+ * DEVICE, in the pattern of the two entries above (host and device copies of every list; every record and work item is
+ * checked on the host against the buffer sizes before anything is launched):
+ *   tsod_jpeg_huffman_i16: coef[0 .. coef_count) = 0, status[0 .. n_images) = 0 (one fill launch), then ONE launch over the
+ *     work list decodes every segment of a batch of any sizes and samplings: coef as tsod_jpeg_entropy_decode writes it at
+ *     table[i].coef_offset[c].  Of a table record only n_comp, hs, vs, blocks_w, blocks_h and coef_offset are read; image
+ *     i's code tables are huff[TSOD_JPEG_HUFF_TABLES i ..].
+ *     Work item (segment, 0, 0, 0): one workgroup of 256 lanes walks the segment in rounds of 256 consecutive subsequences
+ *     of 32 subseq_words bits (the self-synchronising decoder of Weissenberger and Schmidt, workgroup-local).  The parser
+ *     state between symbols is (bit position, block slot in the MCU, zigzag index) or one absorbing ERROR value.  A lane
+ *     decodes every symbol that starts in its subsequence from an assumed state, then again whenever its predecessor's end
+ *     state differs from the start it used (an ERROR end state is never taken over: the lane that meets a true error
+ *     reports it itself), until a workgroup vote finds no change (at most 256 times: after iteration k lanes 0 .. k are
+ *     final - the result never depends on the stream synchronising, only the time does).  Block counts and
+ *     per-component DC sums (wrapping uint32) are scanned over the lanes with the carry of the earlier rounds, and a last
+ *     pass stores the coefficients: natural order, a block's DC the low 16 bits of its running prediction.
+ *     A coefficient is stored only for a block number below the segment's n_mcu x blocks-per-MCU and a zigzag index <= 63,
+ *     at an address made from the checked records; stream loads are clamped to the segment's padded extent: a corrupt file
+ *     never becomes an out-of-range address.  status[image] gets (atomic OR) TSOD_JPEG_STATUS_ERROR when a segment meets an
+ *     invalid code, a DC category above 15, a run past 63 or the end of its bits inside a symbol before its last block,
+ *     TSOD_JPEG_STATUS_BLOCKS when it ends with fewer blocks than its record says, TSOD_JPEG_STATUS_LEFTOVER when 8 or more
+ *     bits are left before a restart marker; it is 0 exactly where tsod_jpeg_entropy_decode returns TSOD_OK.  The
+ *     coefficients of an image with a nonzero status are unspecified (inside the image's own extents).
+ *   TSOD_ERR_INVALID_ARG: subseq_words outside [1, 64]; a negative count; a NULL pointer with work to do; a record with
+ *     n_comp not 1 or 3, another sampling, a block grid that is not whole MCUs, a coef_offset that is negative, not a multiple
+ *     of 64 or whose extent ends beyond coef_count; fewer than TSOD_JPEG_HUFF_TABLES n_images tables; segments that are not
+ *     sorted by image or do not tile the MCUs of every image exactly, in order; a stream_offset that is negative, not a
+ *     multiple of 4 or whose padded extent ends beyond stream_bytes; a bit_length that is negative, not a multiple of 8 or
+ *     above TSOD_JPEG_MAX_SEGMENT_BITS; flags other than 0 or 1; a work item outside [0, n_segments).
+ *   TSOD_ERR_ALIGNMENT: table, segments, work or coef not 16-byte, stream, huff or status not 4-byte aligned.
+ *   n_work == 0: TSOD_OK, nothing is launched. */
+#define TSOD_JPEG_HUFF_TABLES 6
+#define TSOD_JPEG_MAX_SEGMENT_BITS 0x7FF00000
+#define TSOD_JPEG_STATUS_ERROR 1
+#define TSOD_JPEG_STATUS_BLOCKS 2
+#define TSOD_JPEG_STATUS_LEFTOVER 4
+typedef struct tsod_jpeg_huff {
+    uint16_t look[512];            /* (length << 8) | symbol for codes of at most 9 bits, 0: longer or absent */
+    int32_t maxcode[17];           /* largest code of each length, -1 when the length has none */
+    int32_t valoff[17];            /* vals index of a length's first code, minus that code */
+    uint8_t vals[256];
+} tsod_jpeg_huff;
+typedef struct tsod_jpeg_segment {
+    int64_t stream_offset;         /* bytes from stream, a multiple of 4 */
+    int64_t bit_length;            /* 8 x the real bytes */
+    int32_t image, first_mcu, n_mcu, flags;
+} tsod_jpeg_segment;
+int tsod_jpeg_scan_sizes(const tsod_jpeg_info *info, size_t n, int64_t *stream_bytes, int32_t *n_segments);
+int tsod_jpeg_scan_prepare(const uint8_t *data, size_t n, uint8_t *stream, int64_t stream_capacity, int64_t *stream_bytes,
+                           tsod_jpeg_segment *segments, int32_t segment_capacity, int32_t *n_segments, tsod_jpeg_huff *tables);
+int tsod_jpeg_huffman_i16(const tsod_jpeg_image *table_host, const tsod_jpeg_image *table, int32_t n_images,
+                          const tsod_jpeg_segment *segments_host, const tsod_jpeg_segment *segments, int32_t n_segments,
+                          const int32_t *work_host, const int32_t *work, int32_t n_work, const uint8_t *stream, int64_t stream_bytes,
+                          const tsod_jpeg_huff *huff, int64_t n_huff, int16_t *coef, int64_t coef_count, int32_t *status,
+                          int32_t subseq_words, tsod_stream_t stream_handle);
 
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends

@@ -1,4 +1,5 @@
-"""Time the JPEG decoder: the host Huffman pass, the upload and the two kernels, beside Pillow and device copies.
+"""Time the JPEG decoder: the host Huffman pass, the upload and the two kernels, beside Pillow and device copies;
+and the same batch with the Huffman pass on the device (``entropy="device"``).
     python scripts/jpeg_bench.py [--iters N] [--warmup N] [--out profiles/jpeg_mi355x.jsonl]
 
 640x480 4:2:0 quality-90 files of seeded pictures (smooth shapes plus noise), encoded once with Pillow at start (without Pillow
@@ -8,14 +9,25 @@ the script says so and exits).  At batch 1 and 16, one JSON line each:
   * ``idct_us`` / ``to_rgb_us``: each kernel, and ``*_copy_us``: a device-to-device copy of the bytes that kernel reads plus
     writes (a copy moves each byte twice, so the copy is of half that sum) - the floor of a memory-bound kernel, in the same run;
   * ``batch_us_per_image``: the whole ``JPEGDecoder.batch`` call, wall time with one synchronize at the end;
-  * ``pillow_us_per_image``: ``Image.open(...).convert("RGB")`` on one thread - what is being replaced.
+  * ``pillow_us_per_image``: ``Image.open(...).convert("RGB")`` on one thread - what is being replaced;
+  * ``scan_prepare_us_per_image_1t`` / ``_16t``: the host sweep that ``entropy="device"`` leaves (unstuffing, restart markers);
+  * ``huffman_device_us``: ``tsod_jpeg_huffman_i16`` alone - the fill launch and the Huffman launch with the entry's walk over
+    its arguments - at the decoder's default ``subseq_bits``, and ``huffman_device_us_by_bits`` at 256 ... 2048;
+  * ``batch_us_per_image`` / ``batch_device_us_per_image``: the whole ``JPEGDecoder.batch`` call of the two modes, timed in
+    ONE loop that alternates them, each call ending in a synchronize; ``device_upload_bytes`` is what the device mode stages;
+  * ``fixpoint_iterations``: (median, most) fixpoint iterations per round over the batch's files at the default
+    ``subseq_bits``, counted by tests/jpeg_huffman_main.cpp - the kernel's algorithm on the CPU, where the count is exact and
+    free - when a C++ compiler is there (``null`` otherwise).
 Device figures are the median of ``--iters`` calls timed one by one with HIP events, issued back to back after ``--warmup``
 calls; host figures the median of ``--iters`` wall-clock calls."""
 import argparse
 import io
 import json
 import os
+import shutil
+import subprocess
 import sys
+import tempfile
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -54,6 +66,67 @@ def host_median_us(fn, iters, warmup):
         fn()
         times.append((time.perf_counter() - t0) * 1e6)
     return sorted(times)[len(times) // 2]
+
+
+def alternating_medians_us(fns, iters, warmup):
+    """Medians of wall-clock calls of each of `fns`, taken in one loop that alternates them."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    times = [[] for _ in fns]
+    for _ in range(iters):
+        for k, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            fn()
+            times[k].append((time.perf_counter() - t0) * 1e6)
+    return [sorted(t)[len(t) // 2] for t in times]
+
+
+def fixpoint_iterations(files, words):
+    """(median, most) fixpoint iterations per round, from the CPU program; None without a C++ compiler."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        return None
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "jpeg_huffman_main")
+        subprocess.check_call([cxx, "-std=c++17", "-O2", os.path.join(root, "tests", "jpeg_huffman_main.cpp"), "-o", exe])
+        paths = []
+        for i, data in enumerate(files):
+            paths.append(os.path.join(tmp, f"f{i}.jpg"))
+            with open(paths[-1], "wb") as f:
+                f.write(data)
+        lines = [line.split() for line in subprocess.check_output([exe, str(words)] + paths, text=True).splitlines()]
+    assert all(line[:4] == ["0", "0", "0", "1"] for line in lines)
+    return int(np.median([int(line[5]) for line in lines])), max(int(line[4]) for line in lines)
+
+
+def device_pass(dev, raws, infos, plan):
+    """What tsod_jpeg_huffman_i16 takes for this batch, on the host and on the device, and the host sweep that makes it."""
+    seg_dtype = hip_ops.jpeg_segment_dtype()
+    caps = [hip_ops.jpeg_scan_sizes(info, raw.size) for info, raw in zip(infos, raws)]
+    streams = [np.zeros(c[0], dtype=np.uint8) for c in caps]
+    segs = [np.zeros(c[1], dtype=seg_dtype) for c in caps]
+    huff = np.zeros(hip_ops.JPEG_HUFF_BYTES * len(raws), dtype=np.uint8)
+
+    def sweep(i):
+        return hip_ops.jpeg_scan_prepare(raws[i], streams[i], segs[i], huff[hip_ops.JPEG_HUFF_BYTES * i:hip_ops.JPEG_HUFF_BYTES * (i + 1)])
+
+    used, at = [], 0
+    for i in range(len(raws)):
+        status, n_bytes, n_segs = sweep(i)
+        assert status == 0
+        part = segs[i][:n_segs].copy()
+        part["image"], part["stream_offset"] = i, part["stream_offset"] + at
+        used.append((part, streams[i][:n_bytes].copy()))
+        at += n_bytes
+    segments = np.ascontiguousarray(np.concatenate([u[0] for u in used]))
+    stream = np.concatenate([u[1] for u in used])
+    work = np.zeros((len(segments), 4), dtype=np.int32)
+    work[:, 0] = np.arange(len(segments))
+    to_dev = lambda a: torch.from_numpy(a.reshape(-1).view(np.uint8).copy()).to(dev)  # noqa: E731
+    return dict(sweep=sweep, segments=segments, work=work, segments_dev=to_dev(segments), work_dev=to_dev(work), stream=to_dev(stream),
+                huff=to_dev(huff), status=torch.empty(len(raws), dtype=torch.int32, device=dev), stream_bytes=int(stream.size))
 
 
 def picture(rng):
@@ -125,21 +198,52 @@ def main():
         rgb_copy = median_us(lambda: b[:rgb_bytes // 2].copy_(a[:rgb_bytes // 2]), args.iters, args.warmup)
         want = np.asarray(Image.open(io.BytesIO(batch[-1])).convert("RGB"))
         got = out[table[B - 1].out_offset:table[B - 1].out_offset + want.size].view(H, W, 3).cpu().numpy()
+        # the Huffman pass on the device: the host sweep, the entry alone, the whole batch call beside the host mode's
+        dp = device_pass(dev, raws, infos, plan)
+        sweep_us = {}
+        for threads, pool in pools.items():
+            run = (lambda: [dp["sweep"](i) for i in range(B)]) if pool is None else (lambda: list(pool.map(dp["sweep"], range(B))))
+            sweep_us[threads] = host_median_us(run, args.iters, args.warmup) / B
+        coef_dev = torch.empty(plan["coef_count"], dtype=torch.int16, device=dev)
+
+        def huffman_device(bits):
+            return median_us(lambda: hip_ops.jpeg_huffman(table, table_dev, dp["segments"], dp["segments_dev"], dp["work"], dp["work_dev"],
+                                                          dp["stream"], dp["huff"], coef_dev, dp["status"], bits // 32),
+                             args.iters, args.warmup)
+
         dec = image_io.JPEGDecoder(dev, threads=16)
+        dec_device = image_io.JPEGDecoder(dev, threads=16, entropy="device")
+        by_bits = {bits: round(huffman_device(bits), 2) for bits in (256, 512, 1024, 2048)}
+        huffman_dev_us = huffman_device(dec_device.subseq_bits)
+        equals_host_coef = bool(torch.equal(coef_dev, coef)) and not bool(dp["status"].any())
 
         def whole():
             dec.batch(batch)
             torch.cuda.synchronize()
 
-        whole_us = host_median_us(whole, args.iters, args.warmup) / B
+        def whole_device():
+            dec_device.batch(batch)
+            torch.cuda.synchronize()
+
+        whole_us, whole_device_us = (t / B for t in alternating_medians_us([whole, whole_device], args.iters, args.warmup))
+        got_device = dec_device.batch(batch)[-1].cpu().numpy()
+        dec_device.raise_if_corrupt()
         dec.close()
+        dec_device.close()
+        device_upload = dp["stream_bytes"] + dp["segments"].nbytes + dp["work"].nbytes + hip_ops.JPEG_HUFF_BYTES * B
+        iterations = fixpoint_iterations(batch, dec_device.subseq_bits // 32)
         rec = dict(bench="jpeg", batch=B, size=f"{W}x{H}", sampling="4:2:0", quality=QUALITY, iters=args.iters, warmup=args.warmup,
                    file_bytes=int(np.mean([len(f) for f in batch])), huffman_us_per_image_1t=round(host[1], 1),
                    huffman_us_per_image_16t=round(host[16], 1), upload_us=round(upload, 2), upload_bytes=2 * plan["coef_count"],
                    idct_us=round(idct, 2), idct_copy_us=round(idct_copy, 2), idct_over_copy=round(idct / idct_copy, 3),
                    idct_bytes=idct_bytes, to_rgb_us=round(to_rgb, 2), to_rgb_copy_us=round(rgb_copy, 2),
                    to_rgb_over_copy=round(to_rgb / rgb_copy, 3), to_rgb_bytes=rgb_bytes, batch_us_per_image=round(whole_us, 1),
-                   pillow_us_per_image=round(pillow, 1), equals_pillow=bool(np.array_equal(got, want)))
+                   pillow_us_per_image=round(pillow, 1), equals_pillow=bool(np.array_equal(got, want)),
+                   scan_prepare_us_per_image_1t=round(sweep_us[1], 1), scan_prepare_us_per_image_16t=round(sweep_us[16], 1),
+                   subseq_bits=dec_device.subseq_bits, huffman_device_us=round(huffman_dev_us, 2), huffman_device_us_by_bits=by_bits,
+                   segments=int(len(dp["segments"])), device_upload_bytes=int(device_upload),
+                   batch_device_us_per_image=round(whole_device_us, 1), device_equals_host_coefficients=equals_host_coef,
+                   device_equals_pillow=bool(np.array_equal(got_device, want)), fixpoint_iterations=iterations)
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
     pools[16].shutdown()

@@ -192,6 +192,21 @@ class JpegImage(Structure):
                 ("blocks_w", c_int32 * 3), ("blocks_h", c_int32 * 3), ("reserved", c_int32)]
 
 
+JPEG_HUFF_TABLES, JPEG_MAX_SEGMENT_BITS = 6, 0x7FF00000                                      # TSOD_JPEG_*
+JPEG_STATUS_ERROR, JPEG_STATUS_BLOCKS, JPEG_STATUS_LEFTOVER = 1, 2, 4
+
+
+class JpegHuff(Structure):
+    """Mirror of ``tsod_jpeg_huff`` (include/tsod.h): one Huffman code table in the fixed layout the device pass reads."""
+    _fields_ = [("look", c_uint16 * 512), ("maxcode", c_int32 * 17), ("valoff", c_int32 * 17), ("vals", c_uint8 * 256)]
+
+
+class JpegSegment(Structure):
+    """Mirror of ``tsod_jpeg_segment`` (include/tsod.h): one restart interval of one image's unstuffed stream."""
+    _fields_ = [("stream_offset", c_int64), ("bit_length", c_int64), ("image", c_int32), ("first_mcu", c_int32),
+                ("n_mcu", c_int32), ("flags", c_int32)]
+
+
 class AdamWGroup(Structure):
     """Mirror of ``tsod_adamw_group`` (include/tsod.h): the f32 scalars of one AdamW step."""
     _fields_ = [("decay", c_float), ("one_minus_beta1", c_float), ("beta2", c_float), ("one_minus_beta2", c_float),
@@ -433,6 +448,11 @@ _SIGNATURES = {
                                   c_void_p, c_int64, c_void_p]),
     "tsod_jpeg_to_rgb_u8": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                                     c_void_p]),
+    "tsod_jpeg_scan_sizes": (c_int, [POINTER(JpegInfo), c_size_t, POINTER(c_int64), POINTER(c_int32)]),
+    "tsod_jpeg_scan_prepare": (c_int, [c_void_p, c_size_t, c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int32, POINTER(c_int32),
+                                       c_void_p]),
+    "tsod_jpeg_huffman_i16": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                      c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

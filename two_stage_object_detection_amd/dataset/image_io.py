@@ -3,7 +3,11 @@
 Reference: ``Image.open(path).convert("RGB")`` (dataset/dataloader.py:35, multi_inference.py:65).  Here the file's bit-serial
 Huffman pass runs on the host, in the library's C code on a thread pool (ctypes releases the GIL), and everything that is
 arithmetic over pixels - dequantisation, the inverse DCT, chroma upsampling, YCbCr -> RGB and the crop - runs on the GPU in two
-launches for a whole batch, whatever the sizes and samplings of its images.  The pixels are bit-equal to Pillow's
+launches for a whole batch, whatever the sizes and samplings of its images.  With ``entropy="device"`` the Huffman pass runs on
+the GPU too: the host only unstuffs the entropy-coded bytes and checks the restart markers, the upload is the files' own bytes
+instead of 6 bytes of coefficients per pixel, and one more launch (after a fill launch) decodes every restart interval of the
+batch.  Damage inside the entropy-coded data is then found on the device: ``batch`` returns without a host wait, the image's
+pixels are unspecified (inside its own view), ``decoder.status`` is nonzero for it and ``decoder.raise_if_corrupt()`` raises.  The pixels are bit-equal to Pillow's
 (libjpeg-turbo) for every file this decodes: 8-bit baseline or extended-sequential Huffman files, grey or YCbCr with 4:4:4,
 4:2:2 or 4:2:0 sampling.  Anything else raises ``UnsupportedJPEG``, a damaged file ``CorruptJPEG``, both before anything is
 uploaded or launched; there is no CPU fallback - the caller decides what to do with a progressive file.
@@ -88,14 +92,26 @@ def _up(n: int) -> int:
 
 class JPEGDecoder:
     """``JPEGDecoder(device).read(path)`` is the reference's ``Image.open(path).convert("RGB")`` as a u8 [H,W,3] tensor on
-    ``device``.  ``threads`` host threads share the Huffman pass of a batch (at most 16)."""
+    ``device``.  ``threads`` host threads share the host pass of a batch (at most 16).  ``entropy``: ``"host"`` (the Huffman
+    pass on those threads) or ``"device"`` (on the GPU, in subsequences of ``subseq_bits`` bits: a multiple of 32 in [32, 2048]).
 
-    def __init__(self, device="cuda", threads: int = 4):
+    ``status`` is the int32 [B] device tensor of the last ``entropy="device"`` batch: nonzero where an image's entropy-coded
+    data are damaged (``None`` after an ``entropy="host"`` batch, which raises ``CorruptJPEG`` itself)."""
+
+    def __init__(self, device="cuda", threads: int = 4, entropy: str = "host", subseq_bits: int = 1024):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise TsodError(f"JPEGDecoder: {self.device} is not a CUDA/ROCm device; this package is a HIP-only path (there is no "
                             "CPU fallback)")
+        if entropy not in ("host", "device"):
+            raise ValueError(f"JPEGDecoder: entropy is 'host' or 'device', not {entropy!r}")
+        if int(subseq_bits) != subseq_bits or subseq_bits % 32 or not 32 <= subseq_bits <= 2048:
+            raise ValueError(f"JPEGDecoder: subseq_bits is a multiple of 32 in [32, 2048], not {subseq_bits!r}")
         self.threads = min(max(int(threads), 1), MAX_THREADS)
+        self.entropy = entropy
+        self.subseq_bits = int(subseq_bits)
+        self.status = None
+        self._names = []
         self._pool = None
 
     def _map(self, fn, jobs):
@@ -114,7 +130,7 @@ class JPEGDecoder:
     def batch(self, items) -> list:
         """Decode ``items`` (each ``bytes`` / ``bytearray`` / ``memoryview`` / a u8 ndarray holding a file, or a path) into a
         list of u8 [H_i,W_i,3] tensors: contiguous views, each starting on a 256-byte boundary, of ONE device allocation.
-        One upload and two launches on the current stream, no host wait."""
+        One upload and two launches on the current stream (``entropy="device"``: a fill and three launches), no host wait."""
         items = list(items)
         if not items:
             return []
@@ -126,6 +142,9 @@ class JPEGDecoder:
                 _raise(status, i, name, "markers")
             infos.append(info)
         plan = hip_ops.jpeg_plan(infos)
+        if self.entropy == "device":
+            return self._batch_device(files, infos, plan)
+        self.status, self._names = None, []
         table, idct_work, rgb_work = plan["table"], plan["idct_work"], plan["rgb_work"]
         # one staging buffer: table | idct work | rgb work | quantisers | coefficients, each part on a 256-byte boundary
         sizes = (ctypes.sizeof(JpegImage) * len(infos), idct_work.nbytes, rgb_work.nbytes, 2 * plan["quant_count"], 2 * plan["coef_count"])
@@ -159,6 +178,74 @@ class JPEGDecoder:
         return [out[table[i].out_offset:table[i].out_offset + 3 * info.H * info.W].view(info.H, info.W, 3)
                 for i, info in enumerate(infos)]
 
+    def _batch_device(self, files, infos, plan) -> list:
+        """``batch`` with the Huffman pass on the device."""
+        table, idct_work, rgb_work = plan["table"], plan["idct_work"], plan["rgb_work"]
+        n = len(infos)
+        caps = [hip_ops.jpeg_scan_sizes(info, files[i][0].size) for i, info in enumerate(infos)]
+        seg_first = np.concatenate([[0], np.cumsum([c[1] for c in caps])]).astype(np.int64)
+        stream_first = np.concatenate([[0], np.cumsum([c[0] for c in caps])]).astype(np.int64)      # (each a multiple of 4)
+        seg_dtype = hip_ops.jpeg_segment_dtype()
+        n_seg = int(seg_first[-1])
+        # one staging buffer: table | idct work | rgb work | quantisers | code tables | segment records | Huffman work | streams
+        sizes = (ctypes.sizeof(JpegImage) * n, idct_work.nbytes, rgb_work.nbytes, 2 * plan["quant_count"],
+                 hip_ops.JPEG_HUFF_BYTES * n, seg_dtype.itemsize * n_seg, 16 * n_seg, int(stream_first[-1]))
+        starts = [0]
+        for s in sizes:
+            starts.append(starts[-1] + _up(s))
+        staging = _staging(starts[-1])
+        host = staging.numpy()
+        ctypes.memmove(host.ctypes.data + starts[0], table, sizes[0])
+        host[starts[1]:starts[1] + sizes[1]] = idct_work.reshape(-1).view(np.uint8)
+        host[starts[2]:starts[2] + sizes[2]] = rgb_work.reshape(-1).view(np.uint8)
+        quant = host[starts[3]:starts[3] + sizes[3]].view(np.uint16)
+        huff = host[starts[4]:starts[4] + sizes[4]]
+        segments = host[starts[5]:starts[5] + sizes[5]].view(seg_dtype)
+        work = host[starts[6]:starts[6] + sizes[6]].view(np.int32).reshape(-1, 4)
+        stream = host[starts[7]:starts[7] + sizes[7]]
+        for i, info in enumerate(infos):
+            q = np.ctypeslib.as_array(info.quant)[:info.n_comp].reshape(-1)
+            quant[table[i].quant_offset:table[i].quant_offset + q.size] = q
+
+        def sweep(i):
+            segs = segments[seg_first[i]:seg_first[i + 1]]
+            status, _, count = hip_ops.jpeg_scan_prepare(files[i][0], stream[stream_first[i]:stream_first[i + 1]], segs,
+                                                         huff[hip_ops.JPEG_HUFF_BYTES * i:hip_ops.JPEG_HUFF_BYTES * (i + 1)])
+            if status == 0 and count != segs.size:               # (a file that parses holds every interval or is refused)
+                status = -1
+            segs["image"] = i
+            segs["stream_offset"] += stream_first[i]
+            return status
+
+        for i, status in enumerate(self._map(sweep, range(n))):
+            if status:
+                _raise(status, i, files[i][1], "restart markers")
+        work[:] = 0
+        work[:, 0] = np.arange(n_seg, dtype=np.int32)
+        dev = _upload(staging, self.device)
+        part = [dev[starts[k]:starts[k] + sizes[k]] for k in range(8)]
+        coef = _empty(2 * plan["coef_count"], self.device).view(torch.int16)
+        planes = _empty(plan["plane_bytes"], self.device)
+        out = _empty(plan["out_bytes"], self.device)
+        self.status = _empty(4 * n, self.device).view(torch.int32)
+        self._names = [name for _, name in files]
+        hip_ops.jpeg_huffman(table, part[0], segments, part[5], work, part[6], part[7], part[4], coef, self.status,
+                             self.subseq_bits // 32)
+        hip_ops.jpeg_idct(table, part[0], idct_work, part[1], coef, part[3].view(torch.int16), planes)
+        hip_ops.jpeg_to_rgb(table, part[0], rgb_work, part[2], planes, out)
+        return [out[table[i].out_offset:table[i].out_offset + 3 * info.H * info.W].view(info.H, info.W, 3)
+                for i, info in enumerate(infos)]
+
+    def raise_if_corrupt(self) -> None:
+        """The one host read of ``status``: raises ``CorruptJPEG`` naming the first image of the last ``entropy="device"``
+        batch whose entropy-coded data the device found damaged.  Nothing to do after an ``entropy="host"`` batch."""
+        if self.status is None:
+            return
+        bad = torch.nonzero(self.status.cpu()).reshape(-1)
+        if bad.numel():
+            i = int(bad[0])
+            _raise(-1, i, self._names[i] if i < len(self._names) else "", "entropy-coded data, found on the device")
+
     def decode(self, data) -> torch.Tensor:
         """One file's bytes -> u8 [H,W,3] on the device."""
         return self.batch([data])[0]
@@ -171,18 +258,18 @@ class JPEGDecoder:
 _DECODERS = {}
 
 
-def _decoder(device) -> JPEGDecoder:
-    device = torch.device(device)
-    if device not in _DECODERS:
-        _DECODERS[device] = JPEGDecoder(device)
-    return _DECODERS[device]
+def _decoder(device, entropy="host") -> JPEGDecoder:
+    key = (torch.device(device), entropy)
+    if key not in _DECODERS:
+        _DECODERS[key] = JPEGDecoder(key[0], entropy=entropy)
+    return _DECODERS[key]
 
 
-def decode_jpeg(data, device="cuda") -> torch.Tensor:
-    """``JPEGDecoder(device).decode(data)`` on a decoder kept per device."""
-    return _decoder(device).decode(data)
+def decode_jpeg(data, device="cuda", entropy="host") -> torch.Tensor:
+    """``JPEGDecoder(device, entropy=entropy).decode(data)`` on a decoder kept per device and mode."""
+    return _decoder(device, entropy).decode(data)
 
 
-def read_image(path, device="cuda") -> torch.Tensor:
-    """``JPEGDecoder(device).read(path)`` on a decoder kept per device."""
-    return _decoder(device).read(path)
+def read_image(path, device="cuda", entropy="host") -> torch.Tensor:
+    """``JPEGDecoder(device, entropy=entropy).read(path)`` on a decoder kept per device and mode."""
+    return _decoder(device, entropy).read(path)

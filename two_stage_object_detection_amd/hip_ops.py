@@ -2446,3 +2446,71 @@ def jpeg_to_rgb(table, table_dev, work, work_dev, planes, out) -> torch.Tensor:
     check(lib().tsod_jpeg_to_rgb_u8(table, ptr(table_dev), n_images, work.ctypes.data, ptr(work_dev), n_work, ptr(planes),
                                     planes.numel(), ptr(out), out.numel(), stream_ptr()), "jpeg_to_rgb")
     return out
+
+
+def jpeg_segment_dtype():
+    """The NumPy record dtype of ``tsod_jpeg_segment`` (``_ffi.JpegSegment``)."""
+    import numpy as np
+    return np.dtype([("stream_offset", "<i8"), ("bit_length", "<i8"), ("image", "<i4"), ("first_mcu", "<i4"), ("n_mcu", "<i4"),
+                     ("flags", "<i4")])
+
+
+JPEG_HUFF_BYTES = ctypes.sizeof(_ffi.JpegHuff) * _ffi.JPEG_HUFF_TABLES       # the six code tables of one image
+
+
+def jpeg_scan_sizes(info, n: int):
+    """HOST: ``(stream_bytes, n_segments)``, the capacities ``jpeg_scan_prepare`` needs at most for a file of ``n`` bytes
+    whose markers gave ``info`` (``tsod_jpeg_scan_sizes``)."""
+    nbytes, n_seg = ctypes.c_int64(0), ctypes.c_int32(0)
+    check(lib().tsod_jpeg_scan_sizes(byref(info), int(n), byref(nbytes), byref(n_seg)), "jpeg_scan_sizes")
+    return int(nbytes.value), int(n_seg.value)
+
+
+def jpeg_scan_prepare(data, stream, segments, tables):
+    """HOST: the byte-speed sweep that ``entropy="device"`` leaves on the host (``tsod_jpeg_scan_prepare``): the file's
+    entropy-coded bytes, unstuffed and without restart markers, into ``stream`` (a writeable contiguous u8 ndarray), one record
+    per restart interval into ``segments`` (a writeable contiguous ndarray of ``jpeg_segment_dtype()``) and the scan's six code
+    tables into ``tables`` (a writeable contiguous u8 ndarray of ``JPEG_HUFF_BYTES``).  Returns ``(status, stream_bytes,
+    n_segments)``; no exception for a damaged file: the caller names it.  ctypes releases the GIL for the call."""
+    import numpy as np
+    raw = jpeg_bytes(data)
+    for a, dtype, what in ((stream, np.uint8, "stream"), (segments, jpeg_segment_dtype(), "segments"), (tables, np.uint8, "tables")):
+        if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.ndim == 1 and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError(f"jpeg_scan_prepare: {what} is a writeable contiguous 1-d {dtype} ndarray")
+    if tables.size < JPEG_HUFF_BYTES:
+        raise ValueError(f"jpeg_scan_prepare: tables holds {JPEG_HUFF_BYTES} bytes")
+    nbytes, n_seg = ctypes.c_int64(0), ctypes.c_int32(0)
+    rc = int(lib().tsod_jpeg_scan_prepare(raw.ctypes.data, raw.size, stream.ctypes.data, stream.size, byref(nbytes),
+                                          segments.ctypes.data, segments.size, byref(n_seg), tables.ctypes.data))
+    return rc, int(nbytes.value), int(n_seg.value)
+
+
+def jpeg_huffman(table, table_dev, segments, segments_dev, work, work_dev, stream, huff, coef, status, subseq_words: int):
+    """The Huffman pass of a whole batch on the device: a fill launch that clears ``coef`` and ``status``, then ONE launch, one
+    workgroup per restart interval, on the current stream (``tsod_jpeg_huffman_i16``).  ``table`` / ``segments`` / ``work``: the
+    host arrays (``jpeg_plan``'s table, a ``jpeg_segment_dtype()`` ndarray sorted by image, an int32 [n, 4] list of segment
+    numbers); ``*_dev``: their copies in device memory.  ``stream``: u8 device tensor of the unstuffed bytes; ``huff``: u8
+    device tensor, ``JPEG_HUFF_BYTES`` per image; ``coef``: int16 device tensor; ``status``: int32 device tensor, one word per
+    image, nonzero afterwards where the image's entropy-coded data are damaged.  ``subseq_words``: 32-bit words per
+    subsequence, 1 .. 64.  The library checks every record and work item before it launches.  Returns ``coef``."""
+    import numpy as np
+    n_images, n_work = _jpeg_lists(table, table_dev, work, work_dev, "jpeg_huffman")
+    if not (isinstance(segments, np.ndarray) and segments.dtype == jpeg_segment_dtype() and segments.ndim == 1
+            and segments.flags.c_contiguous):
+        raise ValueError("jpeg_huffman: the host segment records are a contiguous 1-d ndarray of jpeg_segment_dtype()")
+    if not (isinstance(segments_dev, torch.Tensor) and segments_dev.is_cuda and segments_dev.is_contiguous()
+            and segments_dev.numel() * segments_dev.element_size() >= segments.nbytes):
+        raise TsodError(f"jpeg_huffman: the device segment records must be a contiguous CUDA/ROCm tensor of at least "
+                        f"{segments.nbytes} bytes (there is no CPU fallback)")
+    dev = table_dev.device
+    _jpeg_buffer(stream, torch.uint8, dev, "jpeg_huffman: stream")
+    _jpeg_buffer(huff, torch.uint8, dev, "jpeg_huffman: huff")
+    _jpeg_buffer(coef, torch.int16, dev, "jpeg_huffman: coef")
+    _jpeg_buffer(status, torch.int32, dev, "jpeg_huffman: status")
+    if status.numel() < n_images:
+        raise ValueError("jpeg_huffman: status holds one word per image")
+    check(lib().tsod_jpeg_huffman_i16(table, ptr(table_dev), n_images, segments.ctypes.data, ptr(segments_dev), segments.size,
+                                      work.ctypes.data, ptr(work_dev), n_work, ptr(stream), stream.numel(), ptr(huff),
+                                      huff.numel() // ctypes.sizeof(_ffi.JpegHuff), ptr(coef), coef.numel(), ptr(status),
+                                      int(subseq_words), stream_ptr()), "jpeg_huffman")
+    return coef
