@@ -1508,7 +1508,40 @@ int tsod_jpeg_to_rgb_u8(const tsod_jpeg_image *table_host, const tsod_jpeg_image
  *     multiple of 4 or whose padded extent ends beyond stream_bytes; a bit_length that is negative, not a multiple of 8 or
  *     above TSOD_JPEG_MAX_SEGMENT_BITS; flags other than 0 or 1; a work item outside [0, n_segments).
  *   TSOD_ERR_ALIGNMENT: table, segments, work or coef not 16-byte, stream, huff or status not 4-byte aligned.
- *   n_work == 0: TSOD_OK, nothing is launched. */
+ *   n_work == 0: TSOD_OK, nothing is launched.
+ *
+ * SPLIT over workgroups ("split over workgroups"): the same pass for segments that are long - a
+ * file without restart markers is ONE segment, so one workgroup above.
+ *   tsod_jpeg_huffman_split_i16: the arguments, the result and the status word of tsod_jpeg_huffman_i16; the work list is a
+ *     chunk list.  A segment of `bits` bits has n = ceil(bits / (32 subseq_words)) subsequences and max(1, ceil(n /
+ *     chunk_subseqs)) chunks; chunk c owns subsequences [c chunk_subseqs, min((c + 1) chunk_subseqs, n)).  Item (segment,
+ *     chunk, list index of the segment's chunk 0, the segment's chunk count); the list holds every segment's chunks in order,
+ *     segment after segment.  After the fill launch, three launches, ordered by the stream alone (no workgroup waits for
+ *     another inside a kernel):
+ *       sync, one workgroup per chunk: one lane per subsequence of the chunk and of up to `overlap` subsequences before it
+ *         (warm-up: they belong to the chunk before and only bring the parse into step), every lane from an assumed state
+ *         (subsequence 0 from the true one), the fixpoint above among them (at most as many passes as lanes).  The owned
+ *         lanes' start state, end state and tally go to the workspace, with the chunk's entry (the start of its first owned
+ *         lane), exit (the end of its last) and total.
+ *       stitch, one workgroup per segment: chunk 0 is true.  Chunk c stands when the final exit of chunk c - 1 equals its
+ *         entry; otherwise it is repaired: its first lane starts from that exit and the fixpoint runs over its own lanes from
+ *         their stored states (at most chunk_subseqs passes).  An ERROR exit ends the walk: a true error was met, and nothing
+ *         after it is looked at, as above.  The boundaries are compared 256 at a time across the lanes; only a mismatch is
+ *         walked to.  An exclusive scan of the chunk totals gives every chunk its base; TSOD_JPEG_STATUS_BLOCKS is set from
+ *         the segment's total; repaired[segment] (when not NULL) = the chunks repaired.  The repair is exact for any
+ *         content, but serial per segment: `overlap` is what keeps it rare.
+ *       write, one workgroup per chunk: the owned lanes' tallies scanned on top of the chunk's base, then the coefficients
+ *         from every lane's final start, with the store rule and the status bits above.
+ *     The result never depends on the parse synchronising inside the overlap, only the time does.  No record of the workspace
+ *     is read before this call has written it.
+ *   tsod_jpeg_huffman_split_workspace_bytes(n_subseqs, n_chunks, n_segments) = 48 n_chunks + 32 (n_subseqs + 256 n_segments),
+ *     n_subseqs the sum of n over the segments (chunk_subseqs lane records per chunk: at most n + chunk_subseqs per segment);
+ *     0 for a negative argument.
+ *   TSOD_ERR_INVALID_ARG: what tsod_jpeg_huffman_i16 refuses; chunk_subseqs outside [1, 256]; overlap outside [0, 256 -
+ *     chunk_subseqs]; a chunk list that is not, segment after segment, every segment's chunks 0 .. count - 1 with the count
+ *     that (bit_length, subseq_words, chunk_subseqs) implies; workspace NULL or smaller than the helper says.
+ *   TSOD_ERR_ALIGNMENT: as above, and workspace not 16-byte or repaired not 4-byte aligned.
+ *   n_chunks == 0: TSOD_OK, nothing is launched. */
 #define TSOD_JPEG_HUFF_TABLES 6
 #define TSOD_JPEG_MAX_SEGMENT_BITS 0x7FF00000
 #define TSOD_JPEG_STATUS_ERROR 1
@@ -1533,6 +1566,13 @@ int tsod_jpeg_huffman_i16(const tsod_jpeg_image *table_host, const tsod_jpeg_ima
                           const int32_t *work_host, const int32_t *work, int32_t n_work, const uint8_t *stream, int64_t stream_bytes,
                           const tsod_jpeg_huff *huff, int64_t n_huff, int16_t *coef, int64_t coef_count, int32_t *status,
                           int32_t subseq_words, tsod_stream_t stream_handle);
+size_t tsod_jpeg_huffman_split_workspace_bytes(int64_t n_subseqs, int32_t n_chunks, int32_t n_segments);
+int tsod_jpeg_huffman_split_i16(const tsod_jpeg_image *table_host, const tsod_jpeg_image *table, int32_t n_images,
+                                const tsod_jpeg_segment *segments_host, const tsod_jpeg_segment *segments, int32_t n_segments,
+                                const int32_t *chunks_host, const int32_t *chunks, int32_t n_chunks, const uint8_t *stream,
+                                int64_t stream_bytes, const tsod_jpeg_huff *huff, int64_t n_huff, int16_t *coef, int64_t coef_count,
+                                int32_t *status, int32_t subseq_words, int32_t chunk_subseqs, int32_t overlap, void *workspace,
+                                size_t workspace_bytes, int32_t *repaired, tsod_stream_t stream_handle);
 
 /* ---- collective: thin wrapper over ncclAllGather (RCCL over xGMI) on the caller's stream.
  * `comm` is an ncclComm_t (from tsod_comm_init_rank below, or any communicator the host already owns); every rank sends

@@ -1,6 +1,7 @@
 """Time the JPEG decoder: the host Huffman pass, the upload and the two kernels, beside Pillow and device copies;
 and the same batch with the Huffman pass on the device (``entropy="device"``).
     python scripts/jpeg_bench.py [--iters N] [--warmup N] [--out profiles/jpeg_mi355x.jsonl]
+                                 [--split S,O ...] [--subseq-bits BITS,BITS,...]
 
 640x480 4:2:0 quality-90 files of seeded pictures (smooth shapes plus noise), encoded once with Pillow at start (without Pillow
 the script says so and exits).  At batch 1 and 16, one JSON line each:
@@ -15,6 +16,10 @@ the script says so and exits).  At batch 1 and 16, one JSON line each:
     its arguments - at the decoder's default ``subseq_bits``, and ``huffman_device_us_by_bits`` at 256 ... 2048;
   * ``batch_us_per_image`` / ``batch_device_us_per_image``: the whole ``JPEGDecoder.batch`` call of the two modes, timed in
     ONE loop that alternates them, each call ending in a synchronize; ``device_upload_bytes`` is what the device mode stages;
+  * ``split``: with ``--split S,O`` (repeatable), one entry per ``--subseq-bits`` value (the decoder's default without the
+    option) and (S, O): ``batch_us_per_image`` of ``JPEGDecoder(entropy="device", subseq_bits=.., split=(S, O))`` from that
+    same alternating loop, ``chunks`` (the workgroups of the sync and write launches for this batch), ``repaired`` (the sum of
+    ``decoder.repaired``: chunks the stitch launch decoded again, one after the other) and ``equals_pillow``;
   * ``fixpoint_iterations``: (median, most) fixpoint iterations per round over the batch's files at the default
     ``subseq_bits``, counted by tests/jpeg_huffman_main.cpp - the kernel's algorithm on the CPU, where the count is exact and
     free - when a C++ compiler is there (``null`` otherwise).
@@ -39,6 +44,7 @@ from two_stage_object_detection_amd import hip_ops  # noqa: E402
 from two_stage_object_detection_amd.dataset import image_io  # noqa: E402
 
 H, W, QUALITY = 480, 640, 90
+DEVICE = "cuda:0"
 
 
 def median_us(fn, iters, warmup):
@@ -143,7 +149,18 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    ap.add_argument("--split", action="append", default=[], metavar="S,O",
+                    help="also time entropy='device' with split=(S, O) in the alternating loop (repeatable)")
+    ap.add_argument("--subseq-bits", default=None, metavar="BITS[,BITS...]", help="the subsequence lengths of the --split rows")
     args = ap.parse_args()
+    try:
+        splits = [tuple(int(v) for v in text.split(",")) for text in args.split]
+        split_bits = [int(v) for v in args.subseq_bits.split(",")] if args.subseq_bits else [image_io.JPEGDecoder(DEVICE).subseq_bits]
+        for bits in split_bits:
+            for split in splits or [None]:
+                image_io.JPEGDecoder(DEVICE, entropy="device", subseq_bits=bits, split=split)
+    except ValueError as e:
+        ap.error(str(e))
     if args.iters < 20 or args.warmup < 3:
         ap.error("at least 20 timed and 3 warm-up calls")
     try:
@@ -151,7 +168,7 @@ def main():
     except ImportError:
         print("scripts/jpeg_bench.py needs Pillow to encode its workload (and as the decoder it is compared with); it is not installed")
         return 1
-    dev = torch.device("cuda:0")
+    dev = torch.device(DEVICE)
     rng = np.random.default_rng(0)
     files = []
     for _ in range(16):
@@ -225,7 +242,26 @@ def main():
             dec_device.batch(batch)
             torch.cuda.synchronize()
 
-        whole_us, whole_device_us = (t / B for t in alternating_medians_us([whole, whole_device], args.iters, args.warmup))
+        split_decs = [image_io.JPEGDecoder(dev, threads=16, entropy="device", subseq_bits=bits, split=split)
+                      for bits in split_bits for split in splits]
+
+        def whole_split(d):
+            def run():
+                d.batch(batch)
+                torch.cuda.synchronize()
+            return run
+
+        medians = alternating_medians_us([whole, whole_device] + [whole_split(d) for d in split_decs], args.iters, args.warmup)
+        whole_us, whole_device_us = medians[0] / B, medians[1] / B
+        split_rows = []
+        for d, t in zip(split_decs, medians[2:]):
+            got_split = d.batch(batch)[-1].cpu().numpy()
+            d.raise_if_corrupt()
+            split_rows.append(dict(subseq_bits=d.subseq_bits, chunk_subseqs=d.split[0], overlap=d.split[1],
+                                   batch_us_per_image=round(t / B, 1), repaired=int(d.repaired.sum()),
+                                   chunks=int(len(hip_ops.jpeg_split_chunks(dp["segments"], d.subseq_bits // 32, d.split[0])[0])),
+                                   equals_pillow=bool(np.array_equal(got_split, want))))
+            d.close()
         got_device = dec_device.batch(batch)[-1].cpu().numpy()
         dec_device.raise_if_corrupt()
         dec.close()
@@ -244,6 +280,8 @@ def main():
                    segments=int(len(dp["segments"])), device_upload_bytes=int(device_upload),
                    batch_device_us_per_image=round(whole_device_us, 1), device_equals_host_coefficients=equals_host_coef,
                    device_equals_pillow=bool(np.array_equal(got_device, want)), fixpoint_iterations=iterations)
+        if split_rows:
+            rec["split"] = split_rows
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
     pools[16].shutdown()

@@ -453,6 +453,10 @@ _SIGNATURES = {
                                        c_void_p]),
     "tsod_jpeg_huffman_i16": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
                                       c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
+    "tsod_jpeg_huffman_split_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "tsod_jpeg_huffman_split_i16": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                                            c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32,
+                                            c_void_p, c_size_t, c_void_p, c_void_p]),
     "tsod_allgather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tsod_comm_unique_id": (c_int, [c_void_p]),
     "tsod_comm_init_rank": (c_int, [POINTER(c_void_p), c_int32, c_void_p, c_int32]),

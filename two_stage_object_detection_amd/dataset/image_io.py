@@ -6,7 +6,9 @@ arithmetic over pixels - dequantisation, the inverse DCT, chroma upsampling, YCb
 launches for a whole batch, whatever the sizes and samplings of its images.  With ``entropy="device"`` the Huffman pass runs on
 the GPU too: the host only unstuffs the entropy-coded bytes and checks the restart markers, the upload is the files' own bytes
 instead of 6 bytes of coefficients per pixel, and one more launch (after a fill launch) decodes every restart interval of the
-batch.  Damage inside the entropy-coded data is then found on the device: ``batch`` returns without a host wait, the image's
+batch; ``split=`` cuts a long interval - a whole file without restart markers - into chunks for one workgroup each, joined
+exactly, in three launches instead of that one.  Damage inside the entropy-coded data is then found on the device: ``batch``
+returns without a host wait, the image's
 pixels are unspecified (inside its own view), ``decoder.status`` is nonzero for it and ``decoder.raise_if_corrupt()`` raises.  The pixels are bit-equal to Pillow's
 (libjpeg-turbo) for every file this decodes: 8-bit baseline or extended-sequential Huffman files, grey or YCbCr with 4:4:4,
 4:2:2 or 4:2:0 sampling.  Anything else raises ``UnsupportedJPEG``, a damaged file ``CorruptJPEG``, both before anything is
@@ -94,11 +96,19 @@ class JPEGDecoder:
     """``JPEGDecoder(device).read(path)`` is the reference's ``Image.open(path).convert("RGB")`` as a u8 [H,W,3] tensor on
     ``device``.  ``threads`` host threads share the host pass of a batch (at most 16).  ``entropy``: ``"host"`` (the Huffman
     pass on those threads) or ``"device"`` (on the GPU, in subsequences of ``subseq_bits`` bits: a multiple of 32 in [32, 2048]).
+    ``split`` (``entropy="device"`` only): ``None`` - one workgroup per restart interval - or ``(chunk_subseqs, overlap)``, which
+    gives every ``chunk_subseqs`` consecutive subsequences of an interval to a workgroup of their own that warms up over the
+    ``overlap`` subsequences before them (``chunk_subseqs`` in [1, 256], ``overlap`` in [0, 256 - ``chunk_subseqs``]); ``True`` is
+    ``(224, 32)``.  The pixels and ``status`` do not depend on it.
 
     ``status`` is the int32 [B] device tensor of the last ``entropy="device"`` batch: nonzero where an image's entropy-coded
-    data are damaged (``None`` after an ``entropy="host"`` batch, which raises ``CorruptJPEG`` itself)."""
+    data are damaged (``None`` after an ``entropy="host"`` batch, which raises ``CorruptJPEG`` itself).  ``repaired`` is the
+    int32 [n_segments] device tensor of the last ``split`` batch: the chunks of every restart interval whose assumed entry was
+    wrong and that were decoded again from the true one (``None`` otherwise)."""
 
-    def __init__(self, device="cuda", threads: int = 4, entropy: str = "host", subseq_bits: int = 1024):
+    SPLIT_DEFAULT = (224, 32)
+
+    def __init__(self, device="cuda", threads: int = 4, entropy: str = "host", subseq_bits: int = 1024, split=None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise TsodError(f"JPEGDecoder: {self.device} is not a CUDA/ROCm device; this package is a HIP-only path (there is no "
@@ -107,10 +117,27 @@ class JPEGDecoder:
             raise ValueError(f"JPEGDecoder: entropy is 'host' or 'device', not {entropy!r}")
         if int(subseq_bits) != subseq_bits or subseq_bits % 32 or not 32 <= subseq_bits <= 2048:
             raise ValueError(f"JPEGDecoder: subseq_bits is a multiple of 32 in [32, 2048], not {subseq_bits!r}")
+        if split is True:
+            split = self.SPLIT_DEFAULT
+        if split is not None:
+            if entropy != "device":
+                raise ValueError("JPEGDecoder: split belongs to entropy='device'")
+            try:
+                chunk, overlap = split
+                ok = int(chunk) == chunk and int(overlap) == overlap and 1 <= chunk <= hip_ops.JPEG_SPLIT_MAX and \
+                    0 <= overlap <= hip_ops.JPEG_SPLIT_MAX - chunk
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"JPEGDecoder: split is None, True or (chunk_subseqs in [1, 256], overlap in [0, 256 - chunk_subseqs]), "
+                                 f"not {split!r}")
+            split = (int(chunk), int(overlap))
         self.threads = min(max(int(threads), 1), MAX_THREADS)
         self.entropy = entropy
         self.subseq_bits = int(subseq_bits)
+        self.split = split
         self.status = None
+        self.repaired = None
         self._names = []
         self._pool = None
 
@@ -130,7 +157,8 @@ class JPEGDecoder:
     def batch(self, items) -> list:
         """Decode ``items`` (each ``bytes`` / ``bytearray`` / ``memoryview`` / a u8 ndarray holding a file, or a path) into a
         list of u8 [H_i,W_i,3] tensors: contiguous views, each starting on a 256-byte boundary, of ONE device allocation.
-        One upload and two launches on the current stream (``entropy="device"``: a fill and three launches), no host wait."""
+        One upload and two launches on the current stream (``entropy="device"``: a fill and three launches, with ``split`` a
+        fill and five), no host wait."""
         items = list(items)
         if not items:
             return []
@@ -144,7 +172,7 @@ class JPEGDecoder:
         plan = hip_ops.jpeg_plan(infos)
         if self.entropy == "device":
             return self._batch_device(files, infos, plan)
-        self.status, self._names = None, []
+        self.status, self.repaired, self._names = None, None, []
         table, idct_work, rgb_work = plan["table"], plan["idct_work"], plan["rgb_work"]
         # one staging buffer: table | idct work | rgb work | quantisers | coefficients, each part on a 256-byte boundary
         sizes = (ctypes.sizeof(JpegImage) * len(infos), idct_work.nbytes, rgb_work.nbytes, 2 * plan["quant_count"], 2 * plan["coef_count"])
@@ -187,9 +215,15 @@ class JPEGDecoder:
         stream_first = np.concatenate([[0], np.cumsum([c[0] for c in caps])]).astype(np.int64)      # (each a multiple of 4)
         seg_dtype = hip_ops.jpeg_segment_dtype()
         n_seg = int(seg_first[-1])
+        words = self.subseq_bits // 32
+        n_work = n_seg
+        if self.split:
+            # the bit lengths come with the sweep: room for the most chunks these streams can hold (a segment of n subsequences
+            # has at most 1 + n / chunk_subseqs chunks, and n is at most 1 + bits / subseq_bits)
+            n_work = n_seg + (int(stream_first[-1]) * 8 // self.subseq_bits + n_seg) // self.split[0]
         # one staging buffer: table | idct work | rgb work | quantisers | code tables | segment records | Huffman work | streams
         sizes = (ctypes.sizeof(JpegImage) * n, idct_work.nbytes, rgb_work.nbytes, 2 * plan["quant_count"],
-                 hip_ops.JPEG_HUFF_BYTES * n, seg_dtype.itemsize * n_seg, 16 * n_seg, int(stream_first[-1]))
+                 hip_ops.JPEG_HUFF_BYTES * n, seg_dtype.itemsize * n_seg, 16 * n_work, int(stream_first[-1]))
         starts = [0]
         for s in sizes:
             starts.append(starts[-1] + _up(s))
@@ -221,7 +255,12 @@ class JPEGDecoder:
             if status:
                 _raise(status, i, files[i][1], "restart markers")
         work[:] = 0
-        work[:, 0] = np.arange(n_seg, dtype=np.int32)
+        if self.split:
+            chunks, n_subseqs = hip_ops.jpeg_split_chunks(segments, words, self.split[0])
+            work[:len(chunks)] = chunks
+            work = work[:len(chunks)]
+        else:
+            work[:, 0] = np.arange(n_seg, dtype=np.int32)
         dev = _upload(staging, self.device)
         part = [dev[starts[k]:starts[k] + sizes[k]] for k in range(8)]
         coef = _empty(2 * plan["coef_count"], self.device).view(torch.int16)
@@ -229,8 +268,14 @@ class JPEGDecoder:
         out = _empty(plan["out_bytes"], self.device)
         self.status = _empty(4 * n, self.device).view(torch.int32)
         self._names = [name for _, name in files]
-        hip_ops.jpeg_huffman(table, part[0], segments, part[5], work, part[6], part[7], part[4], coef, self.status,
-                             self.subseq_bits // 32)
+        self.repaired = None
+        if self.split:
+            workspace = _empty(hip_ops.jpeg_huffman_split_workspace_bytes(n_subseqs, len(work), n_seg), self.device)
+            self.repaired = _empty(4 * n_seg, self.device).view(torch.int32)
+            hip_ops.jpeg_huffman_split(table, part[0], segments, part[5], work, part[6][:work.nbytes], part[7], part[4], coef,
+                                       self.status, words, self.split[0], self.split[1], workspace, self.repaired)
+        else:
+            hip_ops.jpeg_huffman(table, part[0], segments, part[5], work, part[6], part[7], part[4], coef, self.status, words)
         hip_ops.jpeg_idct(table, part[0], idct_work, part[1], coef, part[3].view(torch.int16), planes)
         hip_ops.jpeg_to_rgb(table, part[0], rgb_work, part[2], planes, out)
         return [out[table[i].out_offset:table[i].out_offset + 3 * info.H * info.W].view(info.H, info.W, 3)
@@ -258,18 +303,22 @@ class JPEGDecoder:
 _DECODERS = {}
 
 
-def _decoder(device, entropy="host") -> JPEGDecoder:
-    key = (torch.device(device), entropy)
+def _decoder(device, entropy="host", split=None) -> JPEGDecoder:
+    if split is True:
+        split = JPEGDecoder.SPLIT_DEFAULT
+    elif isinstance(split, list):
+        split = tuple(split)
+    key = (torch.device(device), entropy, split)
     if key not in _DECODERS:
-        _DECODERS[key] = JPEGDecoder(key[0], entropy=entropy)
+        _DECODERS[key] = JPEGDecoder(key[0], entropy=entropy, split=key[2])
     return _DECODERS[key]
 
 
-def decode_jpeg(data, device="cuda", entropy="host") -> torch.Tensor:
-    """``JPEGDecoder(device, entropy=entropy).decode(data)`` on a decoder kept per device and mode."""
-    return _decoder(device, entropy).decode(data)
+def decode_jpeg(data, device="cuda", entropy="host", split=None) -> torch.Tensor:
+    """``JPEGDecoder(device, entropy=entropy, split=split).decode(data)`` on a decoder kept per device and mode."""
+    return _decoder(device, entropy, split).decode(data)
 
 
-def read_image(path, device="cuda", entropy="host") -> torch.Tensor:
-    """``JPEGDecoder(device, entropy=entropy).read(path)`` on a decoder kept per device and mode."""
-    return _decoder(device, entropy).read(path)
+def read_image(path, device="cuda", entropy="host", split=None) -> torch.Tensor:
+    """``JPEGDecoder(device, entropy=entropy, split=split).read(path)`` on a decoder kept per device and mode."""
+    return _decoder(device, entropy, split).read(path)

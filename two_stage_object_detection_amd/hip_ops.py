@@ -2514,3 +2514,70 @@ def jpeg_huffman(table, table_dev, segments, segments_dev, work, work_dev, strea
                                       huff.numel() // ctypes.sizeof(_ffi.JpegHuff), ptr(coef), coef.numel(), ptr(status),
                                       int(subseq_words), stream_ptr()), "jpeg_huffman")
     return coef
+
+
+JPEG_SPLIT_MAX = 256                                                         # chunk_subseqs + overlap: one workgroup
+
+
+def jpeg_split_chunks(segments, subseq_words: int, chunk_subseqs: int):
+    """HOST: the chunk list ``jpeg_huffman_split`` takes for ``segments`` (a ``jpeg_segment_dtype()`` ndarray) and the number of
+    subsequences in all.  A segment of ``bits`` bits has ``n = ceil(bits / (32 subseq_words))`` subsequences and ``max(1, ceil(n /
+    chunk_subseqs))`` chunks; an item is (segment, chunk, list index of the segment's chunk 0, the segment's chunk count).
+    Returns ``(int32 [n_chunks, 4] ndarray, n_subseqs)``."""
+    import numpy as np
+    if not 1 <= int(subseq_words) <= 64 or not 1 <= int(chunk_subseqs) <= JPEG_SPLIT_MAX:
+        raise ValueError("jpeg_split_chunks: subseq_words is in [1, 64] and chunk_subseqs in [1, 256]")
+    bits = np.asarray(segments["bit_length"], dtype=np.int64)
+    subseqs = -(-bits // (32 * int(subseq_words)))
+    counts = np.maximum(-(-subseqs // int(chunk_subseqs)), 1)
+    first = np.cumsum(counts) - counts
+    total = int(counts.sum())
+    chunks = np.empty((total, 4), dtype=np.int32)
+    chunks[:, 0] = np.repeat(np.arange(bits.size), counts)
+    chunks[:, 2] = np.repeat(first, counts)
+    chunks[:, 3] = np.repeat(counts, counts)
+    chunks[:, 1] = np.arange(total) - chunks[:, 2]
+    return chunks, int(subseqs.sum())
+
+
+def jpeg_huffman_split_workspace_bytes(n_subseqs: int, n_chunks: int, n_segments: int) -> int:
+    """Bytes of workspace ``jpeg_huffman_split`` needs (``tsod_jpeg_huffman_split_workspace_bytes``)."""
+    return int(lib().tsod_jpeg_huffman_split_workspace_bytes(int(n_subseqs), int(n_chunks), int(n_segments)))
+
+
+def jpeg_huffman_split(table, table_dev, segments, segments_dev, chunks, chunks_dev, stream, huff, coef, status, subseq_words: int,
+                       chunk_subseqs: int, overlap: int, workspace, repaired=None):
+    """``jpeg_huffman`` with every segment split over several workgroups (``tsod_jpeg_huffman_split_i16``): a fill launch, then
+    three launches on the current stream - sync (one workgroup per chunk of ``chunk_subseqs`` subsequences, warmed up over the
+    ``overlap`` subsequences before it), stitch (one workgroup per segment joins the chunks, repairing a chunk whose assumed entry
+    was wrong) and write.  Arguments as ``jpeg_huffman``, with the work list replaced by ``chunks`` / ``chunks_dev``
+    (``jpeg_split_chunks``); ``workspace``: u8 device tensor of ``jpeg_huffman_split_workspace_bytes`` bytes, never read before
+    it is written; ``repaired``: optional int32 device tensor, one word per segment, that receives the number of chunks the
+    stitch launch repaired.  The coefficients and ``status`` are ``jpeg_huffman``'s, bit for bit.  Returns ``coef``."""
+    import numpy as np
+    n_images, n_chunks = _jpeg_lists(table, table_dev, chunks, chunks_dev, "jpeg_huffman_split")
+    if not (isinstance(segments, np.ndarray) and segments.dtype == jpeg_segment_dtype() and segments.ndim == 1
+            and segments.flags.c_contiguous):
+        raise ValueError("jpeg_huffman_split: the host segment records are a contiguous 1-d ndarray of jpeg_segment_dtype()")
+    if not (isinstance(segments_dev, torch.Tensor) and segments_dev.is_cuda and segments_dev.is_contiguous()
+            and segments_dev.numel() * segments_dev.element_size() >= segments.nbytes):
+        raise TsodError(f"jpeg_huffman_split: the device segment records must be a contiguous CUDA/ROCm tensor of at least "
+                        f"{segments.nbytes} bytes (there is no CPU fallback)")
+    dev = table_dev.device
+    _jpeg_buffer(stream, torch.uint8, dev, "jpeg_huffman_split: stream")
+    _jpeg_buffer(huff, torch.uint8, dev, "jpeg_huffman_split: huff")
+    _jpeg_buffer(coef, torch.int16, dev, "jpeg_huffman_split: coef")
+    _jpeg_buffer(status, torch.int32, dev, "jpeg_huffman_split: status")
+    _jpeg_buffer(workspace, torch.uint8, dev, "jpeg_huffman_split: workspace")
+    if status.numel() < n_images:
+        raise ValueError("jpeg_huffman_split: status holds one word per image")
+    if repaired is not None:
+        _jpeg_buffer(repaired, torch.int32, dev, "jpeg_huffman_split: repaired")
+        if repaired.numel() < segments.size:
+            raise ValueError("jpeg_huffman_split: repaired holds one word per segment")
+    check(lib().tsod_jpeg_huffman_split_i16(table, ptr(table_dev), n_images, segments.ctypes.data, ptr(segments_dev), segments.size,
+                                            chunks.ctypes.data, ptr(chunks_dev), n_chunks, ptr(stream), stream.numel(), ptr(huff),
+                                            huff.numel() // ctypes.sizeof(_ffi.JpegHuff), ptr(coef), coef.numel(), ptr(status),
+                                            int(subseq_words), int(chunk_subseqs), int(overlap), ptr(workspace), workspace.numel(),
+                                            None if repaired is None else ptr(repaired), stream_ptr()), "jpeg_huffman_split")
+    return coef
