@@ -2,7 +2,11 @@
 
 Bars: bit-exact for index / integer results (sort order, NMS keep lists, RoI max pooling which is
 pure gather+compare); <= 1e-3 absolute for f32 box/score arithmetic (in practice ~1e-5);
-convolutions against an f64 CPU convolution with a tolerance scaled by sqrt(K)."""
+convolutions against an f64 CPU convolution with a tolerance scaled by sqrt(K).
+
+The conv tests here cover the K loop at real layer sizes.  The gather paths, the four epilogue bodies and the K-slice / hybrid
+schedules of every (tile, arithmetic) pair are swept in tests/test_conv_kernels_gpu.py against the restatement and the derived
+per-element bars of tests/conv_restated.py."""
 import math
 
 import numpy as np
