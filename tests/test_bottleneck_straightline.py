@@ -6,7 +6,10 @@ f64 CPU block at the smallest shapes that reach every tile pipeline, with the ba
 * a shape at which the launcher's rule really picks 10 rows: the 8-row tiling needs more than one round of the device (two
   workgroups per CU), the 10-row tiling fits in one.  There waves 0, 1 run the 4 / 3-block pipeline and waves 2, 3 the 3 / 2-block
   one, chosen by one scalar branch.  The width follows from the device's CU count.
-Each with the identity shortcut and with the projection shortcut (stacked-K conv3)."""
+Each with the identity shortcut and with the projection shortcut (stacked-K conv3).
+
+The bar here is one max-norm tolerance per tensor; tests/test_fused_kernels_gpu.py holds the same kernels to a per-element bound
+derived in tests/fused_restated.py, at every geometry, pitch, BatchNorm sign, slope and scale switch."""
 import functools
 import math
 

@@ -929,7 +929,8 @@ def test_bottleneck_fused_with_projection_shortcut_matches_the_f64_block(ops, de
     """tsod_bottleneck_fp16x2, desc.projection = 1 (layer1's first block, models/resnet.py:114-116): conv3 and the 1x1 projection
     shortcut as one stacked-K GEMM inside the one-launch bottleneck - y2 chunks from LDS, x chunks from L2, the accumulators
     changing scale between them - against the f64 CPU block; tile edges, inputs 500x larger / 10^4 x smaller, a shortcut operand
-    300x larger than the main path's (the scale switch), Cin != 64, and the abs-max left for the consumer."""
+    300x larger than the main path's (the scale switch), Cin != 64, and the abs-max left for the consumer.
+    (A max-norm bar at layer-sized K; the per-element sweep of the same kernel is tests/test_fused_kernels_gpu.py.)"""
     g = torch.Generator().manual_seed(321 + H)
     x = torch.randn(N, Cin, H, W, generator=g)
     x = torch.maximum(x, 0.25 * x) * gain
@@ -973,7 +974,8 @@ def test_bottleneck_fused_matches_the_f64_block(ops, dev, N, H, W, C, gain):
     """tsod_bottleneck_fp16x2: a whole identity bottleneck in one launch (both 64-channel intermediates in LDS) against the f64
     CPU block - tile edges (H, W not multiples of the 10 x 16 tile; one-tile and multi-tile images), the zero padding of the 3x3
     (y1 is padded, not x: a border pixel's halo must be exact zeros), the tile-local scales of the intermediates and the range
-    words of x (inputs 500x larger / 10^4 x smaller), and the abs-max it leaves for its consumer."""
+    words of x (inputs 500x larger / 10^4 x smaller), and the abs-max it leaves for its consumer.
+    (A max-norm bar at layer-sized K; the per-element sweep of the same kernel is tests/test_fused_kernels_gpu.py.)"""
     g = torch.Generator().manual_seed(123 + H)
     x = torch.randn(N, C, H, W, generator=g)
     x = torch.maximum(x, 0.25 * x) * gain
@@ -1026,7 +1028,9 @@ def test_stem_fused_matches_the_f64_stem(ops, dev, N, H, W, gain):
     """tsod_stem_fp16x2: conv 7x7/2 + BN + PReLU + max pool 3x3/2 in one launch against the f64 CPU stem, from NCHW images and from
     NHWC4 images: tile edges (sizes that are not multiples of the 4 x 16 pooled tile, one-tile and multi-tile images, odd conv
     sizes: the pool's -inf padding), the conv's zero padding, the tile-local pixel scale (inputs 300x larger / 1000x smaller than
-    unit range), the abs-max left for the consumer, and non-finite input raising the flag."""
+    unit range), the abs-max left for the consumer, and non-finite input raising the flag.
+    (A max-norm bar; the per-element sweep of the same kernel, its persistent tile loop at two and three rounds included, is
+    tests/test_fused_kernels_gpu.py.)"""
     from two_stage_object_detection_amd._ffi import NHWC4Images
     g = torch.Generator().manual_seed(77 + H)
     x = torch.randn(N, 3, H, W, generator=g) * gain

@@ -214,7 +214,8 @@ def library_hash() -> str:
 
 def tuning_path(directory, model, shape, device, args: dict) -> str:
     """``args``: the JSON-able tuning arguments the table depends on (FasterRCNN.tune passes its own)."""
-    name = torch.cuda.get_device_name(device) if torch.cuda.is_available() else "cpu"
+    # (a CPU device on a machine that has a GPU is still "cpu": torch.cuda.get_device_name refuses it)
+    name = torch.cuda.get_device_name(device) if torch.cuda.is_available() and torch.device(device).type == "cuda" else "cpu"
     n, _, h, w = (int(v) for v in shape)
     wh = hashlib.sha256(state_dict_hash(model.state_dict()).encode() + config_fingerprint(model)).hexdigest()[:32]
     key = hashlib.sha256(json.dumps({"weights": wh, "device": name, "shape": [n, h, w], "lib": library_hash(), "args": args},
