@@ -12,7 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_scan_restated as S  # noqa: E402
-from test_jpeg_restated import fixtures  # noqa: E402
+from test_jpeg_restated import fixtures, rounds  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -179,6 +179,29 @@ def test_three_rounds_at_the_default_subsequence_length(dev):
         return
     for a, data in zip(got, files):
         assert np.array_equal(a, np.asarray(Image.open(io.BytesIO(data)).convert("RGB")))
+
+
+@pytest.mark.parametrize("words", [1, 2])
+def test_round_boundaries(dev, words):
+    """tests/golden/jpeg_rounds.npz: one workgroup each for a segment of 256, 257, 512 and 513 one-word subsequences, and of
+    256 and 257 two-word ones - a last round that is full, and a last round of one lane that starts from the carried state.
+    The host pass's coefficients, status 0, the guards intact, and Pillow's pixels through the decoder."""
+    from two_stage_object_detection_amd.dataset import image_io
+    cases = [c for c in rounds() if words == 1 or c[3] >= 512]
+    files = [data for _, data, _, _ in cases]
+    prep = _prepare(files)
+    assert len(prep["segments"]) == len(cases)
+    assert [int(-(-b // (32 * words))) for b in prep["segments"]["bit_length"]] == ([256, 257, 512, 513] if words == 1 else [256, 257])
+    coef, status = _launch(dev, prep, words)
+    assert not status.any()
+    table = prep["plan"]["table"]
+    for i, ((name, _, _, _), info) in enumerate(zip(cases, prep["infos"])):
+        first = table[i].coef_offset[0]
+        assert np.array_equal(coef[first:first + info.coef_total], prep["want"][i]), (name, words)
+    decoder = image_io.JPEGDecoder(dev, threads=2, entropy="device", subseq_bits=32 * words)
+    for t, (name, _, pixels, _) in zip(decoder.batch(files), cases):
+        assert np.array_equal(t.cpu().numpy(), pixels), (name, words)
+    decoder.raise_if_corrupt()
 
 
 @pytest.mark.parametrize("name", S.STATUS_FIXTURES)

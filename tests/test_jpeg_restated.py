@@ -25,6 +25,14 @@ def fixtures():
 
 
 @functools.lru_cache(maxsize=None)
+def rounds():
+    """[(name, file bytes, Pillow's u8 [H,W,3], one-word subsequences)] of tests/golden/jpeg_rounds.npz: one segment each, of
+    256, 257, 512 and 513 subsequences - the round boundaries of the device Huffman pass."""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_rounds.npz"))
+    return [(str(n), z[f"file_{i}"].tobytes(), z[f"pixels_{i}"], int(z["subseqs"][i])) for i, n in enumerate(z["names"])]
+
+
+@functools.lru_cache(maxsize=None)
 def restated(i):
     """(info, coefficient arrays) of fixture i by the restatement, computed once."""
     return R.entropy_decode(fixtures()[0][i][1])

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_scan_restated as S  # noqa: E402
-from test_jpeg_restated import fixtures  # noqa: E402
+from test_jpeg_restated import fixtures, rounds  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "two_stage_object_detection_amd", "csrc")
@@ -333,6 +333,22 @@ def test_device_pass_on_the_cpu_under_sanitizers_every_fixture(cpu_program, tmp_
             assert line[2 + 4 * k:4 + 4 * k] == ["0", "1"], (name, k)
         most = max(most, int(line[4]))
     assert 1 < most < 256                                            # 32-bit subsequences do need the fixpoint, and it ends early
+
+
+def test_device_pass_on_the_cpu_under_sanitizers_round_boundaries(cpu_program, tmp_path):
+    """tests/golden/jpeg_rounds.npz: one segment each of 256, 257, 512 and 513 one-word subsequences - a full last round, and a
+    last round of one lane from the carried state - and of 256 and 257 again at two words: the host pass's coefficients."""
+    cases = rounds()
+    assert [n for _, _, _, n in cases] == [256, 257, 512, 513]
+    for name, data, _, n in cases:
+        records = S.scan(data)[2]
+        assert len(records) == 1 and -(-records[0][3] // 32) == n, name
+        assert n < 512 or -(-records[0][3] // 64) == n - 256, name
+    lines = _sweep(cpu_program, tmp_path, [data for _, data, _, _ in cases], "1,2")
+    for (name, _, _, _), line in zip(cases, lines):
+        assert line[:2] == ["0", "0"] and len(line) == 10, name
+        for k in range(2):
+            assert line[2 + 4 * k:4 + 4 * k] == ["0", "1"], (name, k)
 
 
 def test_device_pass_on_the_cpu_under_sanitizers_damaged_files(cpu_program, tmp_path):

@@ -15,11 +15,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_scan_restated as S  # noqa: E402
-from test_jpeg_restated import fixtures  # noqa: E402
+from test_jpeg_restated import fixtures, rounds  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "two_stage_object_detection_amd", "csrc")
 # (subseq_words, chunk_subseqs, overlap)
+ROUND_TRIPLES = ((1, 256, 0), (1, 255, 1), (1, 128, 0))             # for tests/golden/jpeg_rounds.npz: whole, warmed and half rounds
 TRIPLES = ((1, 1, 0), (1, 3, 0), (1, 3, 2), (1, 5, 251), (1, 256, 0), (2, 64, 16), (3, 224, 32), (32, 256, 0), (32, 2, 1))
 
 
@@ -331,6 +332,17 @@ def test_split_pass_on_the_cpu_under_sanitizers_large_files(cpu_program, tmp_pat
     _, accepted, repaired, _ = _totals(lines, 1)
     assert accepted > 0 and repaired > 0
     assert _totals(lines, 2)[2] > 500
+
+
+def test_split_pass_on_the_cpu_under_sanitizers_round_boundaries(cpu_program, tmp_path):
+    """tests/golden/jpeg_rounds.npz - 256, 257, 512 and 513 one-word subsequences - in chunks of a whole round, of a round less
+    one lane after one lane of warm-up, and of half a round: the last chunk is full, or is one lane."""
+    cases = rounds()
+    lines = _sweep(cpu_program, tmp_path, [data for _, data, _, _ in cases], ROUND_TRIPLES)
+    for (name, _, _, n), (head, per) in zip(cases, lines):
+        assert head == ["0", "0"], name
+        for (_, chunk, _), got in zip(ROUND_TRIPLES, per):
+            assert got[:2] == ["0", "1"] and int(got[2]) == -(-n // chunk), (name, chunk)
 
 
 def test_split_pass_on_the_cpu_under_sanitizers_damaged_files(cpu_program, tmp_path):

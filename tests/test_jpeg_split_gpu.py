@@ -14,8 +14,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_scan_restated as S  # noqa: E402
 from test_jpeg_huffman_gpu import _device_copy, _fixture, _guarded, _guards_intact, _large, _prepare  # noqa: E402
-from test_jpeg_restated import fixtures  # noqa: E402
-from test_jpeg_split_abi import TRIPLES  # noqa: E402
+from test_jpeg_restated import fixtures, rounds  # noqa: E402
+from test_jpeg_split_abi import ROUND_TRIPLES, TRIPLES  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +76,25 @@ def test_split_entry_equals_host_pass_on_every_fixture(dev, every_fixture, tripl
         assert accepted > 0 and repaired.sum() > 0
     if triple == (32, 256, 0):
         assert n_chunks == n_segments
+
+
+@pytest.mark.parametrize("triple", ROUND_TRIPLES)
+def test_split_entry_at_the_round_boundaries(dev, triple):
+    """tests/golden/jpeg_rounds.npz - segments of 256, 257, 512 and 513 one-word subsequences - in chunks of a whole round, of a
+    round less one lane after one lane of warm-up, and of half a round: the host pass's coefficients, status 0, the guards
+    intact, and Pillow's pixels through the decoder."""
+    from two_stage_object_detection_amd.dataset import image_io
+    cases = rounds()
+    files = [data for _, data, _, _ in cases]
+    prep = _prepare(files)
+    coef, status, repaired, n_chunks = _launch(dev, prep, triple)
+    assert not status.any()
+    _equals_host_pass(prep, coef)
+    assert n_chunks == sum(-(-n // triple[1]) for _, _, _, n in cases) and repaired.shape == (len(cases),)
+    decoder = image_io.JPEGDecoder(dev, threads=2, entropy="device", subseq_bits=32 * triple[0], split=triple[1:])
+    for t, (name, _, pixels, _) in zip(decoder.batch(files), cases):
+        assert np.array_equal(t.cpu().numpy(), pixels), (name, triple)
+    decoder.raise_if_corrupt()
 
 
 def test_same_bits_from_two_calls_and_from_any_workspace_fill(dev, every_fixture):

@@ -2,6 +2,7 @@
 // behind two C entry points, and the two kernels that turn a batch's coefficients into packed RGB - dequantisation with the
 // 8x8 inverse DCT, then chroma upsampling, colour conversion and the crop.  Every address either kernel forms comes from the
 // table and work list that the entry points checked on the host; file-derived data only ever appear as values.
+#include "jpeg_checks.h"
 #include "jpeg_entropy.h"
 #include "tsod_internal.h"
 
@@ -175,24 +176,19 @@ jpeg_to_rgb_kernel(const tsod_jpeg_image *__restrict__ table, const int4 *__rest
     }
 }
 
-bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+using tsod_jpeg::aligned;
+using tsod_jpeg::fits;
+using tsod_jpeg::grid_fits;
 
-// [offset, offset + extent) inside [0, size), offset a multiple of unit
-bool fits(int64_t offset, int64_t extent, int64_t size, int64_t unit) {
-    return offset >= 0 && offset % unit == 0 && extent >= 0 && offset <= size && extent <= size - offset;
-}
-
-// What both entries need of a record: the component count, the sampling, grids that cover the image, planes inside `plane_bytes`
+// What both entries need of a record: its shape (jpeg_checks.h), the H / W range, grids that cover the image, planes inside
+// `plane_bytes`
 int check_image(const tsod_jpeg_image &im, int64_t plane_bytes) {
-    TSOD_REQUIRE(im.n_comp == 1 || im.n_comp == 3, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(tsod_jpeg::shape_ok(im), TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(im.H > 0 && im.W > 0 && im.H <= 65535 && im.W <= 65535, TSOD_ERR_INVALID_ARG);
-    const bool sampling = im.n_comp == 1 ? (im.hs == 1 && im.vs == 1) : ((im.hs == 1 && im.vs == 1) || (im.hs == 2 && (im.vs == 1 || im.vs == 2)));
-    TSOD_REQUIRE(sampling, TSOD_ERR_INVALID_ARG);
     for (int c = 0; c < im.n_comp; ++c) {
         const int64_t w = c ? tsod_cdiv(im.W, im.hs) : im.W, h = c ? tsod_cdiv(im.H, im.vs) : im.H;
-        TSOD_REQUIRE(im.blocks_w[c] > 0 && im.blocks_h[c] > 0 && im.blocks_w[c] <= 8192 && im.blocks_h[c] <= 8192, TSOD_ERR_INVALID_ARG);
         TSOD_REQUIRE((int64_t)im.blocks_w[c] * 8 >= w && (int64_t)im.blocks_h[c] * 8 >= h, TSOD_ERR_INVALID_ARG);
-        TSOD_REQUIRE(fits(im.plane_offset[c], (int64_t)64 * im.blocks_w[c] * im.blocks_h[c], plane_bytes, 8), TSOD_ERR_INVALID_ARG);
+        TSOD_REQUIRE(grid_fits(im, c, im.plane_offset[c], plane_bytes, 8), TSOD_ERR_INVALID_ARG);
     }
     if (im.n_comp == 3) TSOD_REQUIRE(im.blocks_w[1] == im.blocks_w[2] && im.blocks_h[1] == im.blocks_h[2], TSOD_ERR_INVALID_ARG);
     return TSOD_OK;
@@ -225,7 +221,7 @@ extern "C" int tsod_jpeg_idct_u8(const tsod_jpeg_image *table_host, const tsod_j
         const int rc = check_image(im, plane_bytes);
         if (rc != TSOD_OK) return rc;
         for (int c = 0; c < im.n_comp; ++c)
-            TSOD_REQUIRE(fits(im.coef_offset[c], (int64_t)64 * im.blocks_w[c] * im.blocks_h[c], coef_count, 64), TSOD_ERR_INVALID_ARG);
+            TSOD_REQUIRE(grid_fits(im, c, im.coef_offset[c], coef_count, 64), TSOD_ERR_INVALID_ARG);
         TSOD_REQUIRE(fits(im.quant_offset, (int64_t)64 * im.n_comp, quant_count, 64), TSOD_ERR_INVALID_ARG);
     }
     for (int64_t k = 0; k < n_work; ++k) {

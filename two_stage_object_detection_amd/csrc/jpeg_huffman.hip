@@ -2,9 +2,11 @@
 // DEVICE"): the host sweep of jpeg_scan.h behind two C entry points, and one kernel that decodes every restart interval of a
 // batch, one workgroup per interval, as a workgroup-local self-synchronising decoder.  The per-lane work is
 // jpeg_huffman_core.h, shared with the stand-alone CPU program tests/jpeg_huffman_main.cpp; this file is the orchestration:
-// rounds, the fixpoint vote, the scan and the status word.  Every address comes from records checked on the host.  The split
+// rounds, the fixpoint vote, the scan and the status word.  Every address comes from records checked on the host
+// (jpeg_checks.h, check_batch; check_entry is the opening both launch entries share).  The split
 // mode (tsod_jpeg_huffman_split_i16, jpeg_huffman_split.h) gives a segment's subsequences to several workgroups in chunks: three
 // launches - sync, stitch, write - ordered by the stream alone; the CPU program for it is tests/jpeg_huffman_split_main.cpp.
+#include "jpeg_checks.h"
 #include "jpeg_huffman_core.h"
 #include "jpeg_huffman_split.h"
 #include "jpeg_scan.h"
@@ -99,22 +101,10 @@ jpeg_huffman_kernel(const tsod_jpeg_image *__restrict__ table, const tsod_jpeg_s
     if (flags) atomicOr(status + seg.image, flags);
 }
 
-bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// [offset, offset + extent) inside [0, size), offset a multiple of unit
-bool fits(int64_t offset, int64_t extent, int64_t size, int64_t unit) {
-    return offset >= 0 && offset % unit == 0 && extent >= 0 && offset <= size && extent <= size - offset;
-}
-
-// What the Huffman kernel reads of a record: the component count, the sampling, whole-MCU grids, coefficients inside coef_count
+// What the Huffman kernels read of a record: its shape (jpeg_checks.h), whole-MCU grids, coefficients inside coef_count
 int check_image(const tsod_jpeg_image &im, int64_t coef_count) {
-    TSOD_REQUIRE(im.n_comp == 1 || im.n_comp == 3, TSOD_ERR_INVALID_ARG);
-    const bool sampling = im.n_comp == 1 ? (im.hs == 1 && im.vs == 1) : ((im.hs == 1 && im.vs == 1) || (im.hs == 2 && (im.vs == 1 || im.vs == 2)));
-    TSOD_REQUIRE(sampling, TSOD_ERR_INVALID_ARG);
-    for (int c = 0; c < im.n_comp; ++c) {
-        TSOD_REQUIRE(im.blocks_w[c] > 0 && im.blocks_h[c] > 0 && im.blocks_w[c] <= 8192 && im.blocks_h[c] <= 8192, TSOD_ERR_INVALID_ARG);
-        TSOD_REQUIRE(fits(im.coef_offset[c], (int64_t)64 * im.blocks_w[c] * im.blocks_h[c], coef_count, 64), TSOD_ERR_INVALID_ARG);
-    }
+    TSOD_REQUIRE(shape_ok(im), TSOD_ERR_INVALID_ARG);
+    for (int c = 0; c < im.n_comp; ++c) TSOD_REQUIRE(grid_fits(im, c, im.coef_offset[c], coef_count, 64), TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(im.blocks_w[0] % im.hs == 0 && im.blocks_h[0] % im.vs == 0, TSOD_ERR_INVALID_ARG);
     for (int c = 1; c < im.n_comp; ++c)
         TSOD_REQUIRE(im.blocks_w[c] == im.blocks_w[0] / im.hs && im.blocks_h[c] == im.blocks_h[0] / im.vs, TSOD_ERR_INVALID_ARG);
@@ -147,6 +137,28 @@ int check_batch(const tsod_jpeg_image *table_host, int32_t n_images, const tsod_
     }
     TSOD_REQUIRE(next_mcu == n_mcu && image == n_images - 1, TSOD_ERR_INVALID_ARG);
     return TSOD_OK;
+}
+
+// The opening of both launch entries, `list` being the work list of the one and the chunk list of the other: the lengths,
+// then - unless the list is empty, which is TSOD_OK and for the caller to return on - the pointers (`others`: the entry's
+// further ones are there) and the records.  The entry checks its own list next and the alignment last.
+int check_entry(const tsod_jpeg_image *table_host, const tsod_jpeg_image *table, int32_t n_images, const tsod_jpeg_segment *segments_host,
+                const tsod_jpeg_segment *segments, int32_t n_segments, const int32_t *list_host, const int32_t *list, int32_t n_list,
+                const uint8_t *stream, int64_t stream_bytes, const tsod_jpeg_huff *huff, int64_t n_huff, int16_t *coef, int64_t coef_count,
+                int32_t *status, int32_t subseq_words, bool others) {
+    TSOD_REQUIRE(subseq_words >= 1 && subseq_words <= 64, TSOD_ERR_INVALID_ARG);
+    TSOD_REQUIRE(n_images >= 0 && n_segments >= 0 && n_list >= 0 && stream_bytes >= 0 && n_huff >= 0 && coef_count >= 0, TSOD_ERR_INVALID_ARG);
+    if (n_list == 0) return TSOD_OK;
+    TSOD_REQUIRE(table_host && table && segments_host && segments && list_host && list && stream && huff && coef && status && others,
+                 TSOD_ERR_INVALID_ARG);
+    return check_batch(table_host, n_images, segments_host, n_segments, stream_bytes, n_huff, coef_count);
+}
+
+// The pointers both entries hand to the kernels
+bool entry_aligned(const void *table, const void *segments, const void *list, const void *coef, const void *stream, const void *huff,
+                   const void *status) {
+    return aligned(table, 16) && aligned(segments, 16) && aligned(list, 16) && aligned(coef, 16) && aligned(stream, 4) && aligned(huff, 4) &&
+           aligned(status, 4);
 }
 
 void launch_clear(int16_t *coef, int64_t coef_count, int32_t *status, int32_t n_images, tsod_stream_t stream_handle) {
@@ -401,17 +413,11 @@ extern "C" int tsod_jpeg_huffman_i16(const tsod_jpeg_image *table_host, const ts
                                      const int32_t *work_host, const int32_t *work, int32_t n_work, const uint8_t *stream,
                                      int64_t stream_bytes, const tsod_jpeg_huff *huff, int64_t n_huff, int16_t *coef,
                                      int64_t coef_count, int32_t *status, int32_t subseq_words, tsod_stream_t stream_handle) {
-    TSOD_REQUIRE(subseq_words >= 1 && subseq_words <= 64, TSOD_ERR_INVALID_ARG);
-    TSOD_REQUIRE(n_images >= 0 && n_segments >= 0 && n_work >= 0 && stream_bytes >= 0 && n_huff >= 0 && coef_count >= 0, TSOD_ERR_INVALID_ARG);
-    if (n_work == 0) return TSOD_OK;
-    TSOD_REQUIRE(table_host && table && segments_host && segments && work_host && work && stream && huff && coef && status,
-                 TSOD_ERR_INVALID_ARG);
-    const int rc = check_batch(table_host, n_images, segments_host, n_segments, stream_bytes, n_huff, coef_count);
-    if (rc != TSOD_OK) return rc;
+    const int rc = check_entry(table_host, table, n_images, segments_host, segments, n_segments, work_host, work, n_work, stream, stream_bytes,
+                               huff, n_huff, coef, coef_count, status, subseq_words, true);
+    if (rc != TSOD_OK || n_work == 0) return rc;
     for (int64_t k = 0; k < n_work; ++k) TSOD_REQUIRE(work_host[4 * k] >= 0 && work_host[4 * k] < n_segments, TSOD_ERR_INVALID_ARG);
-    TSOD_REQUIRE(aligned(table, 16) && aligned(segments, 16) && aligned(work, 16) && aligned(coef, 16) && aligned(stream, 4) &&
-                     aligned(huff, 4) && aligned(status, 4),
-                 TSOD_ERR_ALIGNMENT);
+    TSOD_REQUIRE(entry_aligned(table, segments, work, coef, stream, huff, status), TSOD_ERR_ALIGNMENT);
     launch_clear(coef, coef_count, status, n_images, stream_handle);
     hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)n_work), dim3(kThreads), 0, tsod_stream(stream_handle), table, segments,
                        reinterpret_cast<const int4 *>(work), reinterpret_cast<const uint32_t *>(stream), huff, coef, status,
@@ -431,15 +437,12 @@ extern "C" int tsod_jpeg_huffman_split_i16(const tsod_jpeg_image *table_host, co
                                            int64_t coef_count, int32_t *status, int32_t subseq_words, int32_t chunk_subseqs,
                                            int32_t overlap, void *workspace, size_t workspace_bytes, int32_t *repaired,
                                            tsod_stream_t stream_handle) {
-    TSOD_REQUIRE(subseq_words >= 1 && subseq_words <= 64, TSOD_ERR_INVALID_ARG);
+    // (the two lengths of its own first: they are refused with an empty list too, and with the same status as subseq_words)
     TSOD_REQUIRE(chunk_subseqs >= 1 && chunk_subseqs <= kSplitMaxChunk && overlap >= 0 && overlap <= kSplitMaxChunk - chunk_subseqs,
                  TSOD_ERR_INVALID_ARG);
-    TSOD_REQUIRE(n_images >= 0 && n_segments >= 0 && n_chunks >= 0 && stream_bytes >= 0 && n_huff >= 0 && coef_count >= 0, TSOD_ERR_INVALID_ARG);
-    if (n_chunks == 0) return TSOD_OK;
-    TSOD_REQUIRE(table_host && table && segments_host && segments && chunks_host && chunks && stream && huff && coef && status && workspace,
-                 TSOD_ERR_INVALID_ARG);
-    const int rc = check_batch(table_host, n_images, segments_host, n_segments, stream_bytes, n_huff, coef_count);
-    if (rc != TSOD_OK) return rc;
+    const int rc = check_entry(table_host, table, n_images, segments_host, segments, n_segments, chunks_host, chunks, n_chunks, stream,
+                               stream_bytes, huff, n_huff, coef, coef_count, status, subseq_words, workspace != nullptr);
+    if (rc != TSOD_OK || n_chunks == 0) return rc;
     // the chunk list: sorted by segment, every segment's chunks 0 .. count - 1 with the count its bit length implies
     int64_t at = 0, n_subseqs = 0;
     for (int k = 0; k < n_segments; ++k) {
@@ -454,8 +457,7 @@ extern "C" int tsod_jpeg_huffman_split_i16(const tsod_jpeg_image *table_host, co
     }
     TSOD_REQUIRE(at == n_chunks, TSOD_ERR_INVALID_ARG);
     TSOD_REQUIRE(workspace_bytes >= (size_t)split_workspace_bytes(n_subseqs, n_chunks, n_segments), TSOD_ERR_INVALID_ARG);
-    TSOD_REQUIRE(aligned(table, 16) && aligned(segments, 16) && aligned(chunks, 16) && aligned(coef, 16) && aligned(workspace, 16) &&
-                     aligned(stream, 4) && aligned(huff, 4) && aligned(status, 4) && aligned(repaired, 4),
+    TSOD_REQUIRE(entry_aligned(table, segments, chunks, coef, stream, huff, status) && aligned(workspace, 16) && aligned(repaired, 4),
                  TSOD_ERR_ALIGNMENT);
     SplitChunk *records = static_cast<SplitChunk *>(workspace);
     const SplitArgs args = {table, segments, reinterpret_cast<const int4 *>(chunks), reinterpret_cast<const uint32_t *>(stream), huff,

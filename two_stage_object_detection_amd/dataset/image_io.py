@@ -88,8 +88,64 @@ def _empty(nbytes: int, device) -> torch.Tensor:
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-def _up(n: int) -> int:
-    return (n + ALIGN - 1) // ALIGN * ALIGN
+def _stage(infos, plan, more):
+    """ONE staging buffer of byte parts, each on a 256-byte boundary.  The first four - table | idct work | rgb work | quantisers -
+    are what both modes send, and are filled here; one part of every size in ``more`` follows.  Returns ``(host, upload)``:
+    ``host`` holds those further parts as u8 ndarray views for the caller to fill, and ``upload(device)`` is the one copy,
+    returning the four shared parts and the further ones as device tensors."""
+    table, idct_work, rgb_work = plan["table"], plan["idct_work"], plan["rgb_work"]
+    sizes = (ctypes.sizeof(JpegImage) * len(infos), idct_work.nbytes, rgb_work.nbytes, 2 * plan["quant_count"]) + tuple(more)
+    starts = [0]
+    for n in sizes:
+        starts.append(starts[-1] + (n + ALIGN - 1) // ALIGN * ALIGN)
+    spans = [slice(first, first + n) for first, n in zip(starts, sizes)]
+    staging = _staging(starts[-1])
+    host = [staging.numpy()[span] for span in spans]
+    ctypes.memmove(host[0].ctypes.data, table, sizes[0])
+    host[1][:] = idct_work.reshape(-1).view(np.uint8)
+    host[2][:] = rgb_work.reshape(-1).view(np.uint8)
+    quant = host[3].view(np.uint16)
+    for i, info in enumerate(infos):
+        q = np.ctypeslib.as_array(info.quant)[:info.n_comp].reshape(-1)
+        quant[table[i].quant_offset:table[i].quant_offset + q.size] = q
+
+    def upload(device):
+        dev = _upload(staging, device)
+        parts = [dev[span] for span in spans]
+        return parts[:4], parts[4:]
+
+    return host[4:], upload
+
+
+def _pixels(infos, plan, shared, coef) -> list:
+    """``jpeg_idct`` and ``jpeg_to_rgb`` of an uploaded batch (``shared``: the first four parts of ``_stage``) from its
+    coefficients: u8 [H_i,W_i,3] views, each starting on a 256-byte boundary, of one allocation."""
+    table, (table_dev, idct_dev, rgb_dev, quant_dev) = plan["table"], shared
+    planes = _empty(plan["plane_bytes"], coef.device)
+    out = _empty(plan["out_bytes"], coef.device)
+    hip_ops.jpeg_idct(table, table_dev, plan["idct_work"], idct_dev, coef, quant_dev.view(torch.int16), planes)
+    hip_ops.jpeg_to_rgb(table, table_dev, plan["rgb_work"], rgb_dev, planes, out)
+    return [out[table[i].out_offset:table[i].out_offset + 3 * info.H * info.W].view(info.H, info.W, 3) for i, info in enumerate(infos)]
+
+
+def _split_arg(split, entropy):
+    """``split`` as ``JPEGDecoder`` keeps it: ``None`` or a checked ``(chunk_subseqs, overlap)`` of ints."""
+    if split is True:
+        split = JPEGDecoder.SPLIT_DEFAULT
+    if split is None:
+        return None
+    if entropy != "device":
+        raise ValueError("JPEGDecoder: split belongs to entropy='device'")
+    try:
+        chunk, overlap = split
+        ok = int(chunk) == chunk and int(overlap) == overlap and 1 <= chunk <= hip_ops.JPEG_SPLIT_MAX and \
+            0 <= overlap <= hip_ops.JPEG_SPLIT_MAX - chunk
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"JPEGDecoder: split is None, True or (chunk_subseqs in [1, 256], overlap in [0, 256 - chunk_subseqs]), "
+                         f"not {split!r}")
+    return int(chunk), int(overlap)
 
 
 class JPEGDecoder:
@@ -117,25 +173,10 @@ class JPEGDecoder:
             raise ValueError(f"JPEGDecoder: entropy is 'host' or 'device', not {entropy!r}")
         if int(subseq_bits) != subseq_bits or subseq_bits % 32 or not 32 <= subseq_bits <= 2048:
             raise ValueError(f"JPEGDecoder: subseq_bits is a multiple of 32 in [32, 2048], not {subseq_bits!r}")
-        if split is True:
-            split = self.SPLIT_DEFAULT
-        if split is not None:
-            if entropy != "device":
-                raise ValueError("JPEGDecoder: split belongs to entropy='device'")
-            try:
-                chunk, overlap = split
-                ok = int(chunk) == chunk and int(overlap) == overlap and 1 <= chunk <= hip_ops.JPEG_SPLIT_MAX and \
-                    0 <= overlap <= hip_ops.JPEG_SPLIT_MAX - chunk
-            except (TypeError, ValueError):
-                ok = False
-            if not ok:
-                raise ValueError(f"JPEGDecoder: split is None, True or (chunk_subseqs in [1, 256], overlap in [0, 256 - chunk_subseqs]), "
-                                 f"not {split!r}")
-            split = (int(chunk), int(overlap))
         self.threads = min(max(int(threads), 1), MAX_THREADS)
         self.entropy = entropy
         self.subseq_bits = int(subseq_bits)
-        self.split = split
+        self.split = _split_arg(split, entropy)
         self.status = None
         self.repaired = None
         self._names = []
@@ -173,22 +214,9 @@ class JPEGDecoder:
         if self.entropy == "device":
             return self._batch_device(files, infos, plan)
         self.status, self.repaired, self._names = None, None, []
-        table, idct_work, rgb_work = plan["table"], plan["idct_work"], plan["rgb_work"]
-        # one staging buffer: table | idct work | rgb work | quantisers | coefficients, each part on a 256-byte boundary
-        sizes = (ctypes.sizeof(JpegImage) * len(infos), idct_work.nbytes, rgb_work.nbytes, 2 * plan["quant_count"], 2 * plan["coef_count"])
-        starts = [0]
-        for s in sizes:
-            starts.append(starts[-1] + _up(s))
-        staging = _staging(starts[-1])
-        host = staging.numpy()
-        ctypes.memmove(host.ctypes.data + starts[0], table, sizes[0])
-        host[starts[1]:starts[1] + sizes[1]] = idct_work.reshape(-1).view(np.uint8)
-        host[starts[2]:starts[2] + sizes[2]] = rgb_work.reshape(-1).view(np.uint8)
-        quant = host[starts[3]:starts[3] + sizes[3]].view(np.uint16)
-        coef = host[starts[4]:starts[4] + sizes[4]].view(np.int16)
-        for i, info in enumerate(infos):
-            q = np.ctypeslib.as_array(info.quant)[:info.n_comp].reshape(-1)
-            quant[table[i].quant_offset:table[i].quant_offset + q.size] = q
+        table = plan["table"]
+        (coef,), upload = _stage(infos, plan, (2 * plan["coef_count"],))
+        coef = coef.view(np.int16)
 
         def huffman(i):
             first = table[i].coef_offset[0]
@@ -197,18 +225,12 @@ class JPEGDecoder:
         for i, status in enumerate(self._map(huffman, range(len(files)))):
             if status:
                 _raise(status, i, files[i][1], "entropy-coded data")
-        dev = _upload(staging, self.device)
-        part = [dev[starts[k]:starts[k] + sizes[k]] for k in range(5)]
-        planes = _empty(plan["plane_bytes"], self.device)
-        out = _empty(plan["out_bytes"], self.device)
-        hip_ops.jpeg_idct(table, part[0], idct_work, part[1], part[4].view(torch.int16), part[3].view(torch.int16), planes)
-        hip_ops.jpeg_to_rgb(table, part[0], rgb_work, part[2], planes, out)
-        return [out[table[i].out_offset:table[i].out_offset + 3 * info.H * info.W].view(info.H, info.W, 3)
-                for i, info in enumerate(infos)]
+        shared, (coef_dev,) = upload(self.device)
+        return _pixels(infos, plan, shared, coef_dev.view(torch.int16))
 
     def _batch_device(self, files, infos, plan) -> list:
         """``batch`` with the Huffman pass on the device."""
-        table, idct_work, rgb_work = plan["table"], plan["idct_work"], plan["rgb_work"]
+        table = plan["table"]
         n = len(infos)
         caps = [hip_ops.jpeg_scan_sizes(info, files[i][0].size) for i, info in enumerate(infos)]
         seg_first = np.concatenate([[0], np.cumsum([c[1] for c in caps])]).astype(np.int64)
@@ -221,25 +243,10 @@ class JPEGDecoder:
             # the bit lengths come with the sweep: room for the most chunks these streams can hold (a segment of n subsequences
             # has at most 1 + n / chunk_subseqs chunks, and n is at most 1 + bits / subseq_bits)
             n_work = n_seg + (int(stream_first[-1]) * 8 // self.subseq_bits + n_seg) // self.split[0]
-        # one staging buffer: table | idct work | rgb work | quantisers | code tables | segment records | Huffman work | streams
-        sizes = (ctypes.sizeof(JpegImage) * n, idct_work.nbytes, rgb_work.nbytes, 2 * plan["quant_count"],
-                 hip_ops.JPEG_HUFF_BYTES * n, seg_dtype.itemsize * n_seg, 16 * n_work, int(stream_first[-1]))
-        starts = [0]
-        for s in sizes:
-            starts.append(starts[-1] + _up(s))
-        staging = _staging(starts[-1])
-        host = staging.numpy()
-        ctypes.memmove(host.ctypes.data + starts[0], table, sizes[0])
-        host[starts[1]:starts[1] + sizes[1]] = idct_work.reshape(-1).view(np.uint8)
-        host[starts[2]:starts[2] + sizes[2]] = rgb_work.reshape(-1).view(np.uint8)
-        quant = host[starts[3]:starts[3] + sizes[3]].view(np.uint16)
-        huff = host[starts[4]:starts[4] + sizes[4]]
-        segments = host[starts[5]:starts[5] + sizes[5]].view(seg_dtype)
-        work = host[starts[6]:starts[6] + sizes[6]].view(np.int32).reshape(-1, 4)
-        stream = host[starts[7]:starts[7] + sizes[7]]
-        for i, info in enumerate(infos):
-            q = np.ctypeslib.as_array(info.quant)[:info.n_comp].reshape(-1)
-            quant[table[i].quant_offset:table[i].quant_offset + q.size] = q
+        # after the shared parts: code tables | segment records | Huffman work | streams
+        (huff, segments, work, stream), upload = _stage(infos, plan, (hip_ops.JPEG_HUFF_BYTES * n, seg_dtype.itemsize * n_seg, 16 * n_work,
+                                                                      int(stream_first[-1])))
+        segments, work = segments.view(seg_dtype), work.view(np.int32).reshape(-1, 4)
 
         def sweep(i):
             segs = segments[seg_first[i]:seg_first[i + 1]]
@@ -261,25 +268,20 @@ class JPEGDecoder:
             work = work[:len(chunks)]
         else:
             work[:, 0] = np.arange(n_seg, dtype=np.int32)
-        dev = _upload(staging, self.device)
-        part = [dev[starts[k]:starts[k] + sizes[k]] for k in range(8)]
+        shared, (huff_dev, segments_dev, work_dev, stream_dev) = upload(self.device)
         coef = _empty(2 * plan["coef_count"], self.device).view(torch.int16)
-        planes = _empty(plan["plane_bytes"], self.device)
-        out = _empty(plan["out_bytes"], self.device)
         self.status = _empty(4 * n, self.device).view(torch.int32)
         self._names = [name for _, name in files]
         self.repaired = None
         if self.split:
             workspace = _empty(hip_ops.jpeg_huffman_split_workspace_bytes(n_subseqs, len(work), n_seg), self.device)
             self.repaired = _empty(4 * n_seg, self.device).view(torch.int32)
-            hip_ops.jpeg_huffman_split(table, part[0], segments, part[5], work, part[6][:work.nbytes], part[7], part[4], coef,
-                                       self.status, words, self.split[0], self.split[1], workspace, self.repaired)
+            hip_ops.jpeg_huffman_split(table, shared[0], segments, segments_dev, work, work_dev[:work.nbytes], stream_dev, huff_dev,
+                                       coef, self.status, words, self.split[0], self.split[1], workspace, self.repaired)
         else:
-            hip_ops.jpeg_huffman(table, part[0], segments, part[5], work, part[6], part[7], part[4], coef, self.status, words)
-        hip_ops.jpeg_idct(table, part[0], idct_work, part[1], coef, part[3].view(torch.int16), planes)
-        hip_ops.jpeg_to_rgb(table, part[0], rgb_work, part[2], planes, out)
-        return [out[table[i].out_offset:table[i].out_offset + 3 * info.H * info.W].view(info.H, info.W, 3)
-                for i, info in enumerate(infos)]
+            hip_ops.jpeg_huffman(table, shared[0], segments, segments_dev, work, work_dev, stream_dev, huff_dev, coef, self.status,
+                                 words)
+        return _pixels(infos, plan, shared, coef)
 
     def raise_if_corrupt(self) -> None:
         """The one host read of ``status``: raises ``CorruptJPEG`` naming the first image of the last ``entropy="device"``
@@ -304,11 +306,7 @@ _DECODERS = {}
 
 
 def _decoder(device, entropy="host", split=None) -> JPEGDecoder:
-    if split is True:
-        split = JPEGDecoder.SPLIT_DEFAULT
-    elif isinstance(split, list):
-        split = tuple(split)
-    key = (torch.device(device), entropy, split)
+    key = (torch.device(device), entropy, _split_arg(split, entropy))
     if key not in _DECODERS:
         _DECODERS[key] = JPEGDecoder(key[0], entropy=entropy, split=key[2])
     return _DECODERS[key]

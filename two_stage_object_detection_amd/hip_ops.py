@@ -2485,6 +2485,28 @@ def jpeg_scan_prepare(data, stream, segments, tables):
     return rc, int(nbytes.value), int(n_seg.value)
 
 
+def _jpeg_huffman_args(what: str, table, table_dev, segments, segments_dev, work, work_dev, stream, huff, coef, status):
+    """The argument checks ``jpeg_huffman`` and ``jpeg_huffman_split`` share, ``work`` being the work list of the one and the
+    chunk list of the other: ``(n_images, n_work, device)``."""
+    import numpy as np
+    n_images, n_work = _jpeg_lists(table, table_dev, work, work_dev, what)
+    if not (isinstance(segments, np.ndarray) and segments.dtype == jpeg_segment_dtype() and segments.ndim == 1
+            and segments.flags.c_contiguous):
+        raise ValueError(f"{what}: the host segment records are a contiguous 1-d ndarray of jpeg_segment_dtype()")
+    if not (isinstance(segments_dev, torch.Tensor) and segments_dev.is_cuda and segments_dev.is_contiguous()
+            and segments_dev.numel() * segments_dev.element_size() >= segments.nbytes):
+        raise TsodError(f"{what}: the device segment records must be a contiguous CUDA/ROCm tensor of at least "
+                        f"{segments.nbytes} bytes (there is no CPU fallback)")
+    dev = table_dev.device
+    _jpeg_buffer(stream, torch.uint8, dev, f"{what}: stream")
+    _jpeg_buffer(huff, torch.uint8, dev, f"{what}: huff")
+    _jpeg_buffer(coef, torch.int16, dev, f"{what}: coef")
+    _jpeg_buffer(status, torch.int32, dev, f"{what}: status")
+    if status.numel() < n_images:
+        raise ValueError(f"{what}: status holds one word per image")
+    return n_images, n_work, dev
+
+
 def jpeg_huffman(table, table_dev, segments, segments_dev, work, work_dev, stream, huff, coef, status, subseq_words: int):
     """The Huffman pass of a whole batch on the device: a fill launch that clears ``coef`` and ``status``, then ONE launch, one
     workgroup per restart interval, on the current stream (``tsod_jpeg_huffman_i16``).  ``table`` / ``segments`` / ``work``: the
@@ -2493,22 +2515,8 @@ def jpeg_huffman(table, table_dev, segments, segments_dev, work, work_dev, strea
     device tensor, ``JPEG_HUFF_BYTES`` per image; ``coef``: int16 device tensor; ``status``: int32 device tensor, one word per
     image, nonzero afterwards where the image's entropy-coded data are damaged.  ``subseq_words``: 32-bit words per
     subsequence, 1 .. 64.  The library checks every record and work item before it launches.  Returns ``coef``."""
-    import numpy as np
-    n_images, n_work = _jpeg_lists(table, table_dev, work, work_dev, "jpeg_huffman")
-    if not (isinstance(segments, np.ndarray) and segments.dtype == jpeg_segment_dtype() and segments.ndim == 1
-            and segments.flags.c_contiguous):
-        raise ValueError("jpeg_huffman: the host segment records are a contiguous 1-d ndarray of jpeg_segment_dtype()")
-    if not (isinstance(segments_dev, torch.Tensor) and segments_dev.is_cuda and segments_dev.is_contiguous()
-            and segments_dev.numel() * segments_dev.element_size() >= segments.nbytes):
-        raise TsodError(f"jpeg_huffman: the device segment records must be a contiguous CUDA/ROCm tensor of at least "
-                        f"{segments.nbytes} bytes (there is no CPU fallback)")
-    dev = table_dev.device
-    _jpeg_buffer(stream, torch.uint8, dev, "jpeg_huffman: stream")
-    _jpeg_buffer(huff, torch.uint8, dev, "jpeg_huffman: huff")
-    _jpeg_buffer(coef, torch.int16, dev, "jpeg_huffman: coef")
-    _jpeg_buffer(status, torch.int32, dev, "jpeg_huffman: status")
-    if status.numel() < n_images:
-        raise ValueError("jpeg_huffman: status holds one word per image")
+    n_images, n_work, _ = _jpeg_huffman_args("jpeg_huffman", table, table_dev, segments, segments_dev, work, work_dev, stream, huff, coef,
+                                             status)
     check(lib().tsod_jpeg_huffman_i16(table, ptr(table_dev), n_images, segments.ctypes.data, ptr(segments_dev), segments.size,
                                       work.ctypes.data, ptr(work_dev), n_work, ptr(stream), stream.numel(), ptr(huff),
                                       huff.numel() // ctypes.sizeof(_ffi.JpegHuff), ptr(coef), coef.numel(), ptr(status),
@@ -2554,23 +2562,9 @@ def jpeg_huffman_split(table, table_dev, segments, segments_dev, chunks, chunks_
     (``jpeg_split_chunks``); ``workspace``: u8 device tensor of ``jpeg_huffman_split_workspace_bytes`` bytes, never read before
     it is written; ``repaired``: optional int32 device tensor, one word per segment, that receives the number of chunks the
     stitch launch repaired.  The coefficients and ``status`` are ``jpeg_huffman``'s, bit for bit.  Returns ``coef``."""
-    import numpy as np
-    n_images, n_chunks = _jpeg_lists(table, table_dev, chunks, chunks_dev, "jpeg_huffman_split")
-    if not (isinstance(segments, np.ndarray) and segments.dtype == jpeg_segment_dtype() and segments.ndim == 1
-            and segments.flags.c_contiguous):
-        raise ValueError("jpeg_huffman_split: the host segment records are a contiguous 1-d ndarray of jpeg_segment_dtype()")
-    if not (isinstance(segments_dev, torch.Tensor) and segments_dev.is_cuda and segments_dev.is_contiguous()
-            and segments_dev.numel() * segments_dev.element_size() >= segments.nbytes):
-        raise TsodError(f"jpeg_huffman_split: the device segment records must be a contiguous CUDA/ROCm tensor of at least "
-                        f"{segments.nbytes} bytes (there is no CPU fallback)")
-    dev = table_dev.device
-    _jpeg_buffer(stream, torch.uint8, dev, "jpeg_huffman_split: stream")
-    _jpeg_buffer(huff, torch.uint8, dev, "jpeg_huffman_split: huff")
-    _jpeg_buffer(coef, torch.int16, dev, "jpeg_huffman_split: coef")
-    _jpeg_buffer(status, torch.int32, dev, "jpeg_huffman_split: status")
+    n_images, n_chunks, dev = _jpeg_huffman_args("jpeg_huffman_split", table, table_dev, segments, segments_dev, chunks, chunks_dev, stream,
+                                                 huff, coef, status)
     _jpeg_buffer(workspace, torch.uint8, dev, "jpeg_huffman_split: workspace")
-    if status.numel() < n_images:
-        raise ValueError("jpeg_huffman_split: status holds one word per image")
     if repaired is not None:
         _jpeg_buffer(repaired, torch.int32, dev, "jpeg_huffman_split: repaired")
         if repaired.numel() < segments.size:
